@@ -13,6 +13,11 @@ Workload = BASELINE.json configs[1]: synthetic 10-KF x 200-landmark window, A1 4
 `--config 3` = BASELINE.json configs[2]: 1000 landmarks (NUM_OF_F, parameters.h:24), 400 Hz samples (27 per interval), and every
 iteration integrates all 10 intervals of every window again (IMULegIntegrationBase::repropagate, imu_leg_integration_base.cpp:62-86)
 at the biases of the point it linearises, sqrt_info of the new covariances included.
+
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the result line (with the per-kernel table
+and roofline figures taken from those same steps). `--full` adds every side measurement and check (parity sample against the oracle,
+CPU baselines, strong scaling, small batches, host hand-over, one window, two streams, the config-3 and replay side blocks,
+marginalisation). `--dump-outputs DIR` writes what the timed path computed in its last step as float64 .npy files (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -105,6 +110,46 @@ def make_synth_window(cfg, n_landmarks, rate, seed):
     prm = synth.default_params(n_landmarks=n_landmarks, seed=seed)
     prm.imu_rate_hz = float(rate)
     return synth.make_window(cfg, params=prm)
+
+
+def make_synth_windows(cfg, n_landmarks, rate, seeds):
+    """make_synth_window for every seed, in order, on a pool of host threads: the generator is C++ behind ctypes, which releases the GIL,
+    so a 32768-window batch is generated in seconds instead of a minute. The windows are the serial loop's, bit for bit."""
+    from concurrent.futures import ThreadPoolExecutor
+    from cerberus_amd import synth
+    seeds = list(seeds)
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    threads = max(1, min(16, cpus) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))   # (at most 16 per node, shared by its ranks)
+    if threads == 1 or len(seeds) < 256:
+        return [make_synth_window(cfg, n_landmarks, rate, s) for s in seeds]
+    synth.synth_lib()   # (loaded once, before the threads)
+    with ThreadPoolExecutor(threads) as ex:
+        return list(ex.map(lambda s: make_synth_window(cfg, n_landmarks, rate, s), seeds, chunksize=64))
+
+
+DUMP_STATE_BYTES = 48 << 20   # --dump-outputs: per-window states and traces of at most this many bytes (the per-window scalars come on top)
+
+
+def dump_outputs(out_dir, windows, summ, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float64 .npy files — every window's summary
+    (initial / final cost, iterations, successful steps, termination) and, for a fixed seeded sample of the windows (all of them when they
+    fit; always the first, middle and last of sample_indices), the final states and the cost / radius traces. `window_index` names the
+    sampled windows. With more than one rank every rank writes its own files, prefixed rank<r>_."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    W = len(windows)
+    per_window = 8 * (sum(a.size for a in windows[0].state_arrays()) + 2 * len(summ[0].cost_trace))
+    n = min(W, max(1, DUMP_STATE_BYTES // world // per_window))
+    idx = np.arange(W) if n == W else np.union1d(np.random.default_rng(20260925).choice(W, n, replace=False), sample_indices(W))
+    arrays = {"final_cost": [s.final_cost for s in summ], "initial_cost": [s.initial_cost for s in summ],
+              "iterations": [s.iterations for s in summ], "num_successful": [s.num_successful for s in summ],
+              "termination": [s.termination for s in summ], "window_index": idx,
+              "cost_trace": [list(summ[i].cost_trace) for i in idx], "radius_trace": [list(summ[i].radius_trace) for i in idx]}
+    for k, name in enumerate(("pose", "speed_bias", "leg_bias", "ex_pose", "td", "inv_depth")):
+        arrays[name] = np.stack([windows[i].state_arrays()[k] for i in idx])
+    pre = "rank%d_" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, pre + name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_info():
@@ -300,7 +345,7 @@ def host_inclusive_block(ctx, cfg, lib, opts, landmarks, rate, W=4096, reps=3):
     import numpy as np
     from cerberus_amd import api
     from cerberus_amd import _ctypes as T
-    ws = [make_synth_window(cfg, landmarks, rate, 70260925 + i) for i in range(W)]
+    ws = make_synth_windows(cfg, landmarks, rate, [70260925 + i for i in range(W)])
     ctx.preintegrate_windows(ws)
     keep = [w.clone_state() for w in ws]
     lib.vilo_last_download_ms.restype = C.c_double
@@ -371,7 +416,7 @@ def config3_block(ctx, cfg, lib, opts, W=256, steps=2):
     import numpy as np
     from cerberus_amd import api
     t0 = time.perf_counter()
-    windows = [make_synth_window(cfg, 1000, 400, 40260925 + i) for i in range(W)]
+    windows = make_synth_windows(cfg, 1000, 400, [40260925 + i for i in range(W)])
     ctx.preintegrate_windows(windows)
     batch = api.Batch(ctx, windows)
     batch.set_samples()
@@ -422,13 +467,14 @@ def go1_config(cfg):
     return c
 
 
-def replay_block(device, n_images=170, cpu_budget_s=10.0, seed=505, keep_dir=None, prior_form="factor"):
+def replay_block(device, n_images=170, cpu_budget_s=10.0, seed=505, keep_dir=None, prior_form="factor", checks=True, outputs=None):
     """BASELINE configs[4] / [0] (a bag replayed through the estimator, launch/dataset/run_campus_bag_vilo.launch:3-6, src/main.cpp:95-202) with
     the stand-in this container allows: a synthetic Go1-parameter stream (trot, 500 Hz IMU + joints + foot forces, 15 Hz stereo features) written
     as a ROS bag, read back through the bag reader (cerberus_amd/host/vilo_rosbag.cpp) and fed message by message through the node's logic
     (cerberus_amd/rosbag.py) into vilo::SlidingWindow on one GPU: per image the new interval's preintegration, the window's solve, the gauge fix and
     the marginalisation. Beside it the CPU oracle on the windows the replay dumped (solve on one thread + marginalisation with the Hessian build on
-    four, marginalization_factor.h:22): the reported CPU baseline of this configuration."""
+    four, marginalization_factor.h:22): the reported CPU baseline of this configuration. checks=False: the timed replay alone (no second,
+    host-carried replay and no oracle); outputs: a dict that receives the position and calf lengths the estimator reported after every image."""
     import shutil
     import tempfile
     import numpy as np
@@ -494,7 +540,10 @@ def replay_block(device, n_images=170, cpu_budget_s=10.0, seed=505, keep_dir=Non
         # (2) the same bag again with every window dumped for the oracle below — the prior and the records then travel through host
         #     memory between images (what a caller who keeps them on the host pays), timed beside it
         per_image, cnt, wall_s = one_replay(None)
-        per_dump, cnt_dump, wall_dump = one_replay(dumps)
+        if outputs is not None:
+            outputs["position"] = np.array([r["p"] for r in per_image])
+            outputs["rho"] = np.array([r["rho"] for r in per_image])
+        per_dump, cnt_dump, wall_dump = one_replay(dumps) if checks else ([], None, 0.0)
         same = float(max(np.abs(a["p"] - b["p"]).max() for a, b in zip(per_image, per_dump))) if len(per_image) == len(per_dump) else float("inf")
         steady = [r for r in per_image if r["n_opt"] > 12]     # the window is full and the prior has settled
         if not steady:
@@ -508,32 +557,33 @@ def replay_block(device, n_images=170, cpu_budget_s=10.0, seed=505, keep_dir=Non
         rho_err0 = float(np.abs(0.21 - truth[16:20]).max())
         pos_err = float(np.linalg.norm(per_image[-1]["p"] - truth[0:3]))
         # ---- CPU oracle on the dumped windows (checker leg / reported baseline: never part of the product path) ----
-        from oracle import oracle_py as O
-        ocfg = O.config_from(cfg5)
-        files = sorted(os.listdir(dumps))
-        O.lib().orc_set_marginalize_threads(4)
         cpu_solve = cpu_marg = 0.0
         n_cpu, worst = 0, 0.0
-        for fn in files:
-            if cpu_solve + cpu_marg > cpu_budget_s:
-                break
-            _, w, after, ref, flag = window_io.load(os.path.join(dumps, fn))
-            before = w.clone_state()
-            t1 = time.perf_counter()
-            sm = O.solve_window(ocfg, w, O.default_opts(False, 12))
-            cpu_solve += time.perf_counter() - t1
-            O.gauge_fix(before, w)
-            if after is not None:
-                for a, b in zip(w.state_arrays(), after):
-                    if a.size:
-                        worst = max(worst, float(np.abs(a - b).max() / max(1.0, np.abs(b).max())))
-                w.set_state(after)
-            t1 = time.perf_counter()
-            O.marginalize(ocfg, w, flag, synth.PriorData())
-            cpu_marg += time.perf_counter() - t1
-            n_cpu += 1
-        O.lib().orc_set_marginalize_threads(1)
-        return {
+        if checks:
+            from oracle import oracle_py as O
+            ocfg = O.config_from(cfg5)
+            files = sorted(os.listdir(dumps))
+            O.lib().orc_set_marginalize_threads(4)
+            for fn in files:
+                if cpu_solve + cpu_marg > cpu_budget_s:
+                    break
+                _, w, after, ref, flag = window_io.load(os.path.join(dumps, fn))
+                before = w.clone_state()
+                t1 = time.perf_counter()
+                sm = O.solve_window(ocfg, w, O.default_opts(False, 12))
+                cpu_solve += time.perf_counter() - t1
+                O.gauge_fix(before, w)
+                if after is not None:
+                    for a, b in zip(w.state_arrays(), after):
+                        if a.size:
+                            worst = max(worst, float(np.abs(a - b).max() / max(1.0, np.abs(b).max())))
+                    w.set_state(after)
+                t1 = time.perf_counter()
+                O.marginalize(ocfg, w, flag, synth.PriorData())
+                cpu_marg += time.perf_counter() - t1
+                n_cpu += 1
+            O.lib().orc_set_marginalize_threads(1)
+        out = {
             "workload": "BASELINE configs[4] stand-in (no real bag in the container): synthetic Go1-parameter stream (contact_sensor_type 2: foot forces, "
                         "optimize_leg_bias 1: calf lengths estimated on line; 500 Hz IMU / joints / forces, 15 Hz stereo features), %d images written as a "
                         "rosbag-v2 file (%d messages, %d bytes), read back through the bag reader and replayed message by message through the node's "
@@ -558,6 +608,9 @@ def replay_block(device, n_images=170, cpu_budget_s=10.0, seed=505, keep_dir=Non
                                        % (n_cpu, 1e3 * cpu_solve / max(1, n_cpu), 1e3 * cpu_marg / max(1, n_cpu)),
                              "max_state_difference_gpu_vs_oracle": worst},
         }
+        if not checks:
+            out["host_carried_replay"] = out["cpu_baseline"] = None
+        return out
     finally:
         mp = mp_raw = sw = None   # (the estimator objects go before their context)
         import gc
@@ -675,7 +728,7 @@ def main():
                     "3: BASELINE configs[2] (1000 landmarks, 400 Hz, K1 re-propagation inside every iteration); "
                     "5: BASELINE configs[4] stand-in: a synthetic Go1-parameter bag replayed through the sliding-window estimator (--images)")
     ap.add_argument("--images", type=int, default=170, help="--config 5 and the `replay` side block: images of the replayed stream")
-    ap.add_argument("--no-replay", action="store_true", help="skip the `replay` side block of the default line")
+    ap.add_argument("--no-replay", action="store_true", help="skip the `replay` side block of the --full line")
     ap.add_argument("--windows", type=int, default=0, help="independent windows per GPU (default 32768; 1024 with --config 3)")
     ap.add_argument("--total-windows", type=int, default=0, help="BASELINE configs[3] mode: this many windows in total, window w on GPU w mod N (strong scaling)")
     ap.add_argument("--landmarks", type=int, default=0, help="default 200 (1000 with --config 3)")
@@ -683,12 +736,22 @@ def main():
     ap.add_argument("--streams", type=int, default=2, help="resident batches solved concurrently in the multi-stream side figure (default 2: `two_streams`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-strong", action="store_true", help="skip the BASELINE configs[3] (1024 windows in total) side block")
-    ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE configs[2] side block of the default line")
+    ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE configs[2] side block of the --full line")
     ap.add_argument("--single-window-latency", action="store_true", help="also time a batch of one window (default at N = 1)")
     ap.add_argument("--no-single-window", action="store_true", help="skip the one-window timing (rocprofv3 runs: keeps per-kernel averages pure)")
+    ap.add_argument("--full", action="store_true", help="also every side measurement and check: parity sample against the oracle, CPU baselines, "
+                    "strong scaling, small batches, host hand-over, one window, two streams, config-3 and replay side blocks, marginalisation "
+                    "(the --no-* options above then leave single ones out); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last "
+                    "step to DIR/<name>.npy (float64; a fixed seeded sample of the windows' states where all of them would not fit in 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: the headline alone — every side block and check is left out, as its --no-* option would
+        args.no_cpu_baseline = args.no_strong = args.no_config3 = args.no_replay = args.no_single_window = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1), so
         # that a bare invocation can never measure one GPU and label it N
@@ -699,7 +762,14 @@ def main():
         if args.gpus != 1:
             print("bench.py: --config 5 is a single stream on one GPU", file=sys.stderr)
             return 2
-        r = replay_block(int(os.environ.get("LOCAL_RANK", "0")), n_images=args.images, cpu_budget_s=0.0 if args.no_cpu_baseline else 15.0)
+        outs = {}
+        r = replay_block(int(os.environ.get("LOCAL_RANK", "0")), n_images=args.images, cpu_budget_s=0.0 if args.no_cpu_baseline else 15.0,
+                         checks=args.full, outputs=outs)
+        if args.dump_outputs and outs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
         line = {"metric": "images/s, bag replay through the sliding-window VILO estimator (BASELINE configs[4] stand-in)", "value": r.get("value"),
                 "unit": "images/s", "n_gpus": 1, "steps": r.get("steady_images"), "warmup": 12, "ms_per_step": (r.get("ms_per_image") or {}).get("estimator"),
                 "higher_is_better": True, "scaling": "replicas only", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -745,7 +815,7 @@ def main():
         scaling = "weak"
         workload = "BASELINE configs[2]" if rp else "BASELINE configs[1]" if args.landmarks == 200 else "BASELINE configs[2]-sized"
     t0 = time.perf_counter()
-    windows = [make_synth_window(cfg, args.landmarks, args.rate, 20260925 + g) for g in ids]
+    windows = make_synth_windows(cfg, args.landmarks, args.rate, [20260925 + g for g in ids])
     ctx.preintegrate_windows(windows)   # K1 on the GPU: contact preintegration of all 10 * W intervals
 
     def make_batch(c, ws):
@@ -832,6 +902,8 @@ def main():
     summ = batch.download()
     iters_done = sum(s.iterations for s in summ)
     assert iters_done == W * ITERS, "every window must run the fixed iteration count"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, windows, summ, rank, world)
     final_cost = float(np.mean([s.final_cost for s in summ]))
 
     # BASELINE configs[3] as stated, beside the weak-scaling headline: 1024 windows IN TOTAL, window w on GPU w mod N (128 per GPU on 8). Every
@@ -840,7 +912,7 @@ def main():
     strong = None
     if args.total_windows == 0 and not rp and args.landmarks == 200 and not args.no_strong and STRONG_TOTAL % world == 0:
         Ws = STRONG_TOTAL // world
-        wins_s = [make_synth_window(cfg, args.landmarks, args.rate, 50260925 + rank + world * i) for i in range(Ws)]
+        wins_s = make_synth_windows(cfg, args.landmarks, args.rate, [50260925 + rank + world * i for i in range(Ws)])
         ctx.preintegrate_windows(wins_s)
         bs = make_batch(ctx, wins_s)
         lib.vilo_set_profiling(ctx.h, 0)
@@ -868,7 +940,7 @@ def main():
         small = {}
         lib.vilo_set_profiling(ctx.h, 0)
         for Wsm in (128, 256):
-            wsm = [make_synth_window(cfg, args.landmarks, args.rate, 60260925 + i) for i in range(Wsm)]
+            wsm = make_synth_windows(cfg, args.landmarks, args.rate, [60260925 + i for i in range(Wsm)])
             ctx.preintegrate_windows(wsm)
             bsm = make_batch(ctx, wsm)
             for _ in range(3):
@@ -988,7 +1060,7 @@ def main():
                 ctxs, batches = [], []
                 for k in range(S):
                     ck = api.Context(cfg, device=local_rank)
-                    wk = [make_synth_window(cfg, args.landmarks, args.rate, 30260925 + 100000 * k + i) for i in range(Ws)]
+                    wk = make_synth_windows(cfg, args.landmarks, args.rate, [30260925 + 100000 * k + i for i in range(Ws)])
                     ck.preintegrate_windows(wk)
                     ctxs.append(ck); batches.append(make_batch(ck, wk))
                     del wk

@@ -5,6 +5,8 @@ import glob
 import json
 import os
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -87,3 +89,107 @@ def test_sample_indices_cover_head_middle_and_tail():
         idx = bench.sample_indices(W)
         assert idx == sorted(set(idx)) and idx[0] == 0 and idx[-1] == W - 1 and all(0 <= i < W for i in idx) and len(idx) <= 9
     assert bench.sample_indices(32768) == [0, 1, 2, 16383, 16384, 16385, 32765, 32766, 32767]
+
+
+def test_threaded_window_generation_is_the_serial_one(cfg):
+    """bench.py generates its batches on a pool of host threads: the windows must be the serial loop's, bit for bit and in order, or two
+    runs with the same arguments would not time (and dump) the same work."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    seeds = [20260925 + g for g in range(300)]
+    par = bench.make_synth_windows(cfg, 200, 500, seeds)
+    assert len(par) == len(seeds)
+    for s, w in zip(seeds, par):
+        ref = bench.make_synth_window(cfg, 200, 500, s)
+        for name in ("lm_start_frame", "lm_obs_offset", "obs", "obs_is_stereo", "samples", "sample_offsets", "lin", "pose", "speed_bias", "leg_bias",
+                     "ex_pose", "td", "inv_depth"):
+            np.testing.assert_array_equal(getattr(w, name), getattr(ref, name), err_msg="%s of seed %d" % (name, s))
+        np.testing.assert_array_equal(w.prior.J0, ref.prior.J0)
+        np.testing.assert_array_equal(w.prior.r0, ref.prior.r0)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_what_it_computed(tmp_path, cfg, ocfg):
+    """`bench.py --steps K --warmup W` measures the headline alone (no side block, no check against the oracle); `--dump-outputs DIR`
+    writes the last timed step's results as float64 .npy files. Two runs with the same arguments dump the same arrays, and the first and
+    last windows' dumped states are the oracle's after the same fixed iterations."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from cerberus_amd import api
+    from oracle import oracle_py as O
+    W, steps = 300, 3
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--windows", str(W),
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["warmup"] == 1 and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert abs(line["value"] - W * bench.ITERS / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        for side in ("strong_scaling", "small_batches", "host_inclusive", "parity_sample", "single_window_iters_per_s", "two_streams", "config3",
+                     "replay", "marginalize", "cpu_baseline_all_cores"):
+            assert side not in line, side
+        assert line["cpu_baseline"] is None
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        runs.append({f.stem: np.load(f) for f in files})
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    for name in ("final_cost", "iterations", "window_index", "pose", "speed_bias", "leg_bias", "ex_pose", "td", "inv_depth"):
+        assert a[name].dtype == np.float64, name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    np.testing.assert_array_equal(a["window_index"], np.arange(W))     # (300 windows fit: all of them)
+    assert (a["iterations"] == bench.ITERS).all() and a["pose"].shape == (W, bench.make_synth_window(cfg, 200, 500, 0).pose.shape[0], 7)
+    ctx = api.Context(cfg, device=0)
+    try:
+        for i in (0, W - 1):
+            w = bench.make_synth_window(cfg, 200, 500, 20260925 + i)
+            ctx.preintegrate_window(w)
+            osum = O.solve_window(ocfg, w, O.default_opts(fixed_iterations=True, max_num_iterations=bench.ITERS))
+            for name, ref in zip(("pose", "speed_bias", "leg_bias", "ex_pose", "td", "inv_depth"), w.state_arrays()):
+                assert np.abs(a[name][i] - ref).max() <= 1e-8 * max(1.0, np.abs(ref).max()), (i, name)
+            assert abs(a["final_cost"][i] - osum.final_cost) <= 1e-8 * abs(osum.final_cost)
+    finally:
+        ctx.close()
+
+
+def test_dumped_outputs_stay_under_64_mb_with_a_fixed_sample(tmp_path, cfg):
+    """dump_outputs on a batch too large to dump whole: every window's summary, the states of a seeded sample that always holds the first,
+    middle and last windows — the same sample from call to call — in float64 and under 64 MB in all."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from cerberus_amd import _ctypes as T
+    W = 40000
+    w0 = bench.make_synth_window(cfg, 200, 500, 20260925)
+    windows = [w0.twin() for _ in range(W)]
+    for i in (0, W // 2, W - 1):
+        windows[i].pose[0, 0] = i
+    summ = list((T.SolveSummary * W)())
+    for i, s in enumerate(summ):
+        s.iterations, s.final_cost = bench.ITERS, float(i)
+    dumped = []
+    for k in range(2):
+        d = tmp_path / ("d%d" % k)
+        bench.dump_outputs(str(d), windows, summ)
+        files = sorted(d.glob("*.npy"))
+        assert 0 < sum(f.stat().st_size for f in files) <= 64 << 20
+        dumped.append({f.stem: np.load(f) for f in files})
+    a, b = dumped
+    for name in a:
+        assert a[name].dtype == np.float64, name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    idx = a["window_index"].astype(np.int64)
+    assert 1000 < len(idx) < W and (np.diff(idx) > 0).all() and set(bench.sample_indices(W)) <= set(idx.tolist())
+    assert len(a["final_cost"]) == W and (a["final_cost"] == np.arange(W)).all() and (a["iterations"] == bench.ITERS).all()
+    assert a["pose"].shape == (len(idx),) + w0.pose.shape and a["inv_depth"].shape == (len(idx), w0.L)
+    for i in (0, W // 2, W - 1):
+        assert a["pose"][np.searchsorted(idx, i), 0, 0] == i

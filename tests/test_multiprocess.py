@@ -58,7 +58,7 @@ def test_bench_py_itself_on_two_ranks_of_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", VILO_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "64",
-                          "--no-cpu-baseline", "--no-single-window"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--full", "--no-cpu-baseline", "--no-single-window"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["steps"] == 2
@@ -147,7 +147,7 @@ def test_bench_py_survives_an_rccl_that_cannot_start():
     env.pop("VILO_BENCH_BACKEND", None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", "29539", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "64",
-                          "--no-single-window", "--no-strong", "--no-replay", "--no-config3"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--full", "--no-single-window", "--no-strong", "--no-replay", "--no-config3"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["ranks_in_process_group"] == 2

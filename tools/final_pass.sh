@@ -12,9 +12,9 @@ O=gpurun_out/final; mkdir -p $O
 W=${PROF_WINDOWS:-32768}
 timeout 1200 python -m pytest tests -m gpu -q -x 2>&1 | tee $O/pytest.log | tail -3
 SECONDS=0
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$? in $SECONDS s"
-python bench.py --config 3 --steps 5 --warmup 2 > $O/bench_c3.json 2> $O/bench_c3.err; echo "c3 rc=$?"
-python bench.py --config 5 > $O/bench_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench default rc=$? in $SECONDS s"
+python bench.py --full --config 3 --steps 5 --warmup 2 > $O/bench_c3.json 2> $O/bench_c3.err; echo "c3 rc=$?"
+python bench.py --full --config 5 > $O/bench_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?"
 PROFILE_ARGS="--windows $W" bash tools/profile_gpu.sh r6 > gpurun_out/r6_prof.log 2>&1; tail -3 gpurun_out/r6_prof.log | cut -c1-300
 bash tools/profile_sq.sh r6sq $W > gpurun_out/r6_sq.log 2>&1; grep -c "pass" gpurun_out/r6_sq.log
 bash tools/profile_sq.sh r6sqc3 1024 "--config 3 --windows 1024" > gpurun_out/r6_sq_c3.log 2>&1; grep -c "pass" gpurun_out/r6_sq_c3.log
