@@ -89,6 +89,17 @@ class SolveSummary(C.Structure):
                 ("radius_trace", C.c_double * 64)]
 
 
+class CovOpts(C.Structure):
+    """vilo_cov_opts (24 bytes)"""
+    _fields_ = [("gauge", C.c_int32), ("pad0", C.c_int32), ("min_reciprocal_condition", C.c_double), ("want_poses", C.c_int32),
+                ("pad1", C.c_int32)]
+
+
+COV_GAUGES = {"frame0": 0, "none": 1}
+COV_FRAME = 19     # dp dtheta v ba bg rho
+COV_POSES = 79     # 11 poses, ex0, ex1, td
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_landmarks", C.c_int32), ("n_start_frames", C.c_int32), ("imu_rate_hz", C.c_double),
                 ("frame_rate_hz", C.c_double), ("pixel_noise", C.c_double), ("sig_p", C.c_double), ("sig_theta", C.c_double),

@@ -30,6 +30,7 @@ def lib():
         L = C.CDLL(path)
         L.vilo_last_error.restype = C.c_char_p
         L.vilo_last_solve_ms.restype = C.c_double
+        L.vilo_last_covariance_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -49,6 +50,20 @@ def _p(a):
 
 def _c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def default_cov_opts():
+    o = T.CovOpts()
+    lib().vilo_default_cov_opts(C.byref(o))
+    return o
+
+
+def _cov_opts(gauge, poses, min_reciprocal_condition):
+    if gauge not in T.COV_GAUGES:
+        raise ValueError("gauge must be one of %s" % sorted(T.COV_GAUGES))
+    o = default_cov_opts()
+    o.gauge, o.want_poses, o.min_reciprocal_condition = T.COV_GAUGES[gauge], 1 if poses else 0, float(min_reciprocal_condition)
+    return o
 
 
 class Batch:
@@ -102,6 +117,16 @@ class Batch:
         for i, p in enumerate(priors_out):
             C.memmove(C.byref(p.struct), C.byref(outs[i]), C.sizeof(T.Prior))
             p.rebind()
+
+    def covariance(self, gauge="frame0", poses=False, min_reciprocal_condition=1e-14):
+        """vilo_batch_covariance at the batch's device state (normally right after solve()): (frames [W, 11, 19, 19], poses [W, 79, 79] or
+        None, status [W]). gauge: 'frame0' (frame 0's position and world yaw held) or 'none' (H^-1). The batch is left as it was."""
+        n = len(self.windows)
+        o = _cov_opts(gauge, poses, min_reciprocal_condition)
+        frames, status = np.zeros((n, T.F, T.COV_FRAME, T.COV_FRAME)), np.zeros(n, np.int32)
+        pz = np.zeros((n, T.COV_POSES, T.COV_POSES)) if poses else None
+        self.ctx._check(lib().vilo_batch_covariance(self.ctx.h, self.handle, C.byref(o), _p(frames), _p(pz), T.iptr(status)))
+        return frames, pz, status
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -361,6 +386,18 @@ class Context:
         sb.pose, sb.speed_bias, sb.leg_bias, sb.ex_pose, sb.td, sb.inv_depth = [T.dptr(k) for k in keep]
         _, sa = w.desc(T)
         self._check(lib().vilo_gauge_fix(self.h, 1, C.byref(sb), C.byref(sa), w.F))
+
+    def window_covariance(self, windows, gauge="frame0", poses=False, min_reciprocal_condition=1e-14):
+        """vilo_window_covariance: the covariance of host windows at their current state arrays (see Batch.covariance)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        o = _cov_opts(gauge, poses, min_reciprocal_condition)
+        frames, status = np.zeros((n, T.F, T.COV_FRAME, T.COV_FRAME)), np.zeros(n, np.int32)
+        pz = np.zeros((n, T.COV_POSES, T.COV_POSES)) if poses else None
+        self._check(lib().vilo_window_covariance(self.h, n, descs, states, C.byref(o), _p(frames), _p(pz), T.iptr(status)))
+        return frames, pz, status
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -42,6 +42,9 @@ struct vilo_batch {
   void *d_pre = nullptr;
   bool leg = true;
   int *d_prep_bad = nullptr;   // [W * 10] covariance of this record not positive definite
+  // vilo_batch_covariance's device buffer (kernels_cov.hip): its own allocation, grown only when a call needs more, freed with the batch
+  void *cov_buf = nullptr;
+  size_t cov_bytes = 0;
 };
 
 namespace {
@@ -246,10 +249,23 @@ const int *vilo_batch_perm(vilo_batch *bt, int win, int *L) {
   return bt->perm_host.data() + bt->lm_off_host[win];
 }
 
+int vilo_batch_cov_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p) {
+  if (bt->cov_bytes < bytes) {
+    VILO_HIP(hipStreamSynchronize(ctx->stream));
+    if (bt->cov_buf) VILO_HIP(hipFree(bt->cov_buf));
+    bt->cov_buf = nullptr; bt->cov_bytes = 0;
+    VILO_HIP(hipMalloc(&bt->cov_buf, bytes));
+    bt->cov_bytes = bytes;
+  }
+  *p = bt->cov_buf;
+  return VILO_OK;
+}
+
 extern "C" void vilo_batch_destroy(vilo_ctx *ctx, vilo_batch *bt) {
   if (!bt) return;
   if (ctx) (void)hipSetDevice(ctx->device);
   if (bt->gexec) (void)hipGraphExecDestroy(bt->gexec);
+  if (bt->cov_buf) { if (ctx) (void)hipStreamSynchronize(ctx->stream); (void)hipFree(bt->cov_buf); }
   if (ctx) {
     (void)hipStreamSynchronize(ctx->stream);   // nothing of this batch may still be running when its memory is handed on
     for (auto &c : bt->chunks_dev) ctx->pool_free.push_back(c);

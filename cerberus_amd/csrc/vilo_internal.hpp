@@ -35,6 +35,7 @@ struct vilo_ctx {
   hipEvent_t rec_ev[2] = {nullptr, nullptr};   // "the DMA engine is done with staging chunk i" of vilo_batch_create's record upload
   double last_create_ms[4] = {0, 0, 0, 0}, last_create_bytes = 0.0, last_download_ms = 0.0;   // host wall time of the last vilo_batch_create / _download (vilo_last_create_ms)
   double last_marg_ms = 0.0;       // GPU time of the last vilo_marginalize (linearisation + marginalisation kernels)
+  double last_cov_ms = 0.0;        // GPU time of the last vilo_batch_covariance (linearisation + k_covariance)
   int marg_general_count = 0;      // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
@@ -49,7 +50,7 @@ struct vilo_ctx {
   double initial_mu = 1e-8;         // DoglegStrategy's mu at the start of a solve (Ceres: min_mu; vilo_debug_set_initial_mu: per-step comparisons with the oracle)
   int prior_form = 0;               // vilo_set_prior_form: 0 J0 = sqrt(S) V^T as the reference writes it, 1 any X^T with X X^T = A' (pivoted Cholesky factor) where no eigenvalue would be dropped
   int sqrt_info_mode = 0;           // 0: Cholesky of the index-reversed covariance + triangular inverse; 1: the reference's inverse() + LLT, literally
-  bool wave_attr_set = false, mid_attr_set = false, mw8_attr_set = false, asm_s_attr_set = false, marg_attr_set = false, prior_attr_set = false;   // dynamic-LDS opt-ins done on this context's device
+  bool wave_attr_set = false, mid_attr_set = false, mw8_attr_set = false, asm_s_attr_set = false, marg_attr_set = false, prior_attr_set = false, cov_attr_set = false;   // dynamic-LDS opt-ins done on this context's device
   // solver form of the batches this context solves (vilo_set_solver_form; -1: chosen from the batch size) and whether batches created on it
   // may use the compact 16-column visual rows (vilo_set_compact_rows). VILO_SOLVER / VILO_NO_COMPACT give the defaults at vilo_create.
   int solver_form = -1;

@@ -331,6 +331,48 @@ int vilo_optimize_windows_resident(vilo_ctx *ctx, int n_windows, const vilo_wind
 /* GPU time (HIP events on ctx's stream) of the kernels of the last vilo_marginalize: linearisation + marginalisation. */
 double vilo_last_marginalize_ms(const vilo_ctx *ctx);
 
+/* ---- state covariance of a window (no counterpart in the reference: Cerberus publishes odometry with a zero covariance) ----------
+ * Definition. At the window's current state, H = J^T J is the Gauss-Newton Hessian of the solve's problem: Ceres' evaluator Jacobian
+ * (whitened, HuberLoss' Corrector applied to the visual blocks), without LM damping and without Jacobi scaling, in the local coordinates of
+ * PoseLocalParameterization (dp in the world frame, dtheta the body-frame right perturbation q (x) dq(dtheta)). Constant blocks are left
+ * out as the solve leaves them out (ex_const, td_const, leg_bias_const; the leg biases when use_leg == 0). The inverse depths are
+ * eliminated; their variances are not an output.
+ *   VILO_COV_GAUGE_FRAME0 (default): Sigma = N (N^T H N)^-1 N^T, N a basis of the tangent space with frame 0's dp = 0 and
+ *     (R0^T e_z) . dtheta0 = 0: the covariance conditioned on frame 0's position and world yaw, the four quantities double2vector
+ *     resets (vilo_gauge_fix). It does not depend on the choice of N; frame 0's position rows are zero, its rotation block has rank 2.
+ *   VILO_COV_GAUGE_NONE: Sigma = H^-1, meaningful only where the prior fixes the gauge.
+ * Rank deficiency: the landmarks are eliminated first; the reduced camera-side system (restricted to N under FRAME0) is scaled to unit
+ * diagonal and factored, speed / bias chain first, then the 79-wide pose system. A window whose inputs are not finite or one of whose
+ * pivots is not above min_reciprocal_condition (Ceres' Covariance::Options default 1e-14) gets status 1 and NaN in all its outputs
+ * (Covariance::Compute returning false); the other windows are unaffected.
+ * Outputs, per window w:
+ *   frames [W][VILO_MAX_FRAMES][19][19]  diagonal block of each frame in the order dp dtheta v ba bg rho, with the pose <-> speed-bias <->
+ *                                        rho cross terms; zero for absent frames (n_frames < 11) and constant blocks
+ *   poses  [W][79][79]  (want_poses)     joint covariance of the 11 poses (66), ex0 ex1 (12) and td (1); rows of constant / absent blocks zero
+ *   status [W]                           0 OK, 1 rank deficient / not finite, 2 window invalid (a preintegration covariance without
+ *                                        sqrt_info: the window the solve fails with termination FAILURE); NaN outputs for 1 and 2
+ * The covariance is that of the solver's state, not of double2vector's re-anchored output: vilo_gauge_fix rotates the window by a yaw
+ * and shifts it, and Sigma is not transported through that rotation here. */
+#define VILO_COV_GAUGE_FRAME0 0
+#define VILO_COV_GAUGE_NONE 1
+typedef struct {
+  int32_t gauge;                     /* VILO_COV_GAUGE_* */
+  int32_t pad0;
+  double min_reciprocal_condition;   /* pivot threshold of the equilibrated system (default 1e-14) */
+  int32_t want_poses;                /* 1: fill `poses` (then it must not be NULL) */
+  int32_t pad1;
+} vilo_cov_opts;
+void vilo_default_cov_opts(vilo_cov_opts *o);
+/* At the batch's device state, normally right after vilo_batch_solve. Leaves the batch as it was: states, candidate, prior, trust-region
+ * state and the summaries vilo_batch_download reports; a following vilo_batch_solve gives what it gives without this call. Device memory
+ * for it is allocated at the first call and kept with the batch. opts NULL: vilo_default_cov_opts. Bad arguments: VILO_ERR_BAD_ARG. */
+int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_cov_opts *opts, double *frames, double *poses, int32_t *status);
+/* The same for host windows at the given states (e.g. an Estimator after optimization()): one batch is created and destroyed. */
+int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
+                           double *frames, double *poses, int32_t *status);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_covariance: linearisation + covariance kernels, without the copies out. */
+double vilo_last_covariance_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
