@@ -95,6 +95,16 @@ class CovOpts(C.Structure):
                 ("pad1", C.c_int32)]
 
 
+# vilo_debug_batch_path: code -> name per axis (include/vilo_gpu.h); "none": the step was not launched
+PATH_AXES = (
+    ("visual", {-1: "none", 0: "small_c", 1: "tpar_c", 2: "tpar", 3: "pc_imu", 4: "pc", 5: "single_c", 6: "single"}),
+    ("imu", {-1: "none", 0: "fused", 1: "single", 2: "pair"}),
+    ("imu_order", {-1: "none", 0: "last", 1: "first"}),
+    ("assembly", {-1: "none", 0: "small", 1: "full", 2: "accept_wave"}),
+    ("solver", {-1: "none", 0: "wave", 3: "split", 4: "mw8"}),
+    ("rows", {0: "full", 1: "compact"}),
+)
+
 COV_GAUGES = {"frame0": 0, "none": 1}
 COV_FRAME = 19     # dp dtheta v ba bg rho
 COV_POSES = 79     # 11 poses, ex0, ex1, td

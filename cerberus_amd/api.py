@@ -139,6 +139,17 @@ class Batch:
         self.ctx._check(lib().vilo_batch_download(self.ctx.h, self.handle, self._states, summ))
         return list(summ)
 
+    def path(self):
+        """vilo_debug_batch_path: which form of each step the last solve() ran, by name (T.PATH_AXES), plus "replay" (the solve replayed
+        the captured launch sequence) and "wave_order" (VILO_WAVE_ORDER at creation)."""
+        out = np.zeros(8, np.int32)
+        rc = lib().vilo_debug_batch_path(self.handle, T.iptr(out))
+        if rc != 0:
+            raise ViloError("vilo_debug_batch_path -> %d (no solve yet)" % rc)
+        d = {name: codes[int(out[i])] for i, (name, codes) in enumerate(T.PATH_AXES)}
+        d["replay"], d["wave_order"] = bool(out[6]), int(out[7])
+        return d
+
     def fetch(self, what, win=0, max_n=1 << 22):
         out = np.zeros(max_n)
         n = lib().vilo_debug_fetch(self.ctx.h, self.handle, what, win, _p(out), max_n)

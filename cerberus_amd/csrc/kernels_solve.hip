@@ -825,19 +825,23 @@ __global__ void __launch_bounds__(64) k_visual_reduce(BatchDev b, int mode) { vi
 // both forms behind one call (kernel kind 0 of the profiling table).
 // fuse_imu (solve passes of small batches with compact rows; gn = g_norm): the IMU factors are linearised by extra workgroups of the same
 // launch (imu_fused_body) and the second half of the frame-parallel form is left to k_assemble_s's extra workgroups (reduce_later).
+// Returns the form launched (vilo_debug_batch_path's visual code, -1: none); *imu_first: where the fused IMU workgroups went (-1: not fused).
 __global__ void k_lin_small_c(BatchDev b, double sq, double huber_a, double gn, int mode, int n_imu);   // (below, behind the IMU kernels)
-static void launch_visual_linearize(BatchDev &b, double sq, double ha, hipStream_t s, int mode, bool fuse_imu = false, double gn = 0.0) {
-  if (b.n_waves <= 0) return;
+static int launch_visual_linearize(BatchDev &b, double sq, double ha, hipStream_t s, int mode, bool fuse_imu = false, double gn = 0.0, int *imu_first_out = nullptr) {
+  if (imu_first_out) *imu_first_out = -1;
+  if (b.n_waves <= 0) return -1;
   const bool compact = b.compact && mode != 0;   // (the marginalisation's pass keeps td: full 23-column slots)
   if (b.lm_part) {
     // (every (packed wave, frame) workgroup writes all the terms and coupling rows it owns, zeros included: nothing to clear first)
     if (compact && fuse_imu) {
       hipLaunchKernelGGL(k_lin_small_c, dim3(b.W * 10 + b.n_waves * VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, gn, mode, b.W * 10);
-      return;   // (k_assemble_s's extra workgroups finish the frame-parallel form)
+      if (imu_first_out) *imu_first_out = 1;   // (its IMU workgroups are the first W x 10)
+      return 0;   // (k_assemble_s's extra workgroups finish the frame-parallel form)
     }
     if (compact) hipLaunchKernelGGL(k_visual_linearize_tpar_c, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, mode);
     else hipLaunchKernelGGL(k_visual_linearize_tpar, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, mode);
     hipLaunchKernelGGL(k_visual_reduce, dim3(b.n_waves), dim3(64), 0, s, b, mode);
+    return compact ? 1 : 2;
   } else {
     // (VILO_VISUAL_FORM=single keeps the one-wave compact form: A/B runs)
     static const bool pc = [] { const char *e = getenv("VILO_VISUAL_FORM"); return !(e && !strcmp(e, "single")); }();
@@ -846,11 +850,17 @@ static void launch_visual_linearize(BatchDev &b, double sq, double ha, hipStream
       // 128 windows, 986 / 838 k at 256; 1018 / 1054 k at 384, 1227 / 1239 k at 512. VILO_IMU_FIRST = 0 / 1 pins it.)
       static const int imu_first_env = [] { const char *e = getenv("VILO_IMU_FIRST"); return e ? atoi(e) : -1; }();
       const int imu_first = imu_first_env >= 0 ? imu_first_env : (b.W <= 256 ? 1 : 0);
-      if (fuse_imu) hipLaunchKernelGGL(k_visual_linearize_pc_imu, dim3(b.n_waves + (b.W * 10 + 1) / 2), dim3(128), 0, s, b, sq, ha, mode, gn, imu_first);
-      else hipLaunchKernelGGL(k_visual_linearize_pc, dim3(b.n_waves), dim3(128), 0, s, b, sq, ha, mode);
+      if (fuse_imu) {
+        hipLaunchKernelGGL(k_visual_linearize_pc_imu, dim3(b.n_waves + (b.W * 10 + 1) / 2), dim3(128), 0, s, b, sq, ha, mode, gn, imu_first);
+        if (imu_first_out) *imu_first_out = imu_first;
+        return 3;
+      }
+      hipLaunchKernelGGL(k_visual_linearize_pc, dim3(b.n_waves), dim3(128), 0, s, b, sq, ha, mode);
+      return 4;
     }
-    else if (compact) hipLaunchKernelGGL(k_visual_linearize_c, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode);
-    else hipLaunchKernelGGL(k_visual_linearize, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode);
+    if (compact) { hipLaunchKernelGGL(k_visual_linearize_c, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode); return 5; }
+    hipLaunchKernelGGL(k_visual_linearize, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode);
+    return 6;
   }
 }
 // does launch_visual_linearize(fuse_imu = true) take the IMU factors along for this batch?
@@ -1369,6 +1379,10 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
   const int W = b.W;
   int pidx = 0;
   ctx->pev_kind.clear();
+  // which form of each step this sequence takes (vilo_debug_batch_path; -1: the step is not launched — no iterations, no landmarks)
+  int32_t *path = ctx->launch_path;
+  for (int i = 0; i < 8; ++i) path[i] = -1;
+  path[5] = b.compact ? 1 : 0;
   // profile: 0 off, 1 every kernel, 2 + k only kernel kind k (a pair of event records costs the stream ~7 us; ~80 pairs per solve)
   bool pev_open = false;
   auto P0 = [&](int kind) {
@@ -1414,7 +1428,8 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
     // its own reduction kernel: only k_assemble_s has workgroups for that reduction)
     const bool fuse_imu = W <= small_max && visual_launch_takes_imu(b) && (asm_small || !b.lm_part);
     P0(0);
-    launch_visual_linearize(b, sq, ha, s, 1, fuse_imu, gn);
+    path[0] = launch_visual_linearize(b, sq, ha, s, 1, fuse_imu, gn, &path[2]);
+    path[1] = 0;
     P1();
     // (the fused body as a kernel of its own for full batches — one wave per factor, no raw block through HBM — was measured slower than
     // the two kernels: 315 - 319 us against 45 + 245 at 4096 windows: there lanes = factors is the better form of the raw evaluation)
@@ -1427,6 +1442,7 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
         static const int single_max = [] { const char *e = getenv("VILO_IMU_SINGLE_MAX_WINDOWS"); return e ? atoi(e) : 128; }();   // (measured: 128 windows + 1 %, 256 equal, 512 - 3 %)
         const int single = W <= single_max ? 1 : 0;   // (one wave per factor while the batch leaves SIMDs idle)
         hipLaunchKernelGGL(k_imu_linearize, dim3(W * (single ? 10 : 5)), dim3(64), 0, s, b, 1, single);
+        path[1] = single ? 1 : 2;
       }
       P1();
     }
@@ -1435,6 +1451,7 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
       P0(8);
       if (vilo_launch_assemble_small(ctx, b, sp, s, &ap, reduce_later ? b.n_waves : 0) < 0) return VILO_ERR_HIP;
       P1();
+      path[3] = 0;
     } else if (b.compact) {
       P0(8);
       if (vilo_launch_assemble_full(ctx, b, sp, s, ap, 0) != VILO_OK) return VILO_ERR_HIP;
@@ -1442,6 +1459,7 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
       P0(2);
       if (vilo_launch_assemble_full(ctx, b, sp, s, ap, 1) != VILO_OK) return VILO_ERR_HIP;
       P1();
+      path[3] = 1;
     } else {
       // 23-column slots (a window estimates td): the bookkeeping as a kernel of its own, then k_assemble
       P0(5);
@@ -1450,9 +1468,11 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
       P0(8);
       if (vilo_launch_wave_solver(ctx, b, sp, s, 0) != VILO_OK) return VILO_ERR_HIP;
       P1();
+      path[3] = 2;
     }
     ap.init_mode = 0;
-    if (vilo_solver_form(ctx, b) == 3) {
+    path[4] = vilo_solver_form(ctx, b);
+    if (path[4] == 3) {
       // three-stage form (kernels_split.hip): chain -> pose system -> back-substitutions + step, then the complete single-wave solver for
       // the windows a stage flagged (a factorisation failed: the retry loop lives there) — it returns at once for the rest
       P0(12);

@@ -38,6 +38,9 @@ struct vilo_batch {
   vilo_preint *rp_orig = nullptr;   // [W * 10] the records as created, kept from the first vilo_batch_set_samples on
   int n_solves = 0;
   bool graph_failed = false;
+  // vilo_debug_batch_path: the forms of the last solve, and those of the captured launch sequence (what a replay runs)
+  int32_t path[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, gpath[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  int wave_order_mode = 1;   // VILO_WAVE_ORDER at creation
   // what vilo_batch_prepare needs to run the sqrt_info preparation again (the reference does it in every IMULegFactor::Evaluate)
   void *d_pre = nullptr;
   bool leg = true;
@@ -540,6 +543,7 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
     for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
     const char *wo_env = getenv("VILO_WAVE_ORDER");   // tuning aid: 0 = window order, 1 = by length, 2 = by length, groups rotated
     const int wo = wo_env ? atoi(wo_env) : 1;
+    bt->wave_order_mode = wo;
     if (wo >= 1) std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return waves[a].kmax > waves[c].kmax; });
     if (wo == 2) {
       size_t g0 = 0; int gi = 0;
@@ -898,16 +902,24 @@ extern "C" int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *bt, const vilo_solve_
       if (g) (void)hipGraphDestroy(g);
     }
     if (!bt->gexec) { bt->graph_failed = true; (void)hipGetLastError(); ctx->err.clear(); }
-    else { bt->gopts = *opts; bt->g_sqrt_info_mode = ctx->sqrt_info_mode; bt->g_rp_on = bt->d.rp_on; bt->g_initial_mu = ctx->initial_mu; bt->g_solver_form = ctx->solver_form; }
+    else {
+      bt->gopts = *opts; bt->g_sqrt_info_mode = ctx->sqrt_info_mode; bt->g_rp_on = bt->d.rp_on; bt->g_initial_mu = ctx->initial_mu; bt->g_solver_form = ctx->solver_form;
+      memcpy(bt->gpath, ctx->launch_path, sizeof(bt->gpath));
+    }
     rc = VILO_OK;
   }
   VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   if (want_graph && bt->gexec) {
     VILO_HIP(hipGraphLaunch(bt->gexec, ctx->stream));
+    memcpy(bt->path, bt->gpath, sizeof(bt->path));
+    bt->path[6] = 1;
   } else {
     rc = vilo_solve_launch(ctx, bt->d, opts);
     if (rc != VILO_OK) return rc;
+    memcpy(bt->path, ctx->launch_path, sizeof(bt->path));
+    bt->path[6] = 0;
   }
+  bt->path[7] = bt->wave_order_mode;
   ++bt->n_solves;
   VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   VILO_HIP(hipEventSynchronize(ctx->ev1));
@@ -928,6 +940,12 @@ extern "C" int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *bt, const vilo_solve_
       }
     }
   }
+  return VILO_OK;
+}
+
+extern "C" int vilo_debug_batch_path(const vilo_batch *bt, int32_t out[8]) {
+  if (!bt || !out || bt->n_solves < 1) return VILO_ERR_BAD_ARG;
+  memcpy(out, bt->path, sizeof(bt->path));
   return VILO_OK;
 }
 

@@ -60,6 +60,7 @@ struct vilo_ctx {
   int pipe_lanes = 4, pipe_sub = 1024;
   std::vector<vilo_ctx *> lanes;
   int regime_full = 0;   // a lane: its batches take the kernel set of a full batch whatever their size (BatchDev::full_regime)
+  int32_t launch_path[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // forms the last vilo_solve_launch issued (vilo_debug_batch_path codes [0..5])
   vilo::WorkerPool *pool = nullptr;   // a lane's own host threads (null: the library's shared pool)
   std::mutex dma_m, *dma_turn = nullptr;   // the lanes' uploads take turns (a lane points at its parent's mutex)
 };

@@ -421,6 +421,21 @@ int vilo_get_kernel_times(const vilo_ctx *ctx, double *ms, long long *launches, 
  * (x, radius, mu) reached elsewhere: single steps are compared with the oracle this way (tests/test_branches.py). */
 int vilo_debug_set_initial_mu(vilo_ctx *ctx, double mu);
 const char *vilo_kernel_name(int kind);
+/* Which form of each step the last vilo_batch_solve of `batch` ran: the launch sequence depends on the batch size, the number of packed
+ * waves, the row form and the tuning switches read once per process (README "Environment switches"). Host bookkeeping only; a replay of
+ * the captured sequence reports the forms it was captured with. out[8]:
+ *   [0] visual linearisation: 0 k_lin_small_c (frame-parallel, IMU fused), 1 k_visual_linearize_tpar_c + k_visual_reduce,
+ *       2 k_visual_linearize_tpar + k_visual_reduce (23 columns), 3 k_visual_linearize_pc_imu, 4 k_visual_linearize_pc,
+ *       5 k_visual_linearize_c, 6 k_visual_linearize (23 columns); -1 none (no landmark in the batch, or no iteration)
+ *   [1] IMU factors: 0 fused into the visual launch, 1 k_imu_raw + k_imu_linearize with one factor per wave, 2 the same with a pair per wave
+ *   [2] fused IMU workgroups: 1 launched before the visual ones, 0 after them; -1 not fused
+ *   [3] bookkeeping + assembly: 0 k_assemble_s, 1 the two-kernel compact assembly, 2 k_accept + k_assemble (23 columns)
+ *   [4] solver: VILO_SOLVER_MW8, VILO_SOLVER_WAVE or VILO_SOLVER_SPLIT
+ *   [5] visual rows: 1 compact (16 columns), 0 23 columns
+ *   [6] 1: a replay of the captured launch sequence (hipGraph), 0: plain launches
+ *   [7] launch order of the packed waves (VILO_WAVE_ORDER): 0 window order, 1 by length, 2 by length with groups rotated
+ * Steps a solve did not launch read -1. VILO_ERR_BAD_ARG before the batch's first solve. */
+int vilo_debug_batch_path(const vilo_batch *batch, int32_t out[8]);
 /* Copy an internal device array of one window to the host (tests localise parity failures with it). */
 int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *batch, int what, int win, double *out, int max_n);
 /* Streams n doubles (8 B per lane) `reps` times: known byte count to calibrate rocprofv3 FETCH_SIZE / WRITE_SIZE. */

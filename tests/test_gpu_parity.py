@@ -388,10 +388,12 @@ def test_solve_config2_window_and_tolerances(ctx, cfg, ocfg):
 
 
 def test_headline_kernel_set_vs_oracle(ctx, cfg, ocfg):
-    """The exact kernel set bench.py times at its default size, against the oracle: a batch of more than 1024 config-2 windows (seeds
-    20260925 + i, 200 landmarks, 500 Hz: the bench's windows) takes the producer / consumer visual kernel, the compact assembly and the
-    three-stage solver (k_chain / k_solve_mid / k_backsub) — below that size other forms of the same kernels run, so the smaller tests do
-    not see this combination. 12 fixed iterations; first, middle and last window against the oracle at SURVEY 8(c)'s 1e-8."""
+    """A batch of more than 1024 config-2 windows (seeds 20260925 + i, 200 landmarks, 500 Hz: the bench's windows) against the oracle.
+    At 1100 windows it takes the producer / consumer visual kernel with the IMU factors fused into it (k_visual_linearize_pc_imu, IMU
+    workgroups last), the two-kernel compact assembly and the three-stage solver (k_chain / k_solve_mid / k_backsub) — below 1025 windows
+    other solver forms run. The bench's 32 768-window launch differs in the IMU step (k_imu_raw + paired k_imu_linearize, beyond 2048
+    windows): test_the_tail_of_a_headline_sized_batch runs that set, tests/test_kernel_paths.py every other one. 12 fixed iterations;
+    first, middle and last window against the oracle at SURVEY 8(c)'s 1e-8."""
     from cerberus_amd import api, synth
     W = 1100
     ws = [synth.make_window(cfg, params=synth.default_params(n_landmarks=200, seed=20260925 + i)) for i in range(W)]
@@ -410,6 +412,15 @@ def test_headline_kernel_set_vs_oracle(ctx, cfg, ocfg):
         api.lib().vilo_set_profiling(ctx.h, 0)
     assert {"k_chain", "k_solve_mid", "k_backsub", "k_assemble", "k_visual_linearize"} <= ran, ran
     assert all(s.iterations == 12 for s in summ)
+    # (kernel kinds cannot tell the forms apart: the descriptor of the same batch, solved resident, names them)
+    b = api.Batch(ctx, [w.twin() for w in ws])
+    try:
+        b.solve(api.default_solve_opts(True, 1))
+        path = b.path()
+    finally:
+        b.close()
+    assert path == dict(visual="pc_imu", imu="fused", imu_order="last", assembly="full", solver="split", rows="compact", replay=False,
+                        wave_order=1), path
     worst = 0.0
     for i in (0, W // 2, W - 1):
         w_o = synth.make_window(cfg, params=synth.default_params(n_landmarks=200, seed=20260925 + i))
@@ -442,8 +453,12 @@ def test_the_tail_of_a_headline_sized_batch(ctx, cfg, ocfg):
         b.prepare()
         b.solve(api.default_solve_opts(True, 12))
         summ = b.download()
+        path = b.path()
     finally:
         b.close()
+    # the bench's kernel set: producer / consumer visual form, k_imu_raw + k_imu_linearize a pair per wave, two-kernel assembly, three stages
+    assert path == dict(visual="pc", imu="pair", imu_order="none", assembly="full", solver="split", rows="compact", replay=False,
+                        wave_order=1), path
     assert all(s.iterations == 12 for s in summ)
     costs = np.array([s.final_cost for s in summ])
     med = np.median(costs)

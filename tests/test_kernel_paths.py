@@ -1,0 +1,304 @@
+"""Every form of the Gauss-Newton iteration that a batch can take, against the oracle and against each other.
+
+vilo_solve_launch / launch_visual_linearize choose the visual linearisation, the IMU form, the bookkeeping + assembly and the solver from
+the batch size, the number of packed waves, the row form and switches the library reads once per process; one batch size sees one
+combination. Each row below pins its switches in a subprocess of its own (tests/_paths_worker.py, one after another), solves a fixed window
+set through a resident batch three times (plain launches, then replays of the captured sequence), and asserts the descriptor
+vilo_debug_batch_path reports, so that no two rows run the same path by accident.
+
+The window set: two bench windows (200 landmarks, prior), one without a prior, partial windows of 4 and 8 frames, one with interval 4
+skipped, one without landmarks, one with 7 and one with 500 landmarks (multi-chunk groups), at the first, a middle and the last positions;
+twins of the bench windows elsewhere. A second batch of two far-off windows with a huge trust region drives rejected steps through the
+bookkeeping of each assembly form.
+
+Checks: every special window at every position against the oracle (equal iterations / successful steps, cost 1e-8, states 1e-8; the
+far-off windows: equal decisions, states 1e-4 as tests/test_solver_forms.py holds the solver forms); bitwise where the code or the
+documents claim it; 1e-9 elsewhere on the windows with a prior (the solver forms' bound)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+_C = {"VILO_SMALL_FUSE_MAX_WINDOWS": "0"}
+_E = {"VILO_ASM_SMALL_MAX_WINDOWS": "0"}
+_F = dict(_E, VILO_NO_TPAR="1")
+_G = dict(_F, VILO_SMALL_FUSE_MAX_WINDOWS="0", VILO_IMU_SINGLE_MAX_WINDOWS="0", VILO_SOLVER="split")
+SIZES = [128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049]
+
+# row: (environment, worker spec)
+ROWS = {
+    "A": ({}, {"far": 1, "host": 1}),
+    "B1": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "1"}, {"far": 1}),
+    "B0": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "0"}, {"far": 1}),
+    "C": (_C, {"far": 1}),
+    "D": (dict(_C, VILO_IMU_SINGLE_MAX_WINDOWS="0"), {"far": 1}),
+    "E": (_E, {"far": 1}),
+    "F": (_F, {"far": 1}),
+    "G": (_G, {"far": 1}),
+    "H": (dict(_G, VILO_VISUAL_FORM="single"), {"far": 1}),
+    "Itpar": ({}, {"compact": 0, "far": 1}),
+    "Iwalk": ({"VILO_NO_TPAR": "1"}, {"compact": 0, "far": 1}),
+    "J": ({}, {"td": 1}),
+    "K0": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "0"}, {}),
+    "K1": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "1"}, {}),
+    "K2": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "2"}, {}),
+    "L": ({"VILO_NO_GRAPH": "1"}, {}),
+    "M": ({"VILO_FULL_RECORD_UPLOAD": "1", "VILO_NO_PINNED_STAGING": "1"}, {"host_only": 1}),
+    "N": ({}, {"sizes": SIZES, "few_sizes": [300]}),
+}
+
+
+def _p(visual, imu, imu_order, assembly, solver, rows="compact"):
+    return dict(visual=visual, imu=imu, imu_order=imu_order, assembly=assembly, solver=solver, rows=rows)
+
+
+SMALL = _p("small_c", "fused", "first", "small", "mw8")
+PC_SMALL = _p("pc_imu", "fused", "first", "small", "mw8")
+EXPECT = {
+    "A": SMALL, "L": SMALL,
+    "B1": PC_SMALL, "K0": PC_SMALL, "K1": PC_SMALL, "K2": PC_SMALL,
+    "B0": _p("pc_imu", "fused", "last", "small", "mw8"),
+    "C": _p("tpar_c", "single", "none", "small", "mw8"),
+    "D": _p("tpar_c", "pair", "none", "small", "mw8"),
+    "E": _p("tpar_c", "single", "none", "full", "mw8"),
+    "F": _p("pc_imu", "fused", "first", "full", "mw8"),
+    "G": _p("pc", "pair", "none", "full", "split"),
+    "H": _p("single_c", "pair", "none", "full", "split"),
+    "Itpar": _p("tpar", "single", "none", "accept_wave", "mw8", "full"),
+    "Iwalk": _p("single", "single", "none", "accept_wave", "mw8", "full"),
+    "J": _p("tpar", "single", "none", "accept_wave", "mw8", "full"),
+    # row N: the natural thresholds (VILO_ASM_SMALL_MAX_WINDOWS 256, VILO_MW8_MAX_WINDOWS 512, VILO_SPLIT_MIN_WINDOWS 1025,
+    # VILO_SMALL_FUSE_MAX_WINDOWS 2048; IMU workgroups first up to 256 windows) — every such batch has more than 256 packed waves
+    "128": PC_SMALL, "129": PC_SMALL, "256": PC_SMALL,
+    "257": _p("pc_imu", "fused", "last", "full", "mw8"), "512": _p("pc_imu", "fused", "last", "full", "mw8"),
+    "513": _p("pc_imu", "fused", "last", "full", "wave"), "1024": _p("pc_imu", "fused", "last", "full", "wave"),
+    "1025": _p("pc_imu", "fused", "last", "full", "split"), "2048": _p("pc_imu", "fused", "last", "full", "split"),
+    "2049": _p("pc", "pair", "none", "full", "split"),   # the bench's kernel set
+    # 300 windows of a few landmarks: at most 256 packed waves beyond the small assembly
+    "few300": _p("tpar_c", "pair", "none", "full", "mw8"),
+}
+WAVE_ORDER = {"K0": 0, "K2": 2}
+PRIOR = ("bench0", "bench1", "skip4", "no_lm", "lm7", "lm500")   # well-conditioned: the 1e-9 bound between forms
+_cache = {}
+
+
+def _run(row):
+    if row not in _cache:
+        env_row, spec = ROWS[row]
+        env = {k: v for k, v in os.environ.items() if not k.startswith("VILO_") or k == "VILO_GPU_LIB"}
+        env.update(env_row)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_paths_worker.py"), json.dumps(spec)], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (row, p.stderr[-3000:])
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("PATHS_JSON ")][-1]
+        _cache[row] = json.loads(line[len("PATHS_JSON "):])
+    return _cache[row]
+
+
+def _sized(row):
+    """(name, result of one batch) of a row: its W = 32 batch, or row N's sizes."""
+    r = _run(row)
+    return [(k, v) for k, v in r.items() if k != "far"]
+
+
+@pytest.fixture(scope="module")
+def oracle():
+    """The oracle's solve of every special window, the td-estimating window and the far-off windows (the same records the worker builds)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _paths_worker as P
+    from cerberus_amd import synth
+    from oracle import oracle_py as O
+    cfg = synth.default_config()
+    ocfg = O.config_from(cfg)
+    out = {}
+    wins = dict(P.specials(cfg, ocfg), td=P.td_window(cfg, ocfg))
+    for name, w in wins.items():
+        s = O.solve_window(ocfg, w, O.default_opts(True, P.ITERS))
+        out[name] = (s, [a.copy() for a in w.state_arrays()], w.F)
+    for name, w in P.far_windows(cfg, ocfg).items():
+        o = O.default_opts(True, P.FAR_ITERS)
+        o.initial_trust_region_radius = 1e8
+        s = O.solve_window(ocfg, w, o)
+        out[name] = (s, [a.copy() for a in w.state_arrays()], w.F)
+    out["_names"] = list(wins)[:-1]
+    return out
+
+
+def _rel_states(a_list, b_list, F=11):
+    """max over the state arrays of |a - b| / max(1, |b|) (partial windows: the first F frames of the per-frame arrays)."""
+    worst = 0.0
+    for i, (a, b) in enumerate(zip(a_list, b_list)):
+        a, b = np.asarray(a, float), np.asarray(b, float)
+        if a.size == 0:
+            continue
+        if i < 3:   # (pose, speed_bias, leg_bias: per frame)
+            a, b = a[:F], b[:F]
+        worst = max(worst, float(np.abs(a - b).max() / max(1.0, np.abs(b).max())))
+    return worst
+
+
+def _specials_of(res, names):
+    """{(name, block): (state arrays, summary)} of one batch's first solve."""
+    s0 = res["solves"][0]
+    out = {}
+    for bi, block in enumerate(res["positions"]):
+        for p, nm in zip(block, names):
+            out[(nm, bi)] = (s0["state"][str(p)], s0["summ"][p])
+    return out
+
+
+@pytest.mark.parametrize("row", list(ROWS))
+def test_descriptor(row):
+    """vilo_debug_batch_path reports the row's forms; the first solve is plain launches, the later ones replays (VILO_NO_GRAPH: none)."""
+    for name, res in _sized(row):
+        if "solves" not in res:
+            continue   # (row M: Context.solve_windows; no resident batch)
+        exp = EXPECT[row if row != "N" else name]
+        for i, s in enumerate(res["solves"]):
+            got = dict(s["path"])
+            replay, wo = got.pop("replay"), got.pop("wave_order")
+            assert got == exp, (row, name, i, got)
+            assert replay == (i > 0 and row != "L"), (row, name, i)
+            assert wo == WAVE_ORDER.get(row, 1)
+    if "far" in _run(row):
+        for s in _run(row)["far"]["solves"]:
+            got = dict(s["path"]); got.pop("replay"); got.pop("wave_order")
+            assert got == EXPECT[row], (row, "far", got)
+
+
+@pytest.mark.parametrize("row", list(ROWS))
+def test_every_special_window_against_the_oracle(row, oracle):
+    names = oracle["_names"]
+    worst = worst_c = 0.0
+    for name, res in _sized(row):
+        if "solves" in res:
+            sp = _specials_of(res, names)
+        else:
+            sp = {}
+            for bi, block in enumerate(res["positions"]):
+                for p, nm in zip(block, names):
+                    sp[(nm, bi)] = (None, res["host"]["summ"][p])
+        for (nm, bi), (st, sm) in sp.items():
+            so, ost, F = oracle[nm]
+            assert (sm["iterations"], sm["successful"]) == (so.iterations, so.num_successful), (row, name, nm, bi)
+            np.testing.assert_allclose(sm["final_cost"], so.final_cost, rtol=1e-8, err_msg="%s %s %s %d" % (row, name, nm, bi))
+            worst_c = max(worst_c, abs(sm["final_cost"] / so.final_cost - 1))
+            if st is not None:
+                e = _rel_states(st, ost, F)
+                assert e < 1e-8, (row, name, nm, bi, e)
+                worst = max(worst, e)
+        if row == "J":
+            so, ost, F = oracle["td"]
+            p = len(names)
+            e = _rel_states(res["solves"][0]["state"][str(p)], ost)
+            sm = res["solves"][0]["summ"][p]
+            assert (sm["iterations"], sm["successful"]) == (so.iterations, so.num_successful)
+            np.testing.assert_allclose(sm["final_cost"], so.final_cost, rtol=1e-8)
+            assert e < 1e-8, ("td window", e)
+            worst = max(worst, e)
+    far_e = None
+    if "far" in _run(row):
+        far_e = 0.0
+        s0 = _run(row)["far"]["solves"][0]
+        for i, nm in enumerate(("far42", "far51")):
+            so, ost, F = oracle[nm]
+            sm = s0["summ"][i]
+            assert (sm["iterations"], sm["successful"]) == (so.iterations, so.num_successful), (row, nm)
+            assert sm["successful"] + 2 <= sm["iterations"]   # (rejected steps happened)
+            far_e = max(far_e, _rel_states(s0["state"][str(i)], ost))
+        assert far_e < 1e-4, (row, far_e)
+    print("MEASURED test_kernel_paths[%s] vs oracle: states %.2e, cost %.2e, far-off states %s" % (row, worst, worst_c, "-" if far_e is None else "%.2e" % far_e))
+
+
+@pytest.mark.parametrize("row", [r for r in ROWS if r != "M"])
+def test_replays_are_bitwise_the_first_solve(row):
+    for name, res in _sized(row) + ([("far", _run(row)["far"])] if "far" in _run(row) else []):
+        s = res["solves"]
+        for i in (1, 2):
+            assert s[i]["digest"] == s[0]["digest"] and s[i]["summ"] == s[0]["summ"], (row, name, i)
+
+
+def _same(a, b, with_summaries=True, skip=()):
+    ra, rb = _run(a)["32"], _run(b)["32"]
+    da = ra["solves"][0] if "solves" in ra else ra["host"]
+    db = rb["solves"][0] if "solves" in rb else rb["host"]
+    diff = [p for p, (x, y) in enumerate(zip(da["digest"], db["digest"])) if x != y and p not in skip]
+    assert not diff, (a, b, "states differ at positions", diff)
+    if with_summaries:
+        assert [s for p, s in enumerate(da["summ"]) if p not in skip] == [s for p, s in enumerate(db["summ"]) if p not in skip], (a, b)
+    else:
+        for sa, sb in zip(da["summ"], db["summ"]):
+            assert (sa["iterations"], sa["successful"]) == (sb["iterations"], sb["successful"])
+            np.testing.assert_allclose(sa["cost_trace"], sb["cost_trace"], rtol=1e-11)
+    if "far" in _run(a) and "far" in _run(b):
+        fa, fb = _run(a)["far"]["solves"][0], _run(b)["far"]["solves"][0]
+        assert fa["digest"] == fb["digest"], (a, b, "far")
+
+
+@pytest.mark.parametrize("a,b", [("B0", "B1"), ("C", "A"), ("D", "A"), ("H", "G"), ("K0", "B1"), ("K1", "B1"), ("K2", "B1"),
+                                 ("L", "A")])
+def test_bitwise_pairs(a, b):
+    """IMU workgroups first or last; the fused and the separate IMU forms (imu_fused_body: "bitwise the same Gram"); the one-wave and the
+    producer / consumer compact visual forms; the launch order of the packed waves; plain launches instead of replays."""
+    _same(a, b)
+
+
+def test_frame_parallel_and_walking_forms_give_the_same_states():
+    """k_lin_small_c and k_visual_linearize_pc_imu (both with k_assemble_s and the eight-wave solver): the same states bit for bit; the
+    visual cost's partial sums are added in another order, so the summaries agree to rounding."""
+    _same("B1", "A", with_summaries=False)
+
+
+def test_host_hand_over_switches():
+    """VILO_FULL_RECORD_UPLOAD / VILO_NO_PINNED_STAGING through Context.solve_windows: bitwise the default hand-over's answer, which is
+    bitwise the resident batch's."""
+    _same("M", "A")
+    ra = _run("A")["32"]
+    assert ra["host"]["digest"] == ra["solves"][0]["digest"] and ra["host"]["summ"] == ra["solves"][0]["summ"]
+
+
+def test_one_td_estimating_window_sends_the_batch_to_23_columns():
+    """Row J is row I (23-column rows) plus one td-estimating window at the first pad position: every other window bitwise row I's."""
+    _same("J", "Itpar", skip=(9,))
+
+
+def test_the_bench_kernel_set_at_small_and_full_size(oracle):
+    """Row G (the 32 768-window launch's kernel set pinned at 32 windows) and the natural 2049-window batch: the special windows bitwise."""
+    g = _specials_of(_run("G")["32"], oracle["_names"])
+    n = _specials_of(_run("N")["2049"], oracle["_names"])
+    for k in g:
+        assert g[k] == n[k], k
+
+
+@pytest.mark.parametrize("row", ["B0", "E", "F", "G", "Itpar", "Iwalk", "N"])
+def test_other_forms_agree_with_row_A_to_rounding(row, oracle):
+    """Where no bitwise claim exists: 1e-9 relative on the windows with a prior (the bound tests/test_solver_forms.py holds between
+    solver forms), equal decisions everywhere."""
+    names = oracle["_names"]
+    ref = _specials_of(_run("A")["32"], names)
+    worst = 0.0
+    for name, res in _sized(row):
+        sp = _specials_of(res, names)
+        for (nm, bi), (st, sm) in sp.items():
+            st_a, sm_a = ref[(nm, 0)]
+            assert (sm["iterations"], sm["successful"]) == (sm_a["iterations"], sm_a["successful"]), (row, name, nm, bi)
+            if nm in PRIOR:
+                e = _rel_states(st, st_a)
+                assert e < 1e-9, (row, name, nm, bi, e)
+                np.testing.assert_allclose(sm["cost_trace"], sm_a["cost_trace"], rtol=1e-9)
+                worst = max(worst, e)
+    far_e = None
+    if "far" in _run(row):
+        far_e = 0.0
+        fa, fr = _run("A")["far"]["solves"][0], _run(row)["far"]["solves"][0]
+        for i in (0, 1):
+            assert (fr["summ"][i]["iterations"], fr["summ"][i]["successful"]) == (fa["summ"][i]["iterations"], fa["summ"][i]["successful"])
+            far_e = max(far_e, _rel_states(fr["state"][str(i)], fa["state"][str(i)]))
+        assert far_e < 1e-4, far_e
+    print("MEASURED test_kernel_paths[%s] vs row A: states %.2e (windows with a prior), far-off %s" % (row, worst, "-" if far_e is None else "%.2e" % far_e))
