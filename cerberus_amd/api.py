@@ -7,6 +7,7 @@ The methods mirror the reference's operator interface for the hot path:
   solve_windows . Estimator::optimization() solve half (estimator.cpp:1054-1245)
   marginalize ... Estimator::optimization() marginalisation half (estimator.cpp:1247-1455)
 """
+import collections
 import ctypes as C
 import os
 
@@ -64,6 +65,23 @@ def _cov_opts(gauge, poses, min_reciprocal_condition):
     o = default_cov_opts()
     o.gauge, o.want_poses, o.min_reciprocal_condition = T.COV_GAUGES[gauge], 1 if poses else 0, float(min_reciprocal_condition)
     return o
+
+
+LandmarkCovariance = collections.namedtuple("LandmarkCovariance", "inv_depth_var points point_cov offsets status frames poses")
+
+
+def _landmark_covariance(ctx, n_landmarks, gauge, frames, poses, min_reciprocal_condition, call):
+    n = len(n_landmarks)
+    o = _cov_opts(gauge, False, min_reciprocal_condition)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum(n_landmarks)
+    L = int(offsets[-1])
+    var, pts, pcov = np.zeros(L), np.zeros((L, 3)), np.zeros((L, 3, 3))
+    status = np.zeros(n, np.int32)
+    fr = np.zeros((n, T.F, T.COV_FRAME, T.COV_FRAME)) if frames else None
+    pz = np.zeros((n, T.COV_POSES, T.COV_POSES)) if poses else None
+    ctx._check(call(o, _p(fr), _p(pz), _p(var), _p(pts), _p(pcov), T.iptr(status)))
+    return LandmarkCovariance(var, pts, pcov, offsets, status, fr, pz)
 
 
 class Batch:
@@ -127,6 +145,13 @@ class Batch:
         pz = np.zeros((n, T.COV_POSES, T.COV_POSES)) if poses else None
         self.ctx._check(lib().vilo_batch_covariance(self.ctx.h, self.handle, C.byref(o), _p(frames), _p(pz), T.iptr(status)))
         return frames, pz, status
+
+    def landmark_covariance(self, gauge="frame0", frames=False, poses=False, min_reciprocal_condition=1e-14):
+        """vilo_batch_landmark_covariance at the batch's device state: LandmarkCovariance(inv_depth_var [sum L], points [sum L, 3],
+        point_cov [sum L, 3, 3], offsets [W + 1] (window w's landmarks: offsets[w] .. offsets[w + 1], in its own order), status [W],
+        frames [W, 11, 19, 19] or None, poses [W, 79, 79] or None). The batch is left as it was."""
+        return _landmark_covariance(self.ctx, [d.n_landmarks for d in self._descs], gauge, frames, poses, min_reciprocal_condition,
+                                    lambda o, *out: lib().vilo_batch_landmark_covariance(self.ctx.h, self.handle, C.byref(o), *out))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -409,6 +434,16 @@ class Context:
         pz = np.zeros((n, T.COV_POSES, T.COV_POSES)) if poses else None
         self._check(lib().vilo_window_covariance(self.h, n, descs, states, C.byref(o), _p(frames), _p(pz), T.iptr(status)))
         return frames, pz, status
+
+    def window_landmark_covariance(self, windows, gauge="frame0", frames=False, poses=False, min_reciprocal_condition=1e-14):
+        """vilo_window_landmark_covariance: the landmark covariance of host windows at their current state arrays (see
+        Batch.landmark_covariance)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _landmark_covariance(self, [d.n_landmarks for d in descs], gauge, frames, poses, min_reciprocal_condition,
+                                    lambda o, *out: lib().vilo_window_landmark_covariance(self.h, n, descs, states, C.byref(o), *out))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "solve_common.hpp"
+#include "vilo_math.hpp"
 
 int vilo_marg_linearize(vilo_ctx *ctx, BatchDev &b);   // kernels_solve.hip
 BatchDev *vilo_batch_dev(vilo_batch *bt);               // vilo_batch.hip
@@ -553,3 +554,221 @@ extern "C" int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_w
 }
 
 extern "C" double vilo_last_covariance_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_cov_ms : -1.0; }
+
+// ---- landmark covariance (vilo_batch_landmark_covariance, include/vilo_gpu.h) ----
+// Landmarks couple only to the pose system, so with Sigma_PP (k_covariance's `poses` output: unscaled, original basis, symmetric to the
+// bit) and the mode-0 linearisation's E_l (lm_E) and w_l (lm_w, [80][L] per window):
+//   Sigma_rr = 1 / E + w^T Sigma_PP w / E^2,  Sigma_rP = -w^T Sigma_PP / E.
+// k_landmark_covariance, one workgroup of four waves per window: Sigma_PP in LDS (80 x 80, row / column 79 zero). Each wave takes 16
+// landmarks at a time and forms U = Sigma_PP W (80 x 16) as five 16 x 16 FP64-MFMA tiles over 20 k-steps (100 MFMAs). The B operand of
+// k-step ks, W[4 ks + lk][lr], is also W at the accumulator position (row 16 X + lk + 4 r: ks = 4 X + r), so w^T U comes from the
+// registers and a reduction over the four 16-lane groups. The 12 entries of U at pose s and ex0 go through LDS to one lane per landmark,
+// which forms the joint covariance of [dp_s dtheta_s dt_c dtheta_c rho], the world point p = R_s (R_c f / rho + t_c) + P_s and
+// Sigma_p = J Sigma_13 J^T.
+#define LC_T 256
+#define LC_S 0                        // [80][80] Sigma_PP
+#define LC_U (LC_S + CV_NP * CV_NP)   // [4 waves][16][12] U at pose s (dp dtheta) and ex0 (dt dtheta)
+#define LC_N (LC_U + 4 * 16 * 12)     // 57 344 bytes: two workgroups per CU
+
+// pp: Sigma_PP of window w0 + blockIdx.x at pp + blockIdx.x * 6241; status: k_covariance's, by window. Outputs in the caller's landmark
+// order (wm.lm_off + lm_perm).
+__global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0, const double *pp, const int *status, double *var_out,
+                                                             double *pts_out, double *pcov_out) {
+  using namespace vilo;
+  extern __shared__ double lds[];
+  const int w = w0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lk = lane >> 4;
+  const WinMeta wm = b.win[w];
+  if (wm.L == 0) return;
+  if (status[w] != 0) {
+    for (int l = tid; l < wm.L; l += LC_T) {
+      const int o = wm.lm_off + b.lm_perm[wm.lm_off + l];
+      var_out[o] = NAN;
+      for (int c = 0; c < 3; ++c) pts_out[3 * (size_t)o + c] = NAN;
+      for (int c = 0; c < 9; ++c) pcov_out[9 * (size_t)o + c] = NAN;
+    }
+    return;
+  }
+  double *S = lds + LC_S, *Uw = lds + LC_U + wave * 16 * 12;
+  const double *src = pp + (size_t)blockIdx.x * CV_PN;
+  for (int e = tid; e < CV_NP * CV_NP; e += LC_T) {
+    const int i = e / CV_NP, j = e % CV_NP;
+    S[e] = (i < VILO_NPU && j < VILO_NPU) ? src[i * VILO_NPU + j] : 0.0;
+  }
+  __syncthreads();
+  const double *wl = b.lm_w + 80 * (size_t)wm.lm_off;
+  const double *xw = b.x + (size_t)w * XSTRIDE;
+  for (int l0 = 0; l0 < wm.L; l0 += 64) {
+    const int lw0 = l0 + 16 * wave, l = lw0 + lr;   // this lane's landmark (window-local device order)
+    const bool act = lw0 < wm.L, on = l < wm.L;     // (act: wave-uniform)
+    const int s = on ? b.lm_s[wm.lm_off + l] : 0;
+    double q = 0.0;
+    if (act) {
+      double B[20];
+#pragma unroll
+      for (int ks = 0; ks < 20; ++ks) {
+        const int k = 4 * ks + lk;
+        B[ks] = (on && k < VILO_NPU) ? wl[(size_t)k * wm.L + l] : 0.0;
+      }
+      mfma_d4 U[5];
+#pragma unroll
+      for (int X = 0; X < 5; ++X) U[X] = mfma_d4{0.0, 0.0, 0.0, 0.0};
+      // A[row 16 X + lr][k 4 ks + lk] = Sigma_PP[4 ks + lk][16 X + lr] (symmetric): 16 consecutive doubles per lane group
+#pragma unroll
+      for (int ks = 0; ks < 20; ++ks)
+#pragma unroll
+        for (int X = 0; X < 5; ++X) U[X] = __builtin_amdgcn_mfma_f64_16x16x4f64(S[(4 * ks + lk) * CV_NP + 16 * X + lr], B[ks], U[X], 0, 0, 0);
+#pragma unroll
+      for (int X = 0; X < 5; ++X)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          q += U[X][r] * B[4 * X + r];
+          const int row = 16 * X + lk + 4 * r;
+          const int j = (row >= 6 * s && row < 6 * s + 6) ? row - 6 * s : ((row >= CD_EX0 && row < CD_EX0 + 6) ? 6 + row - CD_EX0 : -1);
+          if (j >= 0) Uw[lr * 12 + j] = U[X][r];
+        }
+      q += __shfl_xor(q, 16);
+      q += __shfl_xor(q, 32);
+    }
+    __syncthreads();
+    if (on && lk == 0) {
+      const int gi = wm.lm_off + l, o = wm.lm_off + b.lm_perm[gi];
+      const double Ei = 1.0 / b.lm_E[gi], vr = Ei + q * Ei * Ei;
+      // first observation: the packed wave and lane of device landmark l (t = 0 rows of the wave's [t][11][lanes] image)
+      double f[3] = {0.0, 0.0, 0.0};
+      for (int wi = wm.wave_off; wi < wm.wave_off + wm.n_waves; ++wi) {
+        const WaveMeta wv = b.wave[wi];
+        for (int g = 0; g < wv.nseg; ++g) {
+          const ChunkMeta cm = b.chunk[wv.seg_chunk[g]];
+          const int i = l - cm.lm_local;
+          if (i >= 0 && i < cm.n) {
+            const double *ob = b.obs + wv.obs_off + wv.seg_lane0[g] + i;
+            for (int c = 0; c < 3; ++c) f[c] = ob[(size_t)c * wv.n_lanes];
+          }
+        }
+      }
+      const double ir = 1.0 / b.lam[gi];
+      const m3 Rs = qR(qnormalized(ldq_pose(xw + XO_POSE + 7 * s))), Rc = qR(qnormalized(ldq_pose(xw + XO_EX)));
+      const v3 fv = mk3(f[0], f[1], f[2]), a = fv * ir, bc = Rc * a + ld3(xw + XO_EX);
+      const v3 p = Rs * bc + ld3(xw + XO_POSE + 7 * s);
+      const m3 Dth = -(Rs * skew(bc)), RsRc = Rs * Rc, Dthc = -(RsRc * skew(a));
+      const v3 Dr = -(RsRc * fv) * (ir * ir);
+      // J = [JP | Dr] over [dp_s dtheta_s dt_c dtheta_c | rho];  Sigma_13 = [[S12, c], [c^T, vr]], c = -U12 / E
+      double JP[3][12], cv[12], D[3] = {Dr.x, Dr.y, Dr.z};
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          JP[r][c] = r == c ? 1.0 : 0.0;
+          JP[r][3 + c] = Dth(r, c);
+          JP[r][6 + c] = Rs(r, c);
+          JP[r][9 + c] = Dthc(r, c);
+        }
+#pragma unroll
+      for (int j = 0; j < 12; ++j) cv[j] = -Uw[lr * 12 + j] * Ei;
+      double R[3][3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        double T[12], Jc = 0.0;   // T = (JP S12)_r
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+          const int dj = j < 6 ? 6 * s + j : CD_EX0 + j - 6;
+          double t = 0.0;
+#pragma unroll
+          for (int m = 0; m < 12; ++m) t += JP[r][m] * S[(m < 6 ? 6 * s + m : CD_EX0 + m - 6) * CV_NP + dj];
+          T[j] = t;
+          Jc += JP[r][j] * cv[j];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          double t = 0.0, Jcc = 0.0;
+#pragma unroll
+          for (int j = 0; j < 12; ++j) { t += T[j] * JP[c][j]; Jcc += JP[c][j] * cv[j]; }
+          R[r][c] = t + Jc * D[c] + D[r] * Jcc + vr * D[r] * D[c];
+        }
+      }
+      var_out[o] = vr;
+      st3(pts_out + 3 * (size_t)o, p);
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pcov_out[9 * (size_t)o + 3 * r + c] = 0.5 * (R[r][c] + R[c][r]);
+    }
+    __syncthreads();
+  }
+}
+
+// k_covariance indexes frames / poses by the window's index in the batch: a buffer of one chunk is handed to it shifted back by w0 windows
+static double *cov_chunk_view(char *p, int w0, size_t per_window) { return (double *)((uintptr_t)p - (uintptr_t)w0 * per_window * sizeof(double)); }
+
+extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
+                                              double *points, double *point_cov, int32_t *status) {
+  if (!ctx || !bt || !status) return VILO_ERR_BAD_ARG;
+  vilo_cov_opts o;
+  if (opts) o = *opts; else vilo_default_cov_opts(&o);
+  BatchDev &bd = *vilo_batch_dev(bt);
+  const int W = bd.W, chunk = std::min(W, CV_CHUNK), n_lm = bd.n_lm;
+  if ((o.gauge != VILO_COV_GAUGE_FRAME0 && o.gauge != VILO_COV_GAUGE_NONE) || !(o.min_reciprocal_condition >= 0.0) || !isfinite(o.min_reciprocal_condition) ||
+      (n_lm > 0 && (!inv_depth_var || !points || !point_cov))) {
+    ctx->err = "vilo_batch_landmark_covariance: bad arguments (gauge, min_reciprocal_condition >= 0, landmark output buffers)";
+    return VILO_ERR_BAD_ARG;
+  }
+  VILO_HIP(hipSetDevice(ctx->device));
+  // one grow-only buffer per batch: saved solver state | frames | poses (the whole batch where the caller takes them, else one chunk) |
+  // status | per-window scratch of one chunk | landmark outputs (variance, point, point covariance)
+  const size_t n_fr = frames ? (size_t)W : (size_t)chunk, n_po = poses ? (size_t)W : (size_t)chunk;
+  const size_t o_fr = (sizeof(SolverState) * (size_t)W + 255) & ~(size_t)255;
+  const size_t o_po = o_fr + sizeof(double) * n_fr * CV_FRN, o_stat = o_po + sizeof(double) * n_po * CV_PN;
+  const size_t o_scr = (o_stat + sizeof(int) * (size_t)W + 255) & ~(size_t)255, o_lm = o_scr + sizeof(double) * (size_t)chunk * CS_N;
+  const size_t total = o_lm + sizeof(double) * 13 * (size_t)n_lm;
+  void *buf = nullptr;
+  int rc = vilo_batch_cov_buffer(ctx, bt, total, &buf);
+  if (rc != VILO_OK) return rc;
+  char *base = (char *)buf;
+  double *d_var = (double *)(base + o_lm), *d_pts = d_var + n_lm, *d_pcov = d_pts + 3 * (size_t)n_lm;
+  const size_t lds_bytes = sizeof(double) * CL_N;
+  if (!ctx->cov_attr_set) {
+    VILO_HIP(hipFuncSetAttribute((const void *)k_covariance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    ctx->cov_attr_set = true;
+  }
+  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  VILO_HIP(hipMemcpyAsync(base, bd.st, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
+  rc = vilo_marg_linearize(ctx, bd);
+  if (rc != VILO_OK) return rc;
+  for (int w0 = 0; w0 < W; w0 += chunk) {
+    const int n = std::min(chunk, W - w0);
+    double *fr = frames ? (double *)(base + o_fr) : cov_chunk_view(base + o_fr, w0, CV_FRN);
+    double *po = poses ? (double *)(base + o_po) : cov_chunk_view(base + o_po, w0, CV_PN);
+    hipLaunchKernelGGL(k_covariance, dim3(n), dim3(CV_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, 1,
+                       (double *)(base + o_scr), fr, po, (int *)(base + o_stat));
+    hipLaunchKernelGGL(k_landmark_covariance, dim3(n), dim3(LC_T), sizeof(double) * LC_N, ctx->stream, bd, w0, po + (size_t)w0 * CV_PN,
+                       (const int *)(base + o_stat), d_var, d_pts, d_pcov);
+  }
+  VILO_HIP(hipGetLastError());
+  VILO_HIP(hipMemcpyAsync(bd.st, base, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
+  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  VILO_HIP(hipEventSynchronize(ctx->ev1));
+  float ms = 0.f;
+  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_cov_ms = ms;
+  if (frames) VILO_HIP(hipMemcpy(frames, base + o_fr, sizeof(double) * (size_t)W * CV_FRN, hipMemcpyDeviceToHost));
+  if (poses) VILO_HIP(hipMemcpy(poses, base + o_po, sizeof(double) * (size_t)W * CV_PN, hipMemcpyDeviceToHost));
+  VILO_HIP(hipMemcpy(status, base + o_stat, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost));
+  if (n_lm > 0) {
+    VILO_HIP(hipMemcpy(inv_depth_var, d_var, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
+    VILO_HIP(hipMemcpy(points, d_pts, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost));
+    VILO_HIP(hipMemcpy(point_cov, d_pcov, sizeof(double) * 9 * (size_t)n_lm, hipMemcpyDeviceToHost));
+  }
+  return VILO_OK;
+}
+
+extern "C" int vilo_window_landmark_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                               const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var, double *points,
+                                               double *point_cov, int32_t *status) {
+  if (!ctx || n_windows <= 0 || !in || !state || !status) return VILO_ERR_BAD_ARG;
+  vilo_batch *bt = nullptr;
+  int rc = vilo_batch_create(ctx, n_windows, in, state, &bt);
+  if (rc != VILO_OK) return rc;
+  rc = vilo_batch_landmark_covariance(ctx, bt, opts, frames, poses, inv_depth_var, points, point_cov, status);
+  vilo_batch_destroy(ctx, bt);
+  return rc;
+}

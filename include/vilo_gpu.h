@@ -370,8 +370,34 @@ int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_cov_opts 
 /* The same for host windows at the given states (e.g. an Estimator after optimization()): one batch is created and destroyed. */
 int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
                            double *frames, double *poses, int32_t *status);
-/* GPU time (HIP events on ctx's stream) of the last vilo_batch_covariance: linearisation + covariance kernels, without the copies out. */
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_covariance or vilo_batch_landmark_covariance: linearisation + covariance
+ * kernels, without the copies out. */
 double vilo_last_covariance_ms(const vilo_ctx *ctx);
+
+/* ---- landmark covariance: inverse depths and world points (pubPointCloud's cloud with its uncertainty) -------------------------------
+ * Same problem, gauge and conventions as the state covariance above (H = J^T J at the batch's current state, undamped and unscaled, Huber
+ * corrector applied; FRAME0 or NONE; constant blocks left out). Sigma_PP is what `poses` holds: unscaled, original basis, zero rows for
+ * constant, absent and gauge-held dimensions. For landmark l of a window with start frame s, first observation f (obs[lm_obs_offset[l]][0:3]),
+ * inverse depth rho, E = H_ll and w = H_{P,l} (79 entries; a landmark couples to poses, extrinsics and td only):
+ *   inv_depth_var   Sigma_rr = 1/E + w^T Sigma_PP w / E^2   (and Sigma_rP = -w^T Sigma_PP / E)
+ *   points          p = R_s (R_c f / rho + t_c) + P_s        ((P_s, R_s): pose s of the solver state, (t_c, R_c): ex_pose[0])
+ *   point_cov       Sigma_p = J Sigma_13 J^T (3 x 3), Sigma_13 the joint covariance of [dp_s dtheta_s dt_c dtheta_c rho] (Sigma_PP's dims
+ *                   6s..6s+5 and 66..71, Sigma_rP, Sigma_rr) and J the derivative in PoseLocalParameterization's local coordinates:
+ *                   d/ddp_s = I, d/ddtheta_s = -R_s [R_c f/rho + t_c]x, d/ddt_c = R_s, d/ddtheta_c = -R_s R_c [f/rho]x,
+ *                   d/drho = -R_s R_c f / rho^2 (with ex_const the extrinsic rows of Sigma_PP are zero and drop out).
+ * These are the landmark rows of the full inverse with the landmarks kept: N (N^T H_full N)^-1 N^T, or H_full^-1 under NONE. Like the frame
+ * blocks they belong to the solver's state, not to double2vector's re-anchored output. A window with status 1 or 2 gets NaN for all its
+ * landmarks; the other windows are unaffected. Landmarks' cross-covariances with each other are not an output.
+ * Outputs: landmarks concatenated window by window, inside a window in the caller's vilo_window_desc order (sum L = total landmarks):
+ *   inv_depth_var [sum L], points [sum L][3], point_cov [sum L][3][3], status [W];
+ *   frames, poses: as vilo_batch_covariance returns them (bit for bit), or NULL to leave them out. opts->want_poses is ignored: a non-NULL
+ *   `poses` decides. The landmark buffers may be NULL only when the batch has no landmarks. Bad arguments: VILO_ERR_BAD_ARG.
+ * The batch is left as vilo_batch_covariance leaves it; its device buffer is the same one (grown as needed). */
+int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
+                                   double *points, double *point_cov, int32_t *status);
+/* The same for host windows at the given states: one batch is created and destroyed. */
+int vilo_window_landmark_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
+                                    double *frames, double *poses, double *inv_depth_var, double *points, double *point_cov, int32_t *status);
 
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
