@@ -95,6 +95,20 @@ class CovOpts(C.Structure):
                 ("pad1", C.c_int32)]
 
 
+class ResidualOpts(C.Structure):
+    """vilo_residual_opts (8 bytes)"""
+    _fields_ = [("outlier_threshold_px", C.c_double)]
+
+
+class WindowResidual(C.Structure):
+    """vilo_window_residual (136 bytes)"""
+    _fields_ = [("cost", C.c_double), ("prior_cost", C.c_double), ("imu_cost", C.c_double * 10), ("visual_cost", C.c_double),
+                ("visual_cost_plain", C.c_double), ("n_visual_blocks", C.c_int32), ("n_huber_active", C.c_int32),
+                ("n_outliers", C.c_int32), ("n_negative_depth", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
+
 # vilo_debug_batch_path: code -> name per axis (include/vilo_gpu.h); "none": the step was not launched
 PATH_AXES = (
     ("visual", {-1: "none", 0: "small_c", 1: "tpar_c", 2: "tpar", 3: "pc_imu", 4: "pc", 5: "single_c", 6: "single"}),

@@ -32,6 +32,7 @@ def lib():
         L.vilo_last_error.restype = C.c_char_p
         L.vilo_last_solve_ms.restype = C.c_double
         L.vilo_last_covariance_ms.restype = C.c_double
+        L.vilo_last_residuals_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -82,6 +83,31 @@ def _landmark_covariance(ctx, n_landmarks, gauge, frames, poses, min_reciprocal_
     pz = np.zeros((n, T.COV_POSES, T.COV_POSES)) if poses else None
     ctx._check(call(o, _p(fr), _p(pz), _p(var), _p(pts), _p(pcov), T.iptr(status)))
     return LandmarkCovariance(var, pts, pcov, offsets, status, fr, pz)
+
+
+Residuals = collections.namedtuple("Residuals", "cost prior_cost imu_cost visual_cost visual_cost_plain n_visual_blocks n_huber_active "
+                                                "n_outliers n_negative_depth status lm_cost lm_reproj_px lm_flags offsets obs_residuals "
+                                                "imu_residuals")
+
+
+def _residuals(ctx, descs, outlier_threshold_px, observations, imu, call):
+    n = len(descs)
+    o = T.ResidualOpts()
+    lib().vilo_default_residual_opts(C.byref(o))
+    o.outlier_threshold_px = float(outlier_threshold_px)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    L = int(offsets[-1])
+    rows = sum(d.n_obs for d in descs if d.n_landmarks > 0)   # (a window without landmarks has no observation rows)
+    wr = (T.WindowResidual * n)()
+    lm_cost, lm_px, lm_flags = np.zeros(L), np.zeros(L), np.zeros(L, np.uint8)
+    obs = np.zeros((rows, 4)) if observations else None
+    imr = np.zeros((n, 10, T.IMU_RESIDUAL)) if imu else None
+    ctx._check(call(C.byref(o), wr, _p(lm_cost), _p(lm_px), T.u8ptr(lm_flags), _p(obs), _p(imr)))
+    a = np.frombuffer(wr, dtype=np.dtype([(f, np.float64 if t is C.c_double else (np.float64, 10) if f == "imu_cost" else np.int32)
+                                          for f, t in T.WindowResidual._fields_]), count=n).copy()
+    return Residuals(a["cost"], a["prior_cost"], a["imu_cost"], a["visual_cost"], a["visual_cost_plain"], a["n_visual_blocks"],
+                     a["n_huber_active"], a["n_outliers"], a["n_negative_depth"], a["status"], lm_cost, lm_px, lm_flags, offsets, obs, imr)
 
 
 class Batch:
@@ -152,6 +178,14 @@ class Batch:
         frames [W, 11, 19, 19] or None, poses [W, 79, 79] or None). The batch is left as it was."""
         return _landmark_covariance(self.ctx, [d.n_landmarks for d in self._descs], gauge, frames, poses, min_reciprocal_condition,
                                     lambda o, *out: lib().vilo_batch_landmark_covariance(self.ctx.h, self.handle, C.byref(o), *out))
+
+    def residuals(self, outlier_threshold_px=3.0, observations=False, imu=False):
+        """vilo_batch_residuals at the batch's device state: Residuals(per-window cost, prior_cost, imu_cost [W, 10], visual_cost,
+        visual_cost_plain, n_visual_blocks, n_huber_active, n_outliers, n_negative_depth, status, then lm_cost / lm_reproj_px / lm_flags
+        [sum L] (window w's landmarks: offsets[w] .. offsets[w + 1], in its own order), offsets [W + 1], obs_residuals [sum n_obs, 4] or
+        None, imu_residuals [W, 10, 31] or None). The batch is left as it was."""
+        return _residuals(self.ctx, self._descs, outlier_threshold_px, observations, imu,
+                          lambda o, *out: lib().vilo_batch_residuals(self.ctx.h, self.handle, o, *out))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -444,6 +478,15 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _landmark_covariance(self, [d.n_landmarks for d in descs], gauge, frames, poses, min_reciprocal_condition,
                                     lambda o, *out: lib().vilo_window_landmark_covariance(self.h, n, descs, states, C.byref(o), *out))
+
+    def window_residuals(self, windows, outlier_threshold_px=3.0, observations=False, imu=False):
+        """vilo_window_residuals: the residuals of host windows at their current state arrays (see Batch.residuals)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _residuals(self, descs, outlier_threshold_px, observations, imu,
+                          lambda o, *out: lib().vilo_window_residuals(self.h, n, descs, states, o, *out))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -1,0 +1,355 @@
+// Residuals of every window of a batch at its current device state, and the reference's landmark outlier / failure test
+// (vilo_batch_residuals, include/vilo_gpu.h; Estimator::outliersRejection, estimator.cpp:1741-1798; FeatureManager::setDepth /
+// removeFailures, feature_manager.cpp:142-171).
+//
+// Three launches, one code path for every batch size (no output depends on the batch a window shares, nor on its position):
+//   k_resid_landmarks  one wave per packed visual wave, lane = landmark: walks the frames as k_visual_cost_walk does, at x / lambda. Per
+//                      block the whitened residual (stored in the caller's observation row), rho and |r|^2; per landmark the reference's
+//                      reprojection sum in its own order of operations (no td, no velocities, no sqrt_info) and the flags. Per-landmark
+//                      values go to the caller's landmark order (lm_off + lm_perm): no floating-point atomics.
+//   k_resid_imu        k_imu_cost's layout (lane = factor for the raw residual, then lane = row of sqrt_info): the whitened vector and
+//                      1/2 |u|^2 per interval, whatever the window's solver state.
+//   k_resid_window     one workgroup per window: the prior's cost from its normal-equation form (k_accept's prior_H / prior_b0 / prior_c0),
+//                      then the landmark sums in caller order (a fixed per-thread stride and tree) and the window record.
+// With vilo_batch_set_samples in force the records are first integrated again at x by the marginalisation's pass (k_repropagate mode 0 +
+// the preparation), on copies: the call hands those kernels a BatchDev whose records, prepared records, flags and contact-force filters
+// point into its own buffer, so the batch's are never written.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <algorithm>
+#include <mutex>
+#include <unordered_map>
+
+#include "accept_body.hpp"
+#include "lin_common.hpp"
+#include "vilo_math.hpp"
+
+BatchDev *vilo_batch_dev(vilo_batch *bt);   // vilo_batch.hip
+int vilo_batch_resid_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p, const int **obs_row, int *n_obs_rows);   // vilo_batch.hip
+
+// GPU time of each context's last call (vilo_last_residuals_ms)
+static std::mutex g_resid_ms_mu;
+static std::unordered_map<const vilo_ctx *, double> g_resid_ms;
+
+static_assert(sizeof(vilo_window_residual) == 136, "vilo_window_residual: 136 bytes (include/vilo_gpu.h)");
+static_assert(sizeof(vilo_residual_opts) == 8, "vilo_residual_opts: 8 bytes (include/vilo_gpu.h)");
+
+// per-landmark values the window pass sums (caller order)
+struct ResidLm {
+  double *cost, *reproj, *plain;   // [n_lm] 1/2 sum rho, reprojection error in pixels, 1/2 sum |r|^2
+  int *nb, *nh;                    // [n_lm] residual blocks, of which in Huber's linear region
+  unsigned char *flags;            // [n_lm]
+};
+
+__global__ void __launch_bounds__(64) k_resid_landmarks(BatchDev b, double sq, double huber_a, double focal, double thr, const int *obs_row,
+                                                        ResidLm out, double *obs_res) {
+  using namespace vilo;
+  const WaveMeta wv = b.wave[blockIdx.x];
+  const WinMeta wm = b.win[wv.win];
+  const int lane = threadIdx.x;
+  int cs[4], cn[4], ckm[4], cgo[4];
+  const LaneSeg ls = lane_segment(wv, b.chunk, lane, cs, cn, ckm, cgo);
+  if (!ls.active) return;
+  const int n = wv.n_lanes, s = ls.s, gi = ls.gi, o = wm.lm_off + b.lm_perm[gi];
+  const double *x = b.x + (size_t)wv.win * XSTRIDE;
+  const double *obs = b.obs + wv.obs_off;
+  const unsigned char *flg = b.flags + wv.flag_off;
+  double *orow = obs_res ? obs_res + 4 * (size_t)obs_row[gi] : nullptr;
+  const double lam = b.lam[gi];
+  // the factors' form (k_visual_cost_walk): td-compensated start-frame point, its world point once per landmark
+  const double td = x[XO_TD];
+  const double *ex0 = x + XO_EX, *ex1 = x + XO_EX + 7;
+  const quat qic = ldq_pose(ex0), qic2 = ldq_pose(ex1);
+  const v3 tic = ld3(ex0), tic2 = ld3(ex1);
+  const double inv_lam = 1.0 / lam;
+  const double dti = td - obs[(size_t)10 * n + lane];
+  const v3 pci = mk3((obs[(size_t)0 * n + lane] - obs[(size_t)6 * n + lane] * dti) * inv_lam, (obs[(size_t)1 * n + lane] - obs[(size_t)7 * n + lane] * dti) * inv_lam,
+                     obs[(size_t)2 * n + lane] * inv_lam);
+  const v3 p_i = qrot(qic, pci) + tic;
+  const double *pose_s = x + XO_POSE + 7 * s;
+  const v3 p_w = qrot(ldq_pose(pose_s), p_i) + ld3(pose_s);
+  // Estimator::reprojectionError's form: rotation matrices of the normalised quaternions, depth = 1 / inv_depth, raw points
+  const m3 Ri = qR(qnormalized(ldq_pose(pose_s))), ric0 = qR(qnormalized(qic)), ric1 = qR(qnormalized(qic2));
+  const v3 Pi = ld3(pose_s);
+  const double depth = 1.0 / lam;
+  const v3 uvi = mk3(obs[(size_t)0 * n + lane], obs[(size_t)1 * n + lane], obs[(size_t)2 * n + lane]);
+  const v3 pts_w = Ri * (ric0 * (uvi * depth) + tic) + Pi;
+  double cost = 0.0, plain = 0.0, err = 0.0;
+  int nb = 0, nh = 0, cnt = 0;
+  auto block = [&](const v3 &pcj, double px, double py, double *rout) {
+    const double inv_z = 1.0 / pcj.z;
+    const double r0 = sq * (pcj.x * inv_z - px), r1 = sq * (pcj.y * inv_z - py);
+    const double s2 = r0 * r0 + r1 * r1;
+    double rho[3];
+    huber_rho(huber_a, s2, rho);
+    cost += rho[0];
+    plain += s2;
+    ++nb;
+    if (s2 > huber_a * huber_a) ++nh;
+    if (rout) { rout[0] = r0; rout[1] = r1; }
+  };
+  auto reproj = [&](const m3 &Rj, const v3 &Pj, const m3 &ricj, const v3 &ticj, double ux, double uy) {
+    const v3 pts_cj = tr(ricj) * (tr(Rj) * (pts_w - Pj) - ticj);
+    const double rx = pts_cj.x / pts_cj.z - ux, ry = pts_cj.y / pts_cj.z - uy;
+    err += sqrt(rx * rx + ry * ry);
+    ++cnt;
+  };
+  for (int t = 0; t < wv.kmax; ++t) {
+    const unsigned char fl = flg[(size_t)t * n + lane];
+    if (!(fl & 1)) continue;
+    const double *ob = obs + (size_t)t * 11 * n + lane;
+    double *rr = orow ? orow + 4 * (size_t)t : nullptr;
+    const double dtj = td - ob[(size_t)10 * n];
+    const double *pose_j = x + XO_POSE + 7 * min(s + t, VILO_MAX_FRAMES - 1);
+    const m3 Rj = qR(qnormalized(ldq_pose(pose_j)));
+    const v3 Pj = ld3(pose_j);
+    v3 p_j = p_i;
+    if (t > 0) {
+      p_j = qrot(qinv(ldq_pose(pose_j)), p_w - Pj);
+      block(qrot(qinv(qic), p_j - tic), ob[0] - ob[(size_t)6 * n] * dtj, ob[(size_t)1 * n] - ob[(size_t)7 * n] * dtj, rr);
+      reproj(Rj, Pj, ric0, tic, ob[0], ob[(size_t)1 * n]);
+    } else if (rr) {
+      rr[0] = NAN; rr[1] = NAN;
+    }
+    if (fl & 2) {
+      block(qrot(qinv(qic2), p_j - tic2), ob[(size_t)3 * n] - ob[(size_t)8 * n] * dtj, ob[(size_t)4 * n] - ob[(size_t)9 * n] * dtj, rr ? rr + 2 : nullptr);
+      reproj(Rj, Pj, ric1, tic2, ob[(size_t)3 * n], ob[(size_t)4 * n]);
+    } else if (rr) {
+      rr[2] = NAN; rr[3] = NAN;
+    }
+  }
+  const double px = (err / cnt) * focal;
+  out.cost[o] = 0.5 * cost;
+  out.reproj[o] = px;
+  out.plain[o] = 0.5 * plain;
+  out.nb[o] = nb;
+  out.nh[o] = nh;
+  out.flags[o] = (unsigned char)((px > thr ? 1 : 0) | (depth < 0.0 ? 2 : 0) | (nh > 0 ? 4 : 0));
+}
+
+// one wave per 64 factors (k_imu_cost's layout); cost_out [W * 10], res_out [W * 10][31] or null
+__global__ void __launch_bounds__(64) k_resid_imu(BatchDev b, double g_norm, double *cost_out, double *res_out) {
+  using namespace vilo;
+  __shared__ double rs[32 * 64];   // [entry][factor of the wave]; row 31: 1/2 |u|^2 per factor
+  const int lane = threadIdx.x, f0 = blockIdx.x * 64, f = f0 + lane;
+  const int NF = b.W * 10;
+  bool live = false, bad = false;
+  {
+    double r[31];
+#pragma unroll
+    for (int i = 0; i < 31; ++i) r[i] = 0.0;
+    if (f < NF) {
+      const int win = f / 10, k = f % 10;
+      live = !b.imu_skip[f];
+      bad = live && b.prep_bad && b.prep_bad[f];
+      if (live) {
+        const PreintPrepared &pp = b.prep[f];
+        const double *x = b.x + (size_t)win * XSTRIDE;
+        if (b.win[win].use_leg) {
+          imu_leg_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_LB + 4 * k, x + XO_POSE + 7 * (k + 1),
+                      x + XO_SB + 9 * (k + 1), x + XO_LB + 4 * (k + 1), r, false, nullptr, 0);
+        } else {
+          imu_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_POSE + 7 * (k + 1), x + XO_SB + 9 * (k + 1), r, false, nullptr, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 31; ++i) rs[i * 64 + lane] = r[i];
+    rs[31 * 64 + lane] = 0.0;
+  }
+  lds_barrier();
+  const unsigned long long livem = __ballot(live), badm = __ballot(bad);
+  const int row = min(lane, 30);
+  for (int fl = 0; fl < 64; ++fl) {
+    if (f0 + fl >= NF) break;
+    double u = 0.0;
+    if ((livem >> fl) & 1ULL) {
+      const double *U = b.prep[f0 + fl].sqrt_info + row * 31;
+      double uq[31];
+#pragma unroll
+      for (int q = 0; q < 31; ++q) uq[q] = (q >= row) ? U[q] : 0.0;
+#pragma unroll
+      for (int q = 0; q < 31; ++q) u += uq[q] * rs[q * 64 + fl];
+    }
+    const bool nan_f = (badm >> fl) & 1ULL;
+    if (res_out && lane < 31) res_out[(size_t)(f0 + fl) * 31 + lane] = nan_f ? NAN : u;
+    const double c = wave_sum(lane < 31 ? u * u : 0.0);
+    if (lane == 0) rs[31 * 64 + fl] = nan_f ? NAN : 0.5 * c;
+  }
+  lds_barrier();
+  if (f < NF) cost_out[f] = rs[31 * 64 + lane];
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return __shfl(v, 0, 64);
+}
+
+// one workgroup of 128 threads per window
+__global__ void __launch_bounds__(128) k_resid_window(BatchDev b, ResidLm lm, const double *imu_cost, vilo_window_residual *out) {
+  using namespace vilo;
+  __shared__ double red[128];
+  __shared__ double dxs[VILO_MAX_PRIOR_DIM];
+  __shared__ int ired[8];
+  const int win = blockIdx.x, tid = threadIdx.x;
+  const WinMeta wm = b.win[win];
+  // prior: 1/2 (dx^T (H dx + 2 b0) + c0) at x, k_accept's form (MarginalizationFactor::Evaluate through H = J0^T J0, b0 = J0^T r0, c0 = r0^T r0)
+  double pri = 0.0;
+  if (wm.prior_n > 0) {
+    const int n = wm.prior_n;
+    const double *x = b.x + (size_t)win * XSTRIDE;
+    if (tid < wm.prior_nb)
+      prior_dx(x + b.prior_bstate[win * 40 + tid], b.prior_x0 + (size_t)win * 280 + b.prior_bxoff[win * 40 + tid], b.prior_bsize[win * 40 + tid],
+               dxs + b.prior_bidx[win * 40 + tid]);
+    __syncthreads();
+    const double *Hp = b.prior_H + (size_t)win * 96 * 96, *b0 = b.prior_b0 + (size_t)win * 96;
+    if (tid < n) {
+      double sacc = 0.0;
+      for (int q = 0; q < n; ++q) sacc += Hp[(size_t)q * n + tid] * dxs[q];
+      pri = dxs[tid] * (sacc + 2.0 * b0[tid]);
+    }
+  }
+  // landmark sums in caller order: thread t takes l = t, t + 128, ...; one fixed tree over the threads
+  double vis = 0.0, pl = 0.0;
+  int nb = 0, nh = 0, nout = 0, nneg = 0;
+  for (int l = tid; l < wm.L; l += 128) {
+    const int o = wm.lm_off + l;
+    vis += lm.cost[o];
+    pl += lm.plain[o];
+    nb += lm.nb[o];
+    nh += lm.nh[o];
+    nout += lm.flags[o] & 1;
+    nneg += (lm.flags[o] >> 1) & 1;
+  }
+  block_sum128x3(pri, vis, pl, red);
+  // (integer counts: exact in any order)
+  nb = wave_sum_int(nb); nh = wave_sum_int(nh); nout = wave_sum_int(nout); nneg = wave_sum_int(nneg);
+  if ((tid & 63) == 0) { ired[4 * (tid >> 6) + 0] = nb; ired[4 * (tid >> 6) + 1] = nh; ired[4 * (tid >> 6) + 2] = nout; ired[4 * (tid >> 6) + 3] = nneg; }
+  __syncthreads();
+  if (tid == 0) {
+    vilo_window_residual r;
+    r.prior_cost = wm.prior_n > 0 ? 0.5 * (pri + b.prior_c0[win]) : 0.0;
+    double cost = r.prior_cost;
+    int status = 0;
+    for (int k = 0; k < 10; ++k) {
+      const double c = imu_cost[(size_t)win * 10 + k];
+      r.imu_cost[k] = c;
+      cost += c;
+      if (isnan(c)) status = 2;
+    }
+    r.visual_cost = vis;
+    r.visual_cost_plain = pl;
+    r.cost = cost + vis;
+    r.n_visual_blocks = ired[0] + ired[4];
+    r.n_huber_active = ired[1] + ired[5];
+    r.n_outliers = ired[2] + ired[6];
+    r.n_negative_depth = ired[3] + ired[7];
+    r.status = status;
+    r.pad = 0;
+    out[win] = r;
+  }
+}
+
+extern "C" void vilo_default_residual_opts(vilo_residual_opts *o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->outlier_threshold_px = 3.0;
+}
+
+extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_residual_opts *opts, vilo_window_residual *windows, double *lm_cost,
+                                    double *lm_reproj_px, uint8_t *lm_flags, double *obs_residuals, double *imu_residuals) {
+  if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
+  vilo_residual_opts o;
+  if (opts) o = *opts; else vilo_default_residual_opts(&o);
+  if (!isfinite(o.outlier_threshold_px) || !(o.outlier_threshold_px >= 0.0)) {
+    ctx->err = "vilo_batch_residuals: outlier_threshold_px must be finite and >= 0";
+    return VILO_ERR_BAD_ARG;
+  }
+  VILO_HIP(hipSetDevice(ctx->device));
+  const BatchDev &bd = *vilo_batch_dev(bt);
+  const int W = bd.W, n_lm = bd.n_lm, NF = W * 10;
+  const bool rp = bd.rp_on && bd.rp_samples && bd.leg;
+  // buffer (grow-only, kept with the batch): window records | per-landmark values | interval costs | interval residuals | observation
+  // residuals | re-integration copies (records, prepared records, flags, contact-force filters)
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const int *obs_row = nullptr;
+  int n_rows = 0;
+  size_t at = 0;
+  const size_t o_win = at; at = al(at + sizeof(vilo_window_residual) * (size_t)W);
+  const size_t o_lm = at; at = al(at + (3 * sizeof(double) + 2 * sizeof(int) + 1) * (size_t)n_lm);
+  const size_t o_ic = at; at = al(at + sizeof(double) * (size_t)NF);
+  const size_t o_ir = at; if (imu_residuals) at = al(at + sizeof(double) * 31 * (size_t)NF);
+  const size_t o_or = at;
+  // (the row count is the batch's: asked for below, after the buffer call, so the buffer is sized by an upper bound first)
+  void *buf = nullptr;
+  int rc = vilo_batch_resid_buffer(ctx, bt, 0, &buf, &obs_row, &n_rows);
+  if (rc != VILO_OK) return rc;
+  if (obs_residuals) at = al(at + sizeof(double) * 4 * (size_t)n_rows);
+  const size_t o_rp = at;
+  if (rp) at = al(at + (sizeof(vilo_preint) + sizeof(PreintPrepared) + sizeof(int) + sizeof(double) * VILO_FF_N) * (size_t)NF);
+  rc = vilo_batch_resid_buffer(ctx, bt, at, &buf, &obs_row, &n_rows);
+  if (rc != VILO_OK) return rc;
+  char *base = (char *)buf;
+  ResidLm lm;
+  lm.cost = (double *)(base + o_lm); lm.reproj = lm.cost + n_lm; lm.plain = lm.reproj + n_lm;
+  lm.nb = (int *)(lm.plain + n_lm); lm.nh = lm.nb + n_lm; lm.flags = (unsigned char *)(lm.nh + n_lm);
+  double *d_ic = (double *)(base + o_ic), *d_ir = imu_residuals ? (double *)(base + o_ir) : nullptr, *d_or = obs_residuals ? (double *)(base + o_or) : nullptr;
+  const double sq = ctx->cfg.focal_length / 1.5, ha = ctx->cfg.huber_delta, gn = ctx->cfg.g_norm;
+  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  BatchDev b = bd;
+  if (rp) {
+    // the marginalisation's re-integration at x (records already integrated there are kept: k_repropagate's own test), on copies
+    char *r0 = base + o_rp;
+    b.rp_pre = r0;
+    b.prep = (PreintPrepared *)(r0 + sizeof(vilo_preint) * (size_t)NF);
+    b.prep_bad = (int *)((char *)b.prep + sizeof(PreintPrepared) * (size_t)NF);
+    b.rp_ff = bd.rp_ff ? (double *)((char *)b.prep_bad + sizeof(int) * (size_t)NF) : nullptr;
+    VILO_HIP(hipMemcpyAsync(b.rp_pre, bd.rp_pre, sizeof(vilo_preint) * (size_t)NF, hipMemcpyDeviceToDevice, ctx->stream));
+    if (bd.rp_ff) VILO_HIP(hipMemcpyAsync(b.rp_ff, bd.rp_ff, sizeof(double) * VILO_FF_N * (size_t)NF, hipMemcpyDeviceToDevice, ctx->stream));
+    if (vilo_repropagate_launch(ctx, b, 0, 0) != VILO_OK || vilo_repropagate_launch(ctx, b, 0, 1) != VILO_OK) return VILO_ERR_HIP;
+  }
+  if (bd.n_waves > 0)
+    hipLaunchKernelGGL(k_resid_landmarks, dim3(bd.n_waves), dim3(64), 0, ctx->stream, b, sq, ha, ctx->cfg.focal_length, o.outlier_threshold_px, obs_row,
+                       lm, d_or);
+  hipLaunchKernelGGL(k_resid_imu, dim3((NF + 63) / 64), dim3(64), 0, ctx->stream, b, gn, d_ic, d_ir);
+  hipLaunchKernelGGL(k_resid_window, dim3(W), dim3(128), 0, ctx->stream, b, lm, (const double *)d_ic, (vilo_window_residual *)(base + o_win));
+  VILO_HIP(hipGetLastError());
+  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  VILO_HIP(hipEventSynchronize(ctx->ev1));
+  float ms = 0.f;
+  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  {
+    std::lock_guard<std::mutex> lk(g_resid_ms_mu);
+    g_resid_ms[ctx] = ms;
+  }
+  VILO_HIP(hipMemcpy(windows, base + o_win, sizeof(vilo_window_residual) * (size_t)W, hipMemcpyDeviceToHost));
+  if (n_lm > 0) {
+    if (lm_cost) VILO_HIP(hipMemcpy(lm_cost, lm.cost, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
+    if (lm_reproj_px) VILO_HIP(hipMemcpy(lm_reproj_px, lm.reproj, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
+    if (lm_flags) VILO_HIP(hipMemcpy(lm_flags, lm.flags, (size_t)n_lm, hipMemcpyDeviceToHost));
+  }
+  if (obs_residuals && n_rows > 0) VILO_HIP(hipMemcpy(obs_residuals, d_or, sizeof(double) * 4 * (size_t)n_rows, hipMemcpyDeviceToHost));
+  if (imu_residuals) VILO_HIP(hipMemcpy(imu_residuals, d_ir, sizeof(double) * 31 * (size_t)NF, hipMemcpyDeviceToHost));
+  return VILO_OK;
+}
+
+extern "C" int vilo_window_residuals(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                     const vilo_residual_opts *opts, vilo_window_residual *windows, double *lm_cost, double *lm_reproj_px,
+                                     uint8_t *lm_flags, double *obs_residuals, double *imu_residuals) {
+  if (!ctx || n_windows < 1 || !in || !state || !windows) return VILO_ERR_BAD_ARG;
+  if (opts && (!isfinite(opts->outlier_threshold_px) || !(opts->outlier_threshold_px >= 0.0))) return VILO_ERR_BAD_ARG;
+  vilo_batch *bt = nullptr;
+  int rc = vilo_batch_create(ctx, n_windows, in, state, &bt);
+  if (rc != VILO_OK) return rc;
+  rc = vilo_batch_residuals(ctx, bt, opts, windows, lm_cost, lm_reproj_px, lm_flags, obs_residuals, imu_residuals);
+  vilo_batch_destroy(ctx, bt);
+  return rc;
+}
+
+extern "C" double vilo_last_residuals_ms(const vilo_ctx *ctx) {
+  if (!ctx) return -1.0;
+  std::lock_guard<std::mutex> lk(g_resid_ms_mu);
+  const auto it = g_resid_ms.find(ctx);
+  return it == g_resid_ms.end() ? 0.0 : it->second;
+}

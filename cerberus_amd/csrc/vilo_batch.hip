@@ -48,6 +48,13 @@ struct vilo_batch {
   // vilo_batch_covariance's device buffer (kernels_cov.hip): its own allocation, grown only when a call needs more, freed with the batch
   void *cov_buf = nullptr;
   size_t cov_bytes = 0;
+  // vilo_batch_residuals (kernels_resid.hip): the caller's observation row of each landmark's first observation (device order, rows
+  // concatenated by window: a window without landmarks has none), uploaded with the call's own grow-only buffer at its first call
+  std::vector<int> obs_row_host;
+  int n_obs_rows = 0;
+  void *res_buf = nullptr;
+  size_t res_bytes = 0;
+  int *d_obs_row = nullptr;
 };
 
 namespace {
@@ -264,11 +271,31 @@ int vilo_batch_cov_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p)
   return VILO_OK;
 }
 
+// vilo_batch_residuals' buffer: grow-only like the covariance's; the landmarks' observation rows are uploaded with its first allocation
+int vilo_batch_resid_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p, const int **obs_row, int *n_obs_rows) {
+  const size_t row_bytes = (sizeof(int) * std::max<size_t>(1, bt->obs_row_host.size()) + 255) & ~(size_t)255;
+  if (bt->res_bytes < row_bytes + bytes) {
+    VILO_HIP(hipStreamSynchronize(ctx->stream));
+    if (bt->res_buf) VILO_HIP(hipFree(bt->res_buf));
+    bt->res_buf = nullptr; bt->res_bytes = 0;
+    VILO_HIP(hipMalloc(&bt->res_buf, row_bytes + bytes));
+    bt->res_bytes = row_bytes + bytes;
+    bt->d_obs_row = (int *)bt->res_buf;
+    if (!bt->obs_row_host.empty())
+      VILO_HIP(hipMemcpy(bt->d_obs_row, bt->obs_row_host.data(), sizeof(int) * bt->obs_row_host.size(), hipMemcpyHostToDevice));
+  }
+  *p = (char *)bt->res_buf + row_bytes;
+  *obs_row = bt->d_obs_row;
+  *n_obs_rows = bt->n_obs_rows;
+  return VILO_OK;
+}
+
 extern "C" void vilo_batch_destroy(vilo_ctx *ctx, vilo_batch *bt) {
   if (!bt) return;
   if (ctx) (void)hipSetDevice(ctx->device);
   if (bt->gexec) (void)hipGraphExecDestroy(bt->gexec);
   if (bt->cov_buf) { if (ctx) (void)hipStreamSynchronize(ctx->stream); (void)hipFree(bt->cov_buf); }
+  if (bt->res_buf) { if (ctx) (void)hipStreamSynchronize(ctx->stream); (void)hipFree(bt->res_buf); }
   if (ctx) {
     (void)hipStreamSynchronize(ctx->stream);   // nothing of this batch may still be running when its memory is handed on
     for (auto &c : bt->chunks_dev) ctx->pool_free.push_back(c);
@@ -372,6 +399,9 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
         const int sf = d.lm_start_frame[l], at = fill[sf]++;
         bt->perm_host[base + at] = l; lam0[base + at] = s.inv_depth[l]; lm_s[base + at] = (unsigned char)sf;
       }
+      bt->obs_row_host.resize(base + L);
+      for (int i = 0; i < L; ++i) bt->obs_row_host[base + i] = bt->n_obs_rows + d.lm_obs_offset[bt->perm_host[base + i]];
+      if (L > 0) bt->n_obs_rows += d.lm_obs_offset[L];
       for (int sf = 0; sf < F; ++sf) {
         for (int c0 = first[sf]; c0 < first[sf + 1]; c0 += 64) {
           const int n = std::min(64, first[sf + 1] - c0);

@@ -399,6 +399,65 @@ int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_
 int vilo_window_landmark_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
                                     double *frames, double *poses, double *inv_depth_var, double *points, double *point_cov, int32_t *status);
 
+/* ---- residuals at the current state (Ceres Problem::Evaluate's residuals; Estimator::outliersRejection, estimator.cpp:1741-1798) ----
+ * State: the batch's current state, what vilo_batch_download returns (inverse depths included): the initial state before any solve or after
+ * vilo_batch_reset, the accepted state after a solve. It is the solver's state, not double2vector's re-anchored output (reprojection errors do
+ * not depend on that choice: the gauge fix moves every frame by the same rigid transform).
+ * Costs: Ceres' 1/2 sum rho(|r|^2) over the problem the solve builds, in the units of vilo_solve_summary::final_cost. The IMU-leg / IMU factor
+ * counts its whitened residual; the three projection factors use sqrt_info = focal_length / 1.5, td compensation and the HuberLoss; the prior
+ * is MarginalizationFactor::Evaluate's. Constant blocks change no cost. With vilo_batch_set_samples in force the IMU factors are evaluated on
+ * records integrated again at the current state, as vilo_batch_marginalize does (into buffers of the call's own: the batch's records and
+ * contact-force filters are not touched).
+ * Per landmark (concatenated window by window, inside a window in the caller's vilo_window_desc order, as vilo_batch_landmark_covariance):
+ *   lm_cost       1/2 sum rho over the landmark's residual blocks;
+ *   lm_reproj_px  (err / cnt) * focal_length, err and cnt exactly the sum and count of Estimator::reprojectionError in outliersRejection:
+ *                 frame by frame from the start frame, the left-camera term first (not on the start frame), then the right-camera term of
+ *                 every stereo observation (the start frame included); no td compensation, no velocities, depth = 1 / inv_depth, ex_pose[0]
+ *                 for the start frame and ex_pose[c] for the observing camera c;
+ *   lm_flags      bit 0: (err / cnt) * focal_length > outlier_threshold_px (the set outliersRejection hands to removeOutlier);
+ *                 bit 1: 1 / inv_depth < 0 (setDepth's solve_flag = 2, dropped by removeFailures);
+ *                 bit 2: at least one of the landmark's blocks is in Huber's linear region (|r|^2 > huber_delta^2).
+ * Per observation (obs_residuals rows follow the caller's obs rows, concatenated by window; a window without landmarks has none):
+ *   [0:2] the left camera's whitened residual (ProjectionTwoFrameOneCamFactor against the start frame), [2:4] the right camera's
+ *   (ProjectionTwoFrameTwoCamFactor, or ProjectionOneFrameTwoCamFactor on the start frame): the values Evaluate returns, before the loss.
+ *   A pair is NaN where no block exists: the left pair of the start frame, the right pair of a mono observation.
+ * Per interval (imu_residuals [W][10][31]): the factor's whitened residual; use_leg == 0: entries 15..30 are zero. Intervals without a factor
+ *   are zero; the intervals of a status-2 window whose record has no sqrt_info are NaN.
+ * Side effects: none on the batch's states, candidate, trust-region state, summaries or what a following solve computes (the guarantee of
+ * vilo_batch_covariance). Device memory is allocated at the first call and kept with the batch.
+ * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx, batch or windows, a threshold that is negative or not finite, n_windows < 1. */
+typedef struct {
+  double outlier_threshold_px;   /* 3.0: ave_err * FOCAL_LENGTH > 3 (estimator.cpp:1796) */
+} vilo_residual_opts;
+void vilo_default_residual_opts(vilo_residual_opts *o);
+
+typedef struct {
+  double cost;               /* prior_cost + sum(imu_cost) + visual_cost, in the units of vilo_solve_summary::final_cost */
+  double prior_cost;         /* 0 without a prior */
+  double imu_cost[10];       /* interval k (frames k -> k+1); 0 where the window has no factor (absent frame, sum_dt > 10 s) */
+  double visual_cost;        /* with the HuberLoss, as the solver counts it */
+  double visual_cost_plain;  /* the same residual blocks without the loss */
+  int32_t n_visual_blocks;   /* residual blocks of the three projection factors */
+  int32_t n_huber_active;    /* of which |r|^2 > huber_delta^2 (down-weighted) */
+  int32_t n_outliers;        /* landmarks with flag bit 0 */
+  int32_t n_negative_depth;  /* landmarks with flag bit 1 */
+  int32_t status;            /* 0 OK; 2 window invalid (a record without sqrt_info): its imu_cost entries for those intervals and cost are NaN */
+  int32_t pad;
+} vilo_window_residual;
+
+/* windows [W] is required; every other output may be NULL to leave it out:
+ *   lm_cost, lm_reproj_px [sum L] doubles, lm_flags [sum L] bytes, obs_residuals [sum n_obs][4], imu_residuals [W][10][31].
+ * opts NULL: vilo_default_residual_opts. */
+int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *batch, const vilo_residual_opts *opts, vilo_window_residual *windows, double *lm_cost,
+                         double *lm_reproj_px, uint8_t *lm_flags, double *obs_residuals, double *imu_residuals);
+/* The same for host windows at the given states: one batch is created, reported once and destroyed. */
+int vilo_window_residuals(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                          const vilo_residual_opts *opts, vilo_window_residual *windows, double *lm_cost, double *lm_reproj_px,
+                          uint8_t *lm_flags, double *obs_residuals, double *imu_residuals);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_residuals: its kernels (and, with samples in force, the re-integration),
+ * without the copies out. */
+double vilo_last_residuals_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
