@@ -14,6 +14,7 @@ MAX_PRIOR_DIM = 96
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
 c_uint8_p = C.POINTER(C.c_uint8)
+c_size_t_p = C.POINTER(C.c_size_t)
 
 
 class Config(C.Structure):

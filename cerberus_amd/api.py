@@ -209,6 +209,12 @@ class Batch:
         d["replay"], d["wave_order"] = bool(out[6]), int(out[7])
         return d
 
+    def device_bytes(self):
+        """vilo_debug_batch_device_bytes: (bytes of the arena chunks the batch holds, bytes handed out of them)."""
+        out = (C.c_size_t * 2)()
+        self.ctx._check(lib().vilo_debug_batch_device_bytes(self.handle, C.cast(out, T.c_size_t_p)))
+        return int(out[0]), int(out[1])
+
     def fetch(self, what, win=0, max_n=1 << 22):
         out = np.zeros(max_n)
         n = lib().vilo_debug_fetch(self.ctx.h, self.handle, what, win, _p(out), max_n)

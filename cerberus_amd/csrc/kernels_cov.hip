@@ -20,7 +20,7 @@
 //   5. Backward over the chain: G_k = (H_BB^-1 H_BP)_k, (H_BB^-1)_kk by the selected-inversion recursion
 //      X_kk = L_k^-T L_k^-1 + V_k^T X_{k+1,k+1} V_k (V_k = T_{k+1} L_k^-1), Sigma_BB,kk = X_kk + G_k Sigma_PP G_k^T,
 //      Sigma_PB,k = -Sigma_PP G_k^T; the frame's 19 x 19 block is scaled back and written.
-// Scratch in global memory per window (B blocks, BP / Y / G) lives in a buffer cached on the batch; windows go through it in chunks.
+// Scratch in global memory per window (B blocks, BP / Y / G) is per-call memory of the batch's arena; windows go through it in chunks.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -31,7 +31,6 @@
 
 int vilo_marg_linearize(vilo_ctx *ctx, BatchDev &b);   // kernels_solve.hip
 BatchDev *vilo_batch_dev(vilo_batch *bt);               // vilo_batch.hip
-int vilo_batch_cov_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p);   // vilo_batch.hip: grow-only, freed with the batch
 
 static_assert(sizeof(vilo_cov_opts) == 24, "vilo_cov_opts layout (cerberus_amd/_ctypes.py mirrors it)");
 
@@ -496,63 +495,6 @@ extern "C" void vilo_default_cov_opts(vilo_cov_opts *o) {
   o->want_poses = 0;
 }
 
-extern "C" int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, int32_t *status) {
-  if (!ctx || !bt || !frames || !status) return VILO_ERR_BAD_ARG;
-  vilo_cov_opts o;
-  if (opts) o = *opts; else vilo_default_cov_opts(&o);
-  if ((o.gauge != VILO_COV_GAUGE_FRAME0 && o.gauge != VILO_COV_GAUGE_NONE) || !(o.min_reciprocal_condition >= 0.0) || !isfinite(o.min_reciprocal_condition) ||
-      (o.want_poses && !poses)) {
-    ctx->err = "vilo_batch_covariance: bad options (gauge, min_reciprocal_condition >= 0, want_poses needs a poses buffer)";
-    return VILO_ERR_BAD_ARG;
-  }
-  const int want_poses = o.want_poses ? 1 : 0;
-  VILO_HIP(hipSetDevice(ctx->device));
-  BatchDev &bd = *vilo_batch_dev(bt);
-  const int W = bd.W, chunk = std::min(W, CV_CHUNK);
-  // one grow-only buffer per batch: saved solver state | frames | poses | status | per-window scratch of one chunk
-  const size_t o_st = 0, o_fr = (sizeof(SolverState) * (size_t)W + 255) & ~(size_t)255;
-  const size_t o_po = o_fr + sizeof(double) * (size_t)W * CV_FRN, o_stat = o_po + (want_poses ? sizeof(double) * (size_t)W * CV_PN : 0);
-  const size_t o_scr = (o_stat + sizeof(int) * (size_t)W + 255) & ~(size_t)255, total = o_scr + sizeof(double) * (size_t)chunk * CS_N;
-  void *buf = nullptr;
-  int rc = vilo_batch_cov_buffer(ctx, bt, total, &buf);
-  if (rc != VILO_OK) return rc;
-  char *base = (char *)buf;
-  const size_t lds_bytes = sizeof(double) * CL_N;
-  if (!ctx->cov_attr_set) {
-    VILO_HIP(hipFuncSetAttribute((const void *)k_covariance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    ctx->cov_attr_set = true;
-  }
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(base + o_st, bd.st, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
-  rc = vilo_marg_linearize(ctx, bd);
-  if (rc != VILO_OK) return rc;
-  for (int w0 = 0; w0 < W; w0 += chunk)
-    hipLaunchKernelGGL(k_covariance, dim3(std::min(chunk, W - w0)), dim3(CV_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, want_poses,
-                       (double *)(base + o_scr), (double *)(base + o_fr), (double *)(base + o_po), (int *)(base + o_stat));
-  VILO_HIP(hipGetLastError());
-  VILO_HIP(hipMemcpyAsync(bd.st, base + o_st, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_cov_ms = ms;
-  VILO_HIP(hipMemcpy(frames, base + o_fr, sizeof(double) * (size_t)W * CV_FRN, hipMemcpyDeviceToHost));
-  if (want_poses) VILO_HIP(hipMemcpy(poses, base + o_po, sizeof(double) * (size_t)W * CV_PN, hipMemcpyDeviceToHost));
-  VILO_HIP(hipMemcpy(status, base + o_stat, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost));
-  return VILO_OK;
-}
-
-extern "C" int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
-                                      double *frames, double *poses, int32_t *status) {
-  if (!ctx || n_windows <= 0 || !in || !state || !frames || !status) return VILO_ERR_BAD_ARG;
-  vilo_batch *bt = nullptr;
-  int rc = vilo_batch_create(ctx, n_windows, in, state, &bt);
-  if (rc != VILO_OK) return rc;
-  rc = vilo_batch_covariance(ctx, bt, opts, frames, poses, status);
-  vilo_batch_destroy(ctx, bt);
-  return rc;
-}
-
 extern "C" double vilo_last_covariance_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_cov_ms : -1.0; }
 
 // ---- landmark covariance (vilo_batch_landmark_covariance, include/vilo_gpu.h) ----
@@ -697,34 +639,34 @@ __global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0
   }
 }
 
+// vilo_batch_covariance and vilo_batch_landmark_covariance's arguments: false if the options are bad
+static bool cov_opts(const vilo_cov_opts *opts, vilo_cov_opts *o) {
+  if (opts) *o = *opts; else vilo_default_cov_opts(o);
+  return (o->gauge == VILO_COV_GAUGE_FRAME0 || o->gauge == VILO_COV_GAUGE_NONE) && o->min_reciprocal_condition >= 0.0 && isfinite(o->min_reciprocal_condition);
+}
+
 // k_covariance indexes frames / poses by the window's index in the batch: a buffer of one chunk is handed to it shifted back by w0 windows
 static double *cov_chunk_view(char *p, int w0, size_t per_window) { return (double *)((uintptr_t)p - (uintptr_t)w0 * per_window * sizeof(double)); }
 
-extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
-                                              double *points, double *point_cov, int32_t *status) {
-  if (!ctx || !bt || !status) return VILO_ERR_BAD_ARG;
-  vilo_cov_opts o;
-  if (opts) o = *opts; else vilo_default_cov_opts(&o);
-  BatchDev &bd = *vilo_batch_dev(bt);
-  const int W = bd.W, chunk = std::min(W, CV_CHUNK), n_lm = bd.n_lm;
-  if ((o.gauge != VILO_COV_GAUGE_FRAME0 && o.gauge != VILO_COV_GAUGE_NONE) || !(o.min_reciprocal_condition >= 0.0) || !isfinite(o.min_reciprocal_condition) ||
-      (n_lm > 0 && (!inv_depth_var || !points || !point_cov))) {
-    ctx->err = "vilo_batch_landmark_covariance: bad arguments (gauge, min_reciprocal_condition >= 0, landmark output buffers)";
-    return VILO_ERR_BAD_ARG;
-  }
+// The body of vilo_batch_covariance and vilo_batch_landmark_covariance, arguments checked. want_poses: what k_covariance is told;
+// frames / poses: the caller's outputs, or null to keep them in a buffer of one chunk (poses: only where want_poses); lm: the landmark
+// outputs (inverse-depth variance, point, point covariance) of k_landmark_covariance after each chunk, or null for no landmark pass.
+static int batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts &o, int want_poses, double *frames, double *poses, double *const *lm,
+                            int32_t *status) {
   VILO_HIP(hipSetDevice(ctx->device));
-  // one grow-only buffer per batch: saved solver state | frames | poses (the whole batch where the caller takes them, else one chunk) |
-  // status | per-window scratch of one chunk | landmark outputs (variance, point, point covariance)
-  const size_t n_fr = frames ? (size_t)W : (size_t)chunk, n_po = poses ? (size_t)W : (size_t)chunk;
+  BatchDev &bd = *vilo_batch_dev(bt);
+  const int W = bd.W, chunk = std::min(W, CV_CHUNK), n_lm = lm ? bd.n_lm : 0;
+  // the call's device memory, returned when it returns: saved solver state | frames | poses | status | per-window scratch of one chunk |
+  // landmark outputs (variance, point, point covariance)
+  const size_t n_fr = frames ? (size_t)W : (size_t)chunk, n_po = !want_poses ? 0 : poses ? (size_t)W : (size_t)chunk;
   const size_t o_fr = (sizeof(SolverState) * (size_t)W + 255) & ~(size_t)255;
   const size_t o_po = o_fr + sizeof(double) * n_fr * CV_FRN, o_stat = o_po + sizeof(double) * n_po * CV_PN;
   const size_t o_scr = (o_stat + sizeof(int) * (size_t)W + 255) & ~(size_t)255, o_lm = o_scr + sizeof(double) * (size_t)chunk * CS_N;
-  const size_t total = o_lm + sizeof(double) * 13 * (size_t)n_lm;
-  void *buf = nullptr;
-  int rc = vilo_batch_cov_buffer(ctx, bt, total, &buf);
-  if (rc != VILO_OK) return rc;
-  char *base = (char *)buf;
+  ArenaScope scope(ctx, bt);
+  char *base = (char *)scope.alloc(o_lm + sizeof(double) * 13 * (size_t)n_lm);
+  if (!base) return VILO_ERR_HIP;
   double *d_var = (double *)(base + o_lm), *d_pts = d_var + n_lm, *d_pcov = d_pts + 3 * (size_t)n_lm;
+  int *d_stat = (int *)(base + o_stat);
   const size_t lds_bytes = sizeof(double) * CL_N;
   if (!ctx->cov_attr_set) {
     VILO_HIP(hipFuncSetAttribute((const void *)k_covariance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -732,16 +674,17 @@ extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, con
   }
   VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   VILO_HIP(hipMemcpyAsync(base, bd.st, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
-  rc = vilo_marg_linearize(ctx, bd);
+  int rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
   for (int w0 = 0; w0 < W; w0 += chunk) {
     const int n = std::min(chunk, W - w0);
     double *fr = frames ? (double *)(base + o_fr) : cov_chunk_view(base + o_fr, w0, CV_FRN);
-    double *po = poses ? (double *)(base + o_po) : cov_chunk_view(base + o_po, w0, CV_PN);
-    hipLaunchKernelGGL(k_covariance, dim3(n), dim3(CV_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, 1,
-                       (double *)(base + o_scr), fr, po, (int *)(base + o_stat));
-    hipLaunchKernelGGL(k_landmark_covariance, dim3(n), dim3(LC_T), sizeof(double) * LC_N, ctx->stream, bd, w0, po + (size_t)w0 * CV_PN,
-                       (const int *)(base + o_stat), d_var, d_pts, d_pcov);
+    double *po = poses ? (double *)(base + o_po) : want_poses ? cov_chunk_view(base + o_po, w0, CV_PN) : nullptr;
+    hipLaunchKernelGGL(k_covariance, dim3(n), dim3(CV_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, want_poses,
+                       (double *)(base + o_scr), fr, po, d_stat);
+    if (lm)
+      hipLaunchKernelGGL(k_landmark_covariance, dim3(n), dim3(LC_T), sizeof(double) * LC_N, ctx->stream, bd, w0, po + (size_t)w0 * CV_PN,
+                         d_stat, d_var, d_pts, d_pcov);
   }
   VILO_HIP(hipGetLastError());
   VILO_HIP(hipMemcpyAsync(bd.st, base, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
@@ -752,23 +695,48 @@ extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, con
   ctx->last_cov_ms = ms;
   if (frames) VILO_HIP(hipMemcpy(frames, base + o_fr, sizeof(double) * (size_t)W * CV_FRN, hipMemcpyDeviceToHost));
   if (poses) VILO_HIP(hipMemcpy(poses, base + o_po, sizeof(double) * (size_t)W * CV_PN, hipMemcpyDeviceToHost));
-  VILO_HIP(hipMemcpy(status, base + o_stat, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost));
+  VILO_HIP(hipMemcpy(status, d_stat, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost));
   if (n_lm > 0) {
-    VILO_HIP(hipMemcpy(inv_depth_var, d_var, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-    VILO_HIP(hipMemcpy(points, d_pts, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost));
-    VILO_HIP(hipMemcpy(point_cov, d_pcov, sizeof(double) * 9 * (size_t)n_lm, hipMemcpyDeviceToHost));
+    VILO_HIP(hipMemcpy(lm[0], d_var, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
+    VILO_HIP(hipMemcpy(lm[1], d_pts, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost));
+    VILO_HIP(hipMemcpy(lm[2], d_pcov, sizeof(double) * 9 * (size_t)n_lm, hipMemcpyDeviceToHost));
   }
   return VILO_OK;
+}
+
+extern "C" int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, int32_t *status) {
+  if (!ctx || !bt || !frames || !status) return VILO_ERR_BAD_ARG;
+  vilo_cov_opts o;
+  if (!cov_opts(opts, &o) || (o.want_poses && !poses)) {
+    ctx->err = "vilo_batch_covariance: bad options (gauge, min_reciprocal_condition >= 0, want_poses needs a poses buffer)";
+    return VILO_ERR_BAD_ARG;
+  }
+  return batch_covariance(ctx, bt, o, o.want_poses ? 1 : 0, frames, o.want_poses ? poses : nullptr, nullptr, status);
+}
+
+extern "C" int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
+                                      double *frames, double *poses, int32_t *status) {
+  if (!ctx || n_windows <= 0 || !in || !state || !frames || !status) return VILO_ERR_BAD_ARG;
+  return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) { return vilo_batch_covariance(ctx, bt, opts, frames, poses, status); });
+}
+
+extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
+                                              double *points, double *point_cov, int32_t *status) {
+  if (!ctx || !bt || !status) return VILO_ERR_BAD_ARG;
+  vilo_cov_opts o;
+  if (!cov_opts(opts, &o) || (vilo_batch_dev(bt)->n_lm > 0 && (!inv_depth_var || !points || !point_cov))) {
+    ctx->err = "vilo_batch_landmark_covariance: bad arguments (gauge, min_reciprocal_condition >= 0, landmark output buffers)";
+    return VILO_ERR_BAD_ARG;
+  }
+  double *const lm[3] = {inv_depth_var, points, point_cov};
+  return batch_covariance(ctx, bt, o, 1, frames, poses, lm, status);
 }
 
 extern "C" int vilo_window_landmark_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
                                                const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var, double *points,
                                                double *point_cov, int32_t *status) {
   if (!ctx || n_windows <= 0 || !in || !state || !status) return VILO_ERR_BAD_ARG;
-  vilo_batch *bt = nullptr;
-  int rc = vilo_batch_create(ctx, n_windows, in, state, &bt);
-  if (rc != VILO_OK) return rc;
-  rc = vilo_batch_landmark_covariance(ctx, bt, opts, frames, poses, inv_depth_var, points, point_cov, status);
-  vilo_batch_destroy(ctx, bt);
-  return rc;
+  return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) {
+    return vilo_batch_landmark_covariance(ctx, bt, opts, frames, poses, inv_depth_var, points, point_cov, status);
+  });
 }

@@ -1033,14 +1033,6 @@ extern "C" int vilo_gauge_fix(vilo_ctx *ctx, int W, const vilo_window_state *bef
 struct vilo_batch;
 BatchDev *vilo_batch_dev(vilo_batch *bt);
 const int *vilo_batch_perm(vilo_batch *bt, int win, int *L);
-int vilo_batch_scratch(vilo_ctx *ctx, vilo_batch *bt, void **p, size_t bytes);   // vilo_batch.hip: arena scratch, freed with the batch
-struct View { void *p; template <class T> T *as() { return (T *)p; } };   // a typed look at part of a buffer
-// per-call buffers out of the batch's arena (they go back to the context's pool with the batch)
-struct ArenaBuf {
-  vilo_ctx *c; vilo_batch *b; void *p = nullptr;
-  hipError_t alloc(size_t n) { return vilo_batch_scratch(c, b, &p, n) == VILO_OK ? hipSuccess : hipErrorOutOfMemory; }
-  template <class T> T *as() { return (T *)p; }
-};
 
 // Marginalisation of every window of an existing batch at its current device state (b.x, b.lam). `state` holds the same
 // values on the host (they become keep_block_data of the new prior); modes[w]: 0 MARGIN_OLD, 1 MARGIN_SECOND_NEW, < 0 skip
@@ -1054,7 +1046,6 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   int max_l0 = 1;
   std::vector<std::vector<int>> drops(W);
   std::vector<char> keep_prior(W, 0), skip(W, 0);
-  size_t scratch_total = 0;
   for (int w = 0; w < W; ++w) {
     const vilo_window_desc &d = in[w];
     MargWin &M = mws[w];
@@ -1142,35 +1133,36 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   std::vector<int> drop_flat((size_t)W * max_l0, 0);
   for (int w = 0; w < W; ++w)
     for (size_t i = 0; i < drops[w].size(); ++i) drop_flat[(size_t)w * max_l0 + i] = drops[w][i];
-  // One arena block for what goes up (window tables, dropped-landmark lists) and the flags that come back (status, need_general, "the
-  // IMU factor of interval 0 stands on a covariance without sqrt_info"): one upload, one download per call — a one-window call per image
-  // used to spend more time in its dozen synchronous copies and allocations than in its kernels.
-  ArenaBuf d_blob{ctx, bt}, d_J0{ctx, bt}, d_r0{ctx, bt}, d_clk{ctx, bt};
-  DevBuf d_scr;
+  // Every device buffer of the call comes from one arena scope: given back when the call returns. One block for what goes up (window
+  // tables, dropped-landmark lists, prior-pool slots) and the flags that come back (status, need_general, "the IMU factor of interval 0
+  // stands on a covariance without sqrt_info"): one upload, one download per call — a one-window call per image used to spend more time
+  // in its dozen synchronous copies and allocations than in its kernels.
+  ArenaScope scope(ctx, bt);
   const bool want_clk = getenv("VILO_MARG_CLOCKS") != nullptr;
-  if (want_clk && d_clk.alloc(sizeof(long long) * 8 * W) != hipSuccess) { return VILO_ERR_HIP; }
-  auto fail = [&](int code) { return code; };
   const size_t off_drop = (sizeof(MargWin) * (size_t)W + 15) & ~(size_t)15, off_flags = (off_drop + sizeof(int) * drop_flat.size() + 15) & ~(size_t)15;
-  const size_t blob_bytes = off_flags + sizeof(int) * 3 * (size_t)W;
-  // (the context's reusable page-locked staging: it outlives the asynchronous copy on every return path)
+  const size_t off_slots = off_flags + sizeof(int) * 3 * (size_t)W, blob_bytes = off_slots + sizeof(int) * 2 * (size_t)W;
+  // (the context's reusable page-locked staging: the scope's closing sync outlives the asynchronous copies on every return path)
   char *hblob = (char *)vilo_host_stage(ctx, 6, blob_bytes);
-  if (!hblob) return fail(VILO_ERR_HIP);
+  if (!hblob) return VILO_ERR_HIP;
   memset(hblob, 0, blob_bytes);
   memcpy(hblob, mws.data(), sizeof(MargWin) * (size_t)W);
   if (!drop_flat.empty()) memcpy(hblob + off_drop, drop_flat.data(), sizeof(int) * drop_flat.size());
-  if (d_blob.alloc(blob_bytes) != hipSuccess || d_J0.alloc(sizeof(double) * (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM) != hipSuccess ||
-      d_r0.alloc(sizeof(double) * (size_t)W * VILO_MAX_PRIOR_DIM) != hipSuccess)
-    return fail(VILO_ERR_HIP);
-  View d_mw{d_blob.p}, d_drop{(char *)d_blob.p + off_drop}, d_status{(char *)d_blob.p + off_flags}, d_general{(char *)d_blob.p + off_flags + sizeof(int) * (size_t)W},
-      d_pbad{(char *)d_blob.p + off_flags + 2 * sizeof(int) * (size_t)W};
-  if (hipMemcpyAsync(d_blob.p, hblob, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(VILO_ERR_HIP);
+  char *d_blob = (char *)scope.alloc(blob_bytes);
+  double *d_J0 = (double *)scope.alloc(sizeof(double) * (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM);
+  double *d_r0 = (double *)scope.alloc(sizeof(double) * (size_t)W * VILO_MAX_PRIOR_DIM);
+  long long *d_clk = want_clk ? (long long *)scope.alloc(sizeof(long long) * 8 * W) : nullptr;
+  if (!d_blob || !d_J0 || !d_r0 || (want_clk && !d_clk)) return VILO_ERR_HIP;
+  MargWin *d_mw = (MargWin *)d_blob;
+  int *d_drop = (int *)(d_blob + off_drop), *d_status = (int *)(d_blob + off_flags), *d_general = d_status + W, *d_pbad = d_status + 2 * (size_t)W;
+  int *d_slots = (int *)(d_blob + off_slots);   // [2][W] prior-pool slots: destination, source
+  if (hipMemcpyAsync(d_blob, hblob, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
   // preMarginalize: evaluate the factors at the current state (marginalization_factor.cpp:119-138)
   (void)hipEventRecord(ctx->ev0, ctx->stream);
   rc = vilo_marg_linearize(ctx, bd);
-  if (rc != VILO_OK) return fail(rc);
+  if (rc != VILO_OK) return rc;
   const size_t lds_bytes = (size_t)MG_LDS_DOUBLES * sizeof(double);
   if (!ctx->marg_attr_set) {   // (per context = per device and host thread)
-    if (hipFuncSetAttribute((const void *)k_marginalize_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return fail(VILO_ERR_HIP);
+    if (hipFuncSetAttribute((const void *)k_marginalize_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return VILO_ERR_HIP;
     ctx->marg_attr_set = true;
   }
   const bool force_general = getenv("VILO_MARG_GENERAL") != nullptr;   // test hook: every window through the global-memory eigen path
@@ -1178,15 +1170,15 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   bool have_flags = false;
   if (!force_general) {
     have_flags = true;
-    hipLaunchKernelGGL(k_marginalize_lds, dim3(W), dim3(MGT), lds_bytes, ctx->stream, bd, d_mw.as<MargWin>(), d_drop.as<int>(), max_l0, d_J0.as<double>(),
-                       d_r0.as<double>(), d_status.as<int>(), d_general.as<int>(), want_clk ? d_clk.as<long long>() : nullptr, ctx->prior_form);
-    if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, d_pbad.as<int>());
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize_lds launch failed"; return fail(VILO_ERR_HIP); }
-    if (hipMemcpy(flags.data(), d_status.p, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return fail(VILO_ERR_HIP);
+    hipLaunchKernelGGL(k_marginalize_lds, dim3(W), dim3(MGT), lds_bytes, ctx->stream, bd, d_mw, d_drop, max_l0, d_J0, d_r0, d_status, d_general, d_clk,
+                       ctx->prior_form);
+    if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, d_pbad);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize_lds launch failed"; return VILO_ERR_HIP; }
+    if (hipMemcpy(flags.data(), d_status, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return VILO_ERR_HIP;
     for (int w = 0; w < W; ++w) general[w] = flags[(size_t)W + w];
     if (want_clk) {
       long long c[8];
-      if (hipMemcpy(c, d_clk.p, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess)
+      if (hipMemcpy(c, d_clk, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess)
         fprintf(stderr, "[k_marginalize_lds] window 0 cycles: assemble %lld, landmarks %lld, cholesky %lld, schur %lld, pivoted cholesky %lld, jacobi %lld, output %lld\n", c[1] - c[0],
                 c[2] - c[1], c[3] - c[2], c[4] - c[3], c[7] - c[4], c[5] - c[7], c[6] - c[5]);
     }
@@ -1196,7 +1188,7 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
     if (general[w] && mws[w].m > 0 && mws[w].n > 0) { mws[w].general = 1; ++ctx->marg_general_count; }
   if (ctx->marg_general_count > 0) {
     // rank-deficient Amm (or an over-sized problem): thresholded eigen pseudo-inverse of the full Amm in global memory
-    scratch_total = 0;
+    size_t scratch_total = 0;
     for (int w = 0; w < W; ++w) {
       MargWin &M = mws[w];
       if (!M.general) continue;
@@ -1204,26 +1196,27 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
       const size_t T = (size_t)M.m + M.n;
       scratch_total += T * T + T + 3 * (size_t)M.m * M.m + (size_t)M.n * M.m + 3 * (size_t)M.n * M.n + 2 * M.n + 64;
     }
-    if (d_scr.alloc(sizeof(double) * std::max<size_t>(1, scratch_total)) != hipSuccess ||
-        hipMemcpy(d_mw.p, mws.data(), sizeof(MargWin) * W, hipMemcpyHostToDevice) != hipSuccess)
-      return fail(VILO_ERR_HIP);
+    // the updated window tables go up in stream order behind the first copy, from the same staging updated in place (with the forced
+    // path that copy may still be reading it: whatever it reads, this one lands last)
+    memcpy(hblob, mws.data(), sizeof(MargWin) * (size_t)W);
+    double *d_scr = (double *)scope.alloc(sizeof(double) * std::max<size_t>(1, scratch_total));
+    if (!d_scr || hipMemcpyAsync(d_mw, hblob, sizeof(MargWin) * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
     have_flags = false;   // (this kernel writes status too: read again below)
-    hipLaunchKernelGGL(k_marginalize, dim3(W), dim3(MT), 0, ctx->stream, bd, d_mw.as<MargWin>(), d_drop.as<int>(), max_l0, d_scr.as<double>(),
-                       d_J0.as<double>(), d_r0.as<double>(), d_status.as<int>());
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize launch failed"; return fail(VILO_ERR_HIP); }
+    hipLaunchKernelGGL(k_marginalize, dim3(W), dim3(MT), 0, ctx->stream, bd, d_mw, d_drop, max_l0, d_scr, d_J0, d_r0, d_status);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize launch failed"; return VILO_ERR_HIP; }
   }
   float marg_ms = 0.f;
   if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess || hipEventSynchronize(ctx->ev1) != hipSuccess ||
       hipEventElapsedTime(&marg_ms, ctx->ev0, ctx->ev1) != hipSuccess)
-    return fail(VILO_ERR_HIP);
+    return VILO_ERR_HIP;
   ctx->last_marg_ms = marg_ms;
   // Status first: a window whose result is unusable must not overwrite a pool slot either.
   std::vector<int> status(W, 0);
   int any_bad = 0;
   if (!have_flags) {
-    if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, d_pbad.as<int>());
+    if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, d_pbad);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(flags.data(), d_status.p, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return fail(VILO_ERR_HIP);
+        hipMemcpy(flags.data(), d_status, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return VILO_ERR_HIP;
   }
   for (int w = 0; w < W; ++w) status[w] = flags[w];
   // A preintegration covariance that is not positive definite has no sqrt_info (its bad pivots were replaced by 1 so that the arithmetic
@@ -1252,13 +1245,12 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
     }
   }
   if (refs && refs[0].prior_pool) {
-    ArenaBuf d_dst{ctx, bt}, d_src{ctx, bt};
-    if (d_dst.alloc(sizeof(int) * W) != hipSuccess || d_src.alloc(sizeof(int) * W) != hipSuccess ||
-        hipMemcpy(d_dst.p, dst_slot.data(), sizeof(int) * W, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_src.p, src_slot.data(), sizeof(int) * W, hipMemcpyHostToDevice) != hipSuccess)
-      return VILO_ERR_HIP;
-    hipLaunchKernelGGL(k_prior_scatter, dim3(W), dim3(256), 0, ctx->stream, W, d_mw.as<MargWin>(), d_dst.as<int>(), d_src.as<int>(), d_J0.as<double>(), d_r0.as<double>(),
-                       refs[0].prior_pool->dJ, refs[0].prior_pool->dr);
+    int *h_slots = (int *)(hblob + off_slots);   // (the stream has drained: no copy reads the staging any more)
+    memcpy(h_slots, dst_slot.data(), sizeof(int) * W);
+    memcpy(h_slots + W, src_slot.data(), sizeof(int) * W);
+    if (hipMemcpyAsync(d_slots, h_slots, sizeof(int) * 2 * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+    hipLaunchKernelGGL(k_prior_scatter, dim3(W), dim3(256), 0, ctx->stream, W, d_mw, d_slots, d_slots + W, d_J0, d_r0, refs[0].prior_pool->dJ,
+                       refs[0].prior_pool->dr);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return VILO_ERR_HIP;
   }
   // priors that go back to host memory: through the context's reusable page-locked staging (a fresh pageable vector of W x 74 KB was
@@ -1267,10 +1259,10 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   if (any_host) {
     const size_t nJ = (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM, nr = (size_t)W * VILO_MAX_PRIOR_DIM;
     double *hJ = (double *)vilo_host_stage(ctx, 7, sizeof(double) * (nJ + nr));
-    if (!hJ) return fail(VILO_ERR_HIP);
-    if (hipMemcpyAsync(hJ, d_J0.p, nJ * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(hJ + nJ, d_r0.p, nr * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-      return fail(VILO_ERR_HIP);
+    if (!hJ) return VILO_ERR_HIP;
+    if (hipMemcpyAsync(hJ, d_J0, nJ * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(hJ + nJ, d_r0, nr * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+      return VILO_ERR_HIP;
     J0 = hJ; r0 = hJ + nJ;
   }
   for (int w = 0; w < W; ++w) {
@@ -1325,13 +1317,8 @@ extern "C" int vilo_marginalize(vilo_ctx *ctx, int W, const vilo_window_desc *in
                                 vilo_prior *out) {
   if (!ctx || W <= 0 || !in || !state || !out || (mode != 0 && mode != 1)) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
-  vilo_batch *bt = nullptr;
-  int rc = vilo_batch_create(ctx, W, in, state, &bt);
-  if (rc != VILO_OK) return rc;
   std::vector<int> modes(W, mode);
-  rc = marginalize_batch(ctx, bt, W, in, nullptr, state, modes.data(), out);
-  vilo_batch_destroy(ctx, bt);
-  return rc;
+  return vilo_with_batch(ctx, W, in, state, [&](vilo_batch *bt) { return marginalize_batch(ctx, bt, W, in, nullptr, state, modes.data(), out); });
 }
 
 // The marginalisation half on a batch that is already resident (after vilo_batch_solve + vilo_batch_download): linearised at the batch's

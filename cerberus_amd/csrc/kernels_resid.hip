@@ -13,24 +13,18 @@
 //                      then the landmark sums in caller order (a fixed per-thread stride and tree) and the window record.
 // With vilo_batch_set_samples in force the records are first integrated again at x by the marginalisation's pass (k_repropagate mode 0 +
 // the preparation), on copies: the call hands those kernels a BatchDev whose records, prepared records, flags and contact-force filters
-// point into its own buffer, so the batch's are never written.
+// point into the call's own memory, so the batch's are never written.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 
 #include "accept_body.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
 
 BatchDev *vilo_batch_dev(vilo_batch *bt);   // vilo_batch.hip
-int vilo_batch_resid_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p, const int **obs_row, int *n_obs_rows);   // vilo_batch.hip
-
-// GPU time of each context's last call (vilo_last_residuals_ms)
-static std::mutex g_resid_ms_mu;
-static std::unordered_map<const vilo_ctx *, double> g_resid_ms;
+int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows);   // vilo_batch.hip
 
 static_assert(sizeof(vilo_window_residual) == 136, "vilo_window_residual: 136 bytes (include/vilo_gpu.h)");
 static_assert(sizeof(vilo_residual_opts) == 8, "vilo_residual_opts: 8 bytes (include/vilo_gpu.h)");
@@ -270,27 +264,23 @@ extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_re
   const BatchDev &bd = *vilo_batch_dev(bt);
   const int W = bd.W, n_lm = bd.n_lm, NF = W * 10;
   const bool rp = bd.rp_on && bd.rp_samples && bd.leg;
-  // buffer (grow-only, kept with the batch): window records | per-landmark values | interval costs | interval residuals | observation
-  // residuals | re-integration copies (records, prepared records, flags, contact-force filters)
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const int *obs_row = nullptr;
   int n_rows = 0;
+  const int rc = vilo_batch_obs_rows(ctx, bt, &obs_row, &n_rows);   // (batch data, uploaded at the first call: before the scope opens)
+  if (rc != VILO_OK) return rc;
+  // the call's device memory, returned when it returns: window records | per-landmark values | interval costs | interval residuals |
+  // observation residuals | re-integration copies (records, prepared records, flags, contact-force filters)
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   size_t at = 0;
   const size_t o_win = at; at = al(at + sizeof(vilo_window_residual) * (size_t)W);
   const size_t o_lm = at; at = al(at + (3 * sizeof(double) + 2 * sizeof(int) + 1) * (size_t)n_lm);
   const size_t o_ic = at; at = al(at + sizeof(double) * (size_t)NF);
   const size_t o_ir = at; if (imu_residuals) at = al(at + sizeof(double) * 31 * (size_t)NF);
-  const size_t o_or = at;
-  // (the row count is the batch's: asked for below, after the buffer call, so the buffer is sized by an upper bound first)
-  void *buf = nullptr;
-  int rc = vilo_batch_resid_buffer(ctx, bt, 0, &buf, &obs_row, &n_rows);
-  if (rc != VILO_OK) return rc;
-  if (obs_residuals) at = al(at + sizeof(double) * 4 * (size_t)n_rows);
-  const size_t o_rp = at;
-  if (rp) at = al(at + (sizeof(vilo_preint) + sizeof(PreintPrepared) + sizeof(int) + sizeof(double) * VILO_FF_N) * (size_t)NF);
-  rc = vilo_batch_resid_buffer(ctx, bt, at, &buf, &obs_row, &n_rows);
-  if (rc != VILO_OK) return rc;
-  char *base = (char *)buf;
+  const size_t o_or = at; if (obs_residuals) at = al(at + sizeof(double) * 4 * (size_t)n_rows);
+  const size_t o_rp = at; if (rp) at = al(at + (sizeof(vilo_preint) + sizeof(PreintPrepared) + sizeof(int) + sizeof(double) * VILO_FF_N) * (size_t)NF);
+  ArenaScope scope(ctx, bt);
+  char *base = (char *)scope.alloc(at);
+  if (!base) return VILO_ERR_HIP;
   ResidLm lm;
   lm.cost = (double *)(base + o_lm); lm.reproj = lm.cost + n_lm; lm.plain = lm.reproj + n_lm;
   lm.nb = (int *)(lm.plain + n_lm); lm.nh = lm.nb + n_lm; lm.flags = (unsigned char *)(lm.nh + n_lm);
@@ -319,10 +309,7 @@ extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_re
   VILO_HIP(hipEventSynchronize(ctx->ev1));
   float ms = 0.f;
   VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  {
-    std::lock_guard<std::mutex> lk(g_resid_ms_mu);
-    g_resid_ms[ctx] = ms;
-  }
+  ctx->last_resid_ms = ms;
   VILO_HIP(hipMemcpy(windows, base + o_win, sizeof(vilo_window_residual) * (size_t)W, hipMemcpyDeviceToHost));
   if (n_lm > 0) {
     if (lm_cost) VILO_HIP(hipMemcpy(lm_cost, lm.cost, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
@@ -339,17 +326,9 @@ extern "C" int vilo_window_residuals(vilo_ctx *ctx, int n_windows, const vilo_wi
                                      uint8_t *lm_flags, double *obs_residuals, double *imu_residuals) {
   if (!ctx || n_windows < 1 || !in || !state || !windows) return VILO_ERR_BAD_ARG;
   if (opts && (!isfinite(opts->outlier_threshold_px) || !(opts->outlier_threshold_px >= 0.0))) return VILO_ERR_BAD_ARG;
-  vilo_batch *bt = nullptr;
-  int rc = vilo_batch_create(ctx, n_windows, in, state, &bt);
-  if (rc != VILO_OK) return rc;
-  rc = vilo_batch_residuals(ctx, bt, opts, windows, lm_cost, lm_reproj_px, lm_flags, obs_residuals, imu_residuals);
-  vilo_batch_destroy(ctx, bt);
-  return rc;
+  return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) {
+    return vilo_batch_residuals(ctx, bt, opts, windows, lm_cost, lm_reproj_px, lm_flags, obs_residuals, imu_residuals);
+  });
 }
 
-extern "C" double vilo_last_residuals_ms(const vilo_ctx *ctx) {
-  if (!ctx) return -1.0;
-  std::lock_guard<std::mutex> lk(g_resid_ms_mu);
-  const auto it = g_resid_ms.find(ctx);
-  return it == g_resid_ms.end() ? 0.0 : it->second;
-}
+extern "C" double vilo_last_residuals_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_resid_ms : -1.0; }

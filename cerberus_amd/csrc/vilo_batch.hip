@@ -21,6 +21,7 @@ struct vilo_batch {
   std::vector<std::pair<void *, size_t>> chunks_dev;   // arena chunks (from / back to ctx->pool_free)
   char *cur = nullptr;
   size_t cur_left = 0;
+  size_t used = 0;                  // bytes handed out of the chunks (vilo_debug_batch_device_bytes)
   std::vector<int> lm_off_host;     // per window
   std::vector<int> perm_host;       // device order -> original landmark index (per window, concatenated)
   std::vector<int> L_host;
@@ -45,15 +46,10 @@ struct vilo_batch {
   void *d_pre = nullptr;
   bool leg = true;
   int *d_prep_bad = nullptr;   // [W * 10] covariance of this record not positive definite
-  // vilo_batch_covariance's device buffer (kernels_cov.hip): its own allocation, grown only when a call needs more, freed with the batch
-  void *cov_buf = nullptr;
-  size_t cov_bytes = 0;
   // vilo_batch_residuals (kernels_resid.hip): the caller's observation row of each landmark's first observation (device order, rows
-  // concatenated by window: a window without landmarks has none), uploaded with the call's own grow-only buffer at its first call
+  // concatenated by window: a window without landmarks has none), uploaded into the arena at the first call
   std::vector<int> obs_row_host;
   int n_obs_rows = 0;
-  void *res_buf = nullptr;
-  size_t res_bytes = 0;
   int *d_obs_row = nullptr;
 };
 
@@ -124,7 +120,7 @@ int dev_alloc_bytes(vilo_ctx *ctx, vilo_batch *bt, void **p, size_t bytes) {
     bt->cur = (char *)ch.first; bt->cur_left = ch.second;
   }
   *p = bt->cur;
-  bt->cur += bytes; bt->cur_left -= bytes;
+  bt->cur += bytes; bt->cur_left -= bytes; bt->used += bytes;
   return VILO_OK;
 }
 template <class T>
@@ -251,42 +247,41 @@ int prior_block_cd(int id, int *state_off) {
 }  // namespace
 
 BatchDev *vilo_batch_dev(vilo_batch *bt) { return &bt->d; }
-// scratch that lives as long as the batch, out of its arena (other translation units: the marginalisation's per-call buffers — a
-// hipMalloc / hipFree pair per buffer costs more than the kernels of a one-window call)
-int vilo_batch_scratch(vilo_ctx *ctx, vilo_batch *bt, void **p, size_t bytes) { return dev_alloc_bytes(ctx, bt, p, bytes); }
 const int *vilo_batch_perm(vilo_batch *bt, int win, int *L) {
   *L = bt->L_host[win];
   return bt->perm_host.data() + bt->lm_off_host[win];
 }
 
-int vilo_batch_cov_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p) {
-  if (bt->cov_bytes < bytes) {
-    VILO_HIP(hipStreamSynchronize(ctx->stream));
-    if (bt->cov_buf) VILO_HIP(hipFree(bt->cov_buf));
-    bt->cov_buf = nullptr; bt->cov_bytes = 0;
-    VILO_HIP(hipMalloc(&bt->cov_buf, bytes));
-    bt->cov_bytes = bytes;
+ArenaScope::ArenaScope(vilo_ctx *c, vilo_batch *b) : ctx(c), bt(b), n_chunks(b->chunks_dev.size()), cur_left(b->cur_left), used(b->used), cur(b->cur) {}
+ArenaScope::~ArenaScope() {
+  (void)hipStreamSynchronize(ctx->stream);   // nothing of this call may still run when its memory is handed on
+  for (size_t i = n_chunks; i < bt->chunks_dev.size(); ++i) ctx->pool_free.push_back(bt->chunks_dev[i]);
+  bt->chunks_dev.resize(n_chunks);
+  bt->cur = cur; bt->cur_left = cur_left; bt->used = used;
+}
+void *ArenaScope::alloc(size_t bytes) {
+  void *p = nullptr;
+  return dev_alloc_bytes(ctx, bt, &p, bytes) == VILO_OK ? p : nullptr;
+}
+
+// vilo_batch_residuals: the landmarks' observation rows on the device (batch data, uploaded at the first call: not in a call's scope)
+int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows) {
+  if (!bt->d_obs_row) {
+    int *d = nullptr;
+    int rc = dev_upload(ctx, bt, &d, bt->obs_row_host);
+    if (rc != VILO_OK) return rc;
+    bt->d_obs_row = d;
   }
-  *p = bt->cov_buf;
+  *rows = bt->d_obs_row;
+  *n_rows = bt->n_obs_rows;
   return VILO_OK;
 }
 
-// vilo_batch_residuals' buffer: grow-only like the covariance's; the landmarks' observation rows are uploaded with its first allocation
-int vilo_batch_resid_buffer(vilo_ctx *ctx, vilo_batch *bt, size_t bytes, void **p, const int **obs_row, int *n_obs_rows) {
-  const size_t row_bytes = (sizeof(int) * std::max<size_t>(1, bt->obs_row_host.size()) + 255) & ~(size_t)255;
-  if (bt->res_bytes < row_bytes + bytes) {
-    VILO_HIP(hipStreamSynchronize(ctx->stream));
-    if (bt->res_buf) VILO_HIP(hipFree(bt->res_buf));
-    bt->res_buf = nullptr; bt->res_bytes = 0;
-    VILO_HIP(hipMalloc(&bt->res_buf, row_bytes + bytes));
-    bt->res_bytes = row_bytes + bytes;
-    bt->d_obs_row = (int *)bt->res_buf;
-    if (!bt->obs_row_host.empty())
-      VILO_HIP(hipMemcpy(bt->d_obs_row, bt->obs_row_host.data(), sizeof(int) * bt->obs_row_host.size(), hipMemcpyHostToDevice));
-  }
-  *p = (char *)bt->res_buf + row_bytes;
-  *obs_row = bt->d_obs_row;
-  *n_obs_rows = bt->n_obs_rows;
+extern "C" int vilo_debug_batch_device_bytes(const vilo_batch *bt, size_t out[2]) {
+  if (!bt || !out) return VILO_ERR_BAD_ARG;
+  out[0] = 0;
+  for (const auto &c : bt->chunks_dev) out[0] += c.second;
+  out[1] = bt->used;
   return VILO_OK;
 }
 
@@ -294,8 +289,6 @@ extern "C" void vilo_batch_destroy(vilo_ctx *ctx, vilo_batch *bt) {
   if (!bt) return;
   if (ctx) (void)hipSetDevice(ctx->device);
   if (bt->gexec) (void)hipGraphExecDestroy(bt->gexec);
-  if (bt->cov_buf) { if (ctx) (void)hipStreamSynchronize(ctx->stream); (void)hipFree(bt->cov_buf); }
-  if (bt->res_buf) { if (ctx) (void)hipStreamSynchronize(ctx->stream); (void)hipFree(bt->res_buf); }
   if (ctx) {
     (void)hipStreamSynchronize(ctx->stream);   // nothing of this batch may still be running when its memory is handed on
     for (auto &c : bt->chunks_dev) ctx->pool_free.push_back(c);

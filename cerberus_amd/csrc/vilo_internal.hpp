@@ -27,8 +27,8 @@ struct vilo_ctx {
   hipStream_t stream;
   hipEvent_t ev0, ev1;
   double last_solve_ms;
-  // device memory pool: batches are built and torn down once per image in a replay; their arena chunks come from and return to
-  // this free list (grow-only, released by vilo_destroy) instead of ~65 hipMalloc / hipFree per batch
+  // device memory pool: batches are built and torn down once per image in a replay; their arena chunks (and those of the calls'
+  // ArenaScopes) come from and return to this free list (grow-only, released by vilo_destroy) instead of ~65 hipMalloc / hipFree per batch
   std::vector<std::pair<void *, size_t>> pool_free;
   // reusable host staging (grow-only): the wave-packed observation image and the prior staging of vilo_batch_create
   std::vector<std::pair<void *, size_t>> host_stage;
@@ -36,6 +36,7 @@ struct vilo_ctx {
   double last_create_ms[4] = {0, 0, 0, 0}, last_create_bytes = 0.0, last_download_ms = 0.0;   // host wall time of the last vilo_batch_create / _download (vilo_last_create_ms)
   double last_marg_ms = 0.0;       // GPU time of the last vilo_marginalize (linearisation + marginalisation kernels)
   double last_cov_ms = 0.0;        // GPU time of the last vilo_batch_covariance (linearisation + k_covariance)
+  double last_resid_ms = 0.0;      // GPU time of the last vilo_batch_residuals
   int marg_general_count = 0;      // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
@@ -151,6 +152,32 @@ inline double vilo_win_sum_dt(const vilo_window_desc &d, const vilo_resident_ref
   return d.use_leg ? d.preint[k].sum_dt : d.preint_imu[k].sum_dt;
 }
 struct vilo_batch;
+// Per-call device memory of a batch call (vilo_batch.hip): bump-allocated out of the batch's arena, all of it given back when the scope
+// closes, on every return path. Closing waits for the context's stream first (batch uploads are null-stream copies, which do not wait for
+// it), then hands the arena chunks taken since opening back to ctx->pool_free and rewinds the bump pointer. Bump allocation never moves
+// what it has handed out, so a buffer may be sized partway through a call. The rule: nothing that must outlive the call is allocated
+// inside a scope.
+struct ArenaScope {
+  ArenaScope(vilo_ctx *ctx, vilo_batch *bt);
+  ~ArenaScope();
+  ArenaScope(const ArenaScope &) = delete;
+  ArenaScope &operator=(const ArenaScope &) = delete;
+  void *alloc(size_t bytes);   // 256-byte aligned; null (ctx->err set) when the device has no memory left
+  vilo_ctx *ctx;
+  vilo_batch *bt;
+  size_t n_chunks, cur_left, used;
+  char *cur;
+};
+// The host-window form of a batch call: a batch of the windows at the given states, fn(batch) on it, the batch destroyed.
+template <class Fn>
+int vilo_with_batch(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_window_state *state, Fn &&fn) {
+  vilo_batch *bt = nullptr;
+  int rc = vilo_batch_create(ctx, W, in, state, &bt);
+  if (rc != VILO_OK) return rc;
+  rc = fn(bt);
+  vilo_batch_destroy(ctx, bt);
+  return rc;
+}
 // vilo_batch.hip: a call on many host windows cut into sub-batches over the context's pipeline lanes (false: not a call to cut)
 bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
                        const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out);

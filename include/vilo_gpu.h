@@ -289,7 +289,8 @@ int vilo_marginalize(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, c
                      int mode, vilo_prior *out);
 /* The same on a batch that is already resident, linearised at its device state (after vilo_batch_solve + vilo_batch_download; `state` is
  * the host copy of that state, `in` the descriptors the batch was created from). modes[w]: 0, 1 as above, < 0: leave window w alone.
- * With vilo_batch_set_samples in force the intervals are integrated again at the accepted state first. */
+ * With vilo_batch_set_samples in force the intervals are integrated again at the accepted state first. The call's device memory is
+ * returned to the context's pool when it returns. */
 int vilo_batch_marginalize(vilo_ctx *ctx, vilo_batch *batch, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
                            const int *modes, vilo_prior *out);
 
@@ -364,8 +365,8 @@ typedef struct {
 } vilo_cov_opts;
 void vilo_default_cov_opts(vilo_cov_opts *o);
 /* At the batch's device state, normally right after vilo_batch_solve. Leaves the batch as it was: states, candidate, prior, trust-region
- * state and the summaries vilo_batch_download reports; a following vilo_batch_solve gives what it gives without this call. Device memory
- * for it is allocated at the first call and kept with the batch. opts NULL: vilo_default_cov_opts. Bad arguments: VILO_ERR_BAD_ARG. */
+ * state and the summaries vilo_batch_download reports; a following vilo_batch_solve gives what it gives without this call. Its device
+ * memory is returned when the call returns. opts NULL: vilo_default_cov_opts. Bad arguments: VILO_ERR_BAD_ARG. */
 int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_cov_opts *opts, double *frames, double *poses, int32_t *status);
 /* The same for host windows at the given states (e.g. an Estimator after optimization()): one batch is created and destroyed. */
 int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_cov_opts *opts,
@@ -392,7 +393,7 @@ double vilo_last_covariance_ms(const vilo_ctx *ctx);
  *   inv_depth_var [sum L], points [sum L][3], point_cov [sum L][3][3], status [W];
  *   frames, poses: as vilo_batch_covariance returns them (bit for bit), or NULL to leave them out. opts->want_poses is ignored: a non-NULL
  *   `poses` decides. The landmark buffers may be NULL only when the batch has no landmarks. Bad arguments: VILO_ERR_BAD_ARG.
- * The batch is left as vilo_batch_covariance leaves it; its device buffer is the same one (grown as needed). */
+ * The batch is left as vilo_batch_covariance leaves it; its device memory is likewise returned when the call returns. */
 int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
                                    double *points, double *point_cov, int32_t *status);
 /* The same for host windows at the given states: one batch is created and destroyed. */
@@ -424,7 +425,8 @@ int vilo_window_landmark_covariance(vilo_ctx *ctx, int n_windows, const vilo_win
  * Per interval (imu_residuals [W][10][31]): the factor's whitened residual; use_leg == 0: entries 15..30 are zero. Intervals without a factor
  *   are zero; the intervals of a status-2 window whose record has no sqrt_info are NaN.
  * Side effects: none on the batch's states, candidate, trust-region state, summaries or what a following solve computes (the guarantee of
- * vilo_batch_covariance). Device memory is allocated at the first call and kept with the batch.
+ * vilo_batch_covariance). The call's device memory is returned when it returns; the table of the landmarks' observation rows is uploaded
+ * at the first call and kept with the batch.
  * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx, batch or windows, a threshold that is negative or not finite, n_windows < 1. */
 typedef struct {
   double outlier_threshold_px;   /* 3.0: ave_err * FOCAL_LENGTH > 3 (estimator.cpp:1796) */
@@ -521,6 +523,9 @@ const char *vilo_kernel_name(int kind);
  *   [7] launch order of the packed waves (VILO_WAVE_ORDER): 0 window order, 1 by length, 2 by length with groups rotated
  * Steps a solve did not launch read -1. VILO_ERR_BAD_ARG before the batch's first solve. */
 int vilo_debug_batch_path(const vilo_batch *batch, int32_t out[8]);
+/* Device memory of a batch: out[0] the bytes of the arena chunks it holds, out[1] the bytes handed out of them. A call on the batch gives
+ * back what it took for itself: out[1] is the same before and after it (vilo_batch_residuals' first call adds its observation-row table). */
+int vilo_debug_batch_device_bytes(const vilo_batch *batch, size_t out[2]);
 /* Copy an internal device array of one window to the host (tests localise parity failures with it). */
 int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *batch, int what, int win, double *out, int max_n);
 /* Streams n doubles (8 B per lane) `reps` times: known byte count to calibrate rocprofv3 FETCH_SIZE / WRITE_SIZE. */

@@ -1,0 +1,84 @@
+"""GPU (-m gpu): the per-call device memory of the batch calls. Marginalisation, covariance, landmark covariance and residuals, called in
+turn on one resident batch, each give back what they take (vilo_debug_batch_device_bytes): the batch holds the same arena after ten rounds
+as after one, and every output of the tenth round is bitwise the first's. vilo_last_residuals_ms is a value per context."""
+import numpy as np
+import pytest
+
+from test_covariance_gpu import _window
+
+pytestmark = pytest.mark.gpu
+
+W = 64
+
+
+def _granule(n):
+    """bytes the batch arena hands out for a request of n bytes"""
+    return (max(n, 1) + 255) // 256 * 256
+
+
+def _marginalize(b, modes):
+    from cerberus_amd.synth import PriorData
+    priors = [PriorData() for _ in modes]
+    b.marginalize(modes, priors)
+    return [a for p in priors for a in (p.x0, p.J0, p.r0, np.array([p.struct.valid, p.struct.n, p.struct.n_blocks]), np.array(p.blocks()))]
+
+
+def _arrays(out):
+    return [np.asarray(a) for a in out if a is not None]
+
+
+def test_repeated_calls_give_their_memory_back(cfg, ocfg):
+    from cerberus_amd import api
+    base = [_window(cfg, ocfg, seed=5100 + s, L=60) for s in range(8)]
+    ws = [base[i % len(base)].twin() for i in range(W)]
+    modes = [(0, 0, 1, -1)[i % 4] for i in range(W)]
+    obs_rows = _granule(4 * sum(w.L for w in ws))   # vilo_batch_residuals' first call keeps the landmarks' observation rows with the batch
+    ctx = api.Context(cfg, 0)
+    try:
+        b = api.Batch(ctx, ws)
+        b.set_samples()   # (the re-integration copies of the marginalisation and the residuals come from the calls' memory too)
+        b.solve(api.default_solve_opts(True, 4))
+        b.download()
+        calls = (("marginalize", lambda: _marginalize(b, modes)),
+                 ("covariance", lambda: _arrays(b.covariance(poses=True))),
+                 ("landmark_covariance", lambda: _arrays(b.landmark_covariance())),
+                 ("residuals", lambda: _arrays(b.residuals(observations=True, imu=True))))
+        rounds, held = [], []
+        for r in range(10):
+            outs = {}
+            for name, call in calls:
+                before = b.device_bytes()
+                outs[name] = call()
+                grown = b.device_bytes()[1] - before[1]
+                assert grown == (obs_rows if (r, name) == (0, "residuals") else 0), (r, name, grown)
+            rounds.append(outs)
+            held.append(b.device_bytes())
+        assert held[9] == held[0], held
+        for name, _ in calls:
+            assert len(rounds[9][name]) == len(rounds[0][name])
+            for i, (x, y) in enumerate(zip(rounds[0][name], rounds[9][name])):
+                assert x.shape == y.shape and x.tobytes() == y.tobytes(), (name, i)
+        b.close()
+    finally:
+        ctx.close()
+
+
+def test_residuals_time_is_per_context(cfg, ocfg):
+    from cerberus_amd import api
+    w = _window(cfg, ocfg, seed=5200, L=60)
+    L = api.lib()
+    c1, c2 = api.Context(cfg, 0), api.Context(cfg, 0)
+    try:
+        assert L.vilo_last_residuals_ms(c1.h) == 0.0 and L.vilo_last_residuals_ms(c2.h) == 0.0
+        b1 = api.Batch(c1, [w.twin()])
+        b1.residuals()
+        t1 = L.vilo_last_residuals_ms(c1.h)
+        assert t1 > 0.0 and L.vilo_last_residuals_ms(c2.h) == 0.0
+        b2 = api.Batch(c2, [w.twin()])
+        b2.residuals(observations=True, imu=True)
+        assert L.vilo_last_residuals_ms(c1.h) == t1 and L.vilo_last_residuals_ms(c2.h) > 0.0
+        b1.close()
+        b2.close()
+    finally:
+        c1.close()
+        c2.close()

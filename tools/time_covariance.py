@@ -29,7 +29,7 @@ def main():
         for _ in range(a.reps):
             b.reset()
             solve_ms.append(b.solve(opts))
-        b.covariance()   # (first call allocates the batch's buffer)
+        b.covariance()   # (warm-up: the first call takes its arena chunks from the device, later calls from the context's pool)
         cov_ms, wall_ms = [], []
         for _ in range(a.reps):
             t0 = time.perf_counter()

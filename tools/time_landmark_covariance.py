@@ -25,7 +25,7 @@ def main():
     for W in [int(s) for s in a.sizes.split(",")]:
         b = api.Batch(ctx, [base.twin() for _ in range(W)])
         b.solve(api.default_solve_opts(True, 12))
-        b.covariance()           # (first calls allocate the batch's buffer)
+        b.covariance()           # (warm-up: the first calls take their arena chunks from the device, later calls from the context's pool)
         b.landmark_covariance()
         cov_ms, lm_ms, lm_wall = [], [], []
         for _ in range(a.reps):

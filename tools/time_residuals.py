@@ -26,7 +26,7 @@ def main():
         b = api.Batch(ctx, [base.twin() for _ in range(W)])
         opts = api.default_solve_opts(True, 12)
         solve_ms = min(b.solve(opts) for _ in range(2))
-        b.residuals(observations=True, imu=True)   # (the first call allocates the batch's buffer)
+        b.residuals(observations=True, imu=True)   # (warm-up: the first call uploads the observation rows and takes its arena chunks from the device)
         off_ms, on_ms, on_wall = [], [], []
         for _ in range(a.reps):
             r = b.residuals()
