@@ -610,9 +610,11 @@ __global__ void __launch_bounds__(AF_THREADS) k_assemble_bias(BatchDev b, int ja
 // =================================================================================================
 // launch
 // =================================================================================================
-int vilo_launch_assemble_full(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, const AcceptParams &ap, int which) {
-  (void)ctx;
-  if (which == 0) hipLaunchKernelGGL(k_assemble_pose, dim3(b.W), dim3(AF_THREADS), 0, s, b, sp.jacobi_scaling, sp.min_lm_diagonal, sp.max_lm_diagonal, ap);
-  else hipLaunchKernelGGL(k_assemble_bias, dim3(b.W), dim3(AF_THREADS), 0, s, b, sp.jacobi_scaling, sp.min_lm_diagonal, sp.max_lm_diagonal);
+int vilo_launch_assemble_pose(vilo_ctx *, BatchDev &b, const SolveParams &sp, hipStream_t s, const AcceptParams &ap) {
+  hipLaunchKernelGGL(k_assemble_pose, dim3(b.W), dim3(AF_THREADS), 0, s, b, sp.jacobi_scaling, sp.min_lm_diagonal, sp.max_lm_diagonal, ap);
+  return VILO_OK;
+}
+int vilo_launch_assemble_bias(vilo_ctx *, BatchDev &b, const SolveParams &sp, hipStream_t s) {
+  hipLaunchKernelGGL(k_assemble_bias, dim3(b.W), dim3(AF_THREADS), 0, s, b, sp.jacobi_scaling, sp.min_lm_diagonal, sp.max_lm_diagonal);
   return VILO_OK;
 }

@@ -29,7 +29,6 @@
 #include "solve_common.hpp"
 #include "vilo_math.hpp"
 
-int vilo_marg_linearize(vilo_ctx *ctx, BatchDev &b);   // kernels_solve.hip
 BatchDev *vilo_batch_dev(vilo_batch *bt);               // vilo_batch.hip
 
 static_assert(sizeof(vilo_cov_opts) == 24, "vilo_cov_opts layout (cerberus_amd/_ctypes.py mirrors it)");

@@ -17,7 +17,6 @@
 
 using namespace vilo;
 
-int vilo_marg_linearize(vilo_ctx *ctx, BatchDev &b);   // kernels_solve.hip
 
 namespace {
 

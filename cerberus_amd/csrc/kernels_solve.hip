@@ -822,51 +822,33 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 __global__ void __launch_bounds__(64) k_visual_reduce(BatchDev b, int mode) { visual_reduce_body(b, blockIdx.x, mode, false); }
 
-// both forms behind one call (kernel kind 0 of the profiling table).
-// fuse_imu (solve passes of small batches with compact rows; gn = g_norm): the IMU factors are linearised by extra workgroups of the same
-// launch (imu_fused_body) and the second half of the frame-parallel form is left to k_assemble_s's extra workgroups (reduce_later).
-// Returns the form launched (vilo_debug_batch_path's visual code, -1: none); *imu_first: where the fused IMU workgroups went (-1: not fused).
+// The visual linearisation in the form the plan names (vilo::Visual), mode 0 = the marginalisation's pass, 1 = a solve pass.
+// The fused forms (solve passes of batches with compact rows; gn = g_norm) linearise the IMU factors by extra workgroups of the same launch
+// (imu_fused_body); VIS_SMALL_C leaves the second half of the frame-parallel form to k_assemble_s's extra workgroups.
+// (Frame-parallel forms: every (packed wave, frame) workgroup writes all the terms and coupling rows it owns, zeros included: nothing to
+// clear first.)
 __global__ void k_lin_small_c(BatchDev b, double sq, double huber_a, double gn, int mode, int n_imu);   // (below, behind the IMU kernels)
-static int launch_visual_linearize(BatchDev &b, double sq, double ha, hipStream_t s, int mode, bool fuse_imu = false, double gn = 0.0, int *imu_first_out = nullptr) {
-  if (imu_first_out) *imu_first_out = -1;
-  if (b.n_waves <= 0) return -1;
-  const bool compact = b.compact && mode != 0;   // (the marginalisation's pass keeps td: full 23-column slots)
-  if (b.lm_part) {
-    // (every (packed wave, frame) workgroup writes all the terms and coupling rows it owns, zeros included: nothing to clear first)
-    if (compact && fuse_imu) {
+static void launch_visual_linearize(BatchDev &b, const vilo::SolvePlan &plan, double sq, double ha, double gn, hipStream_t s, int mode) {
+  switch (plan.visual) {
+    case vilo::VIS_SMALL_C:
       hipLaunchKernelGGL(k_lin_small_c, dim3(b.W * 10 + b.n_waves * VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, gn, mode, b.W * 10);
-      if (imu_first_out) *imu_first_out = 1;   // (its IMU workgroups are the first W x 10)
-      return 0;   // (k_assemble_s's extra workgroups finish the frame-parallel form)
-    }
-    if (compact) hipLaunchKernelGGL(k_visual_linearize_tpar_c, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, mode);
-    else hipLaunchKernelGGL(k_visual_linearize_tpar, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, mode);
-    hipLaunchKernelGGL(k_visual_reduce, dim3(b.n_waves), dim3(64), 0, s, b, mode);
-    return compact ? 1 : 2;
-  } else {
-    // (VILO_VISUAL_FORM=single keeps the one-wave compact form: A/B runs)
-    static const bool pc = [] { const char *e = getenv("VILO_VISUAL_FORM"); return !(e && !strcmp(e, "single")); }();
-    if (compact && pc) {
-      // (order of the two kinds of workgroup, measured in the captured launch sequence: IMU first 564 k / last 430 k window-iterations/s at
-      // 128 windows, 986 / 838 k at 256; 1018 / 1054 k at 384, 1227 / 1239 k at 512. VILO_IMU_FIRST = 0 / 1 pins it.)
-      static const int imu_first_env = [] { const char *e = getenv("VILO_IMU_FIRST"); return e ? atoi(e) : -1; }();
-      const int imu_first = imu_first_env >= 0 ? imu_first_env : (b.W <= 256 ? 1 : 0);
-      if (fuse_imu) {
-        hipLaunchKernelGGL(k_visual_linearize_pc_imu, dim3(b.n_waves + (b.W * 10 + 1) / 2), dim3(128), 0, s, b, sq, ha, mode, gn, imu_first);
-        if (imu_first_out) *imu_first_out = imu_first;
-        return 3;
-      }
-      hipLaunchKernelGGL(k_visual_linearize_pc, dim3(b.n_waves), dim3(128), 0, s, b, sq, ha, mode);
-      return 4;
-    }
-    if (compact) { hipLaunchKernelGGL(k_visual_linearize_c, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode); return 5; }
-    hipLaunchKernelGGL(k_visual_linearize, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode);
-    return 6;
+      break;
+    case vilo::VIS_TPAR_C:
+      hipLaunchKernelGGL(k_visual_linearize_tpar_c, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, mode);
+      hipLaunchKernelGGL(k_visual_reduce, dim3(b.n_waves), dim3(64), 0, s, b, mode);
+      break;
+    case vilo::VIS_TPAR:
+      hipLaunchKernelGGL(k_visual_linearize_tpar, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha, mode);
+      hipLaunchKernelGGL(k_visual_reduce, dim3(b.n_waves), dim3(64), 0, s, b, mode);
+      break;
+    case vilo::VIS_PC_IMU:
+      hipLaunchKernelGGL(k_visual_linearize_pc_imu, dim3(b.n_waves + (b.W * 10 + 1) / 2), dim3(128), 0, s, b, sq, ha, mode, gn, plan.imu_order);
+      break;
+    case vilo::VIS_PC: hipLaunchKernelGGL(k_visual_linearize_pc, dim3(b.n_waves), dim3(128), 0, s, b, sq, ha, mode); break;
+    case vilo::VIS_SINGLE_C: hipLaunchKernelGGL(k_visual_linearize_c, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode); break;
+    case vilo::VIS_SINGLE: hipLaunchKernelGGL(k_visual_linearize, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha, mode); break;
+    default: break;   // (no landmark in the batch)
   }
-}
-// does launch_visual_linearize(fuse_imu = true) take the IMU factors along for this batch?
-static bool visual_launch_takes_imu(const BatchDev &b) {
-  static const bool pc = [] { const char *e = getenv("VILO_VISUAL_FORM"); return !(e && !strcmp(e, "single")); }();
-  return b.n_waves > 0 && b.compact && (b.lm_part || pc);
 }
 
 // Residual-only evaluation at the candidate point (TrustRegionMinimizer::ComputeCandidatePointAndEvaluateCost).
@@ -1358,14 +1340,8 @@ __global__ void k_init_state(BatchDev b, double radius0, double mu0, int fail_ba
 // =================================================================================================
 // host-side launch sequence
 // =================================================================================================
-int vilo_launch_wave_solver(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, int stage);   // kernels_wave.hip
-int vilo_launch_assemble_small(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, const AcceptParams *ap, int reduce_waves);   // kernels_asm_small.hip
-bool vilo_assemble_small_takes(const BatchDev &b);                                                                              // kernels_asm_small.hip
-int vilo_launch_split_stage(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, int which);   // kernels_split.hip
-int vilo_solver_form(const vilo_ctx *ctx, const BatchDev &b);                                                                    // kernels_wave.hip
-int vilo_launch_assemble_full(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, const AcceptParams &ap, int which);   // kernels_asm_full.hip
-
-int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
+// Executes `plan` (vilo::plan_solve of this batch): every choice of form was made there.
+int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o, const vilo::SolvePlan &plan) {
   const double sq = ctx->cfg.focal_length / 1.5, ha = ctx->cfg.huber_delta, gn = ctx->cfg.g_norm;
   hipStream_t s = ctx->stream;
   SolveParams sp;
@@ -1379,10 +1355,6 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
   const int W = b.W;
   int pidx = 0;
   ctx->pev_kind.clear();
-  // which form of each step this sequence takes (vilo_debug_batch_path; -1: the step is not launched — no iterations, no landmarks)
-  int32_t *path = ctx->launch_path;
-  for (int i = 0; i < 8; ++i) path[i] = -1;
-  path[5] = b.compact ? 1 : 0;
   // profile: 0 off, 1 every kernel, 2 + k only kernel kind k (a pair of event records costs the stream ~7 us; ~80 pairs per solve)
   bool pev_open = false;
   auto P0 = [&](int kind) {
@@ -1397,7 +1369,20 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
     (void)hipEventRecord(ctx->pev[2 * pidx + 1], s);
     ++pidx;
   };
-  P0(6);
+  // every step: [kind] launch, VILO_ERR_HIP if the launcher says so
+#define STEP(kind, launch)                       \
+  do {                                           \
+    P0(kind);                                    \
+    if ((launch) != VILO_OK) return VILO_ERR_HIP; \
+    P1();                                        \
+  } while (0)
+  auto repropagate = [&]() -> int {
+    if (!b.rp_on) return VILO_OK;
+    STEP(VILO_K_REPROPAGATE, vilo_repropagate_launch(ctx, b, 1, 0));
+    STEP(VILO_K_PREPARE_PREINT, vilo_repropagate_launch(ctx, b, 1, 1));
+    return VILO_OK;
+  };
+  P0(VILO_K_INIT_STATE);
   hipLaunchKernelGGL(k_init_state, dim3((W + 127) / 128), dim3(128), 0, s, b, o->initial_trust_region_radius, ctx->initial_mu, 1);
   P1();
   // the first "candidate" is the initial point itself (IterationZero evaluates and linearises it)
@@ -1405,114 +1390,59 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o) {
   if (b.n_lm > 0) VILO_HIP(hipMemcpyAsync(b.lamc, b.lam, sizeof(double) * (size_t)b.n_lm, hipMemcpyDeviceToDevice, s));
   for (int it = 0; it < o->max_num_iterations; ++it) {
     // cost + linearisation of the candidate -> accept / reject -> (accepted: normal equations) -> step -> next candidate
-    if (b.rp_on) {
-      P0(10);
-      if (vilo_repropagate_launch(ctx, b, 1, 0) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      P0(11);
-      if (vilo_repropagate_launch(ctx, b, 1, 1) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-    }
-    // Which assembly a batch gets (compact slots: td a constant block in every window — all of the reference's configurations):
-    //   up to 256 windows (VILO_ASM_SMALL_MAX_WINDOWS): an iteration is a chain of kernel latencies, so the chain is kept short — the IMU
-    //     factors are linearised by extra workgroups of the visual launch (imu_fused_body: k_imu_raw + k_imu_linearize of one factor in
-    //     one wave, bitwise the same Gram), the bookkeeping, the assembly and the second half of the frame-parallel visual form share one
-    //     launch of 768 threads per window (k_assemble_s): three launches per iteration (linearise, bookkeeping + assemble, solve);
-    //   beyond: the assembly in two kernels by LDS footprint (kernels_asm_full.hip: the pose part at four workgroups per CU with the
-    //     bookkeeping as its first phase — no k_accept launch, the prior's H never read —, the speed / leg-bias part at six).
-    // The IMU workgroups inside the visual launch pay up to 2048 windows (768: + 5 %, 1024: + 2.6 %, 2048: + 0.9 %; at 4096 the two forms
-    // take the same time and the full batch keeps its separate kernels): VILO_SMALL_FUSE_MAX_WINDOWS moves that threshold (0: never).
-    static const int small_max = [] { const char *e = getenv("VILO_SMALL_FUSE_MAX_WINDOWS"); return e ? atoi(e) : 2048; }();
-    const bool asm_small = vilo_assemble_small_takes(b);
-    // (beyond the small form a batch with few packed waves — windows of a handful of landmarks — runs the frame-parallel visual form with
-    // its own reduction kernel: only k_assemble_s has workgroups for that reduction)
-    const bool fuse_imu = W <= small_max && visual_launch_takes_imu(b) && (asm_small || !b.lm_part);
-    P0(0);
-    path[0] = launch_visual_linearize(b, sq, ha, s, 1, fuse_imu, gn, &path[2]);
-    path[1] = 0;
+    if (repropagate() != VILO_OK) return VILO_ERR_HIP;
+    P0(VILO_K_VISUAL_LINEARIZE);
+    launch_visual_linearize(b, plan, sq, ha, gn, s, 1);
     P1();
     // (the fused body as a kernel of its own for full batches — one wave per factor, no raw block through HBM — was measured slower than
     // the two kernels: 315 - 319 us against 45 + 245 at 4096 windows: there lanes = factors is the better form of the raw evaluation)
-    if (!fuse_imu) {
-      P0(7);
+    if (!plan.fuse_imu()) {
+      P0(VILO_K_IMU_RAW);
       hipLaunchKernelGGL(k_imu_raw, dim3((W * 10 + 63) / 64), dim3(64), 0, s, b, gn, 1);
       P1();
-      P0(1);
-      {
-        static const int single_max = [] { const char *e = getenv("VILO_IMU_SINGLE_MAX_WINDOWS"); return e ? atoi(e) : 128; }();   // (measured: 128 windows + 1 %, 256 equal, 512 - 3 %)
-        const int single = W <= single_max ? 1 : 0;   // (one wave per factor while the batch leaves SIMDs idle)
-        hipLaunchKernelGGL(k_imu_linearize, dim3(W * (single ? 10 : 5)), dim3(64), 0, s, b, 1, single);
-        path[1] = single ? 1 : 2;
-      }
+      P0(VILO_K_IMU_LINEARIZE);
+      hipLaunchKernelGGL(k_imu_linearize, dim3(W * (plan.imu_single() ? 10 : 5)), dim3(64), 0, s, b, 1, plan.imu_single() ? 1 : 0);
       P1();
     }
-    if (asm_small) {
-      const bool reduce_later = fuse_imu && b.lm_part;   // (k_assemble_s's extra workgroups run visual_reduce_body)
-      P0(8);
-      if (vilo_launch_assemble_small(ctx, b, sp, s, &ap, reduce_later ? b.n_waves : 0) < 0) return VILO_ERR_HIP;
-      P1();
-      path[3] = 0;
-    } else if (b.compact) {
-      P0(8);
-      if (vilo_launch_assemble_full(ctx, b, sp, s, ap, 0) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      P0(2);
-      if (vilo_launch_assemble_full(ctx, b, sp, s, ap, 1) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      path[3] = 1;
-    } else {
-      // 23-column slots (a window estimates td): the bookkeeping as a kernel of its own, then k_assemble
-      P0(5);
-      hipLaunchKernelGGL(k_accept, dim3(W), dim3(128), 0, s, b, ap);
-      P1();
-      P0(8);
-      if (vilo_launch_wave_solver(ctx, b, sp, s, 0) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      path[3] = 2;
+    switch (plan.assembly) {
+      case vilo::ASM_SMALL:
+        STEP(VILO_K_ASSEMBLE, vilo_launch_assemble_small(ctx, b, sp, s, ap, plan.reduce_later() ? b.n_waves : 0));
+        break;
+      case vilo::ASM_FULL:
+        STEP(VILO_K_ASSEMBLE, vilo_launch_assemble_pose(ctx, b, sp, s, ap));
+        STEP(VILO_K_ASSEMBLE_BIAS, vilo_launch_assemble_bias(ctx, b, sp, s));
+        break;
+      default:   // 23-column slots (a window estimates td): the bookkeeping as a kernel of its own, then k_assemble
+        P0(VILO_K_ACCEPT);
+        hipLaunchKernelGGL(k_accept, dim3(W), dim3(128), 0, s, b, ap);
+        P1();
+        STEP(VILO_K_ASSEMBLE, vilo_launch_assemble_wave(ctx, b, sp, s));
+        break;
     }
     ap.init_mode = 0;
-    path[4] = vilo_solver_form(ctx, b);
-    if (path[4] == 3) {
-      // three-stage form (kernels_split.hip): chain -> pose system -> back-substitutions + step, then the complete single-wave solver for
-      // the windows a stage flagged (a factorisation failed: the retry loop lives there) — it returns at once for the rest
-      P0(12);
-      if (vilo_launch_split_stage(ctx, b, sp, s, 0) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      P0(13);
-      if (vilo_launch_wave_solver(ctx, b, sp, s, 2) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      P0(14);
-      if (vilo_launch_split_stage(ctx, b, sp, s, 1) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-      P0(9);
-      if (vilo_launch_wave_solver(ctx, b, sp, s, 4) != VILO_OK) return VILO_ERR_HIP;
-      P1();
-    } else {
-      P0(9);
-      if (vilo_launch_wave_solver(ctx, b, sp, s, 1) != VILO_OK) return VILO_ERR_HIP;
-      P1();
+    switch (plan.solver) {
+      case vilo::SOLVER_MW8: STEP(VILO_K_SOLVE_WAVE, vilo_launch_mw8_solver(ctx, b, sp, s)); break;
+      case vilo::SOLVER_SPLIT:   // chain -> pose system -> back-substitutions + step, then the complete solver for the windows a stage flagged
+        STEP(VILO_K_CHAIN, vilo_launch_chain(ctx, b, s));
+        STEP(VILO_K_SOLVE_MID, vilo_launch_solve_mid(ctx, b, sp, s));
+        STEP(VILO_K_BACKSUB, vilo_launch_backsub(ctx, b, sp, s));
+        STEP(VILO_K_SOLVE_WAVE, vilo_launch_solve_wave_redo(ctx, b, sp, s));
+        break;
+      default: STEP(VILO_K_SOLVE_WAVE, vilo_launch_solve_wave(ctx, b, sp, s)); break;
     }
   }
   // the last candidate (or, without iterations, the initial point) only needs its cost
-  P0(3);
-  if (b.n_waves > 0) {
-    // few packed waves: one workgroup per (packed wave, frame) fills the chip; many: one wave per packed wave reads every observation once
-    if (b.lm_part) hipLaunchKernelGGL(k_visual_cost, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha);
-    else hipLaunchKernelGGL(k_visual_cost_walk, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha);
-  }
+  P0(VILO_K_VISUAL_COST);
+  // few packed waves: one workgroup per (packed wave, frame) fills the chip; many: one wave per packed wave reads every observation once
+  if (plan.cost == vilo::COST_TPAR) hipLaunchKernelGGL(k_visual_cost, dim3(b.n_waves, VILO_MAX_FRAMES), dim3(64), 0, s, b, sq, ha);
+  else if (plan.cost == vilo::COST_WALK) hipLaunchKernelGGL(k_visual_cost_walk, dim3(b.n_waves), dim3(64), 0, s, b, sq, ha);
   P1();
-  if (b.rp_on) {
-    P0(10);
-    if (vilo_repropagate_launch(ctx, b, 1, 0) != VILO_OK) return VILO_ERR_HIP;
-    P1();
-    P0(11);
-    if (vilo_repropagate_launch(ctx, b, 1, 1) != VILO_OK) return VILO_ERR_HIP;
-    P1();
-  }
-  P0(4);
+  if (repropagate() != VILO_OK) return VILO_ERR_HIP;
+#undef STEP
+  P0(VILO_K_IMU_COST);
   hipLaunchKernelGGL(k_imu_cost, dim3((W * 10 + 63) / 64), dim3(64), 0, s, b, gn);
   P1();
-  P0(5);
+  P0(VILO_K_ACCEPT);
   hipLaunchKernelGGL(k_accept, dim3(W), dim3(128), 0, s, b, ap);
   P1();
   VILO_HIP(hipGetLastError());
@@ -1524,7 +1454,8 @@ int vilo_marg_linearize(vilo_ctx *ctx, BatchDev &b) {
   const double sq = ctx->cfg.focal_length / 1.5, ha = ctx->cfg.huber_delta, gn = ctx->cfg.g_norm;
   hipLaunchKernelGGL(k_init_state, dim3((b.W + 127) / 128), dim3(128), 0, ctx->stream, b, 1e4, 1e-8, 0);
   if (b.rp_on && (vilo_repropagate_launch(ctx, b, 0, 0) != VILO_OK || vilo_repropagate_launch(ctx, b, 0, 1) != VILO_OK)) return VILO_ERR_HIP;
-  launch_visual_linearize(b, sq, ha, ctx->stream, 0);
+  const vilo::SolvePlan plan = vilo::plan_marg_linearize(vilo_batch_shape(b));
+  launch_visual_linearize(b, plan, sq, ha, gn, ctx->stream, 0);
   hipLaunchKernelGGL(k_imu_raw, dim3((b.W * 10 + 63) / 64), dim3(64), 0, ctx->stream, b, gn, 0);
   hipLaunchKernelGGL(k_imu_linearize, dim3(b.W * 5), dim3(64), 0, ctx->stream, b, 0, 0);
   VILO_HIP(hipGetLastError());

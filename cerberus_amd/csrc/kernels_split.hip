@@ -309,12 +309,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BS_WPE,
   PCLK(if (lane == 0) st.phase_clk[27] = clock64());
 }
 
-int vilo_launch_split_stage(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, int which) {
-  (void)ctx;
-  if (which == 0) hipLaunchKernelGGL(k_chain, dim3(b.W), dim3(64), 0, s, b);
-  else {
-    static const int debug_redo = [] { const char *e = getenv("VILO_DEBUG_REDO"); return e ? atoi(e) : 0; }();
-    hipLaunchKernelGGL(k_backsub, dim3(b.W), dim3(64), 0, s, b, sp, debug_redo);
-  }
+int vilo_launch_chain(vilo_ctx *, BatchDev &b, hipStream_t s) {
+  hipLaunchKernelGGL(k_chain, dim3(b.W), dim3(64), 0, s, b);
+  return VILO_OK;
+}
+int vilo_launch_backsub(vilo_ctx *, BatchDev &b, const SolveParams &sp, hipStream_t s) {
+  hipLaunchKernelGGL(k_backsub, dim3(b.W), dim3(64), 0, s, b, sp, vilo::tuning().debug_redo);
   return VILO_OK;
 }

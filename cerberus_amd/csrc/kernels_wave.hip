@@ -1243,39 +1243,29 @@ __global__ void __launch_bounds__(64) k_solve_mid(BatchDev b, SolveParams sp) {
 // =================================================================================================
 // launch
 // =================================================================================================
-int vilo_launch_mw8_solver(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);   // kernels_mw8.hip
-// Which solver (VILO_SOLVER_*: 0 the single wave, 3 the single wave in three stages, 4 eight waves per window): as many waves per window as
-// the batch leaves SIMDs for — eight up to two rounds of one window per CU (512 on an MI355X; measured against the single wave with the
-// two-kernel assembly: 320 windows + 5 %, 384 + 7 %, 512 + 4 %), the single wave beyond, in three stages once the batch fills the
-// two-waves-per-SIMD stages too (VILO_MW8_MAX_WINDOWS / VILO_SPLIT_MIN_WINDOWS move the two thresholds). vilo_set_solver_form
-// pins a form (the tests run every form against the oracle; a deployment that needs bitwise equal answers across batch sizes pins one too).
-int vilo_solver_form(const vilo_ctx *ctx, const BatchDev &b) {
-  const int forced = ctx->solver_form;   // (vilo_set_solver_form; VILO_SOLVER gives the default at vilo_create)
-  static const int max_w8 = [] { const char *e = getenv("VILO_MW8_MAX_WINDOWS"); return e ? atoi(e) : 512; }();
-  static const int min_w3 = [] { const char *e = getenv("VILO_SPLIT_MIN_WINDOWS"); return e ? atoi(e) : 1025; }();
-  if (forced >= 0) return forced;
-  return b.W <= max_w8 ? 4 : (b.W < min_w3 ? 0 : 3);
+int vilo_launch_assemble_wave(vilo_ctx *, BatchDev &b, const SolveParams &sp, hipStream_t s) {
+  hipLaunchKernelGGL(k_assemble, dim3(b.W), dim3(ASM_THREADS), 0, s, b, sp.jacobi_scaling, sp.min_lm_diagonal, sp.max_lm_diagonal);
+  return VILO_OK;
 }
-int vilo_launch_wave_solver(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, int stage) {
-  size_t lds_bytes = (size_t)WS_TOTAL * sizeof(double);
-  if (const char *e = getenv("VILO_WAVE_LDS")) lds_bytes = (size_t)atol(e);   // occupancy experiments: more LDS per workgroup = fewer windows per CU
-  if (stage == 0) {
-    hipLaunchKernelGGL(k_assemble, dim3(b.W), dim3(ASM_THREADS), 0, s, b, sp.jacobi_scaling, sp.min_lm_diagonal, sp.max_lm_diagonal);
-  } else if (vilo_solver_form(ctx, b) == 4) {
-    return vilo_launch_mw8_solver(ctx, b, sp, s);
-  } else {
-    if (!ctx->wave_attr_set) {
-      VILO_HIP(hipFuncSetAttribute((const void *)k_solve_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-      ctx->wave_attr_set = true;
-    }
-    if (stage == 2 && !ctx->mid_attr_set) {   // (k_solve_mid takes the same dynamic LDS, VILO_WAVE_LDS included)
-      VILO_HIP(hipFuncSetAttribute((const void *)k_solve_mid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-      ctx->mid_attr_set = true;
-    }
-    // stage 1: the complete single-wave solver; stages 2 .. 4: the rest of the three-stage form (k_chain is stage 5 in kernels_split.hip)
-    if (stage == 1) hipLaunchKernelGGL(k_solve_wave, dim3(b.W), dim3(64), lds_bytes, s, b, sp, 0);
-    else if (stage == 2) hipLaunchKernelGGL(k_solve_mid, dim3(b.W), dim3(64), lds_bytes, s, b, sp);
-    else if (stage == 4) hipLaunchKernelGGL(k_solve_wave, dim3(b.W), dim3(64), lds_bytes, s, b, sp, 1);
+// dynamic LDS of k_solve_wave and k_solve_mid (VILO_WAVE_LDS: more LDS per workgroup = fewer windows per CU)
+static size_t wave_lds_bytes() { return vilo::tuning().wave_lds >= 0 ? (size_t)vilo::tuning().wave_lds : (size_t)WS_TOTAL * sizeof(double); }
+static int launch_solve_wave(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, int redo_only) {
+  const size_t lds_bytes = wave_lds_bytes();
+  if (!ctx->wave_attr_set) {
+    VILO_HIP(hipFuncSetAttribute((const void *)k_solve_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    ctx->wave_attr_set = true;
   }
+  hipLaunchKernelGGL(k_solve_wave, dim3(b.W), dim3(64), lds_bytes, s, b, sp, redo_only);
+  return VILO_OK;
+}
+int vilo_launch_solve_wave(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s) { return launch_solve_wave(ctx, b, sp, s, 0); }
+int vilo_launch_solve_wave_redo(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s) { return launch_solve_wave(ctx, b, sp, s, 1); }
+int vilo_launch_solve_mid(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s) {
+  const size_t lds_bytes = wave_lds_bytes();
+  if (!ctx->mid_attr_set) {
+    VILO_HIP(hipFuncSetAttribute((const void *)k_solve_mid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    ctx->mid_attr_set = true;
+  }
+  hipLaunchKernelGGL(k_solve_mid, dim3(b.W), dim3(64), lds_bytes, s, b, sp);
   return VILO_OK;
 }

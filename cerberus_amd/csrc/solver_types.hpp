@@ -170,3 +170,5 @@ struct BatchDev {
   int *lin_cur;               // [W] SolverState::cur as the last linearisation pass of a small batch saw it (visual_reduce_body in k_assemble_s's launch)
   int *win_bad;               // [W] 1: a preintegration covariance of the window has no sqrt_info: the window fails alone (termination FAILURE)
 };
+// what the launch plan reads of a batch (launch_plan.hpp)
+inline vilo::BatchShape vilo_batch_shape(const BatchDev &b) { return {b.W, b.n_waves, b.compact != 0, b.lm_part != nullptr, b.full_regime != 0}; }

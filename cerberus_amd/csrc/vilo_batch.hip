@@ -14,8 +14,6 @@
 #include "solver_types.hpp"
 #include "worker_pool.hpp"
 
-int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o);
-
 struct vilo_batch {
   BatchDev d;
   std::vector<std::pair<void *, size_t>> chunks_dev;   // arena chunks (from / back to ctx->pool_free)
@@ -30,7 +28,8 @@ struct vilo_batch {
   // solved a second time with the same options (vilo_batch_reset + vilo_batch_solve loops: replays, Monte-Carlo seeds, bench)
   hipGraphExec_t gexec = nullptr;
   vilo_solve_opts gopts;
-  int g_sqrt_info_mode = 0, g_rp_on = 0, g_solver_form = -1;   // context / batch state the captured launch sequence depends on (part of the cache key)
+  int g_sqrt_info_mode = 0, g_rp_on = 0;   // context / batch state the captured launch sequence depends on (part of the cache key)
+  vilo::SolvePlan gplan;                   // the forms it was captured with
   double g_initial_mu = 1e-8;
   // re-propagation buffers (vilo_batch_set_samples): reused by later calls while they are large enough (the arena cannot free)
   vilo_sample *rp_s = nullptr; int *rp_o = nullptr; double *rp_t = nullptr; size_t rp_cap = 0;
@@ -39,9 +38,7 @@ struct vilo_batch {
   vilo_preint *rp_orig = nullptr;   // [W * 10] the records as created, kept from the first vilo_batch_set_samples on
   int n_solves = 0;
   bool graph_failed = false;
-  // vilo_debug_batch_path: the forms of the last solve, and those of the captured launch sequence (what a replay runs)
-  int32_t path[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, gpath[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-  int wave_order_mode = 1;   // VILO_WAVE_ORDER at creation
+  int32_t path[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // vilo_debug_batch_path: the plan of the last solve, replay or not, the wave order
   // what vilo_batch_prepare needs to run the sqrt_info preparation again (the reference does it in every IMULegFactor::Evaluate)
   void *d_pre = nullptr;
   bool leg = true;
@@ -299,13 +296,6 @@ extern "C" void vilo_batch_destroy(vilo_ctx *ctx, vilo_batch *bt) {
 }
 
 int vilo_launch_preint_gather(vilo_ctx *ctx, const vilo_preint_streams *pool, int n, const int *d_ids, const int *d_dst, void *d_out);
-int vilo_solver_form(const vilo_ctx *ctx, const BatchDev &b);   // kernels_wave.hip
-int vilo_assemble_small_max();                                  // kernels_asm_small.hip
-// up to this many packed waves a batch takes the frame-parallel form of the visual linearisation (tuning aids: VILO_TPAR_MAX_WAVES; VILO_NO_TPAR=1 = 0)
-static size_t vilo_tpar_max_waves() {
-  static const size_t v = [] { const char *e = getenv("VILO_TPAR_MAX_WAVES"); return getenv("VILO_NO_TPAR") ? (size_t)0 : (e ? (size_t)atol(e) : (size_t)256); }();
-  return v;
-}
 
 extern "C" int vilo_batch_create(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_window_state *init, vilo_batch **out) {
   return vilo_batch_create_refs(ctx, W, in, nullptr, init, out);
@@ -564,9 +554,7 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
     // instead of 4 resident waves per CU); with equal lengths adjacent they retire in launch order and the longest ones do not form the tail.
     std::vector<int> order(waves.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-    const char *wo_env = getenv("VILO_WAVE_ORDER");   // tuning aid: 0 = window order, 1 = by length, 2 = by length, groups rotated
-    const int wo = wo_env ? atoi(wo_env) : 1;
-    bt->wave_order_mode = wo;
+    const int wo = vilo::tuning().wave_order;
     if (wo >= 1) std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return waves[a].kmax > waves[c].kmax; });
     if (wo == 2) {
       size_t g0 = 0; int gi = 0;
@@ -602,9 +590,8 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
   // few windows: one workgroup per (packed wave, frame) instead of per packed wave, so that the chip is not left to 3 waves per window
   // (the landmark-side terms every such workgroup writes: all of them, zeros included — nothing reads an entry nobody wrote)
   D.lm_part = nullptr;
-  const size_t tpar_max = vilo_tpar_max_waves();
   D.full_regime = ctx->regime_full;
-  if (waves.size() <= tpar_max && !ctx->regime_full) TRYB(dev_alloc(ctx, bt, &D.lm_part, (size_t)lm_total * VILO_MAX_FRAMES * 2 * 21));
+  if (vilo::shape_takes_tpar(waves.size(), ctx->regime_full != 0, vilo::tuning())) TRYB(dev_alloc(ctx, bt, &D.lm_part, (size_t)lm_total * VILO_MAX_FRAMES * 2 * 21));
   TRYB(dev_alloc(ctx, bt, &D.gram, (size_t)gram_total * VILO_GRAM));
   TRYB(dev_alloc(ctx, bt, &D.chunk_cost, waves.size() * VILO_MAX_FRAMES));   // per (packed wave, frame offset) partial costs
   TRYB(dev_alloc(ctx, bt, &D.prep, (size_t)W * 10));
@@ -696,8 +683,7 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
       }
       host_rec.push_back(w);
     }
-    static const bool no_compact_rec = getenv("VILO_FULL_RECORD_UPLOAD") != nullptr;
-    if (rc == VILO_OK && leg && (int)host_rec.size() == W && ctx->sqrt_info_mode == 0 && !no_compact_rec) {
+    if (rc == VILO_OK && leg && (int)host_rec.size() == W && ctx->sqrt_info_mode == 0 && !vilo::tuning().full_record_upload) {
       // every window's records from host memory, default sqrt_info route: the compact form (above) through the two page-locked chunks, the
       // worker pool gathering chunk k + 1 while the DMA engine reads chunk k; the device expands each chunk behind its copy
       const size_t per_win = sizeof(double) * REC_C_N * 10, chunk_w = std::max<size_t>(1, ((size_t)32 << 20) / per_win);
@@ -912,37 +898,35 @@ extern "C" int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *bt, const vilo_solve_
   if (opts->max_num_iterations < 0 || opts->max_num_iterations > 63) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
   int rc = VILO_OK;
-  const bool want_graph = !ctx->profile && !bt->graph_failed && bt->n_solves >= 1 && getenv("VILO_NO_GRAPH") == nullptr;
+  const vilo::SolvePlan plan = vilo::plan_solve(vilo_batch_shape(bt->d), ctx->solver_form, vilo::tuning(), opts->max_num_iterations > 0);
+  const bool want_graph = !ctx->profile && !bt->graph_failed && bt->n_solves >= 1 && !vilo::tuning().no_graph;
   if (opts->max_solver_time_us < 0) { ctx->err = "vilo_solve_opts.max_solver_time_us < 0 (fill the struct with vilo_default_solve_opts)"; return VILO_ERR_BAD_ARG; }
   if (want_graph && (!bt->gexec || memcmp(&bt->gopts, opts, sizeof(*opts)) != 0 || bt->g_sqrt_info_mode != ctx->sqrt_info_mode || bt->g_rp_on != bt->d.rp_on ||
-                     bt->g_initial_mu != ctx->initial_mu || bt->g_solver_form != ctx->solver_form)) {
+                     bt->g_initial_mu != ctx->initial_mu || bt->gplan != plan)) {
     if (bt->gexec) { (void)hipGraphExecDestroy(bt->gexec); bt->gexec = nullptr; }
     hipGraph_t g = nullptr;
     if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-      rc = vilo_solve_launch(ctx, bt->d, opts);
+      rc = vilo_solve_launch(ctx, bt->d, opts, plan);
       const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
       if (rc != VILO_OK || e != hipSuccess || !g || hipGraphInstantiate(&bt->gexec, g, nullptr, nullptr, 0) != hipSuccess) bt->gexec = nullptr;
       if (g) (void)hipGraphDestroy(g);
     }
     if (!bt->gexec) { bt->graph_failed = true; (void)hipGetLastError(); ctx->err.clear(); }
-    else {
-      bt->gopts = *opts; bt->g_sqrt_info_mode = ctx->sqrt_info_mode; bt->g_rp_on = bt->d.rp_on; bt->g_initial_mu = ctx->initial_mu; bt->g_solver_form = ctx->solver_form;
-      memcpy(bt->gpath, ctx->launch_path, sizeof(bt->gpath));
-    }
+    else { bt->gopts = *opts; bt->g_sqrt_info_mode = ctx->sqrt_info_mode; bt->g_rp_on = bt->d.rp_on; bt->g_initial_mu = ctx->initial_mu; bt->gplan = plan; }
     rc = VILO_OK;
   }
   VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   if (want_graph && bt->gexec) {
     VILO_HIP(hipGraphLaunch(bt->gexec, ctx->stream));
-    memcpy(bt->path, bt->gpath, sizeof(bt->path));
     bt->path[6] = 1;
   } else {
-    rc = vilo_solve_launch(ctx, bt->d, opts);
+    rc = vilo_solve_launch(ctx, bt->d, opts, plan);
     if (rc != VILO_OK) return rc;
-    memcpy(bt->path, ctx->launch_path, sizeof(bt->path));
     bt->path[6] = 0;
   }
-  bt->path[7] = bt->wave_order_mode;
+  const int32_t forms[6] = {plan.visual, plan.imu, plan.imu_order, plan.assembly, plan.solver, plan.rows};
+  memcpy(bt->path, forms, sizeof(forms));
+  bt->path[7] = vilo::tuning().wave_order;
   ++bt->n_solves;
   VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   VILO_HIP(hipEventSynchronize(ctx->ev1));
@@ -951,7 +935,7 @@ extern "C" int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *bt, const vilo_solve_
   ctx->last_solve_ms = ms;
   if (ctx->prep_pending) {   // (recorded on this stream before ev1: complete)
     float t = 0.f;
-    if (hipEventElapsedTime(&t, ctx->prep_ev[0], ctx->prep_ev[1]) == hipSuccess) { ctx->kernel_ms[11] += t; ctx->kernel_launches[11] += 1; }
+    if (hipEventElapsedTime(&t, ctx->prep_ev[0], ctx->prep_ev[1]) == hipSuccess) { ctx->kernel_ms[VILO_K_PREPARE_PREINT] += t; ctx->kernel_launches[VILO_K_PREPARE_PREINT] += 1; }
     ctx->prep_pending = false;
   }
   if (ctx->profile) {
@@ -1072,14 +1056,14 @@ bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in,
     if (in[w].n_frames < 2 || in[w].n_frames > VILO_MAX_FRAMES || in[w].n_landmarks < 0 || in[w].n_landmarks > VILO_NUM_OF_F || !s.pose || !s.speed_bias || !s.leg_bias ||
         !s.ex_pose || !s.td || (in[w].n_landmarks && !s.inv_depth)) return false;
   }
-  // The kernel set of a batch depends on its size (small assembly up to 256 windows, frame-parallel visual form up to 256 packed waves,
-  // compact rows while every window keeps td constant), and those forms agree to rounding, not bitwise. The lanes run the kernel set of a
-  // FULL batch whatever their share (BatchDev::full_regime) with the row form of the whole call, so a call is cut only if as ONE batch it
-  // would certainly be a full one too: more windows than the small assembly takes, more windows with landmarks (>= packed waves) than the
-  // frame-parallel form takes.
+  // The kernel set of a batch depends on its size and those forms agree to rounding, not bitwise. The lanes run the kernel set of a FULL
+  // batch whatever their share (BatchDev::full_regime) with the row form and the solver of the whole call, so a call is cut only if as
+  // ONE batch it would certainly be a full one too.
   int with_lm = 0, all_td_const = 1;
   for (int w = 0; w < n_windows; ++w) { with_lm += in[w].n_landmarks > 0 ? 1 : 0; if (!in[w].td_const) all_td_const = 0; }
-  if (n_windows <= vilo_assemble_small_max() || (size_t)with_lm <= vilo_tpar_max_waves()) return false;
+  if (!vilo::call_is_full_as_one_batch(n_windows, with_lm, vilo::tuning())) return false;
+  const bool compact = ctx->compact_rows && all_td_const;
+  const int form = vilo::plan_solve({n_windows, with_lm, compact, false, true}, ctx->solver_form, vilo::tuning()).solver;   // what ONE batch of all the windows would be solved with
   const int n_sub = (n_windows + sub - 1) / sub, per = (n_windows + n_sub - 1) / n_sub;   // equal shares: no small tail batch
   const int n_lanes = std::min(lanes_want, n_sub);
   while ((int)ctx->lanes.size() < n_lanes) {
@@ -1092,10 +1076,6 @@ bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in,
     l->pool = new vilo::WorkerPool(std::max(2, std::min(16, (hw > 0 ? hw : 1) / std::max(1, lanes_want))) - 1);
     ctx->lanes.push_back(l);
   }
-  BatchDev probe;
-  memset(&probe, 0, sizeof(probe));
-  probe.W = n_windows;
-  const int form = vilo_solver_form(ctx, probe);   // what ONE batch of all the windows would be solved with
   std::vector<int> rcs(n_sub, VILO_OK);
   std::vector<char> ran(n_sub, 0);
   std::vector<std::vector<double>> keep(n_sub);
@@ -1104,7 +1084,7 @@ bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in,
   std::vector<std::thread> th;
   for (int li = 0; li < n_lanes; ++li) {
     vilo_ctx *l = ctx->lanes[li];
-    l->sqrt_info_mode = ctx->sqrt_info_mode; l->solver_form = form; l->compact_rows = (ctx->compact_rows && all_td_const) ? 1 : 0; l->regime_full = 1;
+    l->sqrt_info_mode = ctx->sqrt_info_mode; l->solver_form = form; l->compact_rows = compact ? 1 : 0; l->regime_full = 1;
     l->initial_mu = ctx->initial_mu; l->prior_form = ctx->prior_form; l->err.clear();
   }
   auto lane_work = [&](int li) {

@@ -13,6 +13,7 @@
 
 #include "../../include/vilo_gpu.h"
 #include "factors.hpp"
+#include "launch_plan.hpp"
 #include "worker_pool.hpp"
 
 #define VILO_F 11          // frames in a full window
@@ -20,7 +21,12 @@
 #define VILO_NP 80         // pose part: 11*6 poses + 6 ex0 + 6 ex1 + 1 td = 79, padded to 80
 #define VILO_NPU 79
 #define VILO_NCAM (VILO_F * 19 + 13)   // 222
-#define VILO_NKERNEL 15
+// kernel kinds of the per-kernel timing (vilo_set_profiling, vilo_get_kernel_times): the index of vilo_kernel_name
+enum {
+  VILO_K_VISUAL_LINEARIZE, VILO_K_IMU_LINEARIZE, VILO_K_ASSEMBLE_BIAS, VILO_K_VISUAL_COST, VILO_K_IMU_COST, VILO_K_ACCEPT, VILO_K_INIT_STATE,
+  VILO_K_IMU_RAW, VILO_K_ASSEMBLE, VILO_K_SOLVE_WAVE, VILO_K_REPROPAGATE, VILO_K_PREPARE_PREINT, VILO_K_CHAIN, VILO_K_SOLVE_MID, VILO_K_BACKSUB,
+  VILO_NKERNEL
+};
 struct vilo_ctx {
   vilo_config cfg;
   int device;
@@ -44,7 +50,7 @@ struct vilo_ctx {
   int profile;
   std::vector<hipEvent_t> pev;      // event pool
   std::vector<int> pev_kind;        // kernel kind of interval i = [pev[2i], pev[2i+1]]
-  hipEvent_t prep_ev[2] = {nullptr, nullptr};   // around vilo_batch_prepare's launch (kind 11), read with the next solve's intervals
+  hipEvent_t prep_ev[2] = {nullptr, nullptr};   // around vilo_batch_prepare's launch (VILO_K_PREPARE_PREINT), read with the next solve's intervals
   bool prep_pending = false;
   double kernel_ms[VILO_NKERNEL];
   long long kernel_launches[VILO_NKERNEL];
@@ -61,7 +67,6 @@ struct vilo_ctx {
   int pipe_lanes = 4, pipe_sub = 1024;
   std::vector<vilo_ctx *> lanes;
   int regime_full = 0;   // a lane: its batches take the kernel set of a full batch whatever their size (BatchDev::full_regime)
-  int32_t launch_path[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // forms the last vilo_solve_launch issued (vilo_debug_batch_path codes [0..5])
   vilo::WorkerPool *pool = nullptr;   // a lane's own host threads (null: the library's shared pool)
   std::mutex dma_m, *dma_turn = nullptr;   // the lanes' uploads take turns (a lane points at its parent's mutex)
 };
@@ -116,10 +121,32 @@ struct PreintPrepared {
 static_assert(sizeof(vilo::PreintHead) == 8 * (33 + 45 + 36 + 12), "PreintHead layout");
 static_assert(sizeof(PreintPrepared) == 8 * 1087, "SURVEY 8(d): 1087 doubles per preintegration record");
 
+// ---- launchers called across translation units (each lives in the file of its kernel: no relocatable device code) ----
+struct BatchDev;
+struct SolveParams;
+struct AcceptParams;
+// kernels_solve.hip: the launch sequence of one solve, as `plan` says (vilo::plan_solve); the one pass of preMarginalize
+int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o, const vilo::SolvePlan &plan);
+int vilo_marg_linearize(vilo_ctx *ctx, BatchDev &b);
+// kernels_asm_small.hip: k_assemble_s (reduce_waves: extra workgroups that finish the frame-parallel visual form)
+int vilo_launch_assemble_small(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, const AcceptParams &ap, int reduce_waves);
+// kernels_asm_full.hip: the two-kernel compact assembly
+int vilo_launch_assemble_pose(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s, const AcceptParams &ap);
+int vilo_launch_assemble_bias(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
+// kernels_wave.hip: the 23-column assembly; the complete single-wave solver, its pass over the windows a stage of the three-stage form
+// flagged (a factorisation failed: the retry loop lives there; it returns at once for the rest), the pose system of that form
+int vilo_launch_assemble_wave(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
+int vilo_launch_solve_wave(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
+int vilo_launch_solve_wave_redo(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
+int vilo_launch_solve_mid(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
+// kernels_split.hip: the chain and the back-substitutions + step of the three-stage form
+int vilo_launch_chain(vilo_ctx *ctx, BatchDev &b, hipStream_t s);
+int vilo_launch_backsub(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
+// kernels_mw8.hip: eight waves per window
+int vilo_launch_mw8_solver(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
 // kernels_eval.hip
 int vilo_launch_prepare_preint(vilo_ctx *ctx, int n, const vilo_preint *d_pre, PreintPrepared *d_out, int *d_status, const unsigned char *d_skip, int per_record);
 int vilo_launch_prepare_preint_imu(vilo_ctx *ctx, int n, const vilo_preint_imu *d_pre, PreintPrepared *d_out, int *d_status, const unsigned char *d_skip, int per_record);
-struct BatchDev;
 int vilo_launch_embed_sqrt15(vilo_ctx *ctx, BatchDev &b);
 int vilo_repropagate_launch(vilo_ctx *ctx, BatchDev &b, int mode, int stage);
 

@@ -1,10 +1,10 @@
 """Every form of the Gauss-Newton iteration that a batch can take, against the oracle and against each other.
 
-vilo_solve_launch / launch_visual_linearize choose the visual linearisation, the IMU form, the bookkeeping + assembly and the solver from
-the batch size, the number of packed waves, the row form and switches the library reads once per process; one batch size sees one
-combination. Each row below pins its switches in a subprocess of its own (tests/_paths_worker.py, one after another), solves a fixed window
-set through a resident batch three times (plain launches, then replays of the captured sequence), and asserts the descriptor
-vilo_debug_batch_path reports, so that no two rows run the same path by accident.
+vilo::plan_solve (cerberus_amd/csrc/launch_plan.hpp; pinned on a CPU by tests/test_launch_plan.py) chooses the visual linearisation, the IMU
+form, the bookkeeping + assembly and the solver from the batch size, the number of packed waves, the row form and switches the library reads
+once per process; one batch size sees one combination. Each row below pins its switches in a subprocess of its own (tests/_paths_worker.py,
+one after another), solves a fixed window set through a resident batch three times (plain launches, then replays of the captured sequence),
+and asserts the descriptor vilo_debug_batch_path reports, so that no two rows run the same path by accident.
 
 The window set: two bench windows (200 landmarks, prior), one without a prior, partial windows of 4 and 8 frames, one with interval 4
 skipped, one without landmarks, one with 7 and one with 500 landmarks (multi-chunk groups), at the first, a middle and the last positions;
