@@ -108,6 +108,14 @@ class WindowResidual(C.Structure):
                 ("n_outliers", C.c_int32), ("n_negative_depth", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class WindowGradient(C.Structure):
+    """vilo_window_gradient_record (48 bytes)"""
+    _fields_ = [("max_norm", C.c_double), ("norm", C.c_double), ("scaled_max", C.c_double), ("argmax_kind", C.c_int32),
+                ("argmax_index", C.c_int32), ("argmax_component", C.c_int32), ("n_free", C.c_int32), ("status", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+GRAD_STATE = 222   # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 
 # vilo_debug_batch_path: code -> name per axis (include/vilo_gpu.h); "none": the step was not launched

@@ -33,6 +33,7 @@ def lib():
         L.vilo_last_solve_ms.restype = C.c_double
         L.vilo_last_covariance_ms.restype = C.c_double
         L.vilo_last_residuals_ms.restype = C.c_double
+        L.vilo_last_gradient_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -108,6 +109,27 @@ def _residuals(ctx, descs, outlier_threshold_px, observations, imu, call):
                                           for f, t in T.WindowResidual._fields_]), count=n).copy()
     return Residuals(a["cost"], a["prior_cost"], a["imu_cost"], a["visual_cost"], a["visual_cost_plain"], a["n_visual_blocks"],
                      a["n_huber_active"], a["n_outliers"], a["n_negative_depth"], a["status"], lm_cost, lm_px, lm_flags, offsets, obs, imr)
+
+
+Gradient = collections.namedtuple("Gradient", "max_norm norm scaled_max argmax_kind argmax_index argmax_component n_free status "
+                                              "state_grad state_diag lm_grad lm_diag offsets")
+
+
+def _gradient(ctx, descs, state, diag, landmarks, call):
+    n = len(descs)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    L = int(offsets[-1])
+    wg = (T.WindowGradient * n)()
+    sg = np.zeros((n, T.GRAD_STATE)) if state else None
+    sd = np.zeros((n, T.GRAD_STATE)) if (state and diag) else None
+    lg = np.zeros(L) if landmarks else None
+    ld = np.zeros(L) if (landmarks and diag) else None
+    ctx._check(call(wg, _p(sg), _p(sd), _p(lg), _p(ld)))
+    a = np.frombuffer(wg, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.WindowGradient._fields_]),
+                      count=n).copy()
+    return Gradient(a["max_norm"], a["norm"], a["scaled_max"], a["argmax_kind"], a["argmax_index"], a["argmax_component"], a["n_free"],
+                    a["status"], sg, sd, lg, ld, offsets)
 
 
 class Batch:
@@ -186,6 +208,13 @@ class Batch:
         None, imu_residuals [W, 10, 31] or None). The batch is left as it was."""
         return _residuals(self.ctx, self._descs, outlier_threshold_px, observations, imu,
                           lambda o, *out: lib().vilo_batch_residuals(self.ctx.h, self.handle, o, *out))
+
+    def gradient(self, state=True, diag=True, landmarks=True):
+        """vilo_batch_gradient at the batch's device state: Gradient(per-window max_norm, norm, scaled_max, argmax_kind, argmax_index,
+        argmax_component, n_free, status [W], then state_grad / state_diag [W, 222] (pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4,
+        extrinsics 2 x 6, td) or None, lm_grad / lm_diag [sum L] (window w's landmarks: offsets[w] .. offsets[w + 1], in its own order) or
+        None, offsets [W + 1]). state / landmarks leave the arrays of that side out, diag the two diagonals. The batch is left as it was."""
+        return _gradient(self.ctx, self._descs, state, diag, landmarks, lambda *out: lib().vilo_batch_gradient(self.ctx.h, self.handle, *out))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -493,6 +522,14 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _residuals(self, descs, outlier_threshold_px, observations, imu,
                           lambda o, *out: lib().vilo_window_residuals(self.h, n, descs, states, o, *out))
+
+    def window_gradient(self, windows, state=True, diag=True, landmarks=True):
+        """vilo_window_gradient: the gradient of host windows at their current state arrays (see Batch.gradient)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _gradient(self, descs, state, diag, landmarks, lambda *out: lib().vilo_window_gradient(self.h, n, descs, states, *out))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -460,6 +460,52 @@ int vilo_window_residuals(vilo_ctx *ctx, int n_windows, const vilo_window_desc *
  * without the copies out. */
 double vilo_last_residuals_ms(const vilo_ctx *ctx);
 
+/* ---- cost gradient and Gauss-Newton diagonal at the current state (Ceres Problem::Evaluate's gradient) ----
+ * Definition. At the batch's current state, the one vilo_batch_download returns (inverse depths included), over the residual blocks of the
+ * problem the solve builds:
+ *   g = sum_blocks rho'(s) J^T r        the gradient of the cost vilo_batch_residuals reports,
+ *   h = sum_blocks rho'(s) diag(J^T J)  the diagonal of the Gauss-Newton Hessian,
+ * in the local coordinates of PoseLocalParameterization (dp, dtheta on the 7-dimensional blocks), undamped and without Jacobi scaling, r and
+ * J whitened as the factors return them, the HuberLoss applied to the visual blocks as Ceres' Corrector applies it (first branch, rho'' <= 0:
+ * residual and Jacobian times sqrt(rho')). It is the same H whose inverse vilo_batch_covariance returns (VILO_COV_GAUGE_NONE; the landmarks
+ * kept), so state_diag is that matrix's diagonal, and g_i / sqrt(h_i) is dimensionless.
+ * With vilo_batch_set_samples in force the call does what vilo_batch_covariance does: the linearisation pass both share integrates the
+ * batch's own records again at the current state first, in place, as vilo_batch_marginalize does (an interval already integrated at these
+ * biases is kept as it is).
+ * Layouts. state_grad, state_diag [W][222] in the tangent form of vector2double's order: pose 11 x 6 (dp dtheta), speed-bias 11 x 9
+ * (v ba bg), leg bias 11 x 4, extrinsics 2 x 6 (dt dtheta), td 1. Constant blocks (ex_const, td_const, leg_bias_const; the leg biases when
+ * use_leg == 0) and absent frames (n_frames < 11) are zero in both and not counted in the record. lm_grad, lm_diag [sum L]: the inverse
+ * depths, concatenated window by window, inside a window in the caller's vilo_window_desc order (as vilo_batch_landmark_covariance).
+ * The record's norms run over the free local coordinates, inverse depths included. max_norm is the quantity the solve's
+ * gradient_tolerance test reads (Ceres' gradient_max_norm: unscaled, over exactly this set; the solver forms sum in other orders and
+ * agree with it to rounding). The arg-max is the first entry of the largest |g_i| in the order state_grad, then lm_grad.
+ * A window of status 2 gets NaN in its norms and all its array entries (n_free 0, arg-max -1); the other windows are unaffected. Status 1
+ * leaves the arrays as computed, with NaN norms and arg-max -1.
+ * Side effects: vilo_batch_covariance's. It leaves the batch as it was: states, candidate, prior, trust-region state and the summaries
+ * vilo_batch_download reports; a following vilo_batch_solve gives what it gives without this call. Its device memory is returned when the
+ * call returns. Every output of a window is bitwise independent of the batch it shares and of its position in it.
+ * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx, batch or windows, n_windows < 1. */
+typedef struct {
+  double max_norm;          /* max |g_i| over the free local coordinates, inverse depths included */
+  double norm;              /* sqrt(sum g_i^2) over the same set */
+  double scaled_max;        /* max |g_i| / sqrt(h_i) over entries with h_i > 0 (dimensionless) */
+  int32_t argmax_kind;      /* of max_norm: VILO_BLK_* 0 pose, 1 speed-bias, 2 leg bias, 3 extrinsic, 4 td; 5 inverse depth */
+  int32_t argmax_index;     /* frame / camera index, or the landmark's index in the caller's order */
+  int32_t argmax_component; /* local coordinate inside the block */
+  int32_t n_free;           /* number of free local coordinates counted */
+  int32_t status;           /* 0 OK; 1 an input or a sum is not finite; 2 window invalid (a record without sqrt_info), as vilo_batch_residuals */
+  int32_t pad;
+} vilo_window_gradient_record;   /* 48 bytes (a C typedef cannot share the name of the function vilo_window_gradient) */
+
+/* windows [W] is required; state_grad, state_diag, lm_grad, lm_diag may each be NULL to leave it out. */
+int vilo_batch_gradient(vilo_ctx *ctx, vilo_batch *batch, vilo_window_gradient_record *windows, double *state_grad, double *state_diag,
+                        double *lm_grad, double *lm_diag);
+/* The same for host windows at the given states: one batch is created, reported once and destroyed. */
+int vilo_window_gradient(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                         vilo_window_gradient_record *windows, double *state_grad, double *state_diag, double *lm_grad, double *lm_diag);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_gradient: linearisation + k_gradient, without the copies out. */
+double vilo_last_gradient_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
