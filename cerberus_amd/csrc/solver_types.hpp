@@ -5,21 +5,8 @@
 //   B part (11 x 13, block tridiagonal): frame k -> 80 + 13k + c, c: v 0..2, ba 3..5, bg 6..8, rho 9..12
 // Landmarks (inverse depths) are the eliminated e-blocks (Ceres DENSE_SCHUR ordering).
 #pragma once
+#include "batch_layout.hpp"   // state offsets, camera dimensions, WinMeta / ChunkMeta / WaveMeta
 #include "vilo_internal.hpp"
-
-// state vector layout (doubles) per window: vector2double order (estimator.cpp:848-901)
-#define XO_POSE 0
-#define XO_SB 77
-#define XO_LB 176
-#define XO_EX 220
-#define XO_TD 234
-#define XSTRIDE 240
-
-#define CD_EX0 66
-#define CD_EX1 72
-#define CD_TD 78
-#define CD_B0 80
-#define CD_N 224  // 80 + 143 = 223, padded
 
 // prior pre-assembled once per batch into the solver's LDS image: pose block (80 x 81 padded rows), speed/leg-bias
 // diagonal blocks (11 x 13 x 13) and the 13 x 80 coupling rows of the frame the prior touches
@@ -44,45 +31,6 @@
 #define BI_V 8448       // [CD_N]        v = g / dhat^2
 #define BI_SCAL 8672    // [8]           camera-side sums: q = v^T H v, |D^-1 g|^2, max |g|
 #define BI_N 8704
-
-#define CONST_LB 1
-#define CONST_EX 2
-#define CONST_TD 4
-
-struct WinMeta {
-  int n_frames, L, n_chunks, use_leg;
-  int lm_off;      // first landmark (device order)
-  int chunk_off;   // first group chunk
-  int const_mask;
-  int prior_n;     // 0: no prior
-  int gram_off;    // first Gram slot
-  int n_gram;
-  int prior_nb;
-  int pad;         // frame whose speed/leg-bias block the prior touches (-1: none)
-  int wave_off;    // first packed visual wave
-  int n_waves;
-};
-
-// One wave-sized chunk of the landmarks of a window that share a start frame.
-struct ChunkMeta {
-  int win, s, n, kmax;      // n <= 64 landmarks, kmax = max observations among them
-  int lm_off;               // global device-order index of lane 0
-  int lm_local;             // index inside the window
-  int gram_off;             // global Gram slot of t = 0 (kmax slots)
-  int pad;
-  long long obs_off;        // (unused: observations are stored per packed wave, see WaveMeta)
-  long long flag_off;
-};
-
-// One wave of the visual kernels: up to 4 chunks (different start frames) packed side by side, each starting at a lane
-// that is a multiple of 8 (the MFMA Gram pass walks 8 landmarks per trip); observations are stored per wave.
-struct WaveMeta {
-  int win, nseg, n_lanes, kmax;   // n_lanes: multiple of 8, <= 64; kmax: max over the segments
-  int seg_chunk[4];               // global chunk index
-  int seg_lane0[4];
-  long long obs_off;              // doubles: layout [t][11][n_lanes]
-  long long flag_off;             // bytes:   layout [t][n_lanes]  bit0 valid, bit1 stereo
-};
 
 // Trust-region / dogleg state per window (Ceres 1.14 TrustRegionMinimizer + DoglegStrategy members).
 struct SolverState {

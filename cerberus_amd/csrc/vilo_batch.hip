@@ -11,6 +11,7 @@
 #include <mutex>
 #include <thread>
 
+#include "batch_pack.hpp"
 #include "solver_types.hpp"
 #include "worker_pool.hpp"
 
@@ -128,19 +129,14 @@ int dev_alloc(vilo_ctx *ctx, vilo_batch *bt, T **p, size_t n) {
   return rc;
 }
 template <class T>
-int dev_upload(vilo_ctx *ctx, vilo_batch *bt, T **p, const std::vector<T> &h) {
-  int rc = dev_alloc(ctx, bt, p, h.size());
-  if (rc != VILO_OK) return rc;
-  if (!h.empty()) VILO_HIP(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return VILO_OK;
-}
-template <class T>
 int dev_upload_raw(vilo_ctx *ctx, vilo_batch *bt, T **p, const T *h, size_t n) {
   int rc = dev_alloc(ctx, bt, p, n);
   if (rc != VILO_OK) return rc;
   if (n) VILO_HIP(hipMemcpy(*p, h, n * sizeof(T), hipMemcpyHostToDevice));
   return VILO_OK;
 }
+template <class T>
+int dev_upload(vilo_ctx *ctx, vilo_batch *bt, T **p, const std::vector<T> &h) { return dev_upload_raw(ctx, bt, p, h.data(), h.size()); }
 // The tables of a batch are a dozen and a half small arrays: uploaded one by one, a window's batch pays a blocking copy for each (what a
 // frame-by-frame caller pays per image). They are laid out in ONE host blob at the offsets of one device allocation and go up in one copy;
 // the device pointers are set when the blob is flushed (nothing may read them before). Arrays of 256 KB and more keep their own copy
@@ -160,8 +156,6 @@ struct UploadBlob {
     items.push_back({(void **)p, off});
     return VILO_OK;
   }
-  template <class T>
-  int add(vilo_ctx *ctx, vilo_batch *bt, T **p, const std::vector<T> &h) { return add(ctx, bt, p, h.data(), h.size()); }
   int flush(vilo_ctx *ctx, vilo_batch *bt) {
     if (items.empty()) return VILO_OK;
     void *base = nullptr;
@@ -173,8 +167,6 @@ struct UploadBlob {
     return VILO_OK;
   }
 };
-#define TRYB(x) do { int rc_ = (x); if (rc_ != VILO_OK) { vilo_batch_destroy(ctx, bt); return rc_; } } while (0)
-
 
 // J0 / r0 of the windows whose prior lives in a pool slot: device-to-device into the staging k_prior_pack reads
 __global__ void __launch_bounds__(256) k_prior_gather(int W, const WinMeta *win, const int *slot, const double *pJ, const double *pr, double *J0s, double *r0s) {
@@ -225,19 +217,6 @@ __global__ void __launch_bounds__(256) k_prior_pack(int W, const WinMeta *win, c
     double s = 0.0;
     for (int k = 0; k < n; ++k) s += rl[k] * rl[k];
     c0[w] = s;
-  }
-}
-
-// camera dim of the first local dim of a prior block id; -1 if unsupported
-int prior_block_cd(int id, int *state_off) {
-  const int kind = id / 16, index = id % 16;
-  switch (kind) {
-    case VILO_BLK_POSE: if (index > 10) return -1; *state_off = XO_POSE + 7 * index; return 6 * index;
-    case VILO_BLK_SB: if (index > 10) return -1; *state_off = XO_SB + 9 * index; return CD_B0 + 13 * index;
-    case VILO_BLK_LB: if (index > 10) return -1; *state_off = XO_LB + 4 * index; return CD_B0 + 13 * index + 9;
-    case VILO_BLK_EX: if (index > 1) return -1; *state_off = XO_EX + 7 * index; return CD_EX0 + 6 * index;
-    case VILO_BLK_TD: *state_off = XO_TD; return CD_TD;
-    default: return -1;
   }
 }
 
@@ -301,477 +280,294 @@ extern "C" int vilo_batch_create(vilo_ctx *ctx, int W, const vilo_window_desc *i
   return vilo_batch_create_refs(ctx, W, in, nullptr, init, out);
 }
 
-// refs (optional, [W]): device-resident preintegration objects / prior slots instead of the host records of the descs
+namespace {
+
+// The half-built batch of vilo_batch_create_refs: destroyed on every return but the last one
+struct BatchGuard {
+  vilo_ctx *ctx;
+  vilo_batch *bt;
+  ~BatchGuard() { if (bt) vilo_batch_destroy(ctx, bt); }
+  vilo_batch *release() { vilo_batch *b = bt; bt = nullptr; return b; }
+};
+
+// What the packer (batch_pack.hpp) leaves on the host for one vilo_batch_create_refs call
+struct HostPack {
+  explicit HostPack(size_t W) : res(W), x0(W * XSTRIDE), px0(W * 280), pmap(W * 96), pbs(W * 40), pbi(W * 40), pbx(W * 40), pbst(W * 40), iskip(W * 10) {}
+  vilo::PackPlan plan;
+  std::vector<vilo::PackWindow> res;
+  std::vector<double> x0, px0;
+  std::vector<int> pmap, pbs, pbi, pbx, pbst;
+  std::vector<unsigned char> iskip;
+  // the context's reusable staging: J0 / r0 of the priors packed n x n per window for k_prior_pack (only n x n of a slot is read), the
+  // wave-packed observation image and its flags
+  double *pJ = nullptr, *pr0 = nullptr, *obs = nullptr;
+  unsigned char *flags = nullptr;
+};
+
+// What the packer needs of window w's references (it sees no pool): whether this batch can take them, its prior, its intervals' sum_dt
+vilo::PackWindow resolve_window(const vilo_window_desc &d, const vilo_resident_refs *rf, const vilo_resident_refs *rf0) {
+  vilo::PackWindow r;
+  if (rf && rf->preint_pool && ((d.use_leg != 0) == (rf->preint_pool->kind != 0) || !rf->preint_ids || !rf->preint_sum_dt || rf->preint_pool != rf0->preint_pool))
+    r.refs_defect = "resident preintegration: pool kind must match use_leg, one pool per batch";
+  else if (rf && rf->prior_pool && rf->prior_pool != rf0->prior_pool) r.refs_defect = "one prior pool per batch";
+  if (r.refs_defect) return r;
+  r.resident_records = rf && rf->preint_pool;
+  r.prior = vilo_win_prior(d, rf);
+  // (a window the packer refuses for its sizes or for a missing record array has no sum_dt to read)
+  const bool have = r.resident_records || (d.use_leg ? (const void *)d.preint : (const void *)d.preint_imu) != nullptr;
+  const int n_int = (have && d.n_frames >= 2 && d.n_frames <= VILO_MAX_FRAMES) ? d.n_frames - 1 : 0;
+  for (int k = 0; k < n_int; ++k) r.sum_dt[k] = vilo_win_sum_dt(d, rf, k);
+  return r;
+}
+
+// Every device buffer of a batch but the records', in arena order, each once: `up` a host table (the small ones go up in one blob at
+// the flush; nothing may read their device pointers before), `dev` storage the kernels write, cleared where they rely on it.
+int create_device_buffers(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h) {
+  BatchDev &D = bt->d;
+  const vilo::PackPlan &P = h.plan;
+  const size_t W = (size_t)D.W, lm = (size_t)P.lm_total;
+  const bool CLEAR = true;
+  UploadBlob blob;
+  int rc = VILO_OK;
+  auto up = [&](auto **p, const auto *src, size_t n) { if (rc == VILO_OK) rc = blob.add(ctx, bt, p, src, n); };
+  auto upv = [&](auto **p, const auto &v) { up(p, v.data(), v.size()); };
+  auto dev = [&](auto **p, size_t n, bool clear = false) {
+    if (rc == VILO_OK) rc = dev_alloc(ctx, bt, p, n);
+    if (rc == VILO_OK && clear && hipMemsetAsync(*p, 0, sizeof(**p) * std::max<size_t>(n, 1), ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
+  };
+  upv(&D.win, P.wins); upv(&D.chunk, P.chunks); upv(&D.wave, P.waves); upv(&D.wave_order, P.wave_order);
+  up(&D.obs, h.obs, P.obs_total); up(&D.flags, h.flags, P.flags_total);
+  upv(&D.x0, h.x0); upv(&D.lam0, P.lam0); upv(&D.lm_s, P.lm_s); upv(&D.lm_perm, bt->perm_host);
+  dev(&D.x, W * XSTRIDE); dev(&D.xc, W * XSTRIDE);
+  dev(&D.lam, lm); dev(&D.lamc, lm); dev(&D.lm_E, lm); dev(&D.lm_gbuf[0], lm); dev(&D.lm_gbuf[1], lm);
+  dev(&D.lm_dh2, lm); dev(&D.lm_y, lm); dev(&D.lm_scale, lm); dev(&D.lm_einv, lm);
+  // a landmark's coupling rows with the poses before its start frame are structural zeros: written here once, never again
+  dev(&D.lm_w, lm * 80, CLEAR);
+  // few windows: one workgroup per (packed wave, frame) instead of per packed wave, so that the chip is not left to 3 waves per window
+  // (the landmark-side terms every such workgroup writes: all of them, zeros included — nothing reads an entry nobody wrote)
+  D.lm_part = nullptr;
+  D.full_regime = ctx->regime_full;
+  if (vilo::shape_takes_tpar(P.waves.size(), ctx->regime_full != 0, vilo::tuning())) dev(&D.lm_part, lm * VILO_MAX_FRAMES * 2 * 21);
+  dev(&D.gram, (size_t)P.gram_total * VILO_GRAM);
+  dev(&D.chunk_cost, P.waves.size() * VILO_MAX_FRAMES);   // per (packed wave, frame offset) partial costs
+  dev(&D.prep, W * 10); dev(&D.imu_lin, W * 10 * 31 * 39);
+  dev(&D.imu_raw, W * 10 * 31 * 39, CLEAR);   // (structural zeros written once)
+  dev(&D.imu_gram, W * 10 * 780); dev(&D.imu_cost, W * 10);
+  upv(&D.imu_skip, h.iskip);
+  dev(&D.prior_H, W * 96 * 96, CLEAR); dev(&D.prior_dense, W * PD_N, CLEAR); dev(&D.prior_hd, W * 96);
+  dev(&D.prior_b0, W * 96, CLEAR); dev(&D.prior_c0, W, CLEAR);
+  upv(&D.prior_x0, h.px0); upv(&D.prior_map, h.pmap);
+  upv(&D.prior_bsize, h.pbs); upv(&D.prior_bidx, h.pbi); upv(&D.prior_bxoff, h.pbx); upv(&D.prior_bstate, h.pbst);
+  if (rc == VILO_OK) rc = blob.flush(ctx, bt);   // D.win ... D.prior_bstate are device pointers from here on
+  dev(&D.cam_g, W * CD_N); dev(&D.cam_dh2, W * CD_N); dev(&D.cam_y, W * CD_N); dev(&D.cam_scale, W * CD_N);
+  dev(&D.Lk, W * 11 * 169); dev(&D.TAg, W * 11 * 169); dev(&D.Cimg, W * 3840); dev(&D.Tk, W * TK_N);
+  dev(&D.cam_gin, W * CD_N); dev(&D.Bimg, W * BI_N);
+  dev(&D.st, W, CLEAR); dev(&D.status, 1, CLEAR); dev(&D.lin_cur, W);
+  return rc;
+}
+
+// The priors' J0 / r0 (host staging; pool slots gathered on the device) -> H, b0, c0 and the pre-assembled image, by k_prior_pack
+int upload_priors(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h, const vilo_resident_refs *refs) {
+  BatchDev &D = bt->d;
+  const int W = D.W;
+  double *d_J = nullptr, *d_r = nullptr;
+  int rc = dev_alloc(ctx, bt, &d_J, (size_t)W * 96 * 96);
+  if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &d_r, (size_t)W * 96);
+  if (rc != VILO_OK) return rc;
+  if (hipMemcpyAsync(d_J, h.pJ, sizeof(double) * (size_t)W * 96 * 96, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipMemcpyAsync(d_r, h.pr0, sizeof(double) * (size_t)W * 96, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+  if (refs && refs[0].prior_pool) {
+    std::vector<int> slot(W, -1);
+    for (int w = 0; w < W; ++w)
+      if (refs[w].prior_pool && refs[w].prior_slot >= 0 && refs[w].prior_slot < refs[w].prior_pool->n && h.plan.wins[w].prior_n > 0) slot[w] = refs[w].prior_slot;
+    int *d_slot = nullptr;
+    rc = dev_upload(ctx, bt, &d_slot, slot);
+    if (rc != VILO_OK) return rc;
+    hipLaunchKernelGGL(k_prior_gather, dim3(W), dim3(256), 0, ctx->stream, W, D.win, d_slot, refs[0].prior_pool->dJ, refs[0].prior_pool->dr, d_J, d_r);
+  }
+  const size_t pp_lds = sizeof(double) * (96 * 96 + 96);
+  if (!ctx->prior_attr_set) {
+    if (hipFuncSetAttribute((const void *)k_prior_pack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp_lds) != hipSuccess) return VILO_ERR_HIP;
+    ctx->prior_attr_set = true;
+  }
+  hipLaunchKernelGGL(k_prior_pack, dim3(W), dim3(256), pp_lds, ctx->stream, W, D.win, d_J, d_r, D.prior_map, D.prior_H, D.prior_b0, D.prior_c0, D.prior_dense);
+  return hipGetLastError() == hipSuccess ? VILO_OK : VILO_ERR_HIP;
+}
+
+// Host data to the device through the context's two page-locked staging chunks (slots 4 and 5, up to 32 MB each): the worker pool
+// gathers chunk k + 1 into one while the DMA engine reads chunk k out of the other. gather(item, dst) writes one item's per_item bytes;
+// copy(c0, cn, src) enqueues the copies of items c0 .. c0 + cn - 1 out of src; behind(c0, cn) enqueues what the device does with them.
+template <class Gather, class Copy, class Behind>
+int upload_through_ring(vilo_ctx *ctx, size_t n_items, size_t per_item, Gather gather, Copy copy, Behind behind) {
+  const size_t chunk_n = std::max<size_t>(1, ((size_t)32 << 20) / per_item);
+  char *ring[2] = {(char *)vilo_host_stage(ctx, 4, per_item * chunk_n), (char *)vilo_host_stage(ctx, 5, per_item * chunk_n)};
+  if (!ctx->rec_ev[0]) { (void)hipEventCreateWithFlags(&ctx->rec_ev[0], hipEventDisableTiming); (void)hipEventCreateWithFlags(&ctx->rec_ev[1], hipEventDisableTiming); }
+  if (!ring[0] || !ring[1] || !ctx->rec_ev[0] || !ctx->rec_ev[1]) return VILO_ERR_HIP;
+  bool used[2] = {false, false};
+  for (size_t c0 = 0, ci = 0; c0 < n_items; c0 += chunk_n, ++ci) {
+    const int sl = (int)(ci & 1);
+    const size_t cn = std::min(chunk_n, n_items - c0);
+    if (used[sl] && hipEventSynchronize(ctx->rec_ev[sl]) != hipSuccess) return VILO_ERR_HIP;
+    vilo::parallel_items((int)cn, 4, [&](int i) { gather(c0 + (size_t)i, ring[sl] + per_item * (size_t)i); }, ctx->pool);
+    if (copy(c0, cn, ring[sl]) != VILO_OK || hipEventRecord(ctx->rec_ev[sl], ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+    used[sl] = true;
+    behind(c0, cn);
+  }
+  return VILO_OK;
+}
+
+// The windows' preintegration records into d_pre ([W * 10] vilo_preint / vilo_preint_imu). Host records go through the staging ring (a
+// staged host copy of W x 156 KB at once costs more than the copies; one hipMemcpyAsync per window straight from the caller's pageable
+// arrays moved 640 MB of a 4096-window batch at 11.5 GB/s — the runtime's own bounce buffer, one thread); records of a device pool are
+// gathered there. *compact_bytes: bytes that crossed the bus when not the full records'.
+int upload_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, const vilo_resident_refs *refs, void *d_pre, size_t *compact_bytes) {
+  const int W = bt->W;
+  const bool leg = bt->leg;
+  const size_t rec = leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu);
+  bool partial = false;
+  for (int w = 0; w < W; ++w) partial = partial || in[w].n_frames < VILO_MAX_FRAMES;
+  if (partial && hipMemsetAsync(d_pre, 0, rec * (size_t)W * 10, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+  std::vector<int> g_ids, g_dst, host_rec;   // host_rec: windows whose records come out of the caller's arrays
+  for (int w = 0; w < W; ++w) {
+    if (!(refs && refs[w].preint_pool)) { host_rec.push_back(w); continue; }
+    for (int k = 0; k + 1 < in[w].n_frames; ++k) {
+      const int id = refs[w].preint_ids[k];
+      if (id < 0 || id >= refs[w].preint_pool->n) return VILO_ERR_BAD_ARG;
+      g_ids.push_back(id); g_dst.push_back(w * 10 + k);
+    }
+  }
+  int rc = VILO_OK;
+  if (leg && (int)host_rec.size() == W && ctx->sqrt_info_mode == 0 && !vilo::tuning().full_record_upload) {
+    // every window's records from host memory, default sqrt_info route: the compact form (above); the device expands each chunk behind its copy
+    const size_t per_win = sizeof(double) * REC_C_N * 10;
+    void *d_comp = nullptr;
+    if (dev_alloc_bytes(ctx, bt, &d_comp, per_win * (size_t)W) != VILO_OK) return VILO_ERR_HIP;
+    *compact_bytes = per_win * (size_t)W;
+    rc = upload_through_ring(ctx, (size_t)W, per_win,
+        [&](size_t w, char *to) {
+          const int nr = in[w].n_frames - 1;
+          double *dst = (double *)to;
+          for (int k = 0; k < nr; ++k) rec_compact(in[w].preint + k, dst + (size_t)REC_C_N * k);
+          if (nr < 10) memset(dst + (size_t)REC_C_N * nr, 0, sizeof(double) * REC_C_N * (size_t)(10 - nr));   // (intervals the window does not have: zero records)
+        },
+        [&](size_t c0, size_t cn, const char *src) {
+          return hipMemcpyAsync((char *)d_comp + per_win * c0, src, per_win * cn, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? VILO_OK : VILO_ERR_HIP;
+        },
+        [&](size_t c0, size_t cn) {
+          hipLaunchKernelGGL(k_expand_records, dim3((unsigned)(cn * 10)), dim3(256), 0, ctx->stream, (int)(cn * 10), (const double *)d_comp + (size_t)REC_C_N * 10 * c0,
+                             (vilo_preint *)d_pre + 10 * c0);
+        });
+    if (rc == VILO_OK && hipGetLastError() != hipSuccess) rc = VILO_ERR_HIP;
+  } else if (!host_rec.empty()) {
+    const size_t per_win = rec * 10;
+    rc = upload_through_ring(ctx, host_rec.size(), per_win,
+        [&](size_t i, char *to) {
+          const int w = host_rec[i];
+          memcpy(to, leg ? (const void *)in[w].preint : (const void *)in[w].preint_imu, rec * (size_t)(in[w].n_frames - 1));
+        },
+        [&](size_t c0, size_t cn, const char *src) {   // consecutive windows of the chunk that are consecutive in the batch go up in one copy
+          for (size_t i = 0, j; i < cn; i = j) {
+            for (j = i + 1; j < cn && host_rec[c0 + j] == host_rec[c0 + j - 1] + 1 && in[host_rec[c0 + j - 1]].n_frames == VILO_MAX_FRAMES;) ++j;
+            const size_t bytes_run = (j - i - 1) * per_win + rec * (size_t)(in[host_rec[c0 + j - 1]].n_frames - 1);
+            if (hipMemcpyAsync((char *)d_pre + per_win * (size_t)host_rec[c0 + i], src + per_win * i, bytes_run, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+          }
+          return VILO_OK;
+        },
+        [](size_t, size_t) {});
+  }
+  if (rc == VILO_OK && !g_ids.empty()) {
+    int *d_gi = nullptr, *d_gd = nullptr;
+    rc = dev_upload(ctx, bt, &d_gi, g_ids);
+    if (rc == VILO_OK) rc = dev_upload(ctx, bt, &d_gd, g_dst);
+    if (rc == VILO_OK) rc = vilo_launch_preint_gather(ctx, refs[0].preint_pool, (int)g_ids.size(), d_gi, d_gd, d_pre);
+  }
+  return rc;
+}
+
+// The records, their sqrt_info = chol(cov^-1)^T hoisted out of the iteration loop (the reference recomputes it on every
+// IMULegFactor::Evaluate, imu_leg_factor.cpp:197-198) and the windows a record without one fails
+int create_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, const vilo_resident_refs *refs, size_t *compact_bytes) {
+  BatchDev &D = bt->d;
+  const int W = bt->W;
+  const bool leg = in[0].use_leg != 0;
+  void *d_pre = nullptr;
+  if (dev_alloc_bytes(ctx, bt, &d_pre, (leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu)) * (size_t)W * 10) != VILO_OK) return VILO_ERR_HIP;   // arena: lives as long as the batch
+  bt->d_pre = d_pre; bt->leg = leg;
+  int rc = upload_records(ctx, bt, in, refs, d_pre, compact_bytes);
+  if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &bt->d_prep_bad, (size_t)W * 10);
+  D.prep_bad = bt->d_prep_bad;   // (per-interval flags of the records in force: the marginalisation looks at the intervals it uses)
+  if (rc == VILO_OK) rc = vilo_batch_prepare(ctx, bt);
+  // a covariance that is not positive definite has no sqrt_info: that window alone fails (termination FAILURE, like a non-finite
+  // IterationZero); the flag is looked at for live intervals only — folded per window on the device (no round trip through the host:
+  // a one-window batch is built for every image of a replay)
+  if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &D.win_bad, (size_t)W);
+  if (rc == VILO_OK) {
+    hipLaunchKernelGGL(k_fold_win_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bt->d_prep_bad, D.imu_skip, D.win_bad);
+    if (hipGetLastError() != hipSuccess) rc = VILO_ERR_HIP;
+  }
+  // (the uploads above came out of this call's host memory and the context's reusable staging: they are complete when it returns)
+  if (rc == VILO_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
+  return rc;
+}
+
+}  // namespace
+
+// refs (optional, [W]): device-resident preintegration objects / prior slots instead of the host records of the descs.
+// plan -> staging -> fill (batch_pack.hpp) -> allocate and upload -> records -> prepare and reset
 int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *init, vilo_batch **out) {
   if (!ctx || !in || !init || !out || W <= 0) return VILO_ERR_BAD_ARG;
   *out = nullptr;
   VILO_HIP(hipSetDevice(ctx->device));
-  vilo_batch *bt = new vilo_batch();
+  BatchGuard guard{ctx, new vilo_batch()};
+  vilo_batch *bt = guard.bt;
   bt->W = W;
   memset(&bt->d, 0, sizeof(BatchDev));
   const bool timing = getenv("VILO_HOST_TIMING") != nullptr;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_begin = now();
-  double t_prior = 0.0;
-  size_t rec_bytes_up = 0;   // bytes of preintegration records that crossed the bus when not the full records'
-  std::vector<WinMeta> wins(W);
-  std::vector<ChunkMeta> chunks;
-  std::vector<WaveMeta> waves;
-  std::vector<double> x0((size_t)W * XSTRIDE, 0.0), lam0;
-  std::vector<unsigned char> lm_s;   // start frame per landmark (device order)
-  std::vector<double> px0((size_t)W * 280, 0.0);
-  // J0 / r0 of the priors, packed n x n per window, staged for k_prior_pack (uninitialised storage: only n x n of a slot is read)
-  double *pJ = (double *)vilo_host_stage(ctx, 0, sizeof(double) * (size_t)W * 96 * 96), *pr0 = (double *)vilo_host_stage(ctx, 1, sizeof(double) * (size_t)W * 96);
-  bool any_prior = false;
-  std::vector<unsigned char> iskip((size_t)W * 10, 0);
-  std::vector<int> pmap((size_t)W * 96, 0), pbs((size_t)W * 40, 0), pbi((size_t)W * 40, 0), pbx((size_t)W * 40, 0), pbst((size_t)W * 40, 0);
-  int lm_total = 0, gram_total = 0;
-  size_t obs_total = 0, flags_total = 0;
-  bt->lm_off_host.resize(W);
-  bt->L_host.resize(W);
-
-  // ---- pass 1 (serial, light): validation, chunk / wave tables and every offset ----
-  for (int w = 0; w < W; ++w) {
-    const vilo_window_desc &d = in[w];
-    const vilo_window_state &s = init[w];
-    if (d.n_frames < 2 || d.n_frames > VILO_MAX_FRAMES || d.n_landmarks < 0 || d.n_landmarks > VILO_NUM_OF_F) {
-      ctx->err = "window sizes out of range"; vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG;
-    }
-    if ((d.use_leg != 0) != (in[0].use_leg != 0)) { ctx->err = "all windows of a batch must use the same IMU factor kind (use_leg)"; vilo_batch_destroy(ctx, bt); return VILO_ERR_UNSUPPORTED; }
-    const vilo_resident_refs *rf = refs ? refs + w : nullptr;
-    if (rf && rf->preint_pool && ((d.use_leg != 0) == (rf->preint_pool->kind != 0) || !rf->preint_ids || !rf->preint_sum_dt || rf->preint_pool != refs[0].preint_pool)) {
-      ctx->err = "resident preintegration: pool kind must match use_leg, one pool per batch"; vilo_batch_destroy(ctx, bt); return VILO_ERR_UNSUPPORTED;
-    }
-    if (rf && rf->prior_pool && rf->prior_pool != refs[0].prior_pool) { ctx->err = "one prior pool per batch"; vilo_batch_destroy(ctx, bt); return VILO_ERR_UNSUPPORTED; }
-    if (!d.use_leg && !d.preint_imu && !(rf && rf->preint_pool)) { vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG; }
-    if ((d.use_leg && !d.preint && !(rf && rf->preint_pool)) || !s.pose || !s.speed_bias || !s.leg_bias || !s.ex_pose || !s.td || (d.n_landmarks && (!s.inv_depth || !d.lm_start_frame || !d.lm_obs_offset || !d.obs || !d.obs_is_stereo))) {
-      vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG;
-    }
-    const int F = d.n_frames, L = d.n_landmarks;
-    // the observation table is indexed through lm_obs_offset: [0] = 0, non-decreasing, [L] = n_obs — a window that comes out of a file
-    // (vilo_window_io.h) is untrusted, and the packing below reads obs[11 * (offset + t)] for t < K
-    if (L > 0) {
-      bool ok = d.n_obs >= 0 && d.lm_obs_offset[0] == 0 && d.lm_obs_offset[L] == d.n_obs;
-      for (int l = 0; ok && l < L; ++l) ok = d.lm_obs_offset[l + 1] >= d.lm_obs_offset[l] && d.lm_start_frame[l] >= 0 && d.lm_start_frame[l] < F;
-      if (!ok) { ctx->err = "landmark observation table: lm_obs_offset must start at 0, not decrease and end at n_obs; start frames must lie in the window"; vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG; }
-    }
-    WinMeta &wm = wins[w];
-    memset(&wm, 0, sizeof(wm));
-    wm.n_frames = F; wm.L = L; wm.use_leg = d.use_leg; wm.pad = -1;
-    wm.lm_off = lm_total; wm.chunk_off = (int)chunks.size(); wm.gram_off = gram_total;
-    // use_leg == 0: the leg-bias blocks are not part of the problem (estimator.cpp:1071-1072): masked like constant blocks
-    wm.const_mask = ((d.leg_bias_const || !d.use_leg) ? CONST_LB : 0) | (d.ex_const ? CONST_EX : 0) | (d.td_const ? CONST_TD : 0);
-    bt->lm_off_host[w] = lm_total;
-    bt->L_host[w] = L;
-    // landmark chunks: group by start frame (a stable counting sort: list order preserved inside a group), <= 64 per chunk. The device
-    // order of the window's landmarks is perm_host[lm_total ..): a chunk's landmarks are its lm_off .. lm_off + n entries of it.
-    int local = 0;
-    {
-      int first[VILO_MAX_FRAMES + 1] = {0};
-      for (int l = 0; l < L; ++l) {
-        const int sf = d.lm_start_frame[l];
-        if (sf < 0 || sf >= F) { ctx->err = "landmark start_frame outside the window"; vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG; }
-        ++first[sf + 1];
-      }
-      for (int sf = 0; sf < F; ++sf) first[sf + 1] += first[sf];
-      const size_t base = bt->perm_host.size();
-      bt->perm_host.resize(base + L); lam0.resize(base + L); lm_s.resize(base + L);
-      int fill[VILO_MAX_FRAMES];
-      for (int sf = 0; sf < F; ++sf) fill[sf] = first[sf];
-      for (int l = 0; l < L; ++l) {
-        const int sf = d.lm_start_frame[l], at = fill[sf]++;
-        bt->perm_host[base + at] = l; lam0[base + at] = s.inv_depth[l]; lm_s[base + at] = (unsigned char)sf;
-      }
-      bt->obs_row_host.resize(base + L);
-      for (int i = 0; i < L; ++i) bt->obs_row_host[base + i] = bt->n_obs_rows + d.lm_obs_offset[bt->perm_host[base + i]];
-      if (L > 0) bt->n_obs_rows += d.lm_obs_offset[L];
-      for (int sf = 0; sf < F; ++sf) {
-        for (int c0 = first[sf]; c0 < first[sf + 1]; c0 += 64) {
-          const int n = std::min(64, first[sf + 1] - c0);
-          ChunkMeta cm;
-          memset(&cm, 0, sizeof(cm));
-          cm.win = w; cm.s = sf; cm.n = n; cm.lm_off = lm_total + local; cm.lm_local = local;
-          int kmax = 0;
-          for (int i = 0; i < n; ++i) {
-            const int l = bt->perm_host[base + c0 + i];
-            const int K = d.lm_obs_offset[l + 1] - d.lm_obs_offset[l];
-            if (K < 1 || sf + K > F) { ctx->err = "landmark observation range outside the window"; vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG; }
-            kmax = std::max(kmax, K);
-          }
-          cm.kmax = kmax;
-          cm.gram_off = gram_total;
-          gram_total += kmax;
-          local += n;
-          chunks.push_back(cm);
-        }
-      }
-    }
-    if (local != L) { ctx->err = "landmark start_frame outside the window"; vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG; }
-    wm.n_chunks = (int)chunks.size() - wm.chunk_off;
-    // pack the window's chunks into waves: consecutive chunks side by side, each at a lane multiple of 8, <= 4 per wave
-    wm.wave_off = (int)waves.size();
-    for (int c = wm.chunk_off; c < (int)chunks.size();) {
-      WaveMeta wv;
-      memset(&wv, 0, sizeof(wv));
-      wv.win = w;
-      int lanes = 0;
-      while (c < (int)chunks.size() && wv.nseg < 4) {
-        const int pad = (chunks[c].n + 7) & ~7;
-        if (lanes + pad > 64) break;
-        wv.seg_chunk[wv.nseg] = c; wv.seg_lane0[wv.nseg] = lanes;
-        wv.kmax = std::max(wv.kmax, chunks[c].kmax);
-        lanes += pad; ++wv.nseg; ++c;
-      }
-      wv.n_lanes = lanes;
-      wv.obs_off = (long long)obs_total;
-      wv.flag_off = (long long)flags_total;
-      obs_total += (size_t)wv.kmax * 11 * lanes;
-      flags_total += (size_t)wv.kmax * lanes;
-      waves.push_back(wv);
-    }
-    wm.n_waves = (int)waves.size() - wm.wave_off;
-    wm.n_gram = gram_total - wm.gram_off;
-    lm_total += L;
-    const vilo_prior *pr = vilo_win_prior(d, rf);
-    if (pr && pr->valid && pr->n > 0) {
-      if (pr->n > VILO_MAX_PRIOR_DIM || pr->n_blocks < 0 || pr->n_blocks > VILO_MAX_PRIOR_BLOCKS) { vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG; }
-      // block tables: sizes are the global sizes the estimator uses (1, 4, 7, 9), a block's local rows lie inside the prior, its id
-      // names a block kind and index that exist (kind * 16 + index; the assembly indexes its LDS image through these)
-      for (int k = 0; k < pr->n_blocks; ++k) {
-        const int gs = pr->block_size[k], ls = gs == 7 ? 6 : gs, idx = pr->block_idx[k], id = pr->block_id[k];
-        static const int kind_size[5] = {7, 9, 4, 7, 1};   // VILO_BLK_POSE, _SB, _LB, _EX, _TD
-        if (id < 0 || id >= 16 * 5) continue;   // (not a camera-side block — e.g. a feature: refused as unsupported, with its own message, by the packing pass)
-        if (gs != kind_size[id >> 4] || (id & 15) >= ((id >> 4) == VILO_BLK_EX ? 2 : (id >> 4) == VILO_BLK_TD ? 1 : VILO_MAX_FRAMES) || idx < 0 || idx + ls > pr->n) {
-          ctx->err = "prior block table out of range"; vilo_batch_destroy(ctx, bt); return VILO_ERR_BAD_ARG;
-        }
-      }
-      any_prior = true;
-    }
+  HostPack h((size_t)W);
+  vilo::PackPlan &P = h.plan;
+  for (int w = 0; w < W; ++w) h.res[w] = resolve_window(in[w], refs ? refs + w : nullptr, refs);
+  const vilo::PackStatus st = vilo::plan_batch(W, in, init, h.res.data(), ctx->compact_rows != 0, vilo::tuning(), P);
+  if (st.code != VILO_OK) {
+    if (st.msg) ctx->err = st.msg;
+    return st.code;
   }
-  t_prior = now() - t_begin;   // (pass 1's share of the packing time, for VILO_HOST_TIMING)
-  // ---- pass 2 (one host thread per slice of windows): the heavy copies — wave-packed observation image, states, prior staging ----
-  double *obs = (double *)vilo_host_stage(ctx, 2, sizeof(double) * std::max<size_t>(1, obs_total));
-  unsigned char *flags = (unsigned char *)vilo_host_stage(ctx, 3, std::max<size_t>(1, flags_total));
-  if (!pJ || !pr0 || !obs || !flags) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-  std::vector<int> win_err(W, 0);
-  auto fill_window = [&](int w) {
-    const vilo_window_desc &d = in[w];
-    const vilo_window_state &s = init[w];
-    WinMeta &wm = wins[w];
-    const int F = d.n_frames;
-    // states (vector2double layout)
-    double *xw = &x0[(size_t)w * XSTRIDE];
-    memcpy(xw + XO_POSE, s.pose, sizeof(double) * 7 * F);
-    memcpy(xw + XO_SB, s.speed_bias, sizeof(double) * 9 * F);
-    memcpy(xw + XO_LB, s.leg_bias, sizeof(double) * 4 * F);
-    for (int k = F; k < VILO_MAX_FRAMES; ++k) xw[XO_POSE + 7 * k + 6] = 1.0;
-    memcpy(xw + XO_EX, s.ex_pose, sizeof(double) * 14);
-    xw[XO_TD] = s.td[0];
-    for (int wi = wm.wave_off; wi < wm.wave_off + wm.n_waves; ++wi) {
-      const WaveMeta &wv = waves[wi];
-      const int lanes = wv.n_lanes;
-      double *ob = obs + wv.obs_off;
-      unsigned char *fl = flags + wv.flag_off;
-      memset(ob, 0, sizeof(double) * (size_t)wv.kmax * 11 * lanes);
-      memset(fl, 0, (size_t)wv.kmax * lanes);
-      for (int g = 0; g < wv.nseg; ++g) {
-        const ChunkMeta &cm = chunks[wv.seg_chunk[g]];
-        const int *ids = bt->perm_host.data() + cm.lm_off;   // the chunk's landmarks (window order)
-        for (int i = 0; i < cm.n; ++i) {
-          const int l = ids[i], lane = wv.seg_lane0[g] + i;
-          const int o0 = d.lm_obs_offset[l], K = d.lm_obs_offset[l + 1] - o0;
-          for (int t = 0; t < K; ++t) {
-            for (int f = 0; f < 11; ++f) ob[((size_t)t * 11 + f) * lanes + lane] = d.obs[(size_t)(o0 + t) * 11 + f];
-            fl[(size_t)t * lanes + lane] = (unsigned char)(1 | (d.obs_is_stereo[o0 + t] ? 2 : 0));
-          }
-        }
-      }
-    }
-    const vilo_resident_refs *rf = refs ? refs + w : nullptr;
-    for (int k = 0; k < 10; ++k) iskip[(size_t)w * 10 + k] = (k + 1 < F && !(vilo_win_sum_dt(d, rf, k) > 10.0)) ? 0 : 1;
-    // prior (MarginalizationFactor, marginalization_factor.cpp:335-395): block tables here, H = J0^T J0, b0 = J0^T r0, c0 = r0^T r0 in k_prior_pack
-    const vilo_prior *pr = vilo_win_prior(d, rf);
-    if (pr && pr->valid && pr->n > 0) {
-      const vilo_prior &p = *pr;
-      const int n = p.n;
-      wm.prior_n = n; wm.prior_nb = p.n_blocks;
-      int xo = 0, bframe = -1;
-      for (int k = 0; k < p.n_blocks; ++k) {
-        int soff = 0;
-        const int cd = prior_block_cd(p.block_id[k], &soff);
-        const int gs = p.block_size[k], ls = gs == 7 ? 6 : gs;
-        static const int kind_size[5] = {7, 9, 4, 7, 1};   // global sizes of VILO_BLK_POSE / SB / LB / EX / TD
-        const int kind = p.block_id[k] / 16;
-        if (p.block_id[k] < 0 || kind < 0 || kind > 4 || gs != kind_size[kind] || xo + gs > 280) { win_err[w] = 1; return; }
-        if (cd < 0 || p.block_idx[k] < 0 || p.block_idx[k] + ls > n) { win_err[w] = 1; return; }
-        for (int q = 0; q < k; ++q) {   // local index ranges must not overlap
-          const int lq = p.block_size[q] == 7 ? 6 : p.block_size[q];
-          if (p.block_idx[k] < p.block_idx[q] + lq && p.block_idx[q] < p.block_idx[k] + ls) { win_err[w] = 1; return; }
-        }
-        if (cd >= CD_B0) {
-          const int fr = (cd - CD_B0) / 13;
-          if (bframe >= 0 && bframe != fr) { win_err[w] = 2; return; }
-          bframe = fr;
-        }
-        pbs[(size_t)w * 40 + k] = gs; pbi[(size_t)w * 40 + k] = p.block_idx[k]; pbx[(size_t)w * 40 + k] = xo; pbst[(size_t)w * 40 + k] = soff;
-        for (int c = 0; c < ls; ++c) pmap[(size_t)w * 96 + p.block_idx[k] + c] = cd + c;
-        for (int c = 0; c < gs; ++c) px0[(size_t)w * 280 + xo + c] = p.x0[xo + c];
-        xo += gs;
-      }
-      wm.pad = bframe;
-      if (p.J0) {   // a pool slot keeps J0 / r0 on the device: gathered there, below
-        memcpy(pJ + (size_t)w * 96 * 96, p.J0, sizeof(double) * (size_t)n * n);
-        memcpy(pr0 + (size_t)w * 96, p.r0, sizeof(double) * n);
-      }
-    }
-  };
-  vilo::parallel_items(W, 8, fill_window, ctx->pool);   // (worker_pool.hpp: host threads parked between batches)
-  for (int w = 0; w < W; ++w)
-    if (win_err[w]) {
-      ctx->err = win_err[w] == 1 ? "unsupported prior block" : "prior couples speed/leg biases of two frames";
-      vilo_batch_destroy(ctx, bt);
-      return VILO_ERR_UNSUPPORTED;
-    }
+  const double t_plan = now() - t_begin;   // (the serial table pass's share of the packing time, for VILO_HOST_TIMING)
+  h.pJ = (double *)vilo_host_stage(ctx, 0, sizeof(double) * (size_t)W * 96 * 96);
+  h.pr0 = (double *)vilo_host_stage(ctx, 1, sizeof(double) * (size_t)W * 96);
+  h.obs = (double *)vilo_host_stage(ctx, 2, sizeof(double) * std::max<size_t>(1, P.obs_total));
+  h.flags = (unsigned char *)vilo_host_stage(ctx, 3, std::max<size_t>(1, P.flags_total));
+  if (!h.pJ || !h.pr0 || !h.obs || !h.flags) return VILO_ERR_HIP;
+  vilo::fill_batch(W, in, init, h.res.data(), P, {h.obs, h.flags, h.x0.data(), h.pmap.data(), h.pbs.data(), h.pbi.data(), h.pbx.data(), h.pbst.data(), h.px0.data(), h.pJ, h.pr0, h.iskip.data()},
+                   ctx->pool);   // (worker_pool.hpp: host threads parked between batches)
+  bt->lm_off_host = std::move(P.lm_off); bt->L_host = std::move(P.L); bt->perm_host = std::move(P.perm);
+  bt->obs_row_host = std::move(P.obs_row); bt->n_obs_rows = P.n_obs_rows;
   const double t_packed = now();
   // a lane of vilo_solve_windows' pipeline: the uploads of the lanes go one after the other at the link's rate (side by side every lane's
   // solve would start when ALL uploads are through); held until this batch's uploads are complete, i.e. to the end of the call
   std::unique_lock<std::mutex> dma_turn;
   if (ctx->dma_turn) dma_turn = std::unique_lock<std::mutex>(*ctx->dma_turn);
   BatchDev &D = bt->d;
-  D.W = W; D.n_chunks = (int)chunks.size(); D.n_lm = lm_total; D.n_gram = gram_total; D.n_waves = (int)waves.size();
-  // compact visual rows / Gram slots in the solve passes: td must be a constant block in every window (estimate_td: 0, all of the
-  // reference's configurations); vilo_set_compact_rows(ctx, 0) keeps the 23-column form
-  D.compact = ctx->compact_rows;
-  for (int w = 0; w < W; ++w)
-    if (!(wins[w].const_mask & CONST_TD)) D.compact = 0;
-  UploadBlob blob;
-  TRYB(blob.add(ctx, bt, &D.win, wins));
-  TRYB(blob.add(ctx, bt, &D.chunk, chunks));
-  TRYB(blob.add(ctx, bt, &D.wave, waves));
-  {
-    // launch order of the packed waves: by decreasing number of frames walked. A single-wave workgroup can only start on the SIMD the
-    // dispatcher's cyclic pointer names, so waves of mixed length in flight on one CU leave SIMDs idle behind a long one (measured: 2.7
-    // instead of 4 resident waves per CU); with equal lengths adjacent they retire in launch order and the longest ones do not form the tail.
-    std::vector<int> order(waves.size());
-    for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-    const int wo = vilo::tuning().wave_order;
-    if (wo >= 1) std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return waves[a].kmax > waves[c].kmax; });
-    if (wo == 2) {
-      size_t g0 = 0; int gi = 0;
-      while (g0 < order.size()) {
-        size_t g1 = g0;
-        while (g1 < order.size() && waves[order[g1]].kmax == waves[order[g0]].kmax) ++g1;
-        if (g1 - g0 > 8) std::rotate(order.begin() + g0, order.begin() + g0 + (gi % 8), order.begin() + g1);
-        g0 = g1; ++gi;
-      }
-    }
-    TRYB(blob.add(ctx, bt, &D.wave_order, order));
-  }
-  TRYB(blob.add(ctx, bt, &D.obs, obs, obs_total));
-  TRYB(blob.add(ctx, bt, &D.flags, flags, flags_total));
-  TRYB(blob.add(ctx, bt, &D.x0, x0));
-  TRYB(blob.add(ctx, bt, &D.lam0, lam0));
-  TRYB(blob.add(ctx, bt, &D.lm_s, lm_s));
-  TRYB(blob.add(ctx, bt, &D.lm_perm, bt->perm_host));
-  TRYB(dev_alloc(ctx, bt, &D.x, (size_t)W * XSTRIDE));
-  TRYB(dev_alloc(ctx, bt, &D.xc, (size_t)W * XSTRIDE));
-  TRYB(dev_alloc(ctx, bt, &D.lam, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lamc, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_E, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_gbuf[0], (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_gbuf[1], (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_dh2, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_y, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_scale, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_einv, (size_t)lm_total));
-  TRYB(dev_alloc(ctx, bt, &D.lm_w, (size_t)lm_total * 80));
-  // a landmark's coupling rows with the poses before its start frame are structural zeros: written here once, never again
-  if (hipMemsetAsync(D.lm_w, 0, sizeof(double) * (size_t)std::max(lm_total, 1) * 80, ctx->stream) != hipSuccess) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-  // few windows: one workgroup per (packed wave, frame) instead of per packed wave, so that the chip is not left to 3 waves per window
-  // (the landmark-side terms every such workgroup writes: all of them, zeros included — nothing reads an entry nobody wrote)
-  D.lm_part = nullptr;
-  D.full_regime = ctx->regime_full;
-  if (vilo::shape_takes_tpar(waves.size(), ctx->regime_full != 0, vilo::tuning())) TRYB(dev_alloc(ctx, bt, &D.lm_part, (size_t)lm_total * VILO_MAX_FRAMES * 2 * 21));
-  TRYB(dev_alloc(ctx, bt, &D.gram, (size_t)gram_total * VILO_GRAM));
-  TRYB(dev_alloc(ctx, bt, &D.chunk_cost, waves.size() * VILO_MAX_FRAMES));   // per (packed wave, frame offset) partial costs
-  TRYB(dev_alloc(ctx, bt, &D.prep, (size_t)W * 10));
-  TRYB(dev_alloc(ctx, bt, &D.imu_lin, (size_t)W * 10 * 31 * 39));
-  TRYB(dev_alloc(ctx, bt, &D.imu_raw, (size_t)W * 10 * 31 * 39));
-  if (hipMemsetAsync(D.imu_raw, 0, sizeof(double) * (size_t)W * 10 * 31 * 39, ctx->stream) != hipSuccess) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-  TRYB(dev_alloc(ctx, bt, &D.imu_gram, (size_t)W * 10 * 780));
-  TRYB(dev_alloc(ctx, bt, &D.imu_cost, (size_t)W * 10));
-  TRYB(blob.add(ctx, bt, &D.imu_skip, iskip));
-  TRYB(dev_alloc(ctx, bt, &D.prior_H, (size_t)W * 96 * 96));
-  TRYB(dev_alloc(ctx, bt, &D.prior_dense, (size_t)W * PD_N));
-  TRYB(dev_alloc(ctx, bt, &D.prior_hd, (size_t)W * 96));
-  TRYB(dev_alloc(ctx, bt, &D.prior_b0, (size_t)W * 96));
-  TRYB(dev_alloc(ctx, bt, &D.prior_c0, (size_t)W));
-  TRYB(blob.add(ctx, bt, &D.prior_x0, px0));
-  TRYB(blob.add(ctx, bt, &D.prior_map, pmap));
-  if (hipMemsetAsync(D.prior_dense, 0, sizeof(double) * (size_t)W * PD_N, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(D.prior_b0, 0, sizeof(double) * (size_t)W * 96, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(D.prior_c0, 0, sizeof(double) * (size_t)W, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(D.prior_H, 0, sizeof(double) * (size_t)W * 96 * 96, ctx->stream) != hipSuccess) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-  TRYB(blob.add(ctx, bt, &D.prior_bsize, pbs));
-  TRYB(blob.add(ctx, bt, &D.prior_bidx, pbi));
-  TRYB(blob.add(ctx, bt, &D.prior_bxoff, pbx));
-  TRYB(blob.add(ctx, bt, &D.prior_bstate, pbst));
-  TRYB(blob.flush(ctx, bt));   // D.win ... D.prior_bstate are device pointers from here on
-  TRYB(dev_alloc(ctx, bt, &D.cam_g, (size_t)W * CD_N));
-  TRYB(dev_alloc(ctx, bt, &D.cam_dh2, (size_t)W * CD_N));
-  TRYB(dev_alloc(ctx, bt, &D.cam_y, (size_t)W * CD_N));
-  TRYB(dev_alloc(ctx, bt, &D.cam_scale, (size_t)W * CD_N));
-  TRYB(dev_alloc(ctx, bt, &D.Lk, (size_t)W * 11 * 169));
-  TRYB(dev_alloc(ctx, bt, &D.TAg, (size_t)W * 11 * 169));
-  TRYB(dev_alloc(ctx, bt, &D.Cimg, (size_t)W * 3840));
-  TRYB(dev_alloc(ctx, bt, &D.Tk, (size_t)W * TK_N));
-  TRYB(dev_alloc(ctx, bt, &D.cam_gin, (size_t)W * CD_N));
-  TRYB(dev_alloc(ctx, bt, &D.Bimg, (size_t)W * BI_N));
-  TRYB(dev_alloc(ctx, bt, &D.st, (size_t)W));
-  TRYB(dev_alloc(ctx, bt, &D.status, 1));
-  TRYB(dev_alloc(ctx, bt, &D.lin_cur, (size_t)W));
-  if (hipMemsetAsync(D.status, 0, sizeof(int), ctx->stream) != hipSuccess || hipMemsetAsync(D.st, 0, sizeof(SolverState) * (size_t)W, ctx->stream) != hipSuccess) {
-    vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP;
-  }
-  if (any_prior) {
-    double *d_J = nullptr, *d_r = nullptr;
-    TRYB(dev_alloc(ctx, bt, &d_J, (size_t)W * 96 * 96));
-    TRYB(dev_alloc(ctx, bt, &d_r, (size_t)W * 96));
-    if (hipMemcpyAsync(d_J, pJ, sizeof(double) * (size_t)W * 96 * 96, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d_r, pr0, sizeof(double) * (size_t)W * 96, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-    if (refs && refs[0].prior_pool) {
-      std::vector<int> slot(W, -1);
-      for (int w = 0; w < W; ++w)
-        if (refs[w].prior_pool && refs[w].prior_slot >= 0 && refs[w].prior_slot < refs[w].prior_pool->n && wins[w].prior_n > 0) slot[w] = refs[w].prior_slot;
-      int *d_slot = nullptr;
-      TRYB(dev_upload(ctx, bt, &d_slot, slot));
-      hipLaunchKernelGGL(k_prior_gather, dim3(W), dim3(256), 0, ctx->stream, W, D.win, d_slot, refs[0].prior_pool->dJ, refs[0].prior_pool->dr, d_J, d_r);
-    }
-    {
-      const size_t pp_lds = sizeof(double) * (96 * 96 + 96);
-      if (!ctx->prior_attr_set) {
-        if (hipFuncSetAttribute((const void *)k_prior_pack, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp_lds) != hipSuccess) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-        ctx->prior_attr_set = true;
-      }
-      hipLaunchKernelGGL(k_prior_pack, dim3(W), dim3(256), pp_lds, ctx->stream, W, D.win, d_J, d_r, D.prior_map, D.prior_H, D.prior_b0, D.prior_c0, D.prior_dense);
-    }
-    if (hipGetLastError() != hipSuccess) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }
-  }
+  D.W = W; D.n_chunks = (int)P.chunks.size(); D.n_lm = P.lm_total; D.n_gram = P.gram_total; D.n_waves = (int)P.waves.size();
+  D.compact = P.compact;   // (vilo_set_compact_rows(ctx, 0) keeps the 23-column form)
+  int rc = create_device_buffers(ctx, bt, h);
+  if (rc == VILO_OK && P.any_prior) rc = upload_priors(ctx, bt, h, refs);
+  if (rc != VILO_OK) return rc;
   const double t_uploaded = now();
-  // hoist sqrt_info = chol(cov^-1)^T out of the iteration loop (the reference recomputes it on every
-  // IMULegFactor::Evaluate, imu_leg_factor.cpp:197-198)
-  {
-    const bool leg = in[0].use_leg != 0;
-    void *d_pre = nullptr;
-    const size_t rec = leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu);
-    const size_t bytes = rec * (size_t)W * 10;
-    if (dev_alloc_bytes(ctx, bt, &d_pre, bytes) != VILO_OK) { vilo_batch_destroy(ctx, bt); return VILO_ERR_HIP; }   // arena: lives as long as the batch
-    int rc = VILO_OK;
-    // records go from the caller's arrays straight to the device (a staged host copy of W x 156 KB costs more than the W copies)
-    bool partial = false;
-    for (int w = 0; w < W; ++w) partial = partial || in[w].n_frames < VILO_MAX_FRAMES;
-    if (partial && hipMemsetAsync(d_pre, 0, bytes, ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
-    std::vector<int> g_ids, g_dst, host_rec;   // host_rec: windows whose records come out of the caller's arrays
-    for (int w = 0; w < W && rc == VILO_OK; ++w) {
-      if (refs && refs[w].preint_pool) {
-        for (int k = 0; k + 1 < in[w].n_frames; ++k) {
-          const int id = refs[w].preint_ids[k];
-          if (id < 0 || id >= refs[w].preint_pool->n) { rc = VILO_ERR_BAD_ARG; break; }
-          g_ids.push_back(id); g_dst.push_back(w * 10 + k);
-        }
-        continue;
-      }
-      host_rec.push_back(w);
-    }
-    if (rc == VILO_OK && leg && (int)host_rec.size() == W && ctx->sqrt_info_mode == 0 && !vilo::tuning().full_record_upload) {
-      // every window's records from host memory, default sqrt_info route: the compact form (above) through the two page-locked chunks, the
-      // worker pool gathering chunk k + 1 while the DMA engine reads chunk k; the device expands each chunk behind its copy
-      const size_t per_win = sizeof(double) * REC_C_N * 10, chunk_w = std::max<size_t>(1, ((size_t)32 << 20) / per_win);
-      char *ring[2] = {(char *)vilo_host_stage(ctx, 4, per_win * chunk_w), (char *)vilo_host_stage(ctx, 5, per_win * chunk_w)};
-      if (!ctx->rec_ev[0]) { (void)hipEventCreateWithFlags(&ctx->rec_ev[0], hipEventDisableTiming); (void)hipEventCreateWithFlags(&ctx->rec_ev[1], hipEventDisableTiming); }
-      void *d_comp = nullptr;
-      if (!ring[0] || !ring[1] || !ctx->rec_ev[0] || !ctx->rec_ev[1] || dev_alloc_bytes(ctx, bt, &d_comp, per_win * (size_t)W) != VILO_OK) rc = VILO_ERR_HIP;
-      bool used[2] = {false, false};
-      for (size_t c0 = 0, ci = 0; rc == VILO_OK && c0 < (size_t)W; c0 += chunk_w, ++ci) {
-        const int sl = (int)(ci & 1);
-        const size_t cn = std::min(chunk_w, (size_t)W - c0);
-        if (used[sl] && hipEventSynchronize(ctx->rec_ev[sl]) != hipSuccess) { rc = VILO_ERR_HIP; break; }
-        vilo::parallel_items((int)cn, 4, [&](int i) {
-          const int w = (int)c0 + i, nr = in[w].n_frames - 1;
-          double *dst = (double *)(ring[sl] + per_win * (size_t)i);
-          for (int k = 0; k < nr; ++k) rec_compact(in[w].preint + k, dst + (size_t)REC_C_N * k);
-          if (nr < 10) memset(dst + (size_t)REC_C_N * nr, 0, sizeof(double) * REC_C_N * (size_t)(10 - nr));   // (intervals the window does not have: zero records, as before)
-        }, ctx->pool);
-        if (hipMemcpyAsync((char *)d_comp + per_win * c0, ring[sl], per_win * cn, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = VILO_ERR_HIP; break; }
-        if (hipEventRecord(ctx->rec_ev[sl], ctx->stream) != hipSuccess) { rc = VILO_ERR_HIP; break; }
-        used[sl] = true;
-        hipLaunchKernelGGL(k_expand_records, dim3((unsigned)(cn * 10)), dim3(256), 0, ctx->stream, (int)(cn * 10), (const double *)d_comp + (size_t)REC_C_N * 10 * c0,
-                           (vilo_preint *)d_pre + 10 * c0);
-      }
-      if (rc == VILO_OK && hipGetLastError() != hipSuccess) rc = VILO_ERR_HIP;
-      rec_bytes_up = per_win * (size_t)W;
-    } else if (rc == VILO_OK && !host_rec.empty()) {
-      // The caller's records (156 KB per window, pageable) go up through two page-locked chunks of the context: the worker pool copies
-      // chunk k + 1 into one while the DMA engine reads chunk k out of the other. (One hipMemcpyAsync per window straight from the caller's
-      // arrays moved 640 MB of a 4096-window batch at 11.5 GB/s — the runtime's own bounce buffer, one thread.)
-      const size_t per_win = rec * 10, chunk_w = std::max<size_t>(1, ((size_t)32 << 20) / per_win);
-      char *ring[2] = {(char *)vilo_host_stage(ctx, 4, per_win * chunk_w), (char *)vilo_host_stage(ctx, 5, per_win * chunk_w)};
-      if (!ctx->rec_ev[0]) { (void)hipEventCreateWithFlags(&ctx->rec_ev[0], hipEventDisableTiming); (void)hipEventCreateWithFlags(&ctx->rec_ev[1], hipEventDisableTiming); }
-      bool used[2] = {false, false};
-      if (!ring[0] || !ring[1] || !ctx->rec_ev[0] || !ctx->rec_ev[1]) rc = VILO_ERR_HIP;
-      for (size_t c0 = 0, ci = 0; rc == VILO_OK && c0 < host_rec.size(); c0 += chunk_w, ++ci) {
-        const int sl = (int)(ci & 1);
-        const size_t cn = std::min(chunk_w, host_rec.size() - c0);
-        if (used[sl] && hipEventSynchronize(ctx->rec_ev[sl]) != hipSuccess) { rc = VILO_ERR_HIP; break; }
-        vilo::parallel_items((int)cn, 4, [&](int i) {
-          const int w = host_rec[c0 + i];
-          const void *src = leg ? (const void *)in[w].preint : (const void *)in[w].preint_imu;
-          memcpy(ring[sl] + per_win * (size_t)i, src, rec * (size_t)(in[w].n_frames - 1));
-        }, ctx->pool);
-        // consecutive windows of the chunk that are consecutive in the batch go up in one copy
-        for (size_t i = 0; i < cn && rc == VILO_OK;) {
-          size_t j = i + 1;
-          while (j < cn && host_rec[c0 + j] == host_rec[c0 + j - 1] + 1 && in[host_rec[c0 + j - 1]].n_frames == VILO_MAX_FRAMES) ++j;
-          const size_t bytes_run = (j - i - 1) * per_win + rec * (size_t)(in[host_rec[c0 + j - 1]].n_frames - 1);
-          if (hipMemcpyAsync((char *)d_pre + per_win * (size_t)host_rec[c0 + i], ring[sl] + per_win * i, bytes_run, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
-          i = j;
-        }
-        if (rc == VILO_OK && hipEventRecord(ctx->rec_ev[sl], ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
-        used[sl] = true;
-      }
-    }
-    if (rc == VILO_OK && !g_ids.empty()) {
-      int *d_gi = nullptr, *d_gd = nullptr;
-      rc = dev_upload(ctx, bt, &d_gi, g_ids);
-      if (rc == VILO_OK) rc = dev_upload(ctx, bt, &d_gd, g_dst);
-      if (rc == VILO_OK) rc = vilo_launch_preint_gather(ctx, refs[0].preint_pool, (int)g_ids.size(), d_gi, d_gd, d_pre);
-    }
-    bt->d_pre = d_pre; bt->leg = leg;
-    if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &bt->d_prep_bad, (size_t)W * 10);
-    D.prep_bad = bt->d_prep_bad;   // (per-interval flags of the records in force: the marginalisation looks at the intervals it uses)
-    if (rc == VILO_OK) rc = vilo_batch_prepare(ctx, bt);
-    // a covariance that is not positive definite has no sqrt_info: that window alone fails (termination FAILURE, like a non-finite
-    // IterationZero); the flag is looked at for live intervals only — folded per window on the device (no round trip through the host:
-    // a one-window batch is built for every image of a replay)
-    if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &D.win_bad, (size_t)W);
-    if (rc == VILO_OK) {
-      hipLaunchKernelGGL(k_fold_win_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bt->d_prep_bad, D.imu_skip, D.win_bad);
-      if (hipGetLastError() != hipSuccess) rc = VILO_ERR_HIP;
-    }
-    // (the uploads above came out of this call's host vectors and the context's reusable staging: they are complete when it returns)
-    if (rc == VILO_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
-    if (rc != VILO_OK) { vilo_batch_destroy(ctx, bt); return rc; }
-  }
+  size_t rec_bytes_up = 0;
+  rc = create_records(ctx, bt, in, refs, &rec_bytes_up);
+  if (rc != VILO_OK) return rc;
   const double t_prep = now();
-  int rc = vilo_batch_reset(ctx, bt);
-  if (rc != VILO_OK) { vilo_batch_destroy(ctx, bt); return rc; }
+  rc = vilo_batch_reset(ctx, bt);
+  if (rc != VILO_OK) return rc;
   ctx->last_create_ms[0] = now() - t_begin; ctx->last_create_ms[1] = t_packed - t_begin; ctx->last_create_ms[2] = t_uploaded - t_packed; ctx->last_create_ms[3] = t_prep - t_uploaded;
-  ctx->last_create_bytes = (double)(sizeof(double) * (obs_total + (size_t)W * XSTRIDE + (any_prior ? (size_t)W * (96 * 96 + 96) : 0)) + flags_total +
+  ctx->last_create_bytes = (double)(sizeof(double) * (P.obs_total + (size_t)W * XSTRIDE + (P.any_prior ? (size_t)W * (96 * 96 + 96) : 0)) + P.flags_total +
                                     (rec_bytes_up ? rec_bytes_up : (in[0].use_leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu)) * (size_t)W * 10));
   if (timing)
-    fprintf(stderr, "[vilo_batch_create] W=%d pack %.2f ms (of which the serial table pass %.2f) alloc+upload %.2f ms preint %.2f ms reset %.2f ms\n", W, t_packed - t_begin, t_prior,
+    fprintf(stderr, "[vilo_batch_create] W=%d pack %.2f ms (of which the serial table pass %.2f) alloc+upload %.2f ms preint %.2f ms reset %.2f ms\n", W, t_packed - t_begin, t_plan,
             t_uploaded - t_packed, t_prep - t_uploaded, now() - t_prep);
-  *out = bt;
+  *out = guard.release();
   return VILO_OK;
 }
 

@@ -149,31 +149,33 @@ def test_a_bad_covariance_only_spoils_the_marginalisations_that_use_its_factor(c
     assert summ[0].termination == 2
 
 
-def test_mutated_window_tables_never_reach_the_packing_loops(ctx, cfg, ocfg):
+def test_mutated_window_tables_never_reach_the_packing_loops(ctx, cfg, ocfg, tmp_path):
     """A window that comes out of a file is untrusted (include/vilo_window_io.h bounds its counts by the file's size, nothing more): the tables
     vilo_batch_create indexes through — lm_obs_offset into the observations, lm_start_frame into the frames, the prior's block table into
     the prior and, on the device, into the assembly's LDS image — are checked before anything is packed. 400 seeded
     mutations of one table entry each: every call returns — OK with a finite result where the mutation happened to be harmless,
-    BAD_ARG / UNSUPPORTED with a message otherwise — and a good window solved afterwards on the same context gives what it gave before."""
+    BAD_ARG / UNSUPPORTED with a message otherwise — and a good window solved afterwards on the same context gives what it gave before.
+    The status of every mutation is the one the packing stage alone gives the same window on a CPU (tests/test_batch_pack.py: the checker
+    under the undefined-behaviour sanitizer); NUMERIC can only arise after packing, so it counts as the packer's OK."""
     from cerberus_amd import api
+    from test_batch_pack import build_checker, checker_statuses, table_mutations
     ref = _win(cfg, ocfg, n_landmarks=30, seed=77)
     want = api.Context.solve_windows(ctx, [ref], api.default_solve_opts(True, 3))[0].final_cost
-    rng = np.random.default_rng(11)
+    on_cpu = checker_statuses(build_checker(tmp_path), cfg, ref, str(tmp_path / "w.bin"))
     outcomes = {OK: 0, BAD_ARG: 0, UNSUPPORTED: 0, NUMERIC: 0}
-    for k in range(400):
+    for k, (table, index, big) in enumerate(table_mutations(ref.L, ref.prior.struct.n_blocks)):
         w = _win(cfg, ocfg, n_landmarks=30, seed=77)
         what = k % 5
-        big = int(rng.choice([-1, -7, 1 << 20, 1 << 30, 12, 97, 255, 11, 86, 87]))
         if what == 0:
-            w.lm_obs_offset[rng.integers(0, w.L + 1)] = big
+            w.lm_obs_offset[index] = big
         elif what == 1:
-            w.lm_start_frame[rng.integers(0, w.L)] = big
+            w.lm_start_frame[index] = big
         elif what == 2:
-            w.prior.struct.block_idx[rng.integers(0, w.prior.struct.n_blocks)] = big
+            w.prior.struct.block_idx[index] = big
         elif what == 3:
-            w.prior.struct.block_size[rng.integers(0, w.prior.struct.n_blocks)] = big
+            w.prior.struct.block_size[index] = big
         else:
-            w.prior.struct.block_id[rng.integers(0, w.prior.struct.n_blocks)] = big
+            w.prior.struct.block_id[index] = big
         rc, summ = _solve_rc(ctx, [w])
         assert rc in outcomes, (k, what, big, rc)
         outcomes[rc] += 1
@@ -181,6 +183,7 @@ def test_mutated_window_tables_never_reach_the_packing_loops(ctx, cfg, ocfg):
             assert len(api.lib().vilo_last_error(ctx.h)) > 0
         if rc == OK:
             assert np.isfinite(summ[0].final_cost)
+        assert (OK if rc == NUMERIC else rc) == on_cpu[k][0], (k, table, index, big, rc, on_cpu[k])
     assert outcomes[BAD_ARG] + outcomes[UNSUPPORTED] > 300, outcomes     # (most single-entry mutations break a table)
     again = _win(cfg, ocfg, n_landmarks=30, seed=77)
     assert ctx.solve_windows([again], api.default_solve_opts(True, 3))[0].final_cost == want
