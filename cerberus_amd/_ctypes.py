@@ -115,7 +115,15 @@ class WindowGradient(C.Structure):
                 ("pad", C.c_int32)]
 
 
-GRAD_STATE = 222   # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
+class TriangulateOpts(C.Structure):
+    """vilo_triangulate_opts (24 bytes)"""
+    _fields_ = [("init_depth", C.c_double), ("stereo", C.c_int32), ("select", C.c_int32), ("write", C.c_int32), ("pad", C.c_int32)]
+
+
+TRI_SELECT = {"unset": 0, "all": 1, "mask": 2}   # VILO_TRI_*
+TRI_SELECTED, TRI_STEREO, TRI_FALLBACK, TRI_NOT_FINITE = 1, 2, 4, 8   # bits of a landmark's flags
+
+GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 
 # vilo_debug_batch_path: code -> name per axis (include/vilo_gpu.h); "none": the step was not launched

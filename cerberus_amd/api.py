@@ -34,6 +34,7 @@ def lib():
         L.vilo_last_covariance_ms.restype = C.c_double
         L.vilo_last_residuals_ms.restype = C.c_double
         L.vilo_last_gradient_ms.restype = C.c_double
+        L.vilo_last_triangulate_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -132,6 +133,40 @@ def _gradient(ctx, descs, state, diag, landmarks, call):
                     a["status"], sg, sd, lg, ld, offsets)
 
 
+Triangulation = collections.namedtuple("Triangulation", "depth flags offsets shift_inv_depth")
+
+
+def triangulate_opts(n_landmarks, select="unset", mask=None, write=False, init_depth=5.0, stereo=True):
+    """(T.TriangulateOpts, mask as a contiguous uint8 array or None) of a triangulate call over n_landmarks landmarks; needs no device.
+    select: 'unset' (inverse depth not positive), 'all', or 'mask' with mask [n_landmarks] (non-zero: selected)."""
+    if select not in T.TRI_SELECT:
+        raise ValueError("select must be one of %s" % sorted(T.TRI_SELECT))
+    if (select == "mask") != (mask is not None):
+        raise ValueError("select='mask' and a mask go together")
+    init_depth = float(init_depth)
+    if not (np.isfinite(init_depth) and init_depth > 0.0):
+        raise ValueError("init_depth must be finite and > 0")
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape != (n_landmarks,):
+            raise ValueError("mask must have one entry per landmark of the call (%d), got shape %s" % (n_landmarks, mask.shape))
+    o = T.TriangulateOpts()
+    o.init_depth, o.stereo, o.select, o.write, o.pad = init_depth, 1 if stereo else 0, T.TRI_SELECT[select], 1 if write else 0, 0
+    return o, mask
+
+
+def _triangulate(ctx, descs, select, mask, write, init_depth, stereo, shift, call):
+    n = len(descs)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    L = int(offsets[-1])
+    o, mask = triangulate_opts(L, select, mask, write, init_depth, stereo)
+    depth, flags = np.zeros(L), np.zeros(L, np.uint8)
+    sh = np.zeros(L) if shift else None
+    ctx._check(call(C.byref(o), None if mask is None else T.u8ptr(mask), _p(depth), T.u8ptr(flags), _p(sh)))
+    return Triangulation(depth, flags, offsets, sh)
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -215,6 +250,14 @@ class Batch:
         extrinsics 2 x 6, td) or None, lm_grad / lm_diag [sum L] (window w's landmarks: offsets[w] .. offsets[w + 1], in its own order) or
         None, offsets [W + 1]). state / landmarks leave the arrays of that side out, diag the two diagonals. The batch is left as it was."""
         return _gradient(self.ctx, self._descs, state, diag, landmarks, lambda *out: lib().vilo_batch_gradient(self.ctx.h, self.handle, *out))
+
+    def triangulate(self, select="unset", mask=None, write=False, init_depth=5.0, stereo=True, shift=False):
+        """vilo_batch_triangulate at the batch's device state: Triangulation(depth [sum L], flags [sum L] (T.TRI_* bits), offsets [W + 1]
+        (window w's landmarks: offsets[w] .. offsets[w + 1], in its own order), shift_inv_depth [sum L] or None). select: 'unset' (inverse
+        depth not positive), 'all', 'mask' (mask [sum L] non-zero). write=True stores 1 / depth as the current inverse depth of the selected
+        landmarks; otherwise the batch is left as it was."""
+        return _triangulate(self.ctx, self._descs, select, mask, write, init_depth, stereo, shift,
+                            lambda *a: lib().vilo_batch_triangulate(self.ctx.h, self.handle, *a))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -530,6 +573,16 @@ class Context:
         for i, w in enumerate(windows):
             descs[i], states[i] = w.desc(T)
         return _gradient(self, descs, state, diag, landmarks, lambda *out: lib().vilo_window_gradient(self.h, n, descs, states, *out))
+
+    def window_triangulate(self, windows, select="unset", mask=None, write=False, init_depth=5.0, stereo=True, shift=False):
+        """vilo_window_triangulate: the depths of host windows' landmarks at their current state arrays (see Batch.triangulate); with
+        write=True the windows' inv_depth arrays receive the new values."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _triangulate(self, descs, select, mask, write, init_depth, stereo, shift,
+                            lambda *a: lib().vilo_window_triangulate(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

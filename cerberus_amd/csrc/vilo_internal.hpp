@@ -44,7 +44,8 @@ struct vilo_ctx {
   double last_cov_ms = 0.0;        // GPU time of the last vilo_batch_covariance (linearisation + k_covariance)
   double last_resid_ms = 0.0;      // GPU time of the last vilo_batch_residuals
   double last_grad_ms = 0.0;       // GPU time of the last vilo_batch_gradient (linearisation + k_gradient)
-  int marg_general_count = 0;      // windows of the last vilo_marginalize that took the global-memory eigen path
+  double last_tri_ms = 0.0;        // GPU time of the last vilo_batch_triangulate (k_triangulate)
+  int marg_general_count = 0;     // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
   // per-kernel HIP-event timing of the solve pipeline (vilo_set_profiling)

@@ -506,6 +506,55 @@ int vilo_window_gradient(vilo_ctx *ctx, int n_windows, const vilo_window_desc *i
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_gradient: linearisation + k_gradient, without the copies out. */
 double vilo_last_gradient_ms(const vilo_ctx *ctx);
 
+/* ---- landmark depths from the current poses (FeatureManager::triangulate, feature_manager.cpp:302-382 with triangulatePoint :198-212; the
+ * arithmetic of FeatureManager::removeBackShiftDepth :450-479) ----
+ * State: the batch's current state, what vilo_batch_download returns. Rotation matrices are taken from the normalised quaternions, as
+ * vilo_batch_residuals' reprojection error takes them. Per landmark, concatenated window by window, inside a window in the caller's
+ * vilo_window_desc order (as vilo_batch_landmark_covariance):
+ *   depth  a selected landmark: localPoint.z() of the reference's branch if it is positive, else init_depth. The stereo branch applies when
+ *          opts->stereo is set and the landmark's first observation is stereo: left and right camera of the start frame ([R0^T | -R0^T t0] as
+ *          :312-325 forms it), the first observation's point and pointRight. Otherwise the left camera of the start frame and of the next
+ *          frame, with the first two observations' point. The point is the right singular vector of the smallest singular value of
+ *          triangulatePoint's 4 x 4 design matrix. (The reference's multi-view branch below :383 is not reachable for a landmark with two
+ *          observations and is not built; a landmark with a single mono observation is never selected.)
+ *          An unselected landmark: 1 / inv_depth of the current state, unchanged.
+ *   flags  bit 0: selected; bit 1: the stereo branch was taken; bit 2: the init_depth fallback was taken (localPoint.z() not positive);
+ *          bit 3: localPoint.z() is not finite.
+ *   shift_inv_depth (optional)  removeBackShiftDepth on the inverse depth the call leaves (after the write-back when opts->write is set): for a
+ *          landmark with start frame 0, pts_j = new_R^T (marg_R (point / inv_depth) + marg_P - new_P) with the marg pose the left camera of
+ *          frame 0 and the new pose the left camera of frame 1: 1 / pts_j.z if that is positive, else 1 / init_depth. Every other landmark:
+ *          its inverse depth, unchanged. Erasing tracks and shifting start frames stays with the host's feature window.
+ * opts->select: VILO_TRI_UNSET the landmarks whose inverse depth is not positive (the reference's `estimated_depth > 0` test), VILO_TRI_ALL every
+ * landmark, VILO_TRI_MASK those with mask[l] != 0 (mask [sum L], same order as the outputs).
+ * Side effects: with opts->write == 0 none (the guarantee of vilo_batch_residuals). With opts->write == 1 the current inverse depth of every
+ * selected landmark becomes 1 / depth and nothing else changes: not the uploaded initial state vilo_batch_reset restores, not the camera-side
+ * state, the records or the prior; a following vilo_batch_solve starts from the new values. The call's device memory is returned when it
+ * returns. Every output of a landmark is bitwise independent of the batch its window shares and of the window's position in it.
+ * A batch without landmarks: VILO_OK, the arrays are not touched. flags and shift_inv_depth may be NULL to leave them out; opts NULL:
+ * vilo_default_triangulate_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx or batch, NULL depth with landmarks present, VILO_TRI_MASK without a mask, an unknown select,
+ * init_depth not finite or not positive. */
+#define VILO_TRI_UNSET 0
+#define VILO_TRI_ALL 1
+#define VILO_TRI_MASK 2
+typedef struct {
+  double init_depth;   /* INIT_DEPTH, 5.0 (hardware_a1_vilo_config.yaml) */
+  int32_t stereo;      /* STEREO, 1 */
+  int32_t select;      /* VILO_TRI_* */
+  int32_t write;       /* 1: the batch's current inverse depth of every selected landmark becomes 1 / depth */
+  int32_t pad;
+} vilo_triangulate_opts;
+void vilo_default_triangulate_opts(vilo_triangulate_opts *o);
+
+int vilo_batch_triangulate(vilo_ctx *ctx, vilo_batch *batch, const vilo_triangulate_opts *opts, const uint8_t *mask, double *depth,
+                           uint8_t *flags, double *shift_inv_depth);
+/* The same for host windows at the given states: one batch is created and destroyed; with opts->write the new inverse depths are written
+ * into state[w].inv_depth. */
+int vilo_window_triangulate(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state,
+                            const vilo_triangulate_opts *opts, const uint8_t *mask, double *depth, uint8_t *flags, double *shift_inv_depth);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_triangulate: k_triangulate, without the copies. */
+double vilo_last_triangulate_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
