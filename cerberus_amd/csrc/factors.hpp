@@ -375,9 +375,10 @@ VD void imu_raw(const PreintHead &P, double g_norm, const double *pose_i, const 
 #define IB_RES 63     // residual (31, padded to 32)
 #define IB_ONE 95     // 1.0
 #define IB_N 96
-// pool: IB_N doubles. leg: IMULegFactor (31 residuals), else IMUFactor (15). Returns T = sum_dt.
+// pool: IB_N doubles, entry e at pool[e * ps] (ps = 1: one factor's pool; ps = number of factors: entry-major over a batch).
+// leg: IMULegFactor (31 residuals), else IMUFactor (15; the leg-only entries are not written). Returns T = sum_dt.
 VD double imu_blocks(const PreintHead &P, double g_norm, bool leg, const double *pose_i, const double *sb_i, const double *lb_i,
-                     const double *pose_j, const double *sb_j, const double *lb_j, double *pool) {
+                     const double *pose_j, const double *sb_j, const double *lb_j, double *pool, size_t ps = 1) {
   const v3 G = mk3(0, 0, g_norm);
   const v3 Pi = ld3(pose_i), Vi = ld3(sb_i), Bai = ld3(sb_i + 3), Bgi = ld3(sb_i + 6);
   const v3 Pj = ld3(pose_j), Vj = ld3(sb_j), Baj = ld3(sb_j + 3), Bgj = ld3(sb_j + 6);
@@ -392,35 +393,35 @@ VD double imu_blocks(const PreintHead &P, double g_norm, bool leg, const double 
   const quat Qi_inv = qinv(Qi);
   const v3 a_p = qrot(Qi_inv, G * (0.5 * T * T) + Pj - Pi - Vi * T);
   const v3 a_v = qrot(Qi_inv, G * T + Vj - Vi);
-  double *r = pool + IB_RES;
-  st3(r + 0, a_p - cp);
-  st3(r + 3, qvec(qmul(qinv(cq), qmul(Qi_inv, Qj))) * 2.0);
-  st3(r + 6, a_v - cv);
+  auto res3 = [&](int q, const v3 &v) { pool[(IB_RES + q) * ps] = v.x; pool[(IB_RES + q + 1) * ps] = v.y; pool[(IB_RES + q + 2) * ps] = v.z; };
+  res3(0, a_p - cp);
+  res3(3, qvec(qmul(qinv(cq), qmul(Qi_inv, Qj))) * 2.0);
+  res3(6, a_v - cv);
   if (leg) {
     const v3 dP = qrot(Qi_inv, Pj - Pi);
     for (int j = 0; j < 4; ++j) {
       const double drho = lb_i[j] - P.lin_rho[j];
       const v3 ceps = ld3(P.delta_eps + 3 * j) + ldm(P.dep_dbg[j]) * dbg + ld3(P.dep_drho[j]) * drho;
-      st3(r + 9 + 3 * j, dP - ceps);
-      r[27 + j] = lb_j[j] - lb_i[j];
+      res3(9 + 3 * j, dP - ceps);
+      pool[(IB_RES + 27 + j) * ps] = lb_j[j] - lb_i[j];
     }
-    st3(r + 21, Baj - Bai);
-    st3(r + 24, Bgj - Bgi);
+    res3(21, Baj - Bai);
+    res3(24, Bgj - Bgi);
     const m3 skdP = skew(dP);
-    for (int e = 0; e < 9; ++e) pool[IB_SKDP + e] = skdP.a[e];
+    for (int e = 0; e < 9; ++e) pool[(IB_SKDP + e) * ps] = skdP.a[e];
   } else {
-    st3(r + 9, Baj - Bai);
-    st3(r + 12, Bgj - Bgi);
+    res3(9, Baj - Bai);
+    res3(12, Bgj - Bgi);
   }
   const m3 RiT = qR(Qi_inv), skap = skew(a_p), skav = skew(a_v);
   const m3 qlqr = QleftQright33(qmul(qinv(Qj), Qi), cq);
   const m3 qldq = Qleft33(qmul(qmul(qinv(Qj), Qi), delta_q)) * dq_dbg;
   const m3 ql2 = Qleft33(qmul(qmul(qinv(cq), Qi_inv), Qj));
   for (int e = 0; e < 9; ++e) {
-    pool[IB_RIT + e] = RiT.a[e]; pool[IB_SKAP + e] = skap.a[e]; pool[IB_SKAV + e] = skav.a[e];
-    pool[IB_QLQR + e] = qlqr.a[e]; pool[IB_QLDQ + e] = qldq.a[e]; pool[IB_QL2 + e] = ql2.a[e];
+    pool[(IB_RIT + e) * ps] = RiT.a[e]; pool[(IB_SKAP + e) * ps] = skap.a[e]; pool[(IB_SKAV + e) * ps] = skav.a[e];
+    pool[(IB_QLQR + e) * ps] = qlqr.a[e]; pool[(IB_QLDQ + e) * ps] = qldq.a[e]; pool[(IB_QL2 + e) * ps] = ql2.a[e];
   }
-  pool[IB_ONE] = 1.0;
+  pool[IB_ONE * ps] = 1.0;
   return T;
 }
 
@@ -464,6 +465,49 @@ constexpr ImuGatherTable imu_gather_table(bool leg) {
 static_assert(offsetof(PreintHead, dp_dba) == 33 * 8 && offsetof(PreintHead, dp_dbg) == 42 * 8 && offsetof(PreintHead, dv_dba) == 60 * 8 &&
               offsetof(PreintHead, dv_dbg) == 69 * 8 && offsetof(PreintHead, dep_dbg) == 78 * 8 && offsetof(PreintHead, dep_drho) == 114 * 8,
               "head offsets used by imu_gather_table");
+
+// The same table in the order the whitening's lanes read it. Lane l of the wave (lr = l % 16, lk = l / 16) holds, as the B operand of
+// k-step kk and column tile J, entry (row 4 kk + lk, column 16 J + lr) of the image: its 24 entries (index 3 kk + J) side by side, two
+// per 32-bit word, so a lane fetches them with three 16-byte loads instead of 24 two-byte ones.
+#define IMU_LANE_WORDS 12
+struct alignas(16) ImuLaneGather { unsigned w[64 * IMU_LANE_WORDS]; };
+constexpr ImuLaneGather imu_lane_gather_table(bool leg) {
+  const ImuGatherTable t = imu_gather_table(leg);
+  ImuLaneGather g{};
+  for (int i = 0; i < 64 * IMU_LANE_WORDS; ++i) g.w[i] = 0;
+  for (int lane = 0; lane < 64; ++lane)
+    for (int kk = 0; kk < 8; ++kk)
+      for (int J = 0; J < 3; ++J) {
+        const int i = 3 * kk + J;
+        g.w[lane * IMU_LANE_WORDS + i / 2] |= (unsigned)t.e[(4 * kk + (lane >> 4)) * 48 + 16 * J + (lane & 15)] << (16 * (i & 1));
+      }
+  return g;
+}
+// Where the full batch's k_imu_linearize stages a pair of factors (2 p, 2 p + 1) inside the LDS that becomes Jw afterwards, in doubles:
+// factor h's head at IMU_STG_HEAD(h) (126 doubles, padded to 128), its pool at IMU_STG_POOL(h). Lane l of the wave brings head entries
+// l and l + 64 of both factors, and with one 16-byte load each the entries l and l + 64 (< IB_N) of both entry-major pools.
+#define IMU_STG_HEAD(h) (128 * (h))
+#define IMU_STG_POOL(h) (256 + IB_N * (h))
+#define IMU_STG_N (256 + 2 * IB_N)
+VD void imu_lane_gather_load(const ImuLaneGather &t, int lane, unsigned (&gw)[IMU_LANE_WORDS]) {
+  for (int i = 0; i < IMU_LANE_WORDS; ++i) gw[i] = t.w[lane * IMU_LANE_WORDS + i];
+}
+// A lane's 24 [J | r] operands of the whitening from one factor's block pool (IB_N doubles) and its record's head (PreintHead as
+// doubles; hd[0] = sum_dt = T), each entry from the source and with the coefficient its table word names. The one place the operand
+// image is formed: the fused small-batch body and the full batch's k_imu_linearize both call it.
+VD void imu_gather_operands(const unsigned (&gw)[IMU_LANE_WORDS], const double *hd, const double *pool, double (&bv)[8][3]) {
+  const double T = hd[0];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk)
+#pragma unroll
+    for (int J = 0; J < 3; ++J) {
+      const int i = 3 * kk + J;
+      const unsigned g_ = (gw[i / 2] >> (16 * (i & 1))) & 0xffffu, code = g_ >> 12;
+      const double val = ((g_ & 0x100) ? hd : pool)[g_ & 0xff];
+      const double cf = code == 1 ? 1.0 : (code == 2 ? -1.0 : (code == 3 ? T : -T));
+      bv[kk][J] = code ? cf * val : 0.0;
+    }
+}
 
 // dx of one kept block of the prior (marginalization_factor.cpp:357-377); size = global size (7 -> 6 local).
 VD void prior_dx(const double *x, const double *x0, int size, double *dx) {

@@ -973,22 +973,20 @@ __global__ void __launch_bounds__(64) k_visual_cost_walk(BatchDev b, double sq, 
 #define IMU_NTRI 496   // upper triangle of the 31 x 31 sqrt_info
 
 // IMULegFactor linearisation (imu_leg_factor.cpp:173-386) in two kernels:
-//   k_imu_raw        one THREAD per factor (the code is a scalar dependency chain, so lanes = factors gives 64-way SIMD): raw residual and
-//                    31 x 38 local Jacobian, structural non-zeros only (the zeros are set once when the batch is created), stored
-//                    ENTRY-MAJOR over the batch — b.imu_raw[(row * 39 + col) * NF + f] — so that the 64 lanes of a store are 64 neighbours
-//   k_imu_linearize  one wave per factor, both products on the FP64 matrix cores (v_mfma_f64_16x16x4_f64):
+//   k_imu_raw        one THREAD per factor (the code is a scalar dependency chain, so lanes = factors gives 64-way SIMD): what of [J | r]
+//                    depends on the states — the residual and seven 3 x 3 matrices, the factor's block pool of IB_N = 96 doubles
+//                    (imu_blocks, factors.hpp) — stored ENTRY-MAJOR over the batch, b.imu_raw[e * NF + f], so that the 64 lanes of a
+//                    store are 64 neighbours. Every other entry of [J | r] is an entry of the record's head, +-1 or zero: not stored.
+//   k_imu_linearize  one wave per pair of factors, both products on the FP64 matrix cores (v_mfma_f64_16x16x4_f64):
+//                      operands  the two pools and the two records' heads staged in LDS (coalesced), then every lane forms the 24
+//                                entries of [J | r] it holds through the compile-time gather table (imu_gather_operands)
 //                      whitening Jw = U [J | r]   (U = sqrt_info, upper triangular 31 x 31; 32 x 48 x 32 padded, zero blocks skipped);
-//                                                 operands straight from global memory, only the structurally non-zero entries of [J | r]
+//                                                 U straight from global memory
 //                      Gram      G  = Jw^T Jw     (39 x 39: the factor's J^T J, J^T r and r^T r = its cost; upper tiles only)
 // Operand layout of the instruction: A(16 x 4): lane l holds A[l % 16][l / 16]; B(4 x 16): lane l holds B[l / 16][l % 16];
 // C/D(16 x 16): register r of lane l is C[(l / 16) + 4 r][l % 16]. The whitened block goes to HBM only for the marginalisation (mode 0).
 #define IW_JS 48   // LDS row stride of Jw (conflict-free operand reads of the Gram pass)
-// structural non-zeros of [J | r] (31 rows x 39 columns, bit c of entry r): union of the IMULegFactor and the embedded IMUFactor patterns
-__device__ constexpr unsigned long long c_imu_nz[31] = {
-    0x4000387fffULL, 0x4000387fffULL, 0x4000387fffULL, 0x4001c07038ULL, 0x4001c07038ULL, 0x4001c07038ULL, 0x400e007ff8ULL, 0x400e007ff8ULL,
-    0x400e007ff8ULL, 0x407038fe3fULL, 0x407038fe3fULL, 0x407038fe3fULL, 0x438039703fULL, 0x438039703fULL, 0x438039703fULL, 0x40003a703fULL,
-    0x40003a703fULL, 0x40003a703fULL, 0x40003c703fULL, 0x40003c703fULL, 0x40003c703fULL, 0x4070000e00ULL, 0x4070000e00ULL, 0x4070000e00ULL,
-    0x4380007000ULL, 0x4380007000ULL, 0x4380007000ULL, 0x4400008000ULL, 0x4800010000ULL, 0x5000020000ULL, 0x6000040000ULL};
+__device__ const vilo::ImuLaneGather c_imu_lane_gather[2] = {vilo::imu_lane_gather_table(false), vilo::imu_lane_gather_table(true)};
 
 __global__ void __launch_bounds__(64) k_imu_raw(BatchDev b, double g_norm, int mode) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -999,31 +997,23 @@ __global__ void __launch_bounds__(64) k_imu_raw(BatchDev b, double g_norm, int m
   if (lin_skip(st, mode) || b.imu_skip[f]) return;
   const PreintPrepared &pp = b.prep[f];
   const double *x = (mode ? b.xc : b.x) + (size_t)win * XSTRIDE;
-  double *raw = b.imu_raw + f;
-  double r[31];
-  if (b.win[win].use_leg) {
-    imu_leg_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_LB + 4 * k, x + XO_POSE + 7 * (k + 1),
-                x + XO_SB + 9 * (k + 1), x + XO_LB + 4 * (k + 1), r, true, raw, 39 * NF, NF);
-#pragma unroll
-    for (int i = 0; i < 31; ++i) raw[(size_t)(i * 39 + 38) * NF] = r[i];
-  } else {
-    // plain IMUFactor (estimator.cpp:1160-1171) inside the same 31 x 39 layout: rows 0..14, the frame-j blocks at column 19,
-    // leg-bias columns and rows 15..30 stay zero (sqrt_info is embedded accordingly, k_embed_sqrt15)
-    imu_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_POSE + 7 * (k + 1), x + XO_SB + 9 * (k + 1), r, true, raw, 39 * NF, 19, NF);
-#pragma unroll
-    for (int i = 0; i < 15; ++i) raw[(size_t)(i * 39 + 38) * NF] = r[i];
-  }
+  // plain IMUFactor (estimator.cpp:1160-1171, use_leg = 0): rows 0..14 of the same 31 x 39 layout, the frame-j blocks at column 19;
+  // leg-bias columns and rows 15..30 are zeros of its gather table (sqrt_info is embedded accordingly, k_embed_sqrt15)
+  imu_blocks(pp.head, g_norm, b.win[win].use_leg != 0, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_LB + 4 * k, x + XO_POSE + 7 * (k + 1),
+             x + XO_SB + 9 * (k + 1), x + XO_LB + 4 * (k + 1), b.imu_raw + f, (size_t)NF);
 }
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 
-// One wave per PAIR of consecutive factors (2 p, 2 p + 1; the same window): a lane's 16-byte load of an entry-major raw entry brings
-// both factors' values, which halves the scattered 32-byte sectors the gather touches per factor.
-// single: one wave per FACTOR (workgroup 2 p + h takes factor h of pair p; the pair's loads as before) — small batches, where the second
-// factor of a pair only lengthens the wave's latency chain and half of the SIMDs have nothing to do
+// One wave per PAIR of consecutive factors (2 p, 2 p + 1; the same window, so one gather table): a lane's 16-byte load of an entry-major
+// pool entry brings both factors' values — 96 entries, at most two such loads per lane — and the two heads are 126 contiguous doubles
+// each. Staged in the LDS that becomes Jw afterwards (IMU_STG_HEAD / IMU_STG_POOL, factors.hpp).
+// single: one wave per FACTOR (workgroup 2 p + h takes factor h of pair p; the pair's pool loads as before) — small batches, where the
+// second factor of a pair only lengthens the wave's latency chain and half of the SIMDs have nothing to do
 __global__ void __launch_bounds__(64) k_imu_linearize(BatchDev b, int mode, int single) {
-  __shared__ double Jw[32 * IW_JS];
-  // The entry-major raw Jacobians put the same entry of 8 consecutive factors in one 64-byte line, i.e. four pairs share every line they
+  __shared__ __attribute__((aligned(16))) double Jw[32 * IW_JS];
+  static_assert(IMU_STG_N <= 32 * IW_JS && IB_N > 64 && IB_N <= 128, "staging of a pair's heads and pools inside Jw");
+  // The entry-major pools put the same entry of 8 consecutive factors in one 64-byte line, i.e. four pairs share every line they
   // gather from. Workgroup b runs on XCD b % 8 (its own L2): inside each group of 32 workgroups, the four that land on XCD x take the
   // pairs 4 x .. 4 x + 3, so a line is fetched from HBM by one L2 instead of four. (A permutation of [0, gridDim.x); ragged tail: identity.)
   int pair = blockIdx.x, hsel = -1;
@@ -1034,20 +1024,35 @@ __global__ void __launch_bounds__(64) k_imu_linearize(BatchDev b, int mode, int 
   if (lin_skip(st, mode)) return;
   const int lane = threadIdx.x, lr = lane & 15, lk = lane >> 4;
   const int NF = b.W * 10;
-  // [J | r] tiles of both factors: up to 24 B values per lane and factor (structural non-zeros only), all loads in flight at once
+  // [J | r] tiles of both factors: 24 B values per lane and factor
   double bv[2][8][3];
   {
-    const dbl2 *raw2 = (const dbl2 *)(b.imu_raw + f0);
+    unsigned gw[IMU_LANE_WORDS];
+    vilo::imu_lane_gather_load(c_imu_lane_gather[b.win[win].use_leg ? 1 : 0], lane, gw);
+    const dbl2 *pool2 = (const dbl2 *)(b.imu_raw + f0);
+    const dbl2 p0 = pool2[((size_t)lane * NF) >> 1];
+    dbl2 p1 = {0.0, 0.0};
+    if (lane + 64 < IB_N) p1 = pool2[((size_t)(lane + 64) * NF) >> 1];
+    double hv[2][2];
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk)
+    for (int h = 0; h < 2; ++h) {
+      hv[h][0] = hv[h][1] = 0.0;
+      if (hsel >= 0 && h != hsel) continue;
+      const double *hsrc = (const double *)&b.prep[f0 + h].head;
+      hv[h][0] = hsrc[lane];
+      if (lane + 64 < 126) hv[h][1] = hsrc[lane + 64];
+    }
 #pragma unroll
-      for (int J = 0; J < 3; ++J) {
-        const int q = 4 * kk + lk, col = 16 * J + lr;
-        const bool nz = q < 31 && col < 39 && ((c_imu_nz[min(q, 30)] >> col) & 1ULL);
-        dbl2 v = {0.0, 0.0};
-        if (nz) v = raw2[((size_t)(q * 39 + col) * NF) >> 1];
-        bv[0][kk][J] = v[0]; bv[1][kk][J] = v[1];
-      }
+    for (int h = 0; h < 2; ++h) { Jw[IMU_STG_HEAD(h) + lane] = hv[h][0]; Jw[IMU_STG_HEAD(h) + 64 + lane] = hv[h][1]; }
+    Jw[IMU_STG_POOL(0) + lane] = p0[0]; Jw[IMU_STG_POOL(1) + lane] = p0[1];
+    if (lane + 64 < IB_N) { Jw[IMU_STG_POOL(0) + 64 + lane] = p1[0]; Jw[IMU_STG_POOL(1) + 64 + lane] = p1[1]; }
+    lds_fence();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (hsel >= 0 && h != hsel) continue;
+      vilo::imu_gather_operands(gw, Jw + IMU_STG_HEAD(h), Jw + IMU_STG_POOL(h), bv[h]);
+    }
+    lds_fence();   // (every operand of both factors is in registers before the whitened block overwrites the staging)
   }
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -1124,7 +1129,6 @@ __global__ void __launch_bounds__(64) k_imu_linearize(BatchDev b, int mode, int 
 // The body takes its LDS from the caller, so the workgroups of a visual kernel's launch that are not packed waves can run it — an
 // iteration of a small batch is a chain of kernel latencies, and this takes the two IMU launches out of the chain.
 // lds: IMU_FUSED_LDS doubles = Jw 32 x 48 | PreintHead (126, padded to 128) | the two frames' states (40) | block pool (IB_N = 96)
-__device__ const vilo::ImuGatherTable c_imu_gather[2] = {vilo::imu_gather_table(false), vilo::imu_gather_table(true)};
 __device__ __forceinline__ void imu_fused_body(BatchDev &b, int f, double g_norm, int mode, double *lds) {
   static_assert(32 * IW_JS + 128 + 40 + IB_N == IMU_FUSED_LDS, "LDS of the fused IMU body");
   double *const Jw = lds, *const hd = lds + 32 * IW_JS, *const xl = hd + 128, *const pool = xl + 40;
@@ -1147,14 +1151,8 @@ __device__ __forceinline__ void imu_fused_body(BatchDev &b, int f, double g_norm
   const bool leg = b.win[win].use_leg != 0;
   const long long fc0 = pclk64();
   // this lane's 24 entries of the gather table (operand layout of the whitening: row 4 kk + lk, column 16 J + lr)
-  unsigned short gt[8][3];
-  {
-    const unsigned short *tab = c_imu_gather[leg ? 1 : 0].e;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk)
-#pragma unroll
-      for (int J = 0; J < 3; ++J) gt[kk][J] = tab[(4 * kk + lk) * 48 + 16 * J + lr];
-  }
+  unsigned gw[IMU_LANE_WORDS];
+  vilo::imu_lane_gather_load(c_imu_lane_gather[leg ? 1 : 0], lane, gw);
   {
     // stage the record's head and the two frames' states (coalesced)
     const double *hsrc = (const double *)&pp.head;
@@ -1184,17 +1182,8 @@ __device__ __forceinline__ void imu_fused_body(BatchDev &b, int f, double g_norm
   lds_fence();
   const long long fc2 = pclk64();
   // [J | r] operands of the whitening, each from its source
-  const double T = hd[0];
   double bv[8][3];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk)
-#pragma unroll
-    for (int J = 0; J < 3; ++J) {
-      const unsigned g_ = gt[kk][J], code = g_ >> 12;
-      const double val = ((g_ & 0x100) ? hd : pool)[g_ & 0xff];
-      const double cf = code == 1 ? 1.0 : (code == 2 ? -1.0 : (code == 3 ? T : -T));
-      bv[kk][J] = code ? cf * val : 0.0;
-    }
+  vilo::imu_gather_operands(gw, hd, pool, bv);
   lds_fence();   // (every operand is in registers before the whitened block overwrites the image)
   double *out = b.imu_lin + (size_t)f * IMU_LIN_STRIDE;
 #pragma unroll
@@ -1394,8 +1383,9 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o, cons
     P0(VILO_K_VISUAL_LINEARIZE);
     launch_visual_linearize(b, plan, sq, ha, gn, s, 1);
     P1();
-    // (the fused body as a kernel of its own for full batches — one wave per factor, no raw block through HBM — was measured slower than
-    // the two kernels: 315 - 319 us against 45 + 245 at 4096 windows: there lanes = factors is the better form of the raw evaluation)
+    // (the fused body as a kernel of its own for full batches — one wave per factor, lane 0 evaluating the blocks alone — was measured
+    // slower than the two kernels: 315 - 319 us against 45 + 245 at 4096 windows: lanes = factors is the better form of the block
+    // evaluation. The two kernels keep that form and hand over what the fused body's lane 0 produces: the factor's 96-double block pool)
     if (!plan.fuse_imu()) {
       P0(VILO_K_IMU_RAW);
       hipLaunchKernelGGL(k_imu_raw, dim3((W * 10 + 63) / 64), dim3(64), 0, s, b, gn, 1);

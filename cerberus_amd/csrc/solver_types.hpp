@@ -83,7 +83,7 @@ struct BatchDev {
   double *chunk_cost;         // [n_waves][VILO_MAX_FRAMES] partial visual cost per (packed wave, frame offset)
   // IMU factors
   PreintPrepared *prep;       // [W][10]
-  double *imu_raw;            // [31*39][W*10]   raw [J (31x38) | r], entry-major over the factors; zeros written once, structural non-zeros per linearisation
+  double *imu_raw;            // [IB_N][W*10]    the factors' block pools (imu_blocks), entry-major over the factors; written per linearisation
   double *imu_lin;            // [W][10][31*39]  whitened J (31x38) | whitened r (col 38)
   double *imu_gram;           // [W][10][780]    packed upper triangle of [J | r]^T [J | r]
   double *imu_cost;           // [W][10]

@@ -351,7 +351,9 @@ int create_device_buffers(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h) {
   dev(&D.gram, (size_t)P.gram_total * VILO_GRAM);
   dev(&D.chunk_cost, P.waves.size() * VILO_MAX_FRAMES);   // per (packed wave, frame offset) partial costs
   dev(&D.prep, W * 10); dev(&D.imu_lin, W * 10 * 31 * 39);
-  dev(&D.imu_raw, W * 10 * 31 * 39, CLEAR);   // (structural zeros written once)
+  // (k_imu_linearize's pair loads also bring the pool of a factor k_imu_raw skipped and the entries a plain IMU factor leaves out: never
+  // used, but no kernel is to load memory nobody wrote)
+  dev(&D.imu_raw, W * 10 * IB_N, CLEAR);
   dev(&D.imu_gram, W * 10 * 780); dev(&D.imu_cost, W * 10);
   upv(&D.imu_skip, h.iskip);
   dev(&D.prior_H, W * 96 * 96, CLEAR); dev(&D.prior_dense, W * PD_N, CLEAR); dev(&D.prior_hd, W * 96);
