@@ -956,7 +956,8 @@ extern "C" double vilo_last_download_ms(const vilo_ctx *ctx) { return ctx ? ctx-
 // Test / profiling hook: copy an internal device array of window `win` to the host. Not part of the
 // reference's interface. what: 0 gram slots, 1 lm_E, 2 lm_g, 3 lm_w (80 x L), 4 cam_g, 5 cam_dh2, 6 cam_y,
 // 7 imu_lin, 8 lm_y, 9 lm_dh2, 10 SolverState scalars + cost trace (24 + 64 doubles), 11 landmark permutation (as doubles),
-// 13 the preintegration records (10 x vilo_preint)
+// 13 the preintegration records (10 x vilo_preint), 14 lm_g of the buffer the current linearisation does NOT use (after an accepted last
+// step whose candidate was only costed: the gradients that go with lm_E and lm_w, which have one buffer; what 2 reads is unwritten then)
 extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win, double *out, int max_n) {
   if (!ctx || !bt || win < 0 || win >= bt->W || !out) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
@@ -968,10 +969,11 @@ extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win
   switch (what) {
     case 0: src = bt->d.gram + (size_t)wm.gram_off * VILO_GRAM; n = (size_t)wm.n_gram * VILO_GRAM; break;
     case 1: src = bt->d.lm_E + wm.lm_off; n = wm.L; break;
-    case 2: {
+    case 2:
+    case 14: {
       SolverState sst;
       VILO_HIP(hipMemcpy(&sst, bt->d.st + win, sizeof(SolverState), hipMemcpyDeviceToHost));
-      src = bt->d.lm_gbuf[sst.cur & 1] + wm.lm_off; n = wm.L; break;
+      src = bt->d.lm_gbuf[(sst.cur ^ (what == 14)) & 1] + wm.lm_off; n = wm.L; break;
     }
     case 3: src = bt->d.lm_w + 80 * (size_t)wm.lm_off; n = (size_t)80 * wm.L; break;
     case 4: src = bt->d.cam_g + (size_t)win * CD_N; n = CD_N; break;

@@ -2,6 +2,9 @@
 library reads them once per process) and prints, as JSON, the descriptor of every solve (vilo_debug_batch_path), a digest of every
 window's final state, every window's summary and the full states of the special windows.
 
+Spec key "field": a further resident batch (32 windows, or spec["field_sizes"]) of the ragged, part-mono, outlier-laden windows of
+tests/field_windows.py in turn, each at first, middle and last positions, solved like the main batch.
+
 Also importable (no GPU): the window set and its layout, which the test solves with the oracle."""
 import hashlib
 import json
@@ -143,6 +146,23 @@ def _solve_resident(ctx, ws, opts, keep, n_solves=3):
     return out
 
 
+def field_batch(FS, W, with_td):
+    """W field windows in turn (tests/field_windows.batch_of), the td-estimating one at position 6 where the row runs 23-column rows."""
+    import field_windows as FW
+    return FW.batch_of(FS, W, extra={6: ("f40_td", FS["f40_td"])} if with_td else None)
+
+
+def field_keep(names):
+    """The positions whose states the worker prints: every one of a batch of 32, else each window's first, middle and last position."""
+    if len(names) <= 32:
+        return list(range(len(names)))
+    keep = []
+    for nm in dict.fromkeys(names):
+        at = [p for p, n in enumerate(names) if n == nm]
+        keep += [at[0], at[len(at) // 2], at[-1]]
+    return sorted(set(keep))
+
+
 def _solve_host(ctx, ws, opts):
     init = [w.clone_state() for w in ws]
     summ = ctx.solve_windows(ws, opts)
@@ -202,6 +222,12 @@ def main():
         o.initial_trust_region_radius = 1e8
         fw = list(far_windows(cfg, ocfg).values())
         res["far"] = {"solves": _solve_resident(ctx, fw, o, [0, 1])}
+    if spec.get("field"):
+        import field_windows as FW
+        FS = FW.field_set(cfg, ocfg)
+        for W in spec.get("field_sizes", [32]):
+            ws, names = field_batch(FS, W, bool(spec.get("td")) or spec.get("compact") == 0)
+            res["field%d" % W] = {"W": W, "names": names, "solves": _solve_resident(ctx, ws, opts, field_keep(names))}
     ctx.close()
     print("PATHS_JSON " + json.dumps(res))
 

@@ -73,6 +73,27 @@ def test_parity_with_numpy(ctx, cfg, ocfg, case):
         np.testing.assert_array_equal(po[0], po[0].T)
 
 
+def test_field_windows(ctx, cfg, ocfg):
+    """The windows of tests/field_windows.py, each twice in one solved batch: frame blocks and the pose system against the numpy
+    definition at test_parity_with_numpy's tolerances; the two positions of a window bitwise the same."""
+    import field_windows as FW
+    ws, names = FW.batch_of(FW.field_set(cfg, ocfg, FW.BATCH_NAMES), 2 * len(FW.BATCH_NAMES))
+    b = _solved(ctx, ws, iters=FW.ITERS)
+    fr, po, st = b.covariance(gauge="frame0", poses=True)
+    for nm in FW.BATCH_NAMES:
+        i = names.index(nm)
+        w = ws[i]
+        assert st[i] == 0, (nm, st)
+        fr_r, po_r = cov_ref.window_covariance(ocfg, w, gauge="frame0")
+        err = cov_ref.block_errors(fr[i], fr_r, po[i], po_r)
+        tp, ts = cov_ref.tolerances(bool(w.prior.struct.valid))
+        print("MEASURED covariance of field window %s: %s (tolerances %.0e / %.0e)" % (nm, {k: "%.1e" % v for k, v in err.items()}, tp, ts))
+        assert err["pose"] < tp and err["ex_td"] < tp and err["sb"] < ts, (nm, err)
+        assert np.all(fr[i][fr_r == 0.0] == 0.0) and np.all(po[i][po_r == 0.0] == 0.0), nm
+        j = names.index(nm, i + 1)
+        np.testing.assert_array_equal(fr[j], fr[i]); np.testing.assert_array_equal(po[j], po[i])
+
+
 def test_rank_deficiency_is_per_window(ctx, cfg, ocfg):
     wp = _window(cfg, ocfg, seed=5)
     wn = _window(cfg, ocfg, seed=6, prior=False)

@@ -199,6 +199,24 @@ def test_edge_windows(ctx, cfg, ocfg):
     assert not r.state_grad[0, 165:209].any() and r.n_free[0] == 11 * 15 + 12 + 40
 
 
+def test_field_windows(ctx, cfg, ocfg):
+    """The windows of tests/field_windows.py, each twice in one batch: gradient and Gauss-Newton diagonal against the numpy definition
+    at the measured-floor bounds, before and after a solve; the two positions of a window bitwise the same."""
+    import field_windows as FW
+    from cerberus_amd import api
+    ws, names = FW.batch_of(FW.field_set(cfg, ocfg, FW.BATCH_NAMES), 2 * len(FW.BATCH_NAMES))
+    b = api.Batch(ctx, ws)
+    for stage in ("initial", "solved"):
+        if stage == "solved":
+            b.solve(api.default_solve_opts(True, FW.ITERS))
+            b.download()
+        r = b.gradient()
+        for nm in FW.BATCH_NAMES:
+            i = names.index(nm)
+            _check_parity(r, i, ocfg, ws[i], "field %s %s" % (nm, stage))
+            _bitwise(_window_part(r, names.index(nm, i + 1)), _window_part(r, i))
+
+
 def test_host_window_form_matches_batch(ctx, cfg, ocfg):
     from cerberus_amd import api
     ws = [_window(cfg, ocfg, seed=s, L=70) for s in (21, 22, 23)]

@@ -11,6 +11,12 @@ skipped, one without landmarks, one with 7 and one with 500 landmarks (multi-chu
 twins of the bench windows elsewhere. A second batch of two far-off windows with a huge trust region drives rejected steps through the
 bookkeeping of each assembly form.
 
+A third batch (worker spec "field") holds the windows of tests/field_windows.py, the shape a feature tracker hands over: tracks of any
+length side by side in one packed wave, a quarter of the observations without a right-camera match, mismatches that stay on the Huber
+branch, a landmark with one factor, a group of more than 64 lanes, one all-mono window, one partial one — the six windows in turn over 32
+positions (rows A to L; the td-estimating one at position 6 of the 23-column rows) and over 257, 513 and 2049 positions (row N). The same
+checks and bounds hold on them (tests/test_field_windows.py holds the properties of the windows on a CPU).
+
 Checks: every special window at every position against the oracle (equal iterations / successful steps, cost 1e-8, states 1e-8; the
 far-off windows: equal decisions, states 1e-4 as tests/test_solver_forms.py holds the solver forms); bitwise where the code or the
 documents claim it; 1e-9 elsewhere on the windows with a prior (the solver forms' bound)."""
@@ -33,25 +39,27 @@ SIZES = [128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049]
 
 # row: (environment, worker spec)
 ROWS = {
-    "A": ({}, {"far": 1, "host": 1}),
-    "B1": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "1"}, {"far": 1}),
-    "B0": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "0"}, {"far": 1}),
-    "C": (_C, {"far": 1}),
-    "D": (dict(_C, VILO_IMU_SINGLE_MAX_WINDOWS="0"), {"far": 1}),
-    "E": (_E, {"far": 1}),
-    "F": (_F, {"far": 1}),
-    "G": (_G, {"far": 1}),
-    "H": (dict(_G, VILO_VISUAL_FORM="single"), {"far": 1}),
-    "Itpar": ({}, {"compact": 0, "far": 1}),
-    "Iwalk": ({"VILO_NO_TPAR": "1"}, {"compact": 0, "far": 1}),
-    "J": ({}, {"td": 1}),
-    "K0": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "0"}, {}),
-    "K1": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "1"}, {}),
-    "K2": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "2"}, {}),
-    "L": ({"VILO_NO_GRAPH": "1"}, {}),
+    "A": ({}, {"far": 1, "host": 1, "field": 1}),
+    "B1": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "1"}, {"far": 1, "field": 1}),
+    "B0": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "0"}, {"far": 1, "field": 1}),
+    "C": (_C, {"far": 1, "field": 1}),
+    "D": (dict(_C, VILO_IMU_SINGLE_MAX_WINDOWS="0"), {"far": 1, "field": 1}),
+    "E": (_E, {"far": 1, "field": 1}),
+    "F": (_F, {"far": 1, "field": 1}),
+    "G": (_G, {"far": 1, "field": 1}),
+    "H": (dict(_G, VILO_VISUAL_FORM="single"), {"far": 1, "field": 1}),
+    "Itpar": ({}, {"compact": 0, "far": 1, "field": 1}),
+    "Iwalk": ({"VILO_NO_TPAR": "1"}, {"compact": 0, "far": 1, "field": 1}),
+    "J": ({}, {"td": 1, "field": 1}),
+    "K0": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "0"}, {"field": 1}),
+    "K1": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "1"}, {"field": 1}),
+    "K2": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "2"}, {"field": 1}),
+    "L": ({"VILO_NO_GRAPH": "1"}, {"field": 1}),
     "M": ({"VILO_FULL_RECORD_UPLOAD": "1", "VILO_NO_PINNED_STAGING": "1"}, {"host_only": 1}),
-    "N": ({}, {"sizes": SIZES, "few_sizes": [300]}),
+    "N": ({}, {"sizes": SIZES, "few_sizes": [300], "field": 1, "field_sizes": [257, 513, 2049]}),
 }
+FIELD_ROWS = [r for r in ROWS if "field" in ROWS[r][1]]
+FIELD_PRIOR = ("f40", "f200", "f70_chunks", "f40_allmono")   # the field windows with a prior and compact rows: the 1e-9 bound between forms
 
 
 def _p(visual, imu, imu_order, assembly, solver, rows="compact"):
@@ -104,7 +112,12 @@ def _run(row):
 def _sized(row):
     """(name, result of one batch) of a row: its W = 32 batch, or row N's sizes."""
     r = _run(row)
-    return [(k, v) for k, v in r.items() if k != "far"]
+    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith("field")]
+
+
+def _field(row):
+    """(name, result) of a row's field batches: "field32", or row N's three sizes."""
+    return [(k, v) for k, v in _run(row).items() if k.startswith("field")]
 
 
 @pytest.fixture(scope="module")
@@ -224,8 +237,8 @@ def test_replays_are_bitwise_the_first_solve(row):
             assert s[i]["digest"] == s[0]["digest"] and s[i]["summ"] == s[0]["summ"], (row, name, i)
 
 
-def _same(a, b, with_summaries=True, skip=()):
-    ra, rb = _run(a)["32"], _run(b)["32"]
+def _same(a, b, with_summaries=True, skip=(), key="32"):
+    ra, rb = _run(a)[key], _run(b)[key]
     da = ra["solves"][0] if "solves" in ra else ra["host"]
     db = rb["solves"][0] if "solves" in rb else rb["host"]
     diff = [p for p, (x, y) in enumerate(zip(da["digest"], db["digest"])) if x != y and p not in skip]
@@ -236,7 +249,7 @@ def _same(a, b, with_summaries=True, skip=()):
         for sa, sb in zip(da["summ"], db["summ"]):
             assert (sa["iterations"], sa["successful"]) == (sb["iterations"], sb["successful"])
             np.testing.assert_allclose(sa["cost_trace"], sb["cost_trace"], rtol=1e-11)
-    if "far" in _run(a) and "far" in _run(b):
+    if key == "32" and "far" in _run(a) and "far" in _run(b):
         fa, fb = _run(a)["far"]["solves"][0], _run(b)["far"]["solves"][0]
         assert fa["digest"] == fb["digest"], (a, b, "far")
 
@@ -302,3 +315,124 @@ def test_other_forms_agree_with_row_A_to_rounding(row, oracle):
             far_e = max(far_e, _rel_states(fr["state"][str(i)], fa["state"][str(i)]))
         assert far_e < 1e-4, far_e
     print("MEASURED test_kernel_paths[%s] vs row A: states %.2e (windows with a prior), far-off %s" % (row, worst, "-" if far_e is None else "%.2e" % far_e))
+
+
+# ---- the field windows (tests/field_windows.py): the same rows, the shape a feature tracker hands over ----
+@pytest.fixture(scope="module")
+def field_oracle():
+    """The oracle's solve of every field window, once: {name: (summary, state arrays, F)}."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _paths_worker as P
+    import field_windows as FW
+    from cerberus_amd import synth
+    from oracle import oracle_py as O
+    cfg = synth.default_config()
+    ocfg = O.config_from(cfg)
+    out = {}
+    for name, w in FW.field_set(cfg, ocfg).items():
+        s = O.solve_window(ocfg, w, O.default_opts(True, P.ITERS))
+        out[name] = (s, [a.copy() for a in w.state_arrays()], w.F)
+    return out
+
+
+def _field_by_name(res):
+    """{name: [(position, state arrays or None, summary)]} of a field batch's first solve."""
+    s0 = res["solves"][0]
+    out = {}
+    for p, nm in enumerate(res["names"]):
+        out.setdefault(nm, []).append((p, s0["state"].get(str(p)), s0["summ"][p]))
+    return out
+
+
+@pytest.mark.parametrize("row", FIELD_ROWS)
+def test_field_descriptor(row):
+    """The field batch takes the row's forms (row N: the three sizes' entries), the first solve plain launches, the later ones replays."""
+    got_keys = [k for k, _ in _field(row)]
+    assert got_keys == (["field257", "field513", "field2049"] if row == "N" else ["field32"]), got_keys
+    for name, res in _field(row):
+        exp = EXPECT[row if row != "N" else str(res["W"])]
+        assert len(res["names"]) == res["W"]
+        assert ("f40_td" in res["names"]) == (row in ("J", "Itpar", "Iwalk"))
+        for i, s in enumerate(res["solves"]):
+            got = dict(s["path"])
+            replay, wo = got.pop("replay"), got.pop("wave_order")
+            assert got == exp, (row, name, i, got)
+            assert replay == (i > 0 and row != "L"), (row, name, i)
+            assert wo == WAVE_ORDER.get(row, 1)
+
+
+@pytest.mark.parametrize("row", FIELD_ROWS)
+def test_field_windows_against_the_oracle(row, field_oracle):
+    """Every field window at every position: the oracle's decisions, cost 1e-8, states 1e-8; one window, one answer
+    wherever it sits in the batch; replays bitwise the plain launches."""
+    worst = worst_c = 0.0
+    for name, res in _field(row):
+        s = res["solves"]
+        for i in (1, 2):
+            assert s[i]["digest"] == s[0]["digest"] and s[i]["summ"] == s[0]["summ"], (row, name, i)
+        by_name = _field_by_name(res)
+        assert set(by_name) >= {"f40", "f200", "f130_noprior", "f70_chunks", "f40_allmono", "f60_partial8"}
+        for nm, entries in by_name.items():
+            so, ost, F = field_oracle[nm]
+            if nm != "f40_td":
+                pos = [p for p, _, _ in entries]
+                assert pos[0] < 6 and pos[-1] >= res["W"] - 6 and len(pos) >= 3, (row, name, nm, pos)   # first, middle and last positions
+            n_states = 0
+            for p, st, sm in entries:
+                assert (sm["iterations"], sm["successful"]) == (so.iterations, so.num_successful), (row, name, nm, p)
+                np.testing.assert_allclose(sm["final_cost"], so.final_cost, rtol=1e-8, err_msg="%s %s %s %d" % (row, name, nm, p))
+                worst_c = max(worst_c, abs(sm["final_cost"] / so.final_cost - 1))
+                assert s[0]["digest"][p] == s[0]["digest"][entries[0][0]] and sm == entries[0][2], (row, name, nm, p)
+                if st is not None:
+                    e = _rel_states(st, ost, F)
+                    assert e < 1e-8, (row, name, nm, p, e)
+                    worst = max(worst, e)
+                    n_states += 1
+            assert n_states >= min(3, len(entries)), (row, name, nm)
+    print("MEASURED test_kernel_paths[%s] field windows vs oracle: states %.2e, cost %.2e" % (row, worst, worst_c))
+
+
+@pytest.mark.parametrize("a,b", [("B0", "B1"), ("C", "A"), ("D", "A"), ("H", "G"), ("K0", "B1"), ("K1", "B1"), ("K2", "B1"), ("L", "A")])
+def test_field_bitwise_pairs(a, b):
+    """The pairs of test_bitwise_pairs, on the field batch."""
+    _same(a, b, key="field32")
+
+
+def test_field_frame_parallel_and_walking_forms_give_the_same_states():
+    _same("B1", "A", with_summaries=False, key="field32")
+
+
+def test_field_td_estimating_window_among_23_column_rows():
+    """Rows J and Itpar run the same forms on the same field batch: bitwise on every window but the td-estimating one (position 6 of
+    both), as test_bitwise_pairs' J / Itpar case leaves the td-estimating special out."""
+    names = _run("J")["field32"]["names"]
+    td = tuple(p for p, nm in enumerate(names) if nm == "f40_td")
+    assert td == (6,) and names == _run("Itpar")["field32"]["names"]
+    _same("J", "Itpar", skip=td, key="field32")
+
+
+def test_field_bench_kernel_set_at_small_and_full_size():
+    """Row G's field batch of 32 and row N's of 2049: each field window bitwise the same."""
+    g, n = _field_by_name(_run("G")["field32"]), _field_by_name(_run("N")["field2049"])
+    for nm in g:
+        assert g[nm][0][1] is not None and g[nm][0][1:] == n[nm][0][1:], nm
+
+
+@pytest.mark.parametrize("row", ["B0", "E", "F", "G", "Itpar", "Iwalk", "N"])
+def test_field_other_forms_agree_with_row_A_to_rounding(row):
+    """1e-9 relative on the field windows with a prior, equal decisions on every one."""
+    ref = _field_by_name(_run("A")["field32"])
+    worst = 0.0
+    for name, res in _field(row):
+        for nm, entries in _field_by_name(res).items():
+            if nm not in ref:
+                continue   # (the td-estimating window: rows of 23 columns only)
+            _, st_a, sm_a = ref[nm][0]
+            for p, st, sm in entries:
+                assert (sm["iterations"], sm["successful"]) == (sm_a["iterations"], sm_a["successful"]), (row, name, nm, p)
+                if nm in FIELD_PRIOR and st is not None:
+                    e = _rel_states(st, st_a)
+                    assert e < 1e-9, (row, name, nm, p, e)
+                    np.testing.assert_allclose(sm["cost_trace"], sm_a["cost_trace"], rtol=1e-9)
+                    worst = max(worst, e)
+    print("MEASURED test_kernel_paths[%s] field windows vs row A: states %.2e (windows with a prior)" % (row, worst))

@@ -33,8 +33,8 @@ def _assert_points_close(a, b, tag=""):
     assert err.max() <= lm_cov_ref.TOL_POINT, (tag, float(err.max()))
 
 
-def _check_parity(r, w, ocfg, gauge, has_prior, tag):
-    var, pts, pc = _window_slice(r, 0)
+def _check_parity(r, w, ocfg, gauge, has_prior, tag, i=0):
+    var, pts, pc = _window_slice(r, i)
     var_r, pts_r, pc_r = lm_cov_ref.landmark_covariance(ocfg, w, gauge=gauge)
     e = lm_cov_ref.errors(var, pc, var_r, pc_r)
     tv, tp = lm_cov_ref.tolerances(has_prior)
@@ -54,6 +54,29 @@ def test_parity_with_numpy(ctx, cfg, ocfg, case):
         r = b.landmark_covariance(gauge=g)
         assert r.status[0] == 0 and r.offsets[-1] == w.L, (case, g, r.status)
         _check_parity(r, w, ocfg, g, has_prior, case)
+
+
+def test_field_windows(ctx, cfg, ocfg):
+    """The windows of tests/field_windows.py, each twice in one solved batch, against the numpy definition at test_parity_with_numpy's
+    tolerances — the inverse-depth variance of a landmark with ONE two-residual factor among them; the two positions bitwise the same."""
+    import field_windows as FW
+    ws, names = FW.batch_of(FW.field_set(cfg, ocfg, FW.BATCH_NAMES), 2 * len(FW.BATCH_NAMES))
+    b = _solved(ctx, ws, iters=FW.ITERS)
+    r = b.landmark_covariance(gauge="frame0")
+    for nm in FW.BATCH_NAMES:
+        i = names.index(nm)
+        w = ws[i]
+        assert r.status[i] == 0, (nm, r.status)
+        has_prior = bool(w.prior.struct.valid)
+        _check_parity(r, w, ocfg, "frame0", has_prior, "field " + nm, i)
+        one = int(np.flatnonzero(FW.factor_counts(w) == 1)[0])
+        var = _window_slice(r, i)[0]
+        var_r = lm_cov_ref.landmark_covariance(ocfg, w, gauge="frame0")[0]
+        e_one = abs(var[one] - var_r[one]) / var_r[one]
+        print("MEASURED landmark covariance of field window %s: one-factor landmark %d, variance %.3e, relative error %.1e" % (nm, one, var[one], e_one))
+        assert e_one < lm_cov_ref.tolerances(has_prior)[0], (nm, e_one)
+        for x, y in zip(_window_slice(r, names.index(nm, i + 1)), _window_slice(r, i)):
+            np.testing.assert_array_equal(x, y)
 
 
 def test_points_are_pub_point_cloud(ctx, cfg, ocfg):

@@ -223,6 +223,34 @@ def test_host_window_form_matches_batch(ctx, cfg, ocfg):
         _bitwise(_window_part(fresh, i, oo), _window_part(r, i, oo))
 
 
+def test_field_windows(ctx, cfg, ocfg):
+    """The windows of tests/field_windows.py (tracks of any length in one packed wave, part-mono, outliers on the Huber branch, a
+    one-factor landmark, a group of more than 64 lanes, all-mono, partial), each twice in one batch: every output against the numpy
+    definition before and after a solve, the cost the solver's own, the two positions of a window bitwise the same."""
+    import field_windows as FW
+    from cerberus_amd import api
+    ws, names = FW.batch_of(FW.field_set(cfg, ocfg, FW.BATCH_NAMES), 2 * len(FW.BATCH_NAMES))
+    kw = dict(observations=True, imu=True)
+    oo = _obs_offsets(ws)
+    b = api.Batch(ctx, ws)
+    r0 = b.residuals(**kw)
+    first = {nm: names.index(nm) for nm in FW.BATCH_NAMES}
+    for nm, i in first.items():
+        _check_parity(r0, i, resid_ref.window_residuals(ocfg, ws[i]), oo)
+    b.solve(api.default_solve_opts(True, FW.ITERS))
+    summ = b.download()
+    r1 = b.residuals(**kw)
+    for nm, i in first.items():
+        ref = resid_ref.window_residuals(ocfg, ws[i])
+        _check_parity(r1, i, ref, oo)
+        assert ref["n_huber_active"] >= 0.03 * ref["n_visual_blocks"] and (ref["lm_flags"] & 4).any() and not (ref["lm_flags"] & 4).all(), nm
+        assert abs(r0.cost[i] - summ[i].initial_cost) <= 1e-12 * abs(summ[i].initial_cost), nm
+        assert abs(r1.cost[i] - summ[i].final_cost) <= 1e-12 * abs(summ[i].final_cost), nm
+        j = names.index(nm, i + 1)
+        for r in (r0, r1):
+            _bitwise(_window_part(r, j, oo), _window_part(r, i, oo))
+
+
 def test_bad_arguments(ctx, cfg, ocfg):
     from cerberus_amd import api
     from cerberus_amd import _ctypes as T
