@@ -123,6 +123,22 @@ class TriangulateOpts(C.Structure):
 TRI_SELECT = {"unset": 0, "all": 1, "mask": 2}   # VILO_TRI_*
 TRI_SELECTED, TRI_STEREO, TRI_FALLBACK, TRI_NOT_FINITE = 1, 2, 4, 8   # bits of a landmark's flags
 
+class PnpOpts(C.Structure):
+    """vilo_pnp_opts (24 bytes)"""
+    _fields_ = [("frame", C.c_int32), ("guess", C.c_int32), ("write", C.c_int32), ("max_iterations", C.c_int32),
+                ("step_tolerance", C.c_double)]
+
+
+class WindowPnpRecord(C.Structure):
+    """vilo_window_pnp_record (32 bytes)"""
+    _fields_ = [("final_cost", C.c_double), ("initial_cost", C.c_double), ("n_points", C.c_int32), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+PNP_GUESS = {"previous": 0, "current": 1}   # VILO_PNP_GUESS_*
+PNP_OK, PNP_NOT_ENOUGH_POINTS, PNP_NO_CONVERGENCE, PNP_NUMERIC, PNP_NO_FRAME = 0, 1, 2, 3, 4   # a window's status (VILO_PNP_*)
+MAX_FRAMES = 11   # VILO_MAX_FRAMES
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

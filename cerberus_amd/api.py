@@ -35,6 +35,7 @@ def lib():
         L.vilo_last_residuals_ms.restype = C.c_double
         L.vilo_last_gradient_ms.restype = C.c_double
         L.vilo_last_triangulate_ms.restype = C.c_double
+        L.vilo_last_pnp_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -167,6 +168,36 @@ def _triangulate(ctx, descs, select, mask, write, init_depth, stereo, shift, cal
     return Triangulation(depth, flags, offsets, sh)
 
 
+FramePose = collections.namedtuple("FramePose", "pose final_cost initial_cost n_points iterations status")
+
+
+def pnp_opts(frame=-1, guess="previous", write=False, max_iterations=20, step_tolerance=1e-12):
+    """T.PnpOpts of a frame_pose_pnp call; needs no device. frame: -1 (each window's last frame) or 1 .. T.MAX_FRAMES - 1; guess: 'previous'
+    (the reference: start from frame k - 1's pose) or 'current' (frame k's own)."""
+    if guess not in T.PNP_GUESS:
+        raise ValueError("guess must be one of %s" % sorted(T.PNP_GUESS))
+    if int(frame) != frame or frame < -1 or frame == 0 or frame > T.MAX_FRAMES - 1:
+        raise ValueError("frame must be -1 (the last frame) or 1 .. %d" % (T.MAX_FRAMES - 1))
+    if int(max_iterations) != max_iterations or not 1 <= max_iterations <= 64:
+        raise ValueError("max_iterations must be 1 .. 64")
+    step_tolerance = float(step_tolerance)
+    if not (np.isfinite(step_tolerance) and step_tolerance >= 0.0):
+        raise ValueError("step_tolerance must be finite and not negative")
+    o = T.PnpOpts()
+    o.frame, o.guess, o.write, o.max_iterations, o.step_tolerance = int(frame), T.PNP_GUESS[guess], 1 if write else 0, int(max_iterations), step_tolerance
+    return o
+
+
+def _frame_pose_pnp(ctx, n, frame, guess, write, max_iterations, step_tolerance, call):
+    o = pnp_opts(frame, guess, write, max_iterations, step_tolerance)
+    pose = np.zeros((n, 7))
+    rec = (T.WindowPnpRecord * n)()
+    ctx._check(call(C.byref(o), _p(pose), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.WindowPnpRecord._fields_]),
+                      count=n).copy()
+    return FramePose(pose, a["final_cost"], a["initial_cost"], a["n_points"], a["iterations"], a["status"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -258,6 +289,13 @@ class Batch:
         landmarks; otherwise the batch is left as it was."""
         return _triangulate(self.ctx, self._descs, select, mask, write, init_depth, stereo, shift,
                             lambda *a: lib().vilo_batch_triangulate(self.ctx.h, self.handle, *a))
+
+    def frame_pose_pnp(self, frame=-1, guess="previous", write=False, max_iterations=20, step_tolerance=1e-12):
+        """vilo_batch_frame_pose_pnp at the batch's device state: FramePose(pose [W, 7] as [px py pz qx qy qz qw], final_cost, initial_cost,
+        n_points, iterations, status (T.PNP_*), each [W]) of frame `frame` (-1: each window's last) from the landmarks that have depth.
+        write=True stores the pose of the windows with status T.PNP_OK as that frame's current pose; otherwise the batch is left as it was."""
+        return _frame_pose_pnp(self.ctx, len(self._descs), frame, guess, write, max_iterations, step_tolerance,
+                               lambda *a: lib().vilo_batch_frame_pose_pnp(self.ctx.h, self.handle, *a))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -583,6 +621,16 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _triangulate(self, descs, select, mask, write, init_depth, stereo, shift,
                             lambda *a: lib().vilo_window_triangulate(self.h, n, descs, states, *a))
+
+    def window_frame_pose_pnp(self, windows, frame=-1, guess="previous", write=False, max_iterations=20, step_tolerance=1e-12):
+        """vilo_window_frame_pose_pnp: the PnP pose of a frame of host windows at their current state arrays (see Batch.frame_pose_pnp);
+        with write=True the windows' pose arrays receive the new row."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _frame_pose_pnp(self, n, frame, guess, write, max_iterations, step_tolerance,
+                               lambda *a: lib().vilo_window_frame_pose_pnp(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -24,6 +24,7 @@ struct vilo_batch {
   std::vector<int> lm_off_host;     // per window
   std::vector<int> perm_host;       // device order -> original landmark index (per window, concatenated)
   std::vector<int> L_host;
+  int max_win_waves = 0;            // most packed visual waves of one window (vilo_batch_frame_pose_pnp sizes its LDS by it)
   int W;
   // the launch sequence of one solve (5 + 7 x max_num_iterations kernels) as a hipGraph, captured when the same resident batch is
   // solved a second time with the same options (vilo_batch_reset + vilo_batch_solve loops: replays, Monte-Carlo seeds, bench)
@@ -239,6 +240,8 @@ void *ArenaScope::alloc(size_t bytes) {
   void *p = nullptr;
   return dev_alloc_bytes(ctx, bt, &p, bytes) == VILO_OK ? p : nullptr;
 }
+
+int vilo_batch_max_window_waves(vilo_batch *bt) { return bt->max_win_waves; }
 
 // vilo_batch_residuals: the landmarks' observation rows on the device (batch data, uploaded at the first call: not in a call's scope)
 int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows) {
@@ -545,6 +548,7 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
                    ctx->pool);   // (worker_pool.hpp: host threads parked between batches)
   bt->lm_off_host = std::move(P.lm_off); bt->L_host = std::move(P.L); bt->perm_host = std::move(P.perm);
   bt->obs_row_host = std::move(P.obs_row); bt->n_obs_rows = P.n_obs_rows;
+  for (const WinMeta &wm : P.wins) bt->max_win_waves = std::max(bt->max_win_waves, wm.n_waves);
   const double t_packed = now();
   // a lane of vilo_solve_windows' pipeline: the uploads of the lanes go one after the other at the link's rate (side by side every lane's
   // solve would start when ALL uploads are through); held until this batch's uploads are complete, i.e. to the end of the call

@@ -45,6 +45,7 @@ struct vilo_ctx {
   double last_resid_ms = 0.0;      // GPU time of the last vilo_batch_residuals
   double last_grad_ms = 0.0;       // GPU time of the last vilo_batch_gradient (linearisation + k_gradient)
   double last_tri_ms = 0.0;        // GPU time of the last vilo_batch_triangulate (k_triangulate)
+  double last_pnp_ms = 0.0;        // GPU time of the last vilo_batch_frame_pose_pnp (k_frame_pose_pnp)
   int marg_general_count = 0;     // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;

@@ -15,9 +15,11 @@
 //   slideWindow :1460-1678                                           slideWindow (MARGIN_OLD / MARGIN_SECOND_NEW incl. sample-buffer merge)
 //   outliersRejection :1741-1798, reprojectionError :1729-1739       outliersRejection
 //
-// Not restated (out of scope): initFramePoseByPnP (cv::solvePnP) and solveGyroscopeBias during the first
-// eleven frames — poses of the start-up window come from IMU propagation alone, for which the gyro-bias alignment is the
-// identity. failureDetection() returns false on its first line in the reference and has no counterpart here.
+// Not wired in: initFramePoseByPnP and solveGyroscopeBias during the first eleven frames — poses of the
+// start-up window come from IMU propagation alone, for which the gyro-bias alignment is the identity. The library computes the PnP
+// pose of a frame on the device (vilo_batch_frame_pose_pnp, include/vilo_gpu.h; Gauss-Newton, parity unpinned against cv::solvePnP);
+// this window manager does not call it yet, because that would alter the trajectories it replays. solveGyroscopeBias is not restated.
+// failureDetection() returns false on its first line in the reference and has no counterpart here.
 //
 // Parity status: the reference's Estimator cannot be compiled in this image (ROS / OpenCV / Ceres), so this file is pinned only
 // through its parts: FeatureWindow against the reference's FeatureManager, the solve / marginalise calls against the oracle

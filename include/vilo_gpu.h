@@ -555,6 +555,72 @@ int vilo_window_triangulate(vilo_ctx *ctx, int n_windows, const vilo_window_desc
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_triangulate: k_triangulate, without the copies. */
 double vilo_last_triangulate_ms(const vilo_ctx *ctx);
 
+/* ---- frame pose by PnP from the landmarks that have depth (FeatureManager::initFramePoseByPnP, feature_manager.cpp:259-300, with
+ * solvePoseByPnP :215-257) ----
+ * State: the batch's current state, what vilo_batch_download returns. Rotation matrices are taken from the normalised quaternions, as
+ * vilo_batch_triangulate takes them. Per window, for one frame k with 1 <= k <= n_frames - 1 (opts->frame; -1: the window's last frame):
+ *   points   landmark l is used when its current inverse depth is > 0 and 1 <= k - start_l < n_obs_l. World point
+ *            Rs[s] (ric0 (point_0 / inv_depth) + tic0) + Ps[s] with s = start_l (:273-274); image point: point.xy of observation k - s, no td
+ *            compensation, as in the reference.
+ *            Deviation 1: k - s = 0 is left out. In the reference's call order such a landmark has no depth yet; here it would define the
+ *            pose by itself. Deviation 2: everything stays FP64 (the reference rounds to cv::Point2f / Point3f).
+ *   start    VILO_PNP_GUESS_PREVIOUS (the reference): RCam = Rs[k-1] ric0, PCam = Rs[k-1] tic0 + Ps[k-1]; VILO_PNP_GUESS_CURRENT: the same of
+ *            frame k's own pose. Either is inverted to cam_T_w = (R, t) as :222-223 does.
+ *   iterate  plain Gauss-Newton on sum |pi(R X + t) - uv|^2 with K = I and no distortion: left-multiplicative perturbation (dtheta, dt) on
+ *            cam_T_w (R <- Exp(dtheta) R, t <- Exp(dtheta) t + dt), the 6 x 6 normal system solved by Cholesky; stops when |delta| <=
+ *            opts->step_tolerance, at the latest after opts->max_iterations steps (20: the count cv::solvePnP's iterative mode runs at
+ *            most). This is the library's own restatement: cv::solvePnP's Levenberg-Marquardt stops at FLT_EPSILON; parity is unpinned
+ *            against OpenCV.
+ *   result   Rs[k] = RCam ric0^T, Ps[k] = -RCam ric0^T tic0 + PCam (:292-293) with (RCam, PCam) the inverse of (R, t), written as
+ *            pose[w] = [px py pz qx qy qz qw], the quaternion normalised, qw >= 0.
+ * records[w] (may be NULL): final_cost = 1/2 sum r^2 at the pose returned, initial_cost the same at the start, n_points, iterations (steps
+ * taken) and status:
+ *   VILO_PNP_OK                 the last step was within the tolerance
+ *   VILO_PNP_NOT_ENOUGH_POINTS  fewer than four points (:226)
+ *   VILO_PNP_NO_CONVERGENCE     max_iterations steps, the last above the tolerance; pose is the last iterate
+ *   VILO_PNP_NUMERIC            a Cholesky pivot not positive, a value not finite, or a point with camera-frame z <= 0 at an iterate
+ *   VILO_PNP_NO_FRAME           k out of range for this window
+ * For any status but OK and NO_CONVERGENCE pose[w] is frame k's current pose bit for bit (the reference leaves the pose alone when PnP
+ * fails; NO_FRAME: row k of the padded state) and the costs are those of the last evaluation made, 0 if none was.
+ * Side effects: with opts->write == 0 none. With opts->write == 1 frame k's pose in the batch's current state becomes pose[w] for the
+ * windows with status OK and nothing else changes: vilo_batch_reset still restores the uploaded state; a following
+ * vilo_batch_triangulate or vilo_batch_solve (plain launches or the captured graph) starts from the new pose. The call's device memory is
+ * returned when it returns. Every output of a window is bitwise independent of the batch it shares and of its position in it.
+ * opts NULL: vilo_default_pnp_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx or batch, NULL pose with windows present, an unknown guess, frame below -1, 0 or above
+ * VILO_MAX_FRAMES - 1, max_iterations below 1 or above 64, step_tolerance not finite or negative. */
+#define VILO_PNP_GUESS_PREVIOUS 0
+#define VILO_PNP_GUESS_CURRENT 1
+#define VILO_PNP_OK 0
+#define VILO_PNP_NOT_ENOUGH_POINTS 1
+#define VILO_PNP_NO_CONVERGENCE 2
+#define VILO_PNP_NUMERIC 3
+#define VILO_PNP_NO_FRAME 4
+typedef struct {
+  int32_t frame;            /* -1: the window's last frame */
+  int32_t guess;            /* VILO_PNP_GUESS_* */
+  int32_t write;            /* 1: frame k's pose of the batch's current state becomes the result (status OK only) */
+  int32_t max_iterations;   /* 20 */
+  double step_tolerance;    /* 1e-12 */
+} vilo_pnp_opts;
+void vilo_default_pnp_opts(vilo_pnp_opts *o);
+typedef struct {
+  double final_cost;
+  double initial_cost;
+  int32_t n_points;
+  int32_t iterations;
+  int32_t status;           /* VILO_PNP_* */
+  int32_t pad;
+} vilo_window_pnp_record;
+
+int vilo_batch_frame_pose_pnp(vilo_ctx *ctx, vilo_batch *batch, const vilo_pnp_opts *opts, double *pose, vilo_window_pnp_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed; with opts->write the new pose row is written into
+ * state[w].pose. */
+int vilo_window_frame_pose_pnp(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state, const vilo_pnp_opts *opts,
+                               double *pose, vilo_window_pnp_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_frame_pose_pnp: k_frame_pose_pnp, without the copies. */
+double vilo_last_pnp_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
