@@ -139,6 +139,19 @@ PNP_GUESS = {"previous": 0, "current": 1}   # VILO_PNP_GUESS_*
 PNP_OK, PNP_NOT_ENOUGH_POINTS, PNP_NO_CONVERGENCE, PNP_NUMERIC, PNP_NO_FRAME = 0, 1, 2, 3, 4   # a window's status (VILO_PNP_*)
 MAX_FRAMES = 11   # VILO_MAX_FRAMES
 
+class GyroOpts(C.Structure):
+    """vilo_gyro_opts (8 bytes)"""
+    _fields_ = [("linearization", C.c_int32), ("write", C.c_int32)]
+
+
+class WindowGyroRecord(C.Structure):
+    """vilo_window_gyro_record (24 bytes)"""
+    _fields_ = [("initial_cost", C.c_double), ("model_cost", C.c_double), ("n_intervals", C.c_int32), ("status", C.c_int32)]
+
+
+GYRO_LINEARIZATION = {"record": 0, "corrected": 1}   # VILO_GYRO_RECORD / VILO_GYRO_CORRECTED
+GYRO_OK, GYRO_NO_INTERVALS, GYRO_SINGULAR, GYRO_NUMERIC = 0, 1, 2, 3   # a window's status (VILO_GYRO_*)
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

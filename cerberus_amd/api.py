@@ -36,6 +36,7 @@ def lib():
         L.vilo_last_gradient_ms.restype = C.c_double
         L.vilo_last_triangulate_ms.restype = C.c_double
         L.vilo_last_pnp_ms.restype = C.c_double
+        L.vilo_last_gyro_align_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -198,6 +199,29 @@ def _frame_pose_pnp(ctx, n, frame, guess, write, max_iterations, step_tolerance,
     return FramePose(pose, a["final_cost"], a["initial_cost"], a["n_points"], a["iterations"], a["status"])
 
 
+GyroAlignment = collections.namedtuple("GyroAlignment", "delta_bg initial_cost model_cost n_intervals status")
+
+
+def gyro_opts(linearization="record", write=False):
+    """T.GyroOpts of a gyro_bias_align call; needs no device. linearization: 'record' (the reference: the records' delta_q as they are) or
+    'corrected' (delta_q corrected to first order for the state's gyro biases, as the IMU factors correct it)."""
+    if linearization not in T.GYRO_LINEARIZATION:
+        raise ValueError("linearization must be one of %s" % sorted(T.GYRO_LINEARIZATION))
+    o = T.GyroOpts()
+    o.linearization, o.write = T.GYRO_LINEARIZATION[linearization], 1 if write else 0
+    return o
+
+
+def _gyro_bias_align(ctx, n, linearization, write, call):
+    o = gyro_opts(linearization, write)
+    delta_bg = np.zeros((n, 3))
+    rec = (T.WindowGyroRecord * n)()
+    ctx._check(call(C.byref(o), _p(delta_bg), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.WindowGyroRecord._fields_]),
+                      count=n).copy()
+    return GyroAlignment(delta_bg, a["initial_cost"], a["model_cost"], a["n_intervals"], a["status"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -296,6 +320,14 @@ class Batch:
         write=True stores the pose of the windows with status T.PNP_OK as that frame's current pose; otherwise the batch is left as it was."""
         return _frame_pose_pnp(self.ctx, len(self._descs), frame, guess, write, max_iterations, step_tolerance,
                                lambda *a: lib().vilo_batch_frame_pose_pnp(self.ctx.h, self.handle, *a))
+
+    def gyro_bias_align(self, linearization="record", write=False):
+        """vilo_batch_gyro_bias_align at the batch's device state: GyroAlignment(delta_bg [W, 3], initial_cost, model_cost, n_intervals,
+        status (T.GYRO_*), each [W]): the gyro-bias step that makes the records' preintegrated rotations agree with the poses
+        (solveGyroscopeBias). write=True adds it to every frame's gyro bias of the windows with status T.GYRO_OK; otherwise the batch is
+        left as it was."""
+        return _gyro_bias_align(self.ctx, len(self._descs), linearization, write,
+                                lambda *a: lib().vilo_batch_gyro_bias_align(self.ctx.h, self.handle, *a))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -631,6 +663,16 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _frame_pose_pnp(self, n, frame, guess, write, max_iterations, step_tolerance,
                                lambda *a: lib().vilo_window_frame_pose_pnp(self.h, n, descs, states, *a))
+
+    def window_gyro_bias_align(self, windows, linearization="record", write=False):
+        """vilo_window_gyro_bias_align: the gyro-bias alignment of host windows at their current state arrays (see Batch.gyro_bias_align);
+        with write=True the windows' speed_bias arrays receive the new gyro biases."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _gyro_bias_align(self, n, linearization, write,
+                                lambda *a: lib().vilo_window_gyro_bias_align(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

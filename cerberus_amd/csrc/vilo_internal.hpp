@@ -46,6 +46,7 @@ struct vilo_ctx {
   double last_grad_ms = 0.0;       // GPU time of the last vilo_batch_gradient (linearisation + k_gradient)
   double last_tri_ms = 0.0;        // GPU time of the last vilo_batch_triangulate (k_triangulate)
   double last_pnp_ms = 0.0;        // GPU time of the last vilo_batch_frame_pose_pnp (k_frame_pose_pnp)
+  double last_gyro_ms = 0.0;       // GPU time of the last vilo_batch_gyro_bias_align (k_gyro_bias_align and, with samples in force, the re-integration)
   int marg_general_count = 0;     // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
@@ -208,6 +209,8 @@ int vilo_with_batch(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo
   vilo_batch_destroy(ctx, bt);
   return rc;
 }
+// vilo_batch.hip: the batch's preintegration records on the device ([W * 10] vilo_preint when *leg, else vilo_preint_imu)
+const void *vilo_batch_records(vilo_batch *bt, int *leg);
 // vilo_batch.hip: a call on many host windows cut into sub-batches over the context's pipeline lanes (false: not a call to cut)
 bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
                        const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out);

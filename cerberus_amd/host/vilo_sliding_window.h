@@ -18,7 +18,9 @@
 // Not wired in: initFramePoseByPnP and solveGyroscopeBias during the first eleven frames — poses of the
 // start-up window come from IMU propagation alone, for which the gyro-bias alignment is the identity. The library computes the PnP
 // pose of a frame on the device (vilo_batch_frame_pose_pnp, include/vilo_gpu.h; Gauss-Newton, parity unpinned against cv::solvePnP);
-// this window manager does not call it yet, because that would alter the trajectories it replays. solveGyroscopeBias is not restated.
+// this window manager does not call it yet, because that would alter the trajectories it replays. solveGyroscopeBias is restated too
+// (vilo_batch_gyro_bias_align) and not called by this window manager because, on its IMU-propagated start-up poses, the alignment is
+// the identity.
 // failureDetection() returns false on its first line in the reference and has no counterpart here.
 //
 // Parity status: the reference's Estimator cannot be compiled in this image (ROS / OpenCV / Ceres), so this file is pinned only

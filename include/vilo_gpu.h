@@ -621,6 +621,74 @@ int vilo_window_frame_pose_pnp(vilo_ctx *ctx, int n_windows, const vilo_window_d
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_frame_pose_pnp: k_frame_pose_pnp, without the copies. */
 double vilo_last_pnp_ms(const vilo_ctx *ctx);
 
+/* ---- gyroscope-bias alignment of a window's preintegrated rotations with its poses (solveGyroscopeBias,
+ * src/initial/initial_aligment.cpp:14-40; called by processImage once the window fills, estimator.cpp:738-762) ----
+ * State: the batch's current state, what vilo_batch_download returns. Quaternions are normalised, as vilo_batch_triangulate and
+ * vilo_batch_frame_pose_pnp normalise them. Per window, over EVERY interval k, 0 <= k < n_frames - 1, whether or not it carries a factor
+ * (the reference walks all of all_image_frame; sum_dt > 10 s does not exclude an interval):
+ *   q_ij   q_k^-1 (x) q_{k+1}, from the poses (:30 takes it from the rotation matrices, so its w is >= 0 whatever the sign of the stored
+ *          quaternions; see r_k).
+ *   J_k    the 3 x 3 block d(rotation) / d(gyro bias) of interval k's record Jacobian (:31): rows 3.., columns 24.. of the 31 x 31
+ *          IMU-leg record (ILO_R, ILO_BG, parameters.h:138,145) when use_leg == 1, rows 3.., columns 12.. of the 15 x 15 IMU record
+ *          (O_R, O_BG, parameters.h:121,124) when use_leg == 0. It is the block the IMU factors call dq_dbg.
+ *   gamma  opts->linearization == VILO_GYRO_RECORD (default; the reference, literally): the record's delta_q.
+ *          VILO_GYRO_CORRECTED: delta_q (x) deltaQ(J_k (Bg_k - lin_bg_k)), the corrected rotation the IMU factors use
+ *          (imu_leg_factor.cpp / imu_factor.h: corrected_delta_q), Bg_k frame k's gyro bias of the current state. The two coincide when
+ *          the state's biases are the records' linearisation point, as they are at the reference's call; the corrected form makes the call
+ *          meaningful on a batch whose biases have moved, and makes repeated calls with write-back converge.
+ *   r_k    2 vec(gamma^-1 (x) q_ij) (:32), gamma^-1 the conjugate over the squared norm (Eigen's inverse()), the product negated when its
+ *          w is < 0: q and -q are the same rotation, and pose quaternions of neighbouring frames loaded from another source may lie in
+ *          opposite hemispheres. Where they do not (vector2double's output), nothing is negated and the bits are the reference's formula's.
+ *   step   A = sum J_k^T J_k, b = sum J_k^T r_k (:33-34), delta_bg = A^-1 b by an UNPIVOTED LDL^T of the symmetric 3 x 3. Eigen's ldlt()
+ *          (:36) pivots; the two agree to rounding (A is a sum of squares of blocks close to -sum_dt I).
+ * Outputs per window: delta_bg[w][3], and records[w] (may be NULL): initial_cost = 1/2 sum |r_k|^2, model_cost = 1/2 sum |r_k - J_k delta_bg|^2,
+ * n_intervals = n_frames - 1 and status:
+ *   VILO_GYRO_OK
+ *   VILO_GYRO_NO_INTERVALS  n_frames < 2 (vilo_batch_create refuses such a window: not reachable through a batch created by this library)
+ *   VILO_GYRO_SINGULAR      an LDL^T pivot is <= 0 (e.g. every J_k zero)
+ *   VILO_GYRO_NUMERIC       a sum, a pivot or the step is not finite
+ * For any status but OK delta_bg is 0 and model_cost is initial_cost (NaN where a residual is not finite).
+ * Side effects: with opts->write == 0 none. With opts->write == 1, for the windows with status OK, Bg_i += delta_bg for EVERY frame
+ * i < n_frames of the batch's current state (:39-40: one IEEE addition per component) and nothing else changes: vilo_batch_reset still
+ * restores the uploaded state; a following vilo_batch_solve (plain launches or the captured graph) starts from the new biases.
+ * The reference's trailing repropagate loops (:42-47, estimator.cpp:752-760) are not part of this call. Without samples the batch's records
+ * keep their linearisation point and the factors' first-order correction takes the new bias; with vilo_batch_set_samples in force the
+ * next solve integrates every interval again at the new biases anyway.
+ * With samples in force the records in device memory may sit at a rejected candidate point, so the call first integrates them again at
+ * the current state, on copies of its own, as vilo_batch_residuals does (intervals above 10 s, which carry no factor, keep the record they
+ * have): the batch's records and contact-force filters are not touched, and both linearizations then return the same bits.
+ * The call's device memory is returned when it returns. Every output of a window is bitwise independent of the batch it shares and of
+ * its position in it. opts NULL: vilo_default_gyro_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx or batch, NULL delta_bg with windows present, an unknown linearization, write other than 0
+ * or 1. A batch that holds no preintegration records on the device: VILO_ERR_UNSUPPORTED. A batch without windows: VILO_OK, nothing is
+ * written. */
+#define VILO_GYRO_RECORD 0
+#define VILO_GYRO_CORRECTED 1
+#define VILO_GYRO_OK 0
+#define VILO_GYRO_NO_INTERVALS 1
+#define VILO_GYRO_SINGULAR 2
+#define VILO_GYRO_NUMERIC 3
+typedef struct {
+  int32_t linearization;    /* VILO_GYRO_RECORD / VILO_GYRO_CORRECTED */
+  int32_t write;            /* 1: Bg of every frame of the batch's current state += delta_bg (status OK only) */
+} vilo_gyro_opts;
+void vilo_default_gyro_opts(vilo_gyro_opts *o);
+typedef struct {
+  double initial_cost;
+  double model_cost;
+  int32_t n_intervals;
+  int32_t status;           /* VILO_GYRO_* */
+} vilo_window_gyro_record;
+
+int vilo_batch_gyro_bias_align(vilo_ctx *ctx, vilo_batch *batch, const vilo_gyro_opts *opts, double *delta_bg, vilo_window_gyro_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed; with opts->write the new biases are written into
+ * state[w].speed_bias. */
+int vilo_window_gyro_bias_align(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state, const vilo_gyro_opts *opts,
+                                double *delta_bg, vilo_window_gyro_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_gyro_bias_align: k_gyro_bias_align and, with samples in force, the
+ * re-integration before it, without the copies out. */
+double vilo_last_gyro_align_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
