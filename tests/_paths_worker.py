@@ -5,6 +5,10 @@ window's final state, every window's summary and the full states of the special 
 Spec key "field": a further resident batch (32 windows, or spec["field_sizes"]) of the ragged, part-mono, outlier-laden windows of
 tests/field_windows.py in turn, each at first, middle and last positions, solved like the main batch.
 
+Spec key "alt": one further batch under the alternative configuration of tests/alt_config.py (a context of its own): the field windows
+generated and filled at that configuration, in turn over 32 positions (or spec["alt_sizes"]), reported under "alt32" (row N: also "alt257"
+and "alt2049").
+
 Also importable (no GPU): the window set and its layout, which the test solves with the oracle."""
 import hashlib
 import json
@@ -229,6 +233,23 @@ def main():
             ws, names = field_batch(FS, W, bool(spec.get("td")) or spec.get("compact") == 0)
             res["field%d" % W] = {"W": W, "names": names, "solves": _solve_resident(ctx, ws, opts, field_keep(names))}
     ctx.close()
+    if spec.get("alt"):
+        import alt_config
+        import field_windows as FW
+        acfg = alt_config.alt_config(cfg)
+        oacfg = O.config_from(acfg)
+        actx = api.Context(acfg, 0)
+        if "compact" in spec:
+            actx.set_compact_rows(spec["compact"])
+        import time
+        t0 = time.perf_counter()
+        AS = FW.field_set(acfg, oacfg)
+        for W in spec.get("alt_sizes", [32]):
+            ws, names = field_batch(AS, W, bool(spec.get("td")) or spec.get("compact") == 0)
+            res["alt%d" % W] = {"W": W, "names": names, "solves": _solve_resident(actx, ws, opts, field_keep(names), n_solves=2)}
+            res["alt%d" % W]["seconds"] = time.perf_counter() - t0   # (what this batch adds to the row, window generation included)
+            t0 = time.perf_counter()
+        actx.close()
     print("PATHS_JSON " + json.dumps(res))
 
 

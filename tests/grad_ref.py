@@ -81,7 +81,7 @@ def record(free, sg, sd, lg, ld):
     return r
 
 
-def window_gradient(cfg, w, huber_delta=1.0):
+def window_gradient(cfg, w, huber_delta=None):
     """(cost, state_grad, state_diag, lm_grad, lm_diag, record) of window w at its state arrays"""
     cost, g, h = RG.cost_and_gradient(cfg, w, huber_delta)
     sg, sd, lg, ld = flatten(w, g, h)

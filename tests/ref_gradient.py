@@ -13,9 +13,11 @@ def _blocks(w):
     return {0: w.pose, 1: w.speed_bias, 2: w.leg_bias, 3: w.ex_pose, 4: w.td.reshape(1, 1)}
 
 
-def cost_and_gradient(cfg, w, huber_delta=1.0):
+def cost_and_gradient(cfg, w, huber_delta=None):
     """Returns (cost, g, h): g[(kind, index)] / g[('lam', l)] = gradient in the block's LOCAL coordinates, h likewise = the diagonal of the
     Gauss-Newton Hessian sum_blocks rho' J^T J (what a gradient entry is measured against: g_i / sqrt(h_i) is dimensionless)."""
+    if huber_delta is None:   # (the configuration's threshold: no literal)
+        huber_delta = cfg.huber_delta
     F = w.F
     g, h = {}, {}
     cost = 0.0
@@ -88,10 +90,12 @@ def free_gradient(w, g):
     return np.concatenate(out)
 
 
-def dense_jacobian(cfg, w, huber_delta=1.0):
+def dense_jacobian(cfg, w, huber_delta=None):
     """The whole problem as Ceres' evaluator hands it to the linear solver: r (all residual blocks stacked, loss-corrected) and the dense
     Jacobian in LOCAL coordinates over the free blocks — Corrector's first branch (rho'' <= 0 for Huber: residual and Jacobian of a block
     times sqrt(rho'), corrector.cc) — with the column layout {key: slice}. Inverse depths last."""
+    if huber_delta is None:   # (the configuration's threshold: no literal)
+        huber_delta = cfg.huber_delta
     rows_r, rows_J = [], []
     keys_seen = {}
 

@@ -116,7 +116,7 @@ def window_residuals(cfg, w, outlier_threshold_px=3.0):
     return out
 
 
-def shift_observations(w, landmarks, px=10.0, focal_length=460.0):
+def shift_observations(w, landmarks, px, focal_length):
     """Moves the left-camera point of every non-start observation of the given landmarks by px pixels in x (in place; the inputs are
     copied first, so twins of w keep theirs)."""
     w.obs = w.obs.copy()

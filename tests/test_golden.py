@@ -256,6 +256,58 @@ def test_gpu_force_model_preintegration_vs_reference(gwin):
     c.close()
 
 
+# ------------------------------------------------------------------------------ the alternative configuration (tests/alt_config.py)
+GA = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "preint_alt_config.npz"))
+
+
+def _alt_inputs(ctype):
+    """(configuration, golden window generated at it, samples) for contact_sensor_type 0 (contact flags) or 2 (forces)."""
+    import alt_config as A
+    from test_oracle_vs_reference import force_samples
+    alt = A.alt_config(synth.default_config())
+    w = synth.make_window(alt, n_landmarks=int(G["win_landmarks"]), seed=int(G["win_seed"]))
+    return A.with_type(alt, ctype), w, force_samples(w.samples, seed=int(GA["force_seed"])) if ctype == 2 else w.samples
+
+
+def _check_alt_records(pre, ref, rt_state, rt_jac, rt_cov):
+    np.testing.assert_allclose(pre[:, :33], ref[:, :33], rtol=rt_state, atol=1e-13)
+    np.testing.assert_allclose(pre[:, 33:994], ref[:, 33:994], rtol=rt_jac, atol=1e-11)
+    for k in range(ref.shape[0]):
+        cov = ref[k, 994:]
+        np.testing.assert_allclose(pre[k, 994:], cov, rtol=rt_cov, atol=1e-11 * np.abs(cov).max())
+
+
+def test_golden_alt_config_records_are_not_the_default_configurations():
+    """The frozen records differ from the default configuration's (reference_vectors.npz, preint_force_model.npz) in state, jacobian and
+    covariance: R_br, p_br and rho_fix reach the foot-velocity integrals, the noise values the covariance."""
+    for ref, base in ((GA["preint0"], G["preint"]), (GA["preint2"], GF["preint"])):
+        assert ref.shape == base.shape
+        for k in range(ref.shape[0]):
+            assert _rel(ref[k, 11:23], base[k, 11:23]) > 1e-3 and _rel(ref[k, 33:994], base[k, 33:994]) > 1e-3 and _rel(ref[k, 994:], base[k, 994:]) > 1e-3
+
+
+@pytest.mark.parametrize("ctype", [0, 2])
+def test_oracle_alt_config_preintegration(ctype):
+    """tests/golden/preint_alt_config.npz: the reference's IMULegIntegrationBase at the alternative configuration, both contact models,
+    frozen by tests/golden/make_golden_altcfg.py. The force-model pair's bounds."""
+    cfg, w, smp = _alt_inputs(ctype)
+    oc = O.config_from(cfg)
+    pre = np.array([O.preintegrate_imu_leg(oc, smp[w.sample_offsets[k]:w.sample_offsets[k + 1]], w.lin[k]) for k in range(w.F - 1)])
+    _check_alt_records(pre, GA["preint%d" % ctype], 1e-12, 1e-10, 1e-9)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ctype", [0, 2])
+def test_gpu_alt_config_preintegration_vs_reference(ctype):
+    from cerberus_amd import api
+    cfg, w, smp = _alt_inputs(ctype)
+    c = api.Context(cfg, 0)
+    try:
+        _check_alt_records(c.preintegrate(smp, w.sample_offsets, w.lin), GA["preint%d" % ctype], 1e-11, 1e-9, 1e-8)
+    finally:
+        c.close()
+
+
 # ------------------------------------------------------------------------------ repropagate() with the force-based contact model
 GR = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "preint_force_model_reprop.npz"))
 

@@ -17,6 +17,11 @@ branch, a landmark with one factor, a group of more than 64 lanes, one all-mono 
 positions (rows A to L; the td-estimating one at position 6 of the 23-column rows) and over 257, 513 and 2049 positions (row N). The same
 checks and bounds hold on them (tests/test_field_windows.py holds the properties of the windows on a CPU).
 
+A fourth batch (worker spec "alt") holds the same field windows generated, filled and solved under the alternative configuration of
+tests/alt_config.py, in every row that has the field batch: huber_delta, focal_length and g_norm travel as launch arguments of every
+visual, cost and IMU kernel form, and at their defaults (1.0 among them) a wrong launch line is bitwise right. 32 positions per row; 257
+and 2049 as well in row N, where the plan changes.
+
 Checks: every special window at every position against the oracle (equal iterations / successful steps, cost 1e-8, states 1e-8; the
 far-off windows: equal decisions, states 1e-4 as tests/test_solver_forms.py holds the solver forms); bitwise where the code or the
 documents claim it; 1e-9 elsewhere on the windows with a prior (the solver forms' bound)."""
@@ -39,24 +44,24 @@ SIZES = [128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049]
 
 # row: (environment, worker spec)
 ROWS = {
-    "A": ({}, {"far": 1, "host": 1, "field": 1}),
-    "B1": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "1"}, {"far": 1, "field": 1}),
-    "B0": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "0"}, {"far": 1, "field": 1}),
-    "C": (_C, {"far": 1, "field": 1}),
-    "D": (dict(_C, VILO_IMU_SINGLE_MAX_WINDOWS="0"), {"far": 1, "field": 1}),
-    "E": (_E, {"far": 1, "field": 1}),
-    "F": (_F, {"far": 1, "field": 1}),
-    "G": (_G, {"far": 1, "field": 1}),
-    "H": (dict(_G, VILO_VISUAL_FORM="single"), {"far": 1, "field": 1}),
-    "Itpar": ({}, {"compact": 0, "far": 1, "field": 1}),
-    "Iwalk": ({"VILO_NO_TPAR": "1"}, {"compact": 0, "far": 1, "field": 1}),
-    "J": ({}, {"td": 1, "field": 1}),
-    "K0": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "0"}, {"field": 1}),
-    "K1": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "1"}, {"field": 1}),
-    "K2": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "2"}, {"field": 1}),
-    "L": ({"VILO_NO_GRAPH": "1"}, {"field": 1}),
+    "A": ({}, {"far": 1, "host": 1, "field": 1, "alt": 1}),
+    "B1": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "1"}, {"far": 1, "field": 1, "alt": 1}),
+    "B0": ({"VILO_NO_TPAR": "1", "VILO_IMU_FIRST": "0"}, {"far": 1, "field": 1, "alt": 1}),
+    "C": (_C, {"far": 1, "field": 1, "alt": 1}),
+    "D": (dict(_C, VILO_IMU_SINGLE_MAX_WINDOWS="0"), {"far": 1, "field": 1, "alt": 1}),
+    "E": (_E, {"far": 1, "field": 1, "alt": 1}),
+    "F": (_F, {"far": 1, "field": 1, "alt": 1}),
+    "G": (_G, {"far": 1, "field": 1, "alt": 1}),
+    "H": (dict(_G, VILO_VISUAL_FORM="single"), {"far": 1, "field": 1, "alt": 1}),
+    "Itpar": ({}, {"compact": 0, "far": 1, "field": 1, "alt": 1}),
+    "Iwalk": ({"VILO_NO_TPAR": "1"}, {"compact": 0, "far": 1, "field": 1, "alt": 1}),
+    "J": ({}, {"td": 1, "field": 1, "alt": 1}),
+    "K0": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "0"}, {"field": 1, "alt": 1}),
+    "K1": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "1"}, {"field": 1, "alt": 1}),
+    "K2": ({"VILO_NO_TPAR": "1", "VILO_WAVE_ORDER": "2"}, {"field": 1, "alt": 1}),
+    "L": ({"VILO_NO_GRAPH": "1"}, {"field": 1, "alt": 1}),
     "M": ({"VILO_FULL_RECORD_UPLOAD": "1", "VILO_NO_PINNED_STAGING": "1"}, {"host_only": 1}),
-    "N": ({}, {"sizes": SIZES, "few_sizes": [300], "field": 1, "field_sizes": [257, 513, 2049]}),
+    "N": ({}, {"sizes": SIZES, "few_sizes": [300], "field": 1, "alt": 1, "field_sizes": [257, 513, 2049], "alt_sizes": [32, 257, 2049]}),
 }
 FIELD_ROWS = [r for r in ROWS if "field" in ROWS[r][1]]
 FIELD_PRIOR = ("f40", "f200", "f70_chunks", "f40_allmono")   # the field windows with a prior and compact rows: the 1e-9 bound between forms
@@ -112,7 +117,7 @@ def _run(row):
 def _sized(row):
     """(name, result of one batch) of a row: its W = 32 batch, or row N's sizes."""
     r = _run(row)
-    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith("field")]
+    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith("field") and not k.startswith("alt")]
 
 
 def _field(row):
@@ -361,19 +366,20 @@ def test_field_descriptor(row):
             assert wo == WAVE_ORDER.get(row, 1)
 
 
-@pytest.mark.parametrize("row", FIELD_ROWS)
-def test_field_windows_against_the_oracle(row, field_oracle):
-    """Every field window at every position: the oracle's decisions, cost 1e-8, states 1e-8 (SURVEY 8(c)); one window, one answer
-    wherever it sits in the batch; replays bitwise the plain launches."""
+def _check_field_batches(row, batches, oracle):
+    """Every field window at every position of the batches [(name, result)]: the oracle's decisions, cost 1e-8, states 1e-8 (SURVEY 8(c));
+    each window at first, middle and last positions; one window, one answer wherever it sits; replays bitwise the plain launches.
+    Returns the largest state and cost difference."""
     worst = worst_c = 0.0
-    for name, res in _field(row):
+    for name, res in batches:
         s = res["solves"]
-        for i in (1, 2):
+        assert len(s) >= 2
+        for i in range(1, len(s)):
             assert s[i]["digest"] == s[0]["digest"] and s[i]["summ"] == s[0]["summ"], (row, name, i)
         by_name = _field_by_name(res)
         assert set(by_name) >= {"f40", "f200", "f130_noprior", "f70_chunks", "f40_allmono", "f60_partial8"}
         for nm, entries in by_name.items():
-            so, ost, F = field_oracle[nm]
+            so, ost, F = oracle[nm]
             if nm != "f40_td":
                 pos = [p for p, _, _ in entries]
                 assert pos[0] < 6 and pos[-1] >= res["W"] - 6 and len(pos) >= 3, (row, name, nm, pos)   # first, middle and last positions
@@ -389,6 +395,15 @@ def test_field_windows_against_the_oracle(row, field_oracle):
                     worst = max(worst, e)
                     n_states += 1
             assert n_states >= min(3, len(entries)), (row, name, nm)
+    return worst, worst_c
+
+
+@pytest.mark.parametrize("row", FIELD_ROWS)
+def test_field_windows_against_the_oracle(row, field_oracle):
+    """Every field window at every position: the oracle's decisions, cost 1e-8, states 1e-8 (SURVEY 8(c)); one window, one answer
+    wherever it sits in the batch; replays bitwise the plain launches."""
+    assert all(len(res["solves"]) == 3 for _, res in _field(row))
+    worst, worst_c = _check_field_batches(row, _field(row), field_oracle)
     print("MEASURED test_kernel_paths[%s] field windows vs oracle: states %.2e, cost %.2e" % (row, worst, worst_c))
 
 
@@ -436,3 +451,57 @@ def test_field_other_forms_agree_with_row_A_to_rounding(row):
                     np.testing.assert_allclose(sm["cost_trace"], sm_a["cost_trace"], rtol=1e-9)
                     worst = max(worst, e)
     print("MEASURED test_kernel_paths[%s] field windows vs row A: states %.2e (windows with a prior)" % (row, worst))
+
+
+# ---- the field windows under the alternative configuration (tests/alt_config.py): every form's launch line carries sq, ha and gn ----
+@pytest.fixture(scope="module")
+def alt_oracle():
+    """The oracle's solve of every field window generated and filled at the alternative configuration: {name: (summary, states, F)}."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _paths_worker as P
+    import alt_config
+    import field_windows as FW
+    from cerberus_amd import synth
+    from oracle import oracle_py as O
+    acfg = alt_config.alt_config(synth.default_config())
+    oacfg = O.config_from(acfg)
+    out = {}
+    for name, w in FW.field_set(acfg, oacfg).items():
+        s = O.solve_window(oacfg, w, O.default_opts(True, P.ITERS))
+        out[name] = (s, [a.copy() for a in w.state_arrays()], w.F)
+    return out
+
+
+def _alt(row):
+    return [(k, v) for k, v in _run(row).items() if k.startswith("alt")]
+
+
+@pytest.mark.parametrize("row", FIELD_ROWS)
+def test_alt_config_field_windows_against_the_oracle(row, alt_oracle):
+    """The alternative configuration's batch: the row's forms (row N: the natural ones of 32, 257 and 2049 windows), 1e-9 between forms on
+    the windows with a prior (row A's batch of 32), and test_field_windows_against_the_oracle's checks through the same helper."""
+    got_keys = [k for k, _ in _alt(row)]
+    assert got_keys == (["alt32", "alt257", "alt2049"] if row == "N" else ["alt32"]), got_keys
+    ref = _field_by_name(_run("A")["alt32"])
+    worst_a = 0.0
+    for name, res in _alt(row):
+        exp = EXPECT[row] if row != "N" else (EXPECT["A"] if res["W"] == 32 else EXPECT[str(res["W"])])
+        assert len(res["names"]) == res["W"]
+        for i, sv in enumerate(res["solves"]):
+            got = dict(sv["path"])
+            replay, wo = got.pop("replay"), got.pop("wave_order")
+            assert got == exp, (row, name, i, got)
+            assert replay == (i > 0 and row != "L") and wo == WAVE_ORDER.get(row, 1), (row, name, i)
+        for nm, entries in _field_by_name(res).items():
+            if nm not in FIELD_PRIOR:
+                continue
+            _, st_a, sm_a = ref[nm][0]
+            for p, st, sm in entries:
+                if st is not None:
+                    ea = _rel_states(st, st_a)
+                    assert ea < 1e-9, (row, name, nm, p, ea)
+                    np.testing.assert_allclose(sm["cost_trace"], sm_a["cost_trace"], rtol=1e-9)
+                    worst_a = max(worst_a, ea)
+    worst, worst_c = _check_field_batches(row, _alt(row), alt_oracle)
+    print("MEASURED test_kernel_paths[%s] alternative configuration vs oracle: states %.2e, cost %.2e; vs row A %.2e; %.2f s of the row's worker"
+          % (row, worst, worst_c, worst_a, sum(res["seconds"] for _, res in _alt(row))))

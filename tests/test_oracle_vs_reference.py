@@ -26,16 +26,42 @@ def window(cfg):
     return w
 
 
-def test_kinematics(cfg):
+# ---- the same pins at the alternative configuration (tests/alt_config.py): R_br a skew rotation, p_br non-zero, rho_fix shifted, every
+# noise value, g_norm, focal_length and huber_delta off their defaults. oracle/ref_build/ref_driver.cpp hands every field to the
+# reference's own sources, so nothing but the inputs differs; the bounds are those of the default configuration's tests.
+@pytest.fixture(scope="module")
+def cfg_alt():
+    import alt_config
+    return O.config_from(alt_config.alt_config(synth.default_config()))
+
+
+@pytest.fixture(scope="module")
+def window_alt(cfg_alt):
+    import alt_config
+    w = synth.make_window(alt_config.alt_config(synth.default_config()), n_landmarks=24, seed=5)
+    O.fill_preint(cfg_alt, w)
+    return w
+
+
+def _check_kinematics(rho_fix):
     rng = np.random.default_rng(0)
     for _ in range(20):
         q = np.array([0.2, 0.8, -1.6]) + 0.5 * rng.normal(size=3)
         lc = 0.21 + 0.02 * rng.normal()
-        a = O.kin(q, lc, RF)
+        a = O.kin(q, lc, rho_fix)
         with R.as_oracle():
-            b = O.kin(q, lc, RF)
+            b = O.kin(q, lc, rho_fix)
         for k in a:
             np.testing.assert_allclose(a[k], b[k], rtol=0, atol=1e-14, err_msg=k)
+
+
+def test_kinematics(cfg):
+    _check_kinematics(RF)
+
+
+def test_kinematics_at_the_alternative_configuration(cfg_alt):
+    for j in range(4):
+        _check_kinematics(np.array(list(cfg_alt.rho_fix)[4 * j:4 * j + 4]))
 
 
 def _split(p):
@@ -45,7 +71,14 @@ def _split(p):
 
 
 def test_preintegration_imu_leg(cfg, window):
-    w = window
+    _check_preintegration_imu_leg(cfg, window)
+
+
+def test_preintegration_imu_leg_at_the_alternative_configuration(cfg_alt, window_alt):
+    _check_preintegration_imu_leg(cfg_alt, window_alt)
+
+
+def _check_preintegration_imu_leg(cfg, w):
     for k in range(w.F - 1):
         a, b = w.sample_offsets[k], w.sample_offsets[k + 1]
         po = _split(O.preintegrate_imu_leg(cfg, w.samples[a:b], w.lin[k]))
@@ -68,10 +101,17 @@ def force_samples(samples, seed=0):
 def test_preintegration_contact_sensor_type_2(window):
     """Force-based contact model (imu_leg_integration_base.cpp:195-229, 300-317; go1 configs): adaptive min/max force
     tracker, logistic flag truncated to an integer, 5-sample force variance and the three-term velocity noise."""
+    _check_contact_sensor_type_2(O.default_config(), window)
+
+
+def test_preintegration_contact_sensor_type_2_at_the_alternative_configuration(cfg_alt, window_alt):
+    _check_contact_sensor_type_2(cfg_alt, window_alt)
+
+
+def _check_contact_sensor_type_2(cfg0, w):
     import copy
-    cfg2 = copy.copy(O.default_config())
+    cfg2 = copy.copy(cfg0)
     cfg2.contact_sensor_type = 2
-    w = window
     for k in range(w.F - 1):
         a, b = w.sample_offsets[k], w.sample_offsets[k + 1]
         smp = force_samples(w.samples[a:b], seed=k)
@@ -83,7 +123,7 @@ def test_preintegration_contact_sensor_type_2(window):
         np.testing.assert_allclose(po["jac"], pr["jac"], rtol=1e-10, atol=1e-12)
         np.testing.assert_allclose(po["cov"], pr["cov"], rtol=1e-9, atol=1e-18 + 1e-12 * np.abs(pr["cov"]).max())
         # the model is really different from the flag-based one
-        p0 = _split(O.preintegrate_imu_leg(O.default_config(), w.samples[a:b], w.lin[k]))
+        p0 = _split(O.preintegrate_imu_leg(cfg0, w.samples[a:b], w.lin[k]))
         assert np.abs(po["cov"] - p0["cov"]).max() > 1e-3 * np.abs(p0["cov"]).max()
 
 
@@ -116,7 +156,14 @@ def test_repropagate_on_the_same_object(window):
 
 
 def test_preintegration_imu(cfg, window):
-    w = window
+    _check_preintegration_imu(cfg, window)
+
+
+def test_preintegration_imu_at_the_alternative_configuration(cfg_alt, window_alt):
+    _check_preintegration_imu(cfg_alt, window_alt)
+
+
+def _check_preintegration_imu(cfg, w):
     for k in (0, 4, 9):
         a, b = w.sample_offsets[k], w.sample_offsets[k + 1]
         po = O.preintegrate_imu(cfg, w.samples[a:b], w.lin[k][:6])
@@ -148,6 +195,14 @@ def test_imu_leg_factor(cfg, window):
     """Whitened residual and Jacobians, oracle against the compiled reference: rounding level — the covariance's raw condition number of
     1e13 .. 1e14 is a matter of units (equilibrated: ~ 15, tests/test_oracle_factors.py::test_sqrt_info_routes_against_100_digit_arithmetic),
     and LLT(cov^-1) comes out the same to 1e-15 whichever way it is computed. Measured: 7e-14 per entry, 2e-15 per row."""
+    _check_imu_leg_factor(cfg, window)
+
+
+def test_imu_leg_factor_at_the_alternative_configuration(cfg_alt, window_alt):
+    _check_imu_leg_factor(cfg_alt, window_alt)
+
+
+def _check_imu_leg_factor(cfg, window):
     w, rng = window, np.random.default_rng(3)
     for trial in range(30):
         k = int(rng.integers(0, 10))
@@ -167,6 +222,14 @@ def test_imu_leg_factor(cfg, window):
 
 
 def test_imu_factor(cfg, window):
+    _check_imu_factor(cfg, window)
+
+
+def test_imu_factor_at_the_alternative_configuration(cfg_alt, window_alt):
+    _check_imu_factor(cfg_alt, window_alt)
+
+
+def _check_imu_factor(cfg, window):
     w, rng = window, np.random.default_rng(4)
     for trial in range(30):
         k = int(rng.integers(0, 10))
@@ -181,6 +244,15 @@ def test_imu_factor(cfg, window):
 
 @pytest.mark.parametrize("kind", [0, 1, 2])
 def test_projection_factors(cfg, kind):
+    _check_projection_factors(cfg, kind)
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2])
+def test_projection_factors_at_the_alternative_configuration(cfg_alt, kind):
+    _check_projection_factors(cfg_alt, kind)
+
+
+def _check_projection_factors(cfg, kind):
     rng = np.random.default_rng(10 + kind)
     for _ in range(10):
         pi, pj = rand_pose(rng, 0.5), rand_pose(rng, 0.5)
