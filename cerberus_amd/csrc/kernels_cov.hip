@@ -26,10 +26,9 @@
 
 #include <algorithm>
 
+#include "batch_call.hpp"
 #include "solve_common.hpp"
 #include "vilo_math.hpp"
-
-BatchDev *vilo_batch_dev(vilo_batch *bt);               // vilo_batch.hip
 
 static_assert(sizeof(vilo_cov_opts) == 24, "vilo_cov_opts layout (cerberus_amd/_ctypes.py mirrors it)");
 
@@ -652,53 +651,48 @@ static double *cov_chunk_view(char *p, int w0, size_t per_window) { return (doub
 // outputs (inverse-depth variance, point, point covariance) of k_landmark_covariance after each chunk, or null for no landmark pass.
 static int batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts &o, int want_poses, double *frames, double *poses, double *const *lm,
                             int32_t *status) {
-  VILO_HIP(hipSetDevice(ctx->device));
   BatchDev &bd = *vilo_batch_dev(bt);
-  const int W = bd.W, chunk = std::min(W, CV_CHUNK), n_lm = lm ? bd.n_lm : 0;
-  // the call's device memory, returned when it returns: saved solver state | frames | poses | status | per-window scratch of one chunk |
-  // landmark outputs (variance, point, point covariance)
+  const int W = bd.W, chunk = std::min(W, CV_CHUNK);
+  const size_t n_lm = lm ? (size_t)bd.n_lm : 0;
+  // the call's device memory: saved solver state | frames | poses | status | per-window scratch of one chunk | landmark variance, point, point covariance
   const size_t n_fr = frames ? (size_t)W : (size_t)chunk, n_po = !want_poses ? 0 : poses ? (size_t)W : (size_t)chunk;
-  const size_t o_fr = (sizeof(SolverState) * (size_t)W + 255) & ~(size_t)255;
-  const size_t o_po = o_fr + sizeof(double) * n_fr * CV_FRN, o_stat = o_po + sizeof(double) * n_po * CV_PN;
-  const size_t o_scr = (o_stat + sizeof(int) * (size_t)W + 255) & ~(size_t)255, o_lm = o_scr + sizeof(double) * (size_t)chunk * CS_N;
-  ArenaScope scope(ctx, bt);
-  char *base = (char *)scope.alloc(o_lm + sizeof(double) * 13 * (size_t)n_lm);
-  if (!base) return VILO_ERR_HIP;
-  double *d_var = (double *)(base + o_lm), *d_pts = d_var + n_lm, *d_pcov = d_pts + 3 * (size_t)n_lm;
-  int *d_stat = (int *)(base + o_stat);
+  BatchCall call(ctx, bt, &vilo_ctx::last_cov_ms);
+  const size_t o_st = call.lay.take<SolverState>(W), o_fr = call.lay.take<double>(n_fr * CV_FRN), o_po = call.lay.take<double>(n_po * CV_PN);
+  const size_t o_stat = call.lay.take<int>(W), o_scr = call.lay.take<double>((size_t)chunk * CS_N);
+  const size_t o_var = call.lay.take<double>(n_lm), o_pts = call.lay.take<double>(3 * n_lm), o_pcov = call.lay.take<double>(9 * n_lm);
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  double *d_var = call.ptr<double>(o_var), *d_pts = call.ptr<double>(o_pts), *d_pcov = call.ptr<double>(o_pcov);
+  int *d_stat = call.ptr<int>(o_stat);
   const size_t lds_bytes = sizeof(double) * CL_N;
   if (!ctx->cov_attr_set) {
     VILO_HIP(hipFuncSetAttribute((const void *)k_covariance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     ctx->cov_attr_set = true;
   }
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(base, bd.st, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
-  int rc = vilo_marg_linearize(ctx, bd);
+  VILO_HIP(call.start());
+  SolverStateGuard keep(call, bd, o_st);
+  VILO_HIP(keep.saved);
+  const int rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
   for (int w0 = 0; w0 < W; w0 += chunk) {
     const int n = std::min(chunk, W - w0);
-    double *fr = frames ? (double *)(base + o_fr) : cov_chunk_view(base + o_fr, w0, CV_FRN);
-    double *po = poses ? (double *)(base + o_po) : want_poses ? cov_chunk_view(base + o_po, w0, CV_PN) : nullptr;
+    double *fr = frames ? call.ptr<double>(o_fr) : cov_chunk_view(call.ptr<char>(o_fr), w0, CV_FRN);
+    double *po = poses ? call.ptr<double>(o_po) : want_poses ? cov_chunk_view(call.ptr<char>(o_po), w0, CV_PN) : nullptr;
     hipLaunchKernelGGL(k_covariance, dim3(n), dim3(CV_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, want_poses,
-                       (double *)(base + o_scr), fr, po, d_stat);
+                       call.ptr<double>(o_scr), fr, po, d_stat);
     if (lm)
       hipLaunchKernelGGL(k_landmark_covariance, dim3(n), dim3(LC_T), sizeof(double) * LC_N, ctx->stream, bd, w0, po + (size_t)w0 * CV_PN,
                          d_stat, d_var, d_pts, d_pcov);
   }
   VILO_HIP(hipGetLastError());
-  VILO_HIP(hipMemcpyAsync(bd.st, base, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_cov_ms = ms;
-  if (frames) VILO_HIP(hipMemcpy(frames, base + o_fr, sizeof(double) * (size_t)W * CV_FRN, hipMemcpyDeviceToHost));
-  if (poses) VILO_HIP(hipMemcpy(poses, base + o_po, sizeof(double) * (size_t)W * CV_PN, hipMemcpyDeviceToHost));
-  VILO_HIP(hipMemcpy(status, d_stat, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost));
+  VILO_HIP(keep.restore());
+  VILO_HIP(call.finish());
+  VILO_HIP(call.down(frames, call.ptr<char>(o_fr), sizeof(double) * (size_t)W * CV_FRN));
+  VILO_HIP(call.down(poses, call.ptr<char>(o_po), sizeof(double) * (size_t)W * CV_PN));
+  VILO_HIP(call.down(status, d_stat, sizeof(int) * (size_t)W));
   if (n_lm > 0) {
-    VILO_HIP(hipMemcpy(lm[0], d_var, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-    VILO_HIP(hipMemcpy(lm[1], d_pts, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost));
-    VILO_HIP(hipMemcpy(lm[2], d_pcov, sizeof(double) * 9 * (size_t)n_lm, hipMemcpyDeviceToHost));
+    VILO_HIP(call.down(lm[0], d_var, sizeof(double) * n_lm));
+    VILO_HIP(call.down(lm[1], d_pts, sizeof(double) * 3 * n_lm));
+    VILO_HIP(call.down(lm[2], d_pcov, sizeof(double) * 9 * n_lm));
   }
   return VILO_OK;
 }

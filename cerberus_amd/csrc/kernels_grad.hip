@@ -17,10 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "batch_call.hpp"
 #include "solve_common.hpp"
 #include "vilo_math.hpp"
-
-BatchDev *vilo_batch_dev(vilo_batch *bt);   // vilo_batch.hip
 
 static_assert(sizeof(vilo_window_gradient_record) == 48, "vilo_window_gradient_record: 48 bytes (include/vilo_gpu.h)");
 
@@ -201,41 +200,29 @@ __global__ void __launch_bounds__(GR_T) k_gradient(BatchDev b, vilo_window_gradi
 extern "C" int vilo_batch_gradient(vilo_ctx *ctx, vilo_batch *bt, vilo_window_gradient_record *windows, double *state_grad, double *state_diag,
                                    double *lm_grad, double *lm_diag) {
   if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
-  VILO_HIP(hipSetDevice(ctx->device));
   BatchDev &bd = *vilo_batch_dev(bt);
   const int W = bd.W, n_lm = bd.n_lm;
-  // the call's device memory, returned when it returns: saved solver state | window records | state gradient | state diagonal |
-  // landmark gradient | landmark diagonal
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t at = al(sizeof(SolverState) * (size_t)W);
-  const size_t o_rec = at; at = al(at + sizeof(vilo_window_gradient_record) * (size_t)W);
-  const size_t o_sg = at; at = al(at + sizeof(double) * GR_NS * (size_t)W);
-  const size_t o_sd = at; at = al(at + sizeof(double) * GR_NS * (size_t)W);
-  const size_t o_lg = at; at = al(at + sizeof(double) * (size_t)n_lm);
-  const size_t o_ld = at; at = al(at + sizeof(double) * (size_t)n_lm);
-  ArenaScope scope(ctx, bt);
-  char *base = (char *)scope.alloc(at);
-  if (!base) return VILO_ERR_HIP;
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(base, bd.st, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
+  BatchCall call(ctx, bt, &vilo_ctx::last_grad_ms);
+  // the call's device memory: saved solver state | window records | state gradient | state diagonal | landmark gradient | landmark diagonal
+  const size_t o_st = call.lay.take<SolverState>(W), o_rec = call.lay.take<vilo_window_gradient_record>(W);
+  const size_t o_sg = call.lay.take<double>(GR_NS * (size_t)W), o_sd = call.lay.take<double>(GR_NS * (size_t)W);
+  const size_t o_lg = call.lay.take<double>(n_lm), o_ld = call.lay.take<double>(n_lm);
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  VILO_HIP(call.start());
+  SolverStateGuard keep(call, bd, o_st);
+  VILO_HIP(keep.saved);
   const int rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
-  hipLaunchKernelGGL(k_gradient, dim3(W), dim3(GR_T), 0, ctx->stream, bd, (vilo_window_gradient_record *)(base + o_rec), (double *)(base + o_sg),
-                     (double *)(base + o_sd), (double *)(base + o_lg), (double *)(base + o_ld));
+  hipLaunchKernelGGL(k_gradient, dim3(W), dim3(GR_T), 0, ctx->stream, bd, call.ptr<vilo_window_gradient_record>(o_rec), call.ptr<double>(o_sg),
+                     call.ptr<double>(o_sd), call.ptr<double>(o_lg), call.ptr<double>(o_ld));
   VILO_HIP(hipGetLastError());
-  VILO_HIP(hipMemcpyAsync(bd.st, base, sizeof(SolverState) * (size_t)W, hipMemcpyDeviceToDevice, ctx->stream));
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_grad_ms = ms;
-  VILO_HIP(hipMemcpy(windows, base + o_rec, sizeof(vilo_window_gradient_record) * (size_t)W, hipMemcpyDeviceToHost));
-  if (state_grad) VILO_HIP(hipMemcpy(state_grad, base + o_sg, sizeof(double) * GR_NS * (size_t)W, hipMemcpyDeviceToHost));
-  if (state_diag) VILO_HIP(hipMemcpy(state_diag, base + o_sd, sizeof(double) * GR_NS * (size_t)W, hipMemcpyDeviceToHost));
-  if (n_lm > 0) {
-    if (lm_grad) VILO_HIP(hipMemcpy(lm_grad, base + o_lg, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-    if (lm_diag) VILO_HIP(hipMemcpy(lm_diag, base + o_ld, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-  }
+  VILO_HIP(keep.restore());
+  VILO_HIP(call.finish());
+  VILO_HIP(call.down(windows, call.ptr<char>(o_rec), sizeof(vilo_window_gradient_record) * (size_t)W));
+  VILO_HIP(call.down(state_grad, call.ptr<char>(o_sg), sizeof(double) * GR_NS * (size_t)W));
+  VILO_HIP(call.down(state_diag, call.ptr<char>(o_sd), sizeof(double) * GR_NS * (size_t)W));
+  VILO_HIP(call.down(lm_grad, call.ptr<char>(o_lg), sizeof(double) * (size_t)n_lm));
+  VILO_HIP(call.down(lm_diag, call.ptr<char>(o_ld), sizeof(double) * (size_t)n_lm));
   return VILO_OK;
 }
 

@@ -17,10 +17,9 @@
 #include <math.h>
 #include <stddef.h>
 
+#include "batch_call.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
-
-BatchDev *vilo_batch_dev(vilo_batch *bt);   // vilo_batch.hip
 
 static_assert(sizeof(vilo_gyro_opts) == 8, "vilo_gyro_opts: 8 bytes (include/vilo_gpu.h)");
 static_assert(sizeof(vilo_window_gyro_record) == 24, "vilo_window_gyro_record: 24 bytes (include/vilo_gpu.h)");
@@ -42,20 +41,6 @@ struct GyroArgs {
   double *delta_bg;                // [W][3]
   vilo_window_gyro_record *rec;    // [W]
 };
-
-namespace {
-
-// sums of v over the 16 lanes of a window, the same bits in every one of them
-template <int N>
-__device__ __forceinline__ void gyro_group_sum(double (&v)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int off = GYRO_LANES / 2; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, GYRO_LANES);
-  }
-}
-
-}  // namespace
 
 __global__ void __launch_bounds__(GYRO_THREADS) k_gyro_bias_align(BatchDev b, GyroRecLayout L, GyroArgs a) {
   using namespace vilo;
@@ -102,7 +87,7 @@ __global__ void __launch_bounds__(GYRO_THREADS) k_gyro_bias_align(BatchDev b, Gy
     for (int i = 0; i < 3; ++i) s[6 + i] = J.a[i] * r.x + J.a[3 + i] * r.y + J.a[6 + i] * r.z;
     s[9] = dot(r, r);
   }
-  gyro_group_sum<GYRO_NSUM>(s);
+  lanes_sum<GYRO_NSUM, GYRO_LANES>(s);   // over the 16 lanes of a window
 
   int status = VILO_GYRO_OK;
   double d[3] = {0.0, 0.0, 0.0};
@@ -143,7 +128,7 @@ __global__ void __launch_bounds__(GYRO_THREADS) k_gyro_bias_align(BatchDev b, Gy
     const v3 e = r - J * mk3(d[0], d[1], d[2]);
     mc[0] = dot(e, e);
   }
-  gyro_group_sum<1>(mc);
+  lanes_sum<1, GYRO_LANES>(mc);
 
   if (!win_ok) return;
   if (k == 0) {
@@ -189,12 +174,12 @@ extern "C" int vilo_batch_gyro_bias_align(vilo_ctx *ctx, vilo_batch *bt, const v
   const int rc = gyro_check_opts(ctx, opts, &o);
   if (rc != VILO_OK) return rc;
   const BatchDev &bd = *vilo_batch_dev(bt);
-  const int W = bd.W, NF = W * 10;
+  const int W = bd.W;
   if (W > 0 && !delta_bg) {
     ctx->err = "vilo_batch_gyro_bias_align: delta_bg is NULL";
     return VILO_ERR_BAD_ARG;
   }
-  ctx->last_gyro_ms = 0.0;
+  BatchCall call(ctx, bt, &vilo_ctx::last_gyro_ms);
   if (W == 0) return VILO_OK;
   int leg = 1;
   const void *recs = vilo_batch_records(bt, &leg);
@@ -202,30 +187,15 @@ extern "C" int vilo_batch_gyro_bias_align(vilo_ctx *ctx, vilo_batch *bt, const v
     ctx->err = "vilo_batch_gyro_bias_align: the batch has no preintegration records";
     return VILO_ERR_UNSUPPORTED;
   }
-  VILO_HIP(hipSetDevice(ctx->device));
-  const bool rp = bd.rp_on && bd.rp_samples && bd.leg;
-  // the call's device memory, returned when it returns: steps | records | re-integration copies (records, contact-force filters)
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t at = 0;
-  const size_t o_d = at; at = al(at + sizeof(double) * 3 * (size_t)W);
-  const size_t o_r = at; at = al(at + sizeof(vilo_window_gyro_record) * (size_t)W);
-  const size_t o_rp = at; if (rp) at = al(at + (sizeof(vilo_preint) + sizeof(double) * VILO_FF_N) * (size_t)NF);
-  ArenaScope scope(ctx, bt);
-  char *base = (char *)scope.alloc(at);
-  if (!base) return VILO_ERR_HIP;
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  if (rp) {
-    // the batch's records may sit at a rejected candidate point: integrated again at x on copies, as vilo_batch_residuals does (records
-    // already integrated there are kept: k_repropagate's own test). Only the integration: no factor is whitened here, so the sqrt_info
-    // stage that follows it elsewhere is left out, and with it every write to the batch's prepared records and flags.
-    BatchDev b = bd;
-    b.rp_pre = base + o_rp;
-    b.rp_ff = bd.rp_ff ? (double *)(base + o_rp + sizeof(vilo_preint) * (size_t)NF) : nullptr;
-    VILO_HIP(hipMemcpyAsync(b.rp_pre, bd.rp_pre, sizeof(vilo_preint) * (size_t)NF, hipMemcpyDeviceToDevice, ctx->stream));
-    if (bd.rp_ff) VILO_HIP(hipMemcpyAsync(b.rp_ff, bd.rp_ff, sizeof(double) * VILO_FF_N * (size_t)NF, hipMemcpyDeviceToDevice, ctx->stream));
-    if (vilo_repropagate_launch(ctx, b, 0, 0) != VILO_OK) return VILO_ERR_HIP;
-    recs = b.rp_pre;
-  }
+  // the call's device memory: steps | records | re-integration copies. Only the integration: no factor is whitened here, so the sqrt_info
+  // stage that follows it elsewhere is left out, and with it every write to the batch's prepared records and flags.
+  const size_t o_d = call.lay.take<double>(3 * (size_t)W), o_r = call.lay.take<vilo_window_gyro_record>(W);
+  const ReintegrationBlocks rp(call.lay, bd, 1);
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  VILO_HIP(call.start());
+  BatchDev b = bd;
+  if (call.reintegrate(b, rp) != VILO_OK) return VILO_ERR_HIP;
+  if (rp.on) recs = b.rp_pre;
   GyroRecLayout L;
   L.rec = (const double *)recs;
   if (leg) {
@@ -239,18 +209,13 @@ extern "C" int vilo_batch_gyro_bias_align(vilo_ctx *ctx, vilo_batch *bt, const v
   }
   GyroArgs a;
   a.corrected = o.linearization == VILO_GYRO_CORRECTED ? 1 : 0; a.write = o.write;
-  a.delta_bg = (double *)(base + o_d);
-  a.rec = (vilo_window_gyro_record *)(base + o_r);
+  a.delta_bg = call.ptr<double>(o_d);
+  a.rec = call.ptr<vilo_window_gyro_record>(o_r);
   const int per_block = GYRO_THREADS / GYRO_LANES;
   hipLaunchKernelGGL(k_gyro_bias_align, dim3((W + per_block - 1) / per_block), dim3(GYRO_THREADS), 0, ctx->stream, bd, L, a);
-  VILO_HIP(hipGetLastError());
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_gyro_ms = ms;
-  VILO_HIP(hipMemcpy(delta_bg, a.delta_bg, sizeof(double) * 3 * (size_t)W, hipMemcpyDeviceToHost));
-  if (records) VILO_HIP(hipMemcpy(records, a.rec, sizeof(vilo_window_gyro_record) * (size_t)W, hipMemcpyDeviceToHost));
+  VILO_HIP(call.finish());
+  VILO_HIP(call.down(delta_bg, a.delta_bg, sizeof(double) * 3 * (size_t)W));
+  VILO_HIP(call.down(records, a.rec, sizeof(vilo_window_gyro_record) * (size_t)W));
   return VILO_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <chrono>
 
 #include <type_traits>
+#include "batch_call.hpp"
 #include "solve_common.hpp"
 
 using namespace vilo;
@@ -1028,11 +1029,6 @@ extern "C" int vilo_gauge_fix(vilo_ctx *ctx, int W, const vilo_window_state *bef
   return VILO_OK;
 }
 
-// Batch internals needed here (defined in vilo_batch.hip)
-struct vilo_batch;
-BatchDev *vilo_batch_dev(vilo_batch *bt);
-const int *vilo_batch_perm(vilo_batch *bt, int win, int *L);
-
 // Marginalisation of every window of an existing batch at its current device state (b.x, b.lam). `state` holds the same
 // values on the host (they become keep_block_data of the new prior); modes[w]: 0 MARGIN_OLD, 1 MARGIN_SECOND_NEW, < 0 skip
 // (out[w] untouched). The batch is left alive.
@@ -1132,31 +1128,31 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   std::vector<int> drop_flat((size_t)W * max_l0, 0);
   for (int w = 0; w < W; ++w)
     for (size_t i = 0; i < drops[w].size(); ++i) drop_flat[(size_t)w * max_l0 + i] = drops[w][i];
-  // Every device buffer of the call comes from one arena scope: given back when the call returns. One block for what goes up (window
-  // tables, dropped-landmark lists, prior-pool slots) and the flags that come back (status, need_general, "the IMU factor of interval 0
-  // stands on a covariance without sqrt_info"): one upload, one download per call — a one-window call per image used to spend more time
-  // in its dozen synchronous copies and allocations than in its kernels.
-  ArenaScope scope(ctx, bt);
+  // The call's device memory (BatchCall: given back when the call returns) starts with one block for what goes up (window tables,
+  // dropped-landmark lists, prior-pool slots) and the flags that come back (status, need_general, "the IMU factor of interval 0 stands on
+  // a covariance without sqrt_info"): one upload, one download per call — a one-window call per image used to spend more time in its
+  // dozen synchronous copies and allocations than in its kernels. Behind it J0, r0 and the clock stamps, which stay on the device.
   const bool want_clk = getenv("VILO_MARG_CLOCKS") != nullptr;
-  const size_t off_drop = (sizeof(MargWin) * (size_t)W + 15) & ~(size_t)15, off_flags = (off_drop + sizeof(int) * drop_flat.size() + 15) & ~(size_t)15;
-  const size_t off_slots = off_flags + sizeof(int) * 3 * (size_t)W, blob_bytes = off_slots + sizeof(int) * 2 * (size_t)W;
+  BatchCall call(ctx, bt, &vilo_ctx::last_marg_ms);
+  const size_t off_mw = call.lay.take<MargWin>(W), off_drop = call.lay.take<int>(drop_flat.size());
+  const size_t off_flags = call.lay.take<int>(3 * (size_t)W), off_slots = call.lay.take<int>(2 * (size_t)W), blob_bytes = call.lay.bytes();
+  const size_t nJ0 = (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM, nr0 = (size_t)W * VILO_MAX_PRIOR_DIM;
+  const size_t off_J0 = call.lay.take<double>(nJ0), off_r0 = call.lay.take<double>(nr0), off_clk = call.lay.take<long long>(8 * (size_t)W, want_clk);
   // (the context's reusable page-locked staging: the scope's closing sync outlives the asynchronous copies on every return path)
   char *hblob = (char *)vilo_host_stage(ctx, 6, blob_bytes);
   if (!hblob) return VILO_ERR_HIP;
   memset(hblob, 0, blob_bytes);
-  memcpy(hblob, mws.data(), sizeof(MargWin) * (size_t)W);
+  memcpy(hblob + off_mw, mws.data(), sizeof(MargWin) * (size_t)W);
   if (!drop_flat.empty()) memcpy(hblob + off_drop, drop_flat.data(), sizeof(int) * drop_flat.size());
-  char *d_blob = (char *)scope.alloc(blob_bytes);
-  double *d_J0 = (double *)scope.alloc(sizeof(double) * (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM);
-  double *d_r0 = (double *)scope.alloc(sizeof(double) * (size_t)W * VILO_MAX_PRIOR_DIM);
-  long long *d_clk = want_clk ? (long long *)scope.alloc(sizeof(long long) * 8 * W) : nullptr;
-  if (!d_blob || !d_J0 || !d_r0 || (want_clk && !d_clk)) return VILO_ERR_HIP;
-  MargWin *d_mw = (MargWin *)d_blob;
-  int *d_drop = (int *)(d_blob + off_drop), *d_status = (int *)(d_blob + off_flags), *d_general = d_status + W, *d_pbad = d_status + 2 * (size_t)W;
-  int *d_slots = (int *)(d_blob + off_slots);   // [2][W] prior-pool slots: destination, source
-  if (hipMemcpyAsync(d_blob, hblob, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  double *d_J0 = call.ptr<double>(off_J0), *d_r0 = call.ptr<double>(off_r0);
+  long long *d_clk = want_clk ? call.ptr<long long>(off_clk) : nullptr;
+  MargWin *d_mw = call.ptr<MargWin>(off_mw);   // (the first block: the blob starts here)
+  int *d_drop = call.ptr<int>(off_drop), *d_status = call.ptr<int>(off_flags), *d_general = d_status + W, *d_pbad = d_status + 2 * (size_t)W;
+  int *d_slots = call.ptr<int>(off_slots);   // [2][W] prior-pool slots: destination, source
+  if (hipMemcpyAsync(d_mw, hblob, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
   // preMarginalize: evaluate the factors at the current state (marginalization_factor.cpp:119-138)
-  (void)hipEventRecord(ctx->ev0, ctx->stream);
+  VILO_HIP(call.start());
   rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
   const size_t lds_bytes = (size_t)MG_LDS_DOUBLES * sizeof(double);
@@ -1197,18 +1193,14 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
     }
     // the updated window tables go up in stream order behind the first copy, from the same staging updated in place (with the forced
     // path that copy may still be reading it: whatever it reads, this one lands last)
-    memcpy(hblob, mws.data(), sizeof(MargWin) * (size_t)W);
-    double *d_scr = (double *)scope.alloc(sizeof(double) * std::max<size_t>(1, scratch_total));
-    if (!d_scr || hipMemcpyAsync(d_mw, hblob, sizeof(MargWin) * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+    memcpy(hblob + off_mw, mws.data(), sizeof(MargWin) * (size_t)W);
+    double *d_scr = (double *)call.scope->alloc(sizeof(double) * std::max<size_t>(1, scratch_total));   // (sized only now: an allocation of its own)
+    if (!d_scr || hipMemcpyAsync(d_mw, hblob + off_mw, sizeof(MargWin) * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
     have_flags = false;   // (this kernel writes status too: read again below)
     hipLaunchKernelGGL(k_marginalize, dim3(W), dim3(MT), 0, ctx->stream, bd, d_mw, d_drop, max_l0, d_scr, d_J0, d_r0, d_status);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize launch failed"; return VILO_ERR_HIP; }
   }
-  float marg_ms = 0.f;
-  if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess || hipEventSynchronize(ctx->ev1) != hipSuccess ||
-      hipEventElapsedTime(&marg_ms, ctx->ev0, ctx->ev1) != hipSuccess)
-    return VILO_ERR_HIP;
-  ctx->last_marg_ms = marg_ms;
+  VILO_HIP(call.finish());
   // Status first: a window whose result is unusable must not overwrite a pool slot either.
   std::vector<int> status(W, 0);
   int any_bad = 0;
@@ -1256,13 +1248,12 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   // zero-filled, then filled again through the runtime's bounce buffer: most of a fleet's marginalisation call)
   const double *J0 = nullptr, *r0 = nullptr;
   if (any_host) {
-    const size_t nJ = (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM, nr = (size_t)W * VILO_MAX_PRIOR_DIM;
-    double *hJ = (double *)vilo_host_stage(ctx, 7, sizeof(double) * (nJ + nr));
+    double *hJ = (double *)vilo_host_stage(ctx, 7, sizeof(double) * (nJ0 + nr0));
     if (!hJ) return VILO_ERR_HIP;
-    if (hipMemcpyAsync(hJ, d_J0, nJ * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(hJ + nJ, d_r0, nr * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+    if (hipMemcpyAsync(hJ, d_J0, nJ0 * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(hJ + nJ0, d_r0, nr0 * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
       return VILO_ERR_HIP;
-    J0 = hJ; r0 = hJ + nJ;
+    J0 = hJ; r0 = hJ + nJ0;
   }
   for (int w = 0; w < W; ++w) {
     const MargWin &M = mws[w];

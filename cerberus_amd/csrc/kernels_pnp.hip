@@ -17,11 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "batch_call.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
-
-BatchDev *vilo_batch_dev(vilo_batch *bt);          // vilo_batch.hip
-int vilo_batch_max_window_waves(vilo_batch *bt);   // vilo_batch.hip
 
 static_assert(sizeof(vilo_pnp_opts) == 24, "vilo_pnp_opts: 24 bytes (include/vilo_gpu.h)");
 static_assert(sizeof(vilo_window_pnp_record) == 32, "vilo_window_pnp_record: 32 bytes (include/vilo_gpu.h)");
@@ -29,7 +27,6 @@ static_assert(sizeof(vilo_window_pnp_record) == 32, "vilo_window_pnp_record: 32 
 #define PNP_THREADS 256
 #define PNP_WAVES 4
 #define PNP_NSUM 28        // upper triangle of J^T J (21), J^T r (6), r^T r
-#define PNP_XS 96          // LDS copy of the window's poses (77 doubles) and extrinsics (14, at 80)
 #define PNP_PT 5           // world point and image point of a landmark
 #define PNP_MAX_TRIPS 7    // VILO_NUM_OF_F landmarks make at most 26 packed waves (15 full chunks + one ragged chunk per start frame)
 
@@ -42,15 +39,11 @@ struct PnpArgs {
 
 namespace {
 
-// sums of v over the workgroup, the same bits in every lane: xor butterfly inside a wave (both partners add the same two values), then the
+// sums of v over the workgroup, the same bits in every lane: xor butterfly inside a wave (lanes_sum), then the
 // four waves' sums in wave order. red: [PNP_WAVES][N] of LDS, free again when the call returns.
 template <int N>
 __device__ __forceinline__ void pnp_block_sum(double (&v)[N], double *red, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-  }
+  lanes_sum<N, 64>(v);
   if (lane == 0) {
 #pragma unroll
     for (int i = 0; i < N; ++i) red[wave * N + i] = v[i];
@@ -163,20 +156,16 @@ __device__ __forceinline__ void pnp_quat(const vilo::m3 &R, double *q) {
 __global__ void __launch_bounds__(PNP_THREADS) k_frame_pose_pnp(BatchDev b, PnpArgs a) {
   using namespace vilo;
   extern __shared__ double pnp_pts[];   // [trip - 1][PNP_PT][PNP_THREADS]: a lane's points of the trips after the first
-  __shared__ double xs[PNP_XS];
+  __shared__ double xs[WIN_XS];
   __shared__ double red[PNP_WAVES * PNP_NSUM];
   const int win = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const WinMeta wm = b.win[win];
-  {
-    const double *x = b.x + (size_t)win * XSTRIDE;
-    if (tid < 7 * VILO_MAX_FRAMES) xs[tid] = x[XO_POSE + tid];
-    if (tid >= 80 && tid < 94) xs[tid] = x[XO_EX + tid - 80];
-  }
+  stage_window_frames(xs, b.x + (size_t)win * XSTRIDE, tid, PNP_THREADS);
   __syncthreads();
   const int k = a.frame < 0 ? wm.n_frames - 1 : a.frame;   // (the host keeps a.frame <= VILO_MAX_FRAMES - 1: row k of xs exists)
   const bool frame_ok = k >= 1 && k <= wm.n_frames - 1;
-  const m3 ric0 = qR(qnormalized(ldq_pose(xs + 80)));
-  const v3 tic0 = ld3(xs + 80);
+  const m3 ric0 = qR(qnormalized(ldq_pose(xs + WIN_XS_EX)));
+  const v3 tic0 = ld3(xs + WIN_XS_EX);
 
   // ---- the points: once, before the first iteration ----
   const int n_trips = frame_ok ? min((wm.n_waves + PNP_WAVES - 1) / PNP_WAVES, PNP_MAX_TRIPS) : 0;
@@ -340,7 +329,7 @@ extern "C" int vilo_batch_frame_pose_pnp(vilo_ctx *ctx, vilo_batch *bt, const vi
     ctx->err = "vilo_batch_frame_pose_pnp: pose is NULL";
     return VILO_ERR_BAD_ARG;
   }
-  ctx->last_pnp_ms = 0.0;
+  BatchCall call(ctx, bt, &vilo_ctx::last_pnp_ms);
   if (W == 0) return VILO_OK;
   // a lane's points beyond its first live in LDS: one slot per further trip over the window's packed waves
   const int trips = (vilo_batch_max_window_waves(bt) + PNP_WAVES - 1) / PNP_WAVES;
@@ -349,28 +338,18 @@ extern "C" int vilo_batch_frame_pose_pnp(vilo_ctx *ctx, vilo_batch *bt, const vi
     return VILO_ERR_UNSUPPORTED;
   }
   const size_t lds_bytes = sizeof(double) * PNP_PT * PNP_THREADS * (size_t)(trips > 1 ? trips - 1 : 0);
-  VILO_HIP(hipSetDevice(ctx->device));
-  // the call's device memory, returned when it returns: poses | records
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_r = al(sizeof(double) * 7 * (size_t)W), total = o_r + al(sizeof(vilo_window_pnp_record) * (size_t)W);
-  ArenaScope scope(ctx, bt);
-  char *base = (char *)scope.alloc(total);
-  if (!base) return VILO_ERR_HIP;
+  const size_t o_p = call.lay.take<double>(7 * (size_t)W), o_r = call.lay.take<vilo_window_pnp_record>(W);   // the call's device memory: poses | records
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
   PnpArgs a;
   a.frame = o.frame; a.guess = o.guess; a.write = o.write ? 1 : 0; a.max_iterations = o.max_iterations;
   a.step_tolerance = o.step_tolerance;
-  a.pose = (double *)base;
-  a.rec = (vilo_window_pnp_record *)(base + o_r);
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  a.pose = call.ptr<double>(o_p);
+  a.rec = call.ptr<vilo_window_pnp_record>(o_r);
+  VILO_HIP(call.start());
   hipLaunchKernelGGL(k_frame_pose_pnp, dim3(W), dim3(PNP_THREADS), lds_bytes, ctx->stream, bd, a);
-  VILO_HIP(hipGetLastError());
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_pnp_ms = ms;
-  VILO_HIP(hipMemcpy(pose, a.pose, sizeof(double) * 7 * (size_t)W, hipMemcpyDeviceToHost));
-  if (records) VILO_HIP(hipMemcpy(records, a.rec, sizeof(vilo_window_pnp_record) * (size_t)W, hipMemcpyDeviceToHost));
+  VILO_HIP(call.finish());
+  VILO_HIP(call.down(pose, a.pose, sizeof(double) * 7 * (size_t)W));
+  VILO_HIP(call.down(records, a.rec, sizeof(vilo_window_pnp_record) * (size_t)W));
   return VILO_OK;
 }
 

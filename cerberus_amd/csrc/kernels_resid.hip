@@ -20,11 +20,9 @@
 #include <algorithm>
 
 #include "accept_body.hpp"
+#include "batch_call.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
-
-BatchDev *vilo_batch_dev(vilo_batch *bt);   // vilo_batch.hip
-int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows);   // vilo_batch.hip
 
 static_assert(sizeof(vilo_window_residual) == 136, "vilo_window_residual: 136 bytes (include/vilo_gpu.h)");
 static_assert(sizeof(vilo_residual_opts) == 8, "vilo_residual_opts: 8 bytes (include/vilo_gpu.h)");
@@ -263,61 +261,39 @@ extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_re
   VILO_HIP(hipSetDevice(ctx->device));
   const BatchDev &bd = *vilo_batch_dev(bt);
   const int W = bd.W, n_lm = bd.n_lm, NF = W * 10;
-  const bool rp = bd.rp_on && bd.rp_samples && bd.leg;
   const int *obs_row = nullptr;
   int n_rows = 0;
   const int rc = vilo_batch_obs_rows(ctx, bt, &obs_row, &n_rows);   // (batch data, uploaded at the first call: before the scope opens)
   if (rc != VILO_OK) return rc;
-  // the call's device memory, returned when it returns: window records | per-landmark values | interval costs | interval residuals |
-  // observation residuals | re-integration copies (records, prepared records, flags, contact-force filters)
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t at = 0;
-  const size_t o_win = at; at = al(at + sizeof(vilo_window_residual) * (size_t)W);
-  const size_t o_lm = at; at = al(at + (3 * sizeof(double) + 2 * sizeof(int) + 1) * (size_t)n_lm);
-  const size_t o_ic = at; at = al(at + sizeof(double) * (size_t)NF);
-  const size_t o_ir = at; if (imu_residuals) at = al(at + sizeof(double) * 31 * (size_t)NF);
-  const size_t o_or = at; if (obs_residuals) at = al(at + sizeof(double) * 4 * (size_t)n_rows);
-  const size_t o_rp = at; if (rp) at = al(at + (sizeof(vilo_preint) + sizeof(PreintPrepared) + sizeof(int) + sizeof(double) * VILO_FF_N) * (size_t)NF);
-  ArenaScope scope(ctx, bt);
-  char *base = (char *)scope.alloc(at);
-  if (!base) return VILO_ERR_HIP;
+  BatchCall call(ctx, bt, &vilo_ctx::last_resid_ms);
+  // the call's device memory: window records | per-landmark values | interval costs, residuals | observation residuals | re-integration copies
+  const size_t o_win = call.lay.take<vilo_window_residual>(W);
+  const size_t o_lc = call.lay.take<double>(n_lm), o_lr = call.lay.take<double>(n_lm), o_lp = call.lay.take<double>(n_lm);
+  const size_t o_nb = call.lay.take<int>(n_lm), o_nh = call.lay.take<int>(n_lm), o_fl = call.lay.take<unsigned char>(n_lm);
+  const size_t o_ic = call.lay.take<double>(NF), o_ir = call.lay.take<double>(31 * (size_t)NF, imu_residuals != nullptr);
+  const size_t o_or = call.lay.take<double>(4 * (size_t)n_rows, obs_residuals != nullptr);
+  const ReintegrationBlocks rp(call.lay, bd, 2);
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
   ResidLm lm;
-  lm.cost = (double *)(base + o_lm); lm.reproj = lm.cost + n_lm; lm.plain = lm.reproj + n_lm;
-  lm.nb = (int *)(lm.plain + n_lm); lm.nh = lm.nb + n_lm; lm.flags = (unsigned char *)(lm.nh + n_lm);
-  double *d_ic = (double *)(base + o_ic), *d_ir = imu_residuals ? (double *)(base + o_ir) : nullptr, *d_or = obs_residuals ? (double *)(base + o_or) : nullptr;
+  lm.cost = call.ptr<double>(o_lc); lm.reproj = call.ptr<double>(o_lr); lm.plain = call.ptr<double>(o_lp);
+  lm.nb = call.ptr<int>(o_nb); lm.nh = call.ptr<int>(o_nh); lm.flags = call.ptr<unsigned char>(o_fl);
+  double *d_ic = call.ptr<double>(o_ic), *d_ir = imu_residuals ? call.ptr<double>(o_ir) : nullptr, *d_or = obs_residuals ? call.ptr<double>(o_or) : nullptr;
   const double sq = ctx->cfg.focal_length / 1.5, ha = ctx->cfg.huber_delta, gn = ctx->cfg.g_norm;
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  VILO_HIP(call.start());
   BatchDev b = bd;
-  if (rp) {
-    // the marginalisation's re-integration at x (records already integrated there are kept: k_repropagate's own test), on copies
-    char *r0 = base + o_rp;
-    b.rp_pre = r0;
-    b.prep = (PreintPrepared *)(r0 + sizeof(vilo_preint) * (size_t)NF);
-    b.prep_bad = (int *)((char *)b.prep + sizeof(PreintPrepared) * (size_t)NF);
-    b.rp_ff = bd.rp_ff ? (double *)((char *)b.prep_bad + sizeof(int) * (size_t)NF) : nullptr;
-    VILO_HIP(hipMemcpyAsync(b.rp_pre, bd.rp_pre, sizeof(vilo_preint) * (size_t)NF, hipMemcpyDeviceToDevice, ctx->stream));
-    if (bd.rp_ff) VILO_HIP(hipMemcpyAsync(b.rp_ff, bd.rp_ff, sizeof(double) * VILO_FF_N * (size_t)NF, hipMemcpyDeviceToDevice, ctx->stream));
-    if (vilo_repropagate_launch(ctx, b, 0, 0) != VILO_OK || vilo_repropagate_launch(ctx, b, 0, 1) != VILO_OK) return VILO_ERR_HIP;
-  }
+  if (call.reintegrate(b, rp) != VILO_OK) return VILO_ERR_HIP;
   if (bd.n_waves > 0)
     hipLaunchKernelGGL(k_resid_landmarks, dim3(bd.n_waves), dim3(64), 0, ctx->stream, b, sq, ha, ctx->cfg.focal_length, o.outlier_threshold_px, obs_row,
                        lm, d_or);
   hipLaunchKernelGGL(k_resid_imu, dim3((NF + 63) / 64), dim3(64), 0, ctx->stream, b, gn, d_ic, d_ir);
-  hipLaunchKernelGGL(k_resid_window, dim3(W), dim3(128), 0, ctx->stream, b, lm, (const double *)d_ic, (vilo_window_residual *)(base + o_win));
-  VILO_HIP(hipGetLastError());
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_resid_ms = ms;
-  VILO_HIP(hipMemcpy(windows, base + o_win, sizeof(vilo_window_residual) * (size_t)W, hipMemcpyDeviceToHost));
-  if (n_lm > 0) {
-    if (lm_cost) VILO_HIP(hipMemcpy(lm_cost, lm.cost, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-    if (lm_reproj_px) VILO_HIP(hipMemcpy(lm_reproj_px, lm.reproj, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-    if (lm_flags) VILO_HIP(hipMemcpy(lm_flags, lm.flags, (size_t)n_lm, hipMemcpyDeviceToHost));
-  }
-  if (obs_residuals && n_rows > 0) VILO_HIP(hipMemcpy(obs_residuals, d_or, sizeof(double) * 4 * (size_t)n_rows, hipMemcpyDeviceToHost));
-  if (imu_residuals) VILO_HIP(hipMemcpy(imu_residuals, d_ir, sizeof(double) * 31 * (size_t)NF, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(k_resid_window, dim3(W), dim3(128), 0, ctx->stream, b, lm, (const double *)d_ic, call.ptr<vilo_window_residual>(o_win));
+  VILO_HIP(call.finish());
+  VILO_HIP(call.down(windows, call.ptr<char>(o_win), sizeof(vilo_window_residual) * (size_t)W));
+  VILO_HIP(call.down(lm_cost, lm.cost, sizeof(double) * (size_t)n_lm));
+  VILO_HIP(call.down(lm_reproj_px, lm.reproj, sizeof(double) * (size_t)n_lm));
+  VILO_HIP(call.down(lm_flags, lm.flags, (size_t)n_lm));
+  VILO_HIP(call.down(obs_residuals, d_or, sizeof(double) * 4 * (size_t)n_rows));
+  VILO_HIP(call.down(imu_residuals, d_ir, sizeof(double) * 31 * (size_t)NF));
   return VILO_OK;
 }
 

@@ -16,16 +16,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "batch_call.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
-
-BatchDev *vilo_batch_dev(vilo_batch *bt);   // vilo_batch.hip
 
 static_assert(sizeof(vilo_triangulate_opts) == 24, "vilo_triangulate_opts: 24 bytes (include/vilo_gpu.h)");
 
 #define TRI_SWEEPS 60       // sweep limit of the one-sided Jacobi iteration
 #define TRI_OFF_TOL 1e-15   // a lane stops when max |u_p . u_q| / (|u_p| |u_q|) of a sweep is below this
-#define TRI_XS 96           // LDS copy of the window's poses (77 doubles) and extrinsics (14, at 80)
 
 struct TriArgs {
   double init_depth;
@@ -105,15 +103,11 @@ __device__ __forceinline__ void tri_smallest_right_singular_vector4(double (&U)[
 
 __global__ void __launch_bounds__(64) k_triangulate(BatchDev b, TriArgs a) {
   using namespace vilo;
-  __shared__ double xs[TRI_XS];
+  __shared__ double xs[WIN_XS];
   const WaveMeta wv = b.wave[blockIdx.x];
   const WinMeta wm = b.win[wv.win];
   const int lane = threadIdx.x;
-  {
-    const double *x = b.x + (size_t)wv.win * XSTRIDE;
-    for (int e = lane; e < 7 * VILO_MAX_FRAMES; e += 64) xs[e] = x[XO_POSE + e];
-    if (lane < 14) xs[80 + lane] = x[XO_EX + lane];
-  }
+  stage_window_frames(xs, b.x + (size_t)wv.win * XSTRIDE, lane, 64);
   __syncthreads();
   int cs[4], cn[4], ckm[4], cgo[4];
   const LaneSeg ls = lane_segment(wv, b.chunk, lane, cs, cn, ckm, cgo);
@@ -129,14 +123,14 @@ __global__ void __launch_bounds__(64) k_triangulate(BatchDev b, TriArgs a) {
   if (!st && !two_views) sel = false;   // a single mono observation: nothing to triangulate with (the reference leaves its depth alone)
   const v3 uv0 = mk3(obs[lane], obs[(size_t)n + lane], obs[(size_t)2 * n + lane]);
   const int j = min(s + 1, VILO_MAX_FRAMES - 1);
-  const m3 ric0 = qR(qnormalized(ldq_pose(xs + 80)));
-  const v3 tic0 = ld3(xs + 80);
+  const m3 ric0 = qR(qnormalized(ldq_pose(xs + WIN_XS_EX)));
+  const v3 tic0 = ld3(xs + WIN_XS_EX);
   const TriCam c0 = tri_camera(qR(qnormalized(ldq_pose(xs + 7 * s))), ld3(xs + 7 * s), ric0, tic0);
   double depth = 1.0 / lam;
   unsigned fl = 0;
   if (sel) {
     // second view: the right camera on the start frame, or the left camera on the next frame
-    const double *pose1 = xs + 7 * (st ? s : j), *ex1 = xs + 80 + (st ? 7 : 0);
+    const double *pose1 = xs + 7 * (st ? s : j), *ex1 = xs + WIN_XS_EX + (st ? 7 : 0);
     const TriCam c1 = tri_camera(qR(qnormalized(ldq_pose(pose1))), ld3(pose1), qR(qnormalized(ldq_pose(ex1))), ld3(ex1));
     const double p1x = st ? obs[(size_t)3 * n + lane] : obs[(size_t)11 * n + lane];
     const double p1y = st ? obs[(size_t)4 * n + lane] : obs[(size_t)12 * n + lane];
@@ -216,38 +210,26 @@ extern "C" int vilo_batch_triangulate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
     ctx->err = "vilo_batch_triangulate: depth is NULL";
     return VILO_ERR_BAD_ARG;
   }
-  ctx->last_tri_ms = 0.0;
+  BatchCall call(ctx, bt, &vilo_ctx::last_tri_ms);
   if (n_lm == 0 || bd.n_waves == 0) return VILO_OK;   // nothing to report: the caller's arrays are not touched
-  VILO_HIP(hipSetDevice(ctx->device));
   const bool masked = o.select == VILO_TRI_MASK;
-  // the call's device memory, returned when it returns: depths | shifted inverse depths | flags | mask
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t at = 0;
-  const size_t o_d = at; at = al(at + sizeof(double) * (size_t)n_lm);
-  const size_t o_s = at; if (shift_inv_depth) at = al(at + sizeof(double) * (size_t)n_lm);
-  const size_t o_f = at; at = al(at + (size_t)n_lm);
-  const size_t o_m = at; if (masked) at = al(at + (size_t)n_lm);
-  ArenaScope scope(ctx, bt);
-  char *base = (char *)scope.alloc(at);
-  if (!base) return VILO_ERR_HIP;
+  // the call's device memory: depths | shifted inverse depths | flags | mask
+  const size_t o_d = call.lay.take<double>(n_lm), o_s = call.lay.take<double>(n_lm, shift_inv_depth != nullptr);
+  const size_t o_f = call.lay.take<unsigned char>(n_lm), o_m = call.lay.take<unsigned char>(n_lm, masked);
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
   TriArgs a;
   a.init_depth = o.init_depth; a.stereo = o.stereo ? 1 : 0; a.select = o.select; a.write = o.write ? 1 : 0;
-  a.mask = masked ? (const unsigned char *)(base + o_m) : nullptr;
-  a.depth = (double *)(base + o_d);
-  a.shift = shift_inv_depth ? (double *)(base + o_s) : nullptr;
-  a.flags = (unsigned char *)(base + o_f);
-  if (masked) VILO_HIP(hipMemcpyAsync(base + o_m, mask, (size_t)n_lm, hipMemcpyHostToDevice, ctx->stream));
-  VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  a.mask = masked ? call.ptr<unsigned char>(o_m) : nullptr;
+  a.depth = call.ptr<double>(o_d);
+  a.shift = shift_inv_depth ? call.ptr<double>(o_s) : nullptr;
+  a.flags = call.ptr<unsigned char>(o_f);
+  if (masked) VILO_HIP(hipMemcpyAsync(call.ptr<char>(o_m), mask, (size_t)n_lm, hipMemcpyHostToDevice, ctx->stream));   // (not timed)
+  VILO_HIP(call.start());
   hipLaunchKernelGGL(k_triangulate, dim3(bd.n_waves), dim3(64), 0, ctx->stream, bd, a);
-  VILO_HIP(hipGetLastError());
-  VILO_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  VILO_HIP(hipEventSynchronize(ctx->ev1));
-  float ms = 0.f;
-  VILO_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->last_tri_ms = ms;
-  VILO_HIP(hipMemcpy(depth, a.depth, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
-  if (flags) VILO_HIP(hipMemcpy(flags, a.flags, (size_t)n_lm, hipMemcpyDeviceToHost));
-  if (shift_inv_depth) VILO_HIP(hipMemcpy(shift_inv_depth, a.shift, sizeof(double) * (size_t)n_lm, hipMemcpyDeviceToHost));
+  VILO_HIP(call.finish());
+  VILO_HIP(call.down(depth, a.depth, sizeof(double) * (size_t)n_lm));
+  VILO_HIP(call.down(flags, a.flags, (size_t)n_lm));
+  VILO_HIP(call.down(shift_inv_depth, a.shift, sizeof(double) * (size_t)n_lm));
   return VILO_OK;
 }
 

@@ -1,5 +1,5 @@
 // Pieces of the linearisation pass that more than one translation unit needs: which buffer a pass writes, the per-lane view of a packed
-// wave, and the second half of the frame-parallel visual form (k_visual_reduce's body: kernels_solve.hip launches it as a kernel of its
+// wave, the staged frame poses and the in-wave sum of the query kernels, and the second half of the frame-parallel visual form (k_visual_reduce's body: kernels_solve.hip launches it as a kernel of its
 // own, kernels_asm_small.hip runs it in extra workgroups of k_assemble_s for small batches).
 #pragma once
 #include "solve_common.hpp"
@@ -37,6 +37,22 @@ __device__ __forceinline__ LaneSeg lane_segment(const WaveMeta &wv, const ChunkM
     }
   }
   return ls;
+}
+// LDS copy of a window's frame poses (7 doubles at 7 k, 77 in all) and extrinsics (two of 7, at WIN_XS_EX), staged by n_threads threads
+#define WIN_XS 96
+#define WIN_XS_EX 80
+__device__ __forceinline__ void stage_window_frames(double *xs, const double *x, int tid, int n_threads) {
+  for (int e = tid; e < 7 * VILO_MAX_FRAMES; e += n_threads) xs[e] = x[XO_POSE + e];
+  for (int e = tid; e < 14; e += n_threads) xs[WIN_XS_EX + e] = x[XO_EX + e];
+}
+// sums of v over the WIDTH lanes of a group, the same bits in every one: xor butterfly, both partners add the same two values
+template <int N, int WIDTH>
+__device__ __forceinline__ void lanes_sum(double (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int off = WIDTH / 2; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, WIDTH);
+  }
 }
 
 

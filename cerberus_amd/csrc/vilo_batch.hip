@@ -242,7 +242,6 @@ void *ArenaScope::alloc(size_t bytes) {
 }
 
 int vilo_batch_max_window_waves(vilo_batch *bt) { return bt->max_win_waves; }
-// (vilo_internal.hpp; vilo_batch_gyro_bias_align reads them)
 const void *vilo_batch_records(vilo_batch *bt, int *leg) { *leg = bt->leg; return bt->d_pre; }
 
 // vilo_batch_residuals: the landmarks' observation rows on the device (batch data, uploaded at the first call: not in a call's scope)

@@ -187,7 +187,8 @@ struct vilo_batch;
 // closes, on every return path. Closing waits for the context's stream first (batch uploads are null-stream copies, which do not wait for
 // it), then hands the arena chunks taken since opening back to ctx->pool_free and rewinds the bump pointer. Bump allocation never moves
 // what it has handed out, so a buffer may be sized partway through a call. The rule: nothing that must outlive the call is allocated
-// inside a scope.
+// inside a scope. The calls that query a resident batch do not open one by hand: batch_call.hpp's BatchCall owns the scope, allocates the
+// blocks its CallLayout lists in one piece, and carries the timed region and the downloads around the call's kernels.
 struct ArenaScope {
   ArenaScope(vilo_ctx *ctx, vilo_batch *bt);
   ~ArenaScope();
@@ -211,6 +212,11 @@ int vilo_with_batch(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo
 }
 // vilo_batch.hip: the batch's preintegration records on the device ([W * 10] vilo_preint when *leg, else vilo_preint_imu)
 const void *vilo_batch_records(vilo_batch *bt, int *leg);
+BatchDev *vilo_batch_dev(vilo_batch *bt);            // vilo_batch.hip, as the next three: the batch's device tables
+int vilo_batch_max_window_waves(vilo_batch *bt);     // the most packed visual waves any of its windows has
+// the landmarks' observation rows on the device (batch data that stays with the batch, uploaded at the first call: outside any call's scope)
+int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows);
+const int *vilo_batch_perm(vilo_batch *bt, int win, int *L);   // window win's landmark order on the host
 // vilo_batch.hip: a call on many host windows cut into sub-batches over the context's pipeline lanes (false: not a call to cut)
 bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
                        const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out);

@@ -1,6 +1,8 @@
-"""GPU (-m gpu): the per-call device memory of the batch calls. Marginalisation, covariance, landmark covariance and residuals, called in
-turn on one resident batch, each give back what they take (vilo_debug_batch_device_bytes): the batch holds the same arena after ten rounds
-as after one, and every output of the tenth round is bitwise the first's. vilo_last_residuals_ms is a value per context."""
+"""GPU (-m gpu): the per-call device memory of the batch calls. Marginalisation, covariance, landmark covariance, residuals, gradient,
+triangulation (masked, with the shifted inverse depths: every optional block), frame pose by PnP and gyroscope-bias alignment (at the
+corrected rotations: the re-integration copies), called in turn on one resident batch — the last three without writing to it, which keeps
+the rounds comparable —, each give back what they take (vilo_debug_batch_device_bytes): the batch holds the same arena after ten rounds as
+after one, and every output of the tenth round is bitwise the first's. vilo_last_residuals_ms is a value per context."""
 import numpy as np
 import pytest
 
@@ -33,16 +35,21 @@ def test_repeated_calls_give_their_memory_back(cfg, ocfg):
     ws = [base[i % len(base)].twin() for i in range(W)]
     modes = [(0, 0, 1, -1)[i % 4] for i in range(W)]
     obs_rows = _granule(4 * sum(w.L for w in ws))   # vilo_batch_residuals' first call keeps the landmarks' observation rows with the batch
+    mask = (np.arange(sum(w.L for w in ws)) % 3 != 0).astype(np.uint8)
     ctx = api.Context(cfg, 0)
     try:
         b = api.Batch(ctx, ws)
-        b.set_samples()   # (the re-integration copies of the marginalisation and the residuals come from the calls' memory too)
+        b.set_samples()   # (the re-integration copies of the marginalisation, the residuals and the gyro alignment come from the calls' memory too)
         b.solve(api.default_solve_opts(True, 4))
         b.download()
         calls = (("marginalize", lambda: _marginalize(b, modes)),
                  ("covariance", lambda: _arrays(b.covariance(poses=True))),
                  ("landmark_covariance", lambda: _arrays(b.landmark_covariance())),
-                 ("residuals", lambda: _arrays(b.residuals(observations=True, imu=True))))
+                 ("residuals", lambda: _arrays(b.residuals(observations=True, imu=True))),
+                 ("gradient", lambda: _arrays(b.gradient())),
+                 ("triangulate", lambda: _arrays(b.triangulate(select="mask", mask=mask, shift=True, write=False))),
+                 ("frame_pose_pnp", lambda: _arrays(b.frame_pose_pnp(write=False))),
+                 ("gyro_bias_align", lambda: _arrays(b.gyro_bias_align(linearization="corrected", write=False))))
         rounds, held = [], []
         for r in range(10):
             outs = {}
