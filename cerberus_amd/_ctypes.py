@@ -152,6 +152,20 @@ class WindowGyroRecord(C.Structure):
 GYRO_LINEARIZATION = {"record": 0, "corrected": 1}   # VILO_GYRO_RECORD / VILO_GYRO_CORRECTED
 GYRO_OK, GYRO_NO_INTERVALS, GYRO_SINGULAR, GYRO_NUMERIC = 0, 1, 2, 3   # a window's status (VILO_GYRO_*)
 
+class PredictOpts(C.Structure):
+    """vilo_predict_opts (8 bytes)"""
+    _fields_ = [("mode", C.c_int32), ("pad", C.c_int32)]
+
+
+class WindowPredictRecord(C.Structure):
+    """vilo_window_predict_record (8 bytes)"""
+    _fields_ = [("n_predicted", C.c_int32), ("status", C.c_int32)]
+
+
+PREDICT_MODE = {"constant_velocity": 0, "given": 1}   # VILO_PREDICT_CONSTANT_VELOCITY / VILO_PREDICT_GIVEN
+PREDICT_OK, PREDICT_TOO_FEW_FRAMES, PREDICT_NUMERIC = 0, 1, 2   # a window's status (VILO_PREDICT_*)
+PREDICT_PREDICTED, PREDICT_BEHIND, PREDICT_NOT_FINITE, PREDICT_BEHIND_RIGHT = 1, 2, 4, 8   # bits of a landmark's flags
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

@@ -37,6 +37,7 @@ def lib():
         L.vilo_last_triangulate_ms.restype = C.c_double
         L.vilo_last_pnp_ms.restype = C.c_double
         L.vilo_last_gyro_align_ms.restype = C.c_double
+        L.vilo_last_predict_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -222,6 +223,42 @@ def _gyro_bias_align(ctx, n, linearization, write, call):
     return GyroAlignment(delta_bg, a["initial_cost"], a["model_cost"], a["n_intervals"], a["status"])
 
 
+NextFramePrediction = collections.namedtuple("NextFramePrediction", "pts_cam pts_cam_right flags offsets next_pose n_predicted status")
+
+
+def predict_opts(mode="constant_velocity", next_pose=None, n_windows=None):
+    """(T.PredictOpts, next_pose as a contiguous float64 array [W, 7] or None) of a predict_next_frame call; needs no device.
+    mode: 'constant_velocity' (the reference: the last two frames' motion once more) or 'given' with next_pose, one row
+    [px py pz qx qy qz qw] per window (n_windows of them, where that is given)."""
+    if mode not in T.PREDICT_MODE:
+        raise ValueError("mode must be one of %s" % sorted(T.PREDICT_MODE))
+    if (mode == "given") != (next_pose is not None):
+        raise ValueError("mode='given' and a next_pose go together")
+    if next_pose is not None:
+        next_pose = np.ascontiguousarray(next_pose, dtype=np.float64)
+        if next_pose.ndim != 2 or next_pose.shape[1] != 7 or (n_windows is not None and next_pose.shape[0] != n_windows):
+            raise ValueError("next_pose must have one row of 7 per window of the call%s, got shape %s"
+                             % ("" if n_windows is None else " (%d)" % n_windows, next_pose.shape))
+    o = T.PredictOpts()
+    o.mode, o.pad = T.PREDICT_MODE[mode], 0
+    return o, next_pose
+
+
+def _predict_next_frame(ctx, descs, mode, next_pose, right, call):
+    n = len(descs)
+    o, given = predict_opts(mode, next_pose, n)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    L = int(offsets[-1])
+    pts, flags = np.zeros((L, 3)), np.zeros(L, np.uint8)
+    ptr = np.zeros((L, 3)) if right else None
+    pose = np.zeros((n, 7))
+    rec = (T.WindowPredictRecord * n)()
+    ctx._check(call(C.byref(o), _p(given), _p(pts), _p(ptr), T.u8ptr(flags), _p(pose), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowPredictRecord._fields_]), count=n).copy()
+    return NextFramePrediction(pts, ptr, flags, offsets, pose, a["n_predicted"], a["status"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -328,6 +365,15 @@ class Batch:
         left as it was."""
         return _gyro_bias_align(self.ctx, len(self._descs), linearization, write,
                                 lambda *a: lib().vilo_batch_gyro_bias_align(self.ctx.h, self.handle, *a))
+
+    def predict_next_frame(self, mode="constant_velocity", next_pose=None, right=False):
+        """vilo_batch_predict_next_frame at the batch's device state: NextFramePrediction(pts_cam [sum L, 3], pts_cam_right [sum L, 3] or
+        None, flags [sum L] (T.PREDICT_* bits), offsets [W + 1] (window w's landmarks: offsets[w] .. offsets[w + 1], in its own order),
+        next_pose [W, 7], n_predicted, status (T.PREDICT_*), each [W]): the landmarks whose tracks reach the last frame, in the left (and
+        with right=True the right) camera of the next frame, whose pose is the last two frames' motion applied once more
+        (predictPtsInNextFrame) or, with mode='given', the caller's next_pose [W, 7]. The batch is left as it was."""
+        return _predict_next_frame(self.ctx, self._descs, mode, next_pose, right,
+                                   lambda *a: lib().vilo_batch_predict_next_frame(self.ctx.h, self.handle, *a))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -673,6 +719,16 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _gyro_bias_align(self, n, linearization, write,
                                 lambda *a: lib().vilo_window_gyro_bias_align(self.h, n, descs, states, *a))
+
+    def window_predict_next_frame(self, windows, mode="constant_velocity", next_pose=None, right=False):
+        """vilo_window_predict_next_frame: the next-frame prediction of host windows' landmarks at their current state arrays (see
+        Batch.predict_next_frame)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _predict_next_frame(self, descs, mode, next_pose, right,
+                                   lambda *a: lib().vilo_window_predict_next_frame(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -689,6 +689,72 @@ int vilo_window_gyro_bias_align(vilo_ctx *ctx, int n_windows, const vilo_window_
  * re-integration before it, without the copies out. */
 double vilo_last_gyro_align_ms(const vilo_ctx *ctx);
 
+/* ---- where the landmarks will be in the next frame's cameras (Estimator::predictPtsInNextFrame, estimator.cpp:1694-1727; called by
+ * processImage after the solve and the outlier rejection, :811-819) ----
+ * State: the batch's current state, what vilo_batch_download returns. Rotation matrices are taken from the normalised quaternions, as
+ * vilo_batch_triangulate takes them. Per window, with k = n_frames - 1 (the reference's frame_count):
+ *   next pose  opts->mode == VILO_PREDICT_CONSTANT_VELOCITY (default; the reference, :1700-1703): nextT = curT (prevT^-1 curT) with curT the
+ *              pose of frame k and prevT that of frame k - 1, written as
+ *                P_n = P_k + R_k R_{k-1}^T (P_k - P_{k-1}),   q_n = normalise(q_k (x) q_{k-1}^-1 (x) q_k)
+ *              on the normalised pose quaternions, with no change of hemisphere.
+ *              VILO_PREDICT_GIVEN: P_n, q_n = next_pose_in[w] = [px py pz qx qy qz qw], the quaternion normalised by the call: a caller that
+ *              dead-reckons the pose of the frame to come from IMU and leg odometry (processIMULeg) has something better than constant
+ *              velocity.
+ *              In both modes R_n is the rotation matrix of q_n normalised (once more, in the constant-velocity mode): everything after the
+ *              next pose is one code path, and VILO_PREDICT_GIVEN with the next_pose a constant-velocity call returned gives that call's
+ *              points and flags bit for bit.
+ *   selection  (:1708-1713) landmark l is predicted when its current inverse depth is > 0, it has at least two observations and its track
+ *              ends at the last frame: start_l + n_obs_l - 1 == k. The batch holds the tracks the solve uses; the reference also predicts
+ *              tracks too short for the solve.
+ *   point      (:1715-1719) pts_j = ric0 (point_0 (1 / inv_depth)) + tic0, point_0 the first observation's point; pts_w = R_s pts_j + P_s
+ *              with s = start_l; pts_local = R_n^T (pts_w - P_n); pts_cam = ric0^T (pts_local - tic0). With pts_cam_right given, the same
+ *              with ric1, tic1 in the last step: where a stereo tracker searches in the right image. ric / tic are the batch's extrinsics
+ *              state; the call reads no field of vilo_config.
+ * Outputs per landmark, concatenated window by window, inside a window in the caller's vilo_window_desc order (as vilo_batch_triangulate):
+ *   pts_cam [sum L][3]        zeros for a landmark that is not predicted
+ *   pts_cam_right [sum L][3]  (may be NULL) the same for the right camera
+ *   flags [sum L]             (may be NULL) bit 0: predicted; bit 1: pts_cam.z is not positive (behind the next left camera: a projection
+ *                             would divide by it); bit 2: a component of pts_cam (or pts_cam_right) is not finite; bit 3: as bit 1 for
+ *                             pts_cam_right. 0 for a landmark that is not predicted.
+ * Outputs per window: next_pose[w][7] (may be NULL) = [P_n, q_n] and records[w] (may be NULL): n_predicted, the number of landmarks with
+ * bit 0 set, and status:
+ *   VILO_PREDICT_OK
+ *   VILO_PREDICT_TOO_FEW_FRAMES  constant-velocity mode with n_frames < 3 (the reference's `frame_count < 2` return, :1697). In
+ *                                VILO_PREDICT_GIVEN a window of two frames predicts as any other.
+ *   VILO_PREDICT_NUMERIC         a value that is not finite in the poses of the window's frames, in its extrinsics (the right camera's only
+ *                                when pts_cam_right is given), in next_pose_in[w] or in the next pose formed (a zero quaternion).
+ * For any status but OK nothing is predicted (pts_cam zeros, flags 0, n_predicted 0), next_pose[w] is frame k's current pose bit for bit, and
+ * the other windows of the batch are not affected.
+ * Side effects: none, and no option to have any: nothing of the state is being estimated. The call's device memory is returned when it
+ * returns. Every output of a window is bitwise independent of the batch it shares and of its position in it. A batch whose windows have
+ * no landmarks still reports next_pose and records; the landmark arrays are not touched. opts NULL: vilo_default_predict_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG, the caller's arrays untouched): NULL ctx or batch, NULL pts_cam with landmarks present, an unknown mode,
+ * VILO_PREDICT_GIVEN without next_pose_in. */
+#define VILO_PREDICT_CONSTANT_VELOCITY 0
+#define VILO_PREDICT_GIVEN 1
+#define VILO_PREDICT_OK 0
+#define VILO_PREDICT_TOO_FEW_FRAMES 1
+#define VILO_PREDICT_NUMERIC 2
+typedef struct {
+  int32_t mode;             /* VILO_PREDICT_CONSTANT_VELOCITY / VILO_PREDICT_GIVEN */
+  int32_t pad;
+} vilo_predict_opts;
+void vilo_default_predict_opts(vilo_predict_opts *o);
+typedef struct {
+  int32_t n_predicted;
+  int32_t status;           /* VILO_PREDICT_* */
+} vilo_window_predict_record;
+
+int vilo_batch_predict_next_frame(vilo_ctx *ctx, vilo_batch *batch, const vilo_predict_opts *opts, const double *next_pose_in, double *pts_cam,
+                                  double *pts_cam_right, uint8_t *flags, double *next_pose, vilo_window_predict_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed. */
+int vilo_window_predict_next_frame(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                   const vilo_predict_opts *opts, const double *next_pose_in, double *pts_cam, double *pts_cam_right,
+                                   uint8_t *flags, double *next_pose, vilo_window_predict_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_predict_next_frame: k_predict_next_frame and k_predict_windows, without the
+ * upload of next_pose_in and the copies out. */
+double vilo_last_predict_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
