@@ -166,6 +166,19 @@ PREDICT_MODE = {"constant_velocity": 0, "given": 1}   # VILO_PREDICT_CONSTANT_VE
 PREDICT_OK, PREDICT_TOO_FEW_FRAMES, PREDICT_NUMERIC = 0, 1, 2   # a window's status (VILO_PREDICT_*)
 PREDICT_PREDICTED, PREDICT_BEHIND, PREDICT_NOT_FINITE, PREDICT_BEHIND_RIGHT = 1, 2, 4, 8   # bits of a landmark's flags
 
+class DeadReckonOpts(C.Structure):
+    """vilo_dead_reckon_opts (8 bytes)"""
+    _fields_ = [("from_frame", C.c_int32), ("write", C.c_int32)]
+
+
+class WindowDeadReckonRecord(C.Structure):
+    """vilo_window_dead_reckon_record (8 bytes)"""
+    _fields_ = [("n_steps", C.c_int32), ("status", C.c_int32)]
+
+
+DR_OK, DR_NO_FRAME, DR_NUMERIC = 0, 1, 2   # a window's status (VILO_DR_*)
+DR_STATE = 10   # P (3), quaternion x y z w, V (3)
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

@@ -38,6 +38,7 @@ def lib():
         L.vilo_last_pnp_ms.restype = C.c_double
         L.vilo_last_gyro_align_ms.restype = C.c_double
         L.vilo_last_predict_ms.restype = C.c_double
+        L.vilo_last_dead_reckon_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -259,6 +260,41 @@ def _predict_next_frame(ctx, descs, mode, next_pose, right, call):
     return NextFramePrediction(pts, ptr, flags, offsets, pose, a["n_predicted"], a["status"])
 
 
+DeadReckoning = collections.namedtuple("DeadReckoning", "state trajectory step_offsets n_steps status")
+
+
+def dead_reckon_opts(from_frame=-1, write=False):
+    """T.DeadReckonOpts of a dead_reckon call; needs no device. from_frame: -1 (each window's last frame) or 0 .. T.MAX_FRAMES - 1;
+    write=True (the result becomes the state of frame from_frame + 1) needs an explicit frame."""
+    if int(from_frame) != from_frame or not -1 <= from_frame <= T.MAX_FRAMES - 1:
+        raise ValueError("from_frame must be -1 (the last frame) or 0 .. %d" % (T.MAX_FRAMES - 1))
+    if write and from_frame == -1:
+        raise ValueError("write=True needs an explicit from_frame: the frame after a window's last does not exist")
+    o = T.DeadReckonOpts()
+    o.from_frame, o.write = int(from_frame), 1 if write else 0
+    return o
+
+
+def _dead_reckon(ctx, n, samples, offsets, from_frame, write, trajectory, call):
+    o = dead_reckon_opts(from_frame, write)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    if offsets.shape != (n + 1,):
+        raise ValueError("offsets must have one entry per window of the call and one more (%d), got shape %s" % (n + 1, offsets.shape))
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must start at 0 and must not decrease")
+    samples = _c(samples).reshape(-1, T.SAMPLE_DOUBLES)
+    if len(samples) < offsets[-1]:
+        raise ValueError("offsets reach sample %d, samples holds %d" % (offsets[-1], len(samples)))
+    step_offsets = np.zeros(n + 1, np.int64)
+    step_offsets[1:] = np.cumsum(np.maximum(np.diff(offsets) - 1, 0))
+    state = np.zeros((n, T.DR_STATE))
+    traj = np.zeros((int(step_offsets[-1]), T.DR_STATE)) if trajectory else None
+    rec = (T.WindowDeadReckonRecord * n)()
+    ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(state), _p(traj), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowDeadReckonRecord._fields_]), count=n).copy()
+    return DeadReckoning(state, traj, step_offsets, a["n_steps"], a["status"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -374,6 +410,16 @@ class Batch:
         (predictPtsInNextFrame) or, with mode='given', the caller's next_pose [W, 7]. The batch is left as it was."""
         return _predict_next_frame(self.ctx, self._descs, mode, next_pose, right,
                                    lambda *a: lib().vilo_batch_predict_next_frame(self.ctx.h, self.handle, *a))
+
+    def dead_reckon(self, samples, offsets, from_frame=-1, write=False, trajectory=False):
+        """vilo_batch_dead_reckon at the batch's device state: DeadReckoning(state [W, 10] as [P, qx qy qz qw, V], trajectory
+        [sum n_steps, 10] or None, step_offsets [W + 1] (window w's trajectory rows: step_offsets[w] .. step_offsets[w + 1]), n_steps,
+        status (T.DR_*), each [W]): frame from_frame (-1: each window's last) carried through the window's samples
+        [offsets[w], offsets[w + 1]) of samples [n, 35] by the mid-point recurrence of processIMULeg, the first sample of a range playing
+        (acc_0, gyr_0). The quaternion is not normalised. write=True stores the result as the pose and velocity of frame from_frame + 1 of
+        the windows with status T.DR_OK; otherwise the batch is left as it was."""
+        return _dead_reckon(self.ctx, len(self._descs), samples, offsets, from_frame, write, trajectory,
+                            lambda *a: lib().vilo_batch_dead_reckon(self.ctx.h, self.handle, *a))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -729,6 +775,16 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _predict_next_frame(self, descs, mode, next_pose, right,
                                    lambda *a: lib().vilo_window_predict_next_frame(self.h, n, descs, states, *a))
+
+    def window_dead_reckon(self, windows, samples, offsets, from_frame=-1, write=False, trajectory=False):
+        """vilo_window_dead_reckon: the dead reckoning of host windows at their current state arrays (see Batch.dead_reckon); with
+        write=True the windows' pose and speed_bias arrays receive the new rows."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _dead_reckon(self, n, samples, offsets, from_frame, write, trajectory,
+                            lambda *a: lib().vilo_window_dead_reckon(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -48,7 +48,8 @@ struct vilo_ctx {
   double last_pnp_ms = 0.0;        // GPU time of the last vilo_batch_frame_pose_pnp (k_frame_pose_pnp)
   double last_gyro_ms = 0.0;       // GPU time of the last vilo_batch_gyro_bias_align (k_gyro_bias_align and, with samples in force, the re-integration)
   double last_predict_ms = 0.0;    // GPU time of the last vilo_batch_predict_next_frame (k_predict_next_frame + k_predict_windows)
-  int marg_general_count = 0;     // windows of the last vilo_marginalize that took the global-memory eigen path
+  double last_dead_reckon_ms = 0.0;   // GPU time of the last vilo_batch_dead_reckon (k_dead_reckon)
+  int marg_general_count = 0;    // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
   // per-kernel HIP-event timing of the solve pipeline (vilo_set_profiling)

@@ -755,6 +755,69 @@ int vilo_window_predict_next_frame(vilo_ctx *ctx, int n_windows, const vilo_wind
  * upload of next_pose_in and the copies out. */
 double vilo_last_predict_ms(const vilo_ctx *ctx);
 
+/* ---- mid-point dead reckoning of a frame's state through IMU samples (Estimator::processIMULeg, estimator.cpp:639-646, run on every
+ * IMU / leg message on the newest frame, which starts as a copy of the frame before it, :794-802; fastPredictIMU / updateLatestStates,
+ * :1800-1840, run the same recurrence again after every image) ----
+ * State: the batch's current state, what vilo_batch_download returns. Per window, with f = opts->from_frame (-1: the window's last frame)
+ * and the window's samples [offsets[w], offsets[w + 1]) in vilo_preintegrate's convention: the first sample of the range plays
+ * (acc_0, gyr_0) and its dt is ignored (not even read), every later sample is one step. Only dt, acc and gyr of a sample are read.
+ *   start  P, V, Ba, Bg of frame f; R = R(q_f / |q_f|); g = (0, 0, cfg.g_norm)
+ *   step   with sample s after the previous sample s0 (:639-646, in this order of operations):
+ *            un_acc_0 = R (s0.acc - Ba) - g
+ *            un_gyr   = 1/2 (s0.gyr + s.gyr) - Bg
+ *            R        = R * R(deltaQ(un_gyr s.dt))        deltaQ = (1, theta / 2) un-normalised (utility.h:28-41) and Eigen's
+ *                                                         toRotationMatrix, which does not normalise either: the reference, literally
+ *            un_acc_1 = R (s.acc - Ba) - g
+ *            un_acc   = 1/2 (un_acc_0 + un_acc_1)
+ *            P        = P + V dt + 1/2 dt^2 un_acc
+ *            V        = V + dt un_acc
+ *   state  [P(3), Quaterniond(R) as x y z w, V(3)]: what vector2double (:852-866) hands the solver for that frame. The quaternion is NOT
+ *          re-normalised and R is not re-orthogonalised: R drifts from a rotation at second order in |un_gyr dt| per step, exactly as
+ *          the reference's Rs[j] does between two images. vilo_batch_predict_next_frame normalises the pose it is given; the solver's
+ *          PoseLocalParameterization normalises at its first step.
+ * Outputs: state_out[w][10], the state after the window's last step; trajectory_out (may be NULL) [sum n_steps][10], the state after every
+ * step, window by window in batch order (window w's rows start at the sum of the n_steps before it; its last row is state_out[w] bit
+ * for bit); records[w] (may be NULL): n_steps = max(0, offsets[w + 1] - offsets[w] - 1), whatever the status, and status:
+ *   VILO_DR_OK        a range of 0 or 1 samples makes no step; state_out then goes through the same path: P, Quaterniond(R(q_f / |q_f|)), V
+ *   VILO_DR_NO_FRAME  the window has no frame f; with opts->write also: it has no frame f + 1
+ *   VILO_DR_NUMERIC   a value that is not finite in the start state (P, q, V, Ba, Bg of frame f), in a sample value the range reads, or
+ *                     in the result
+ * For NO_FRAME and NUMERIC state_out[w] and the window's trajectory rows are zeros and nothing is written; the other windows of the batch
+ * are not affected.
+ * Side effects: with opts->write == 0 none. With opts->write == 1, for the windows with status OK, P, the quaternion and V become the
+ * current pose and velocity of frame f + 1 (the reference's newest frame) and nothing else changes, not that frame's biases or leg
+ * biases: vilo_batch_reset still restores the uploaded state; a following vilo_batch_solve (plain launches or the captured graph) starts
+ * from the new state. write needs an explicit from_frame: the frame after a window's last does not exist.
+ * The call's device memory is returned when it returns. Every output of a window is bitwise independent of the batch it shares and of
+ * its position in it. opts NULL: vilo_default_dead_reckon_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched, the caller's arrays untouched): NULL ctx or batch; with windows present NULL offsets
+ * or state_out; offsets[0] != 0 or offsets decreasing; NULL samples with offsets[W] > 0; from_frame below -1 or above
+ * VILO_MAX_FRAMES - 1; write other than 0 or 1; write == 1 with from_frame == -1. */
+#define VILO_DR_OK 0
+#define VILO_DR_NO_FRAME 1
+#define VILO_DR_NUMERIC 2
+typedef struct {
+  int32_t from_frame;       /* -1: each window's last frame; else 0 .. VILO_MAX_FRAMES - 1 */
+  int32_t write;            /* 1: the result becomes the current pose and velocity of frame from_frame + 1 (status OK only) */
+} vilo_dead_reckon_opts;
+void vilo_default_dead_reckon_opts(vilo_dead_reckon_opts *o);
+typedef struct {
+  int32_t n_steps;
+  int32_t status;           /* VILO_DR_* */
+} vilo_window_dead_reckon_record;
+
+int vilo_batch_dead_reckon(vilo_ctx *ctx, vilo_batch *batch, const vilo_dead_reckon_opts *opts, const vilo_sample *samples,
+                           const int32_t *offsets, double *state_out, double *trajectory_out, vilo_window_dead_reckon_record *records);
+/* The same for host windows at the given states (SlidingWindow::processIMULeg, cerberus_amd/host/vilo_sliding_window.cpp, is the
+ * one-robot host form): one batch is created and destroyed; with opts->write the new rows are written into state[w].pose and
+ * state[w].speed_bias. */
+int vilo_window_dead_reckon(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state,
+                            const vilo_dead_reckon_opts *opts, const vilo_sample *samples, const int32_t *offsets, double *state_out,
+                            double *trajectory_out, vilo_window_dead_reckon_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_dead_reckon: k_dead_reckon, without the packing and upload of the samples
+ * and the copies out. */
+double vilo_last_dead_reckon_ms(const vilo_ctx *ctx);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
