@@ -354,17 +354,24 @@ k_assemble_pose(BatchDev b, int jacobi_scaling, double min_lm_diagonal, double m
   // ---- pose blocks of the IMU factor Grams (factor k: frames k, k + 1; packed 39 x 39 [pose_i 6 | speed / leg-bias_i 13 | pose_j 6 | ... | r]):
   //      I1 pose_i x pose_i (21, twin pose_j x pose_j), I3 the pose gradient (6, twin), I4 pose_i x pose_j (36): 63 owner threads, straight
   //      from global memory, all of a thread's 20 loads in flight ----
-  if (tid >= 64 && tid < 127) {
-    int pa = 0, pbc = 0, pcls = 0;
+  //      The adds wait for a workgroup barrier: their targets (pose blocks, pose gradient) are also targets of the pass loop's owners in
+  //      OTHER waves, and a wave that leaves its last pass early would otherwise add its IMU terms before another wave's last visual
+  //      terms — the same sum in another order, an ulp apart, from one run to the next (seen at the tail of a launch, where loads are fast).
+  const bool imu_owner = tid >= 64 && tid < 127;
+  int pa = 0, pbc = 0, pcls = 0;
+  double vm[10], vt[10];
+  if (imu_owner) {
     const int q = tid - 64;
     if (q < 21) { pcls = 1; int rem = q; while (rem >= 6 - pa) { rem -= 6 - pa; ++pa; } pbc = pa + rem; }
     else if (q < 27) { pcls = 3; pa = q - 21; pbc = 38; }
     else { pcls = 4; pa = (q - 27) / 6; pbc = 19 + (q - 27) % 6; }
     const int pe1 = tri39(pa, pbc), pe2 = (pcls == 4) ? pe1 : tri39(pa + 19, pcls == 3 ? 38 : pbc + 19);
     const double *igram = b.imu_gram + (size_t)win * 10 * 780;
-    double vm[10], vt[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) { vm[k] = igram[780 * k + pe1]; vt[k] = igram[780 * k + pe2]; }
+  }
+  __syncthreads();   // (every wave's last pass has added its terms)
+  if (imu_owner) {
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
       if (k < F - 1) {

@@ -1196,7 +1196,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   E_BARRIER();
   if (wave == 4) {
     if (lane < 11) pose_plus(xl + XO_POSE + 7 * lane, del + 6 * lane, xc + XO_POSE + 7 * lane);
-    else if (lane < 13) pose_plus(xl + XO_EX + 7 * (lane - 11), del + CD_EX0 + 6 * (lane - 11), xc + XO_EX + 7 * (lane - 11));
+    else if (lane < 13) ex_candidate(lane - 11, F, cmask, xl, del, xc);
     else if (lane == 13) xc[XO_TD] = xl[XO_TD] + del[CD_TD];
   } else if (wave == 0) {
     for (int e = lane; e < 143; e += 64) {

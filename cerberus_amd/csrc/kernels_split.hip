@@ -299,7 +299,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BS_WPE,
   }
   lds_fence();
   if (lane < 11) pose_plus(x + XO_POSE + 7 * lane, del + 6 * lane, xc + XO_POSE + 7 * lane);
-  else if (lane < 13) pose_plus(x + XO_EX + 7 * (lane - 11), del + CD_EX0 + 6 * (lane - 11), xc + XO_EX + 7 * (lane - 11));
+  else if (lane < 13) ex_candidate(lane - 11, F, cmask, x, del, xc);
   else if (lane == 13) xc[XO_TD] = x[XO_TD] + del[CD_TD];
   for (int e = lane; e < 143; e += 64) {
     const int k = e / 13, c = e - 13 * k;

@@ -164,6 +164,15 @@ __device__ __forceinline__ bool cd_active(int cd, int F, int cmask) {
   return k < F && !(c >= 9 && (cmask & CONST_LB));
 }
 
+// The candidate of an extrinsic block: PoseLocalParameterization::Plus where the block is part of the problem, the block itself where it is
+// constant. Ceres never touches a constant parameter block; Plus with a zero step still multiplies and normalises, which moves a quaternion
+// that is a unit one only to rounding by an ulp per accepted step.
+__device__ __forceinline__ void ex_candidate(int c, int F, int cmask, const double *x, const double *del, double *xc) {
+  if (cd_active(CD_EX0 + 6 * c, F, cmask)) vilo::pose_plus(x + XO_EX + 7 * c, del + CD_EX0 + 6 * c, xc + XO_EX + 7 * c);
+  else
+    for (int i = 0; i < 7; ++i) xc[XO_EX + 7 * c + i] = x[XO_EX + 7 * c + i];
+}
+
 // DoglegStrategy::ComputeTraditionalDoglegStep in scalar form + TrustRegionMinimizer's model_cost_change.
 // (S: SolverState, or a register copy of the fields it reads and writes)
 template <class S>

@@ -9,6 +9,11 @@ Spec key "alt": one further batch under the alternative configuration of tests/a
 generated and filled at that configuration, in turn over 32 positions (or spec["alt_sizes"]), reported under "alt32" (row N: also "alt257"
 and "alt2049").
 
+Spec keys "const" and "vins": two further resident batches of the windows of tests/const_windows.py (the block-constancy masks the reference
+produces; leg and IMU-only windows apart, a batch holds one IMU factor kind), in turn over 32 positions (or spec["const_sizes"] /
+spec["vins_sizes"]), the td-estimating window of each set at position 6 where the row runs 23-column rows, reported under "const32" /
+"vins32". Spec key "const_alone": the named leg windows each in a batch of their own, under "alone_<name>".
+
 Also importable (no GPU): the window set and its layout, which the test solves with the oracle."""
 import hashlib
 import json
@@ -232,6 +237,22 @@ def main():
         for W in spec.get("field_sizes", [32]):
             ws, names = field_batch(FS, W, bool(spec.get("td")) or spec.get("compact") == 0)
             res["field%d" % W] = {"W": W, "names": names, "solves": _solve_resident(ctx, ws, opts, field_keep(names))}
+    if spec.get("const") or spec.get("vins") or spec.get("const_alone"):
+        import time
+        import const_windows as CW
+        with_td = bool(spec.get("td")) or spec.get("compact") == 0
+        for key, make in (("const", CW.const_set), ("vins", CW.vins_set)):
+            if not spec.get(key):
+                continue
+            t0 = time.perf_counter()
+            CS = make(cfg, ocfg)
+            for W in spec.get(key + "_sizes", [32]):
+                ws, names = CW.batch_of(CS, W, with_td)
+                res["%s%d" % (key, W)] = {"W": W, "names": names, "solves": _solve_resident(ctx, ws, opts, field_keep(names))}
+                res["%s%d" % (key, W)]["seconds"] = time.perf_counter() - t0   # (what this batch adds to the row, window generation included)
+                t0 = time.perf_counter()
+        for nm in spec.get("const_alone", []):
+            res["alone_" + nm] = {"W": 1, "names": [nm], "solves": _solve_resident(ctx, [CW.leg_window(cfg, ocfg, nm)], opts, [0])}
     ctx.close()
     if spec.get("alt"):
         import alt_config

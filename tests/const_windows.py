@@ -1,0 +1,184 @@
+"""Test helper (no test in it): windows under the block-constancy masks the reference and the library's window manager produce. A window's
+mask (leg_bias_const, ex_const, td_const, and use_leg = 0, which makes the leg biases constant) is read by every visual kernel family's
+landmark-coupling rows, by cd_active in every assembly, solver and gradient kernel and by three hand-written copies of its predicate; under
+the default mask (td constant, everything else free) a dropped or inverted test in any of them is bitwise invisible.
+tests/test_const_windows.py holds, on a CPU and with the oracle alone, that each flag moves the answer by 1000 times the parity bound, that
+constant blocks stay put and that no trust-region decision of the set sits near a threshold; tests/test_kernel_paths.py solves the set in
+every kernel form.
+
+Every window is the generator's (cerberus_amd/host/synth.cpp), filled by the oracle's preintegration, its start perturbations scaled by
+field_windows.START as the field windows' are, so that the four iterations arrive."""
+import numpy as np
+
+import field_windows as FW
+
+ITERS = FW.ITERS   # (tests/_paths_worker.py: the iteration count of every solve of these windows)
+
+# The extrinsics start EX_START away from the calibration the observations were generated with (metres, radians; the generator starts them
+# at the truth): an extrinsic calibration is a few millimetres and a few tenths of a degree off, which is why the reference estimates it.
+# Constant extrinsics then keep that error and free ones remove it: ex_const moves the answer, and a kernel that lets a constant block move
+# shows at once.
+EX_START = (0.004, 0.003)
+
+# Leg set (use_leg = 1), one batch kind.
+#   name: (landmarks, generator seed, shaper seed or None, generator parameters, flags, frames or None)
+# Where each mask comes from:
+#   c40_free      TD         estimator.cpp:1074-1105 with the shipped a1 / go1 vilo yaml on a moving robot (ESTIMATE_EXTRINSIC 1, |Vs[0]| > 0.2,
+#                            ESTIMATE_TD 0, OPTIMIZE_LEG_BIAS 1): the control, the mask every other test solves
+#   c40_ex        EX|TD      estimator.cpp:1090-1098 / vilo_sliding_window.cpp:263-271: a full window of a slow or starting robot (v0 <= 0.2);
+#                            any window under estimate_extrinsic: 0 (hardware_go1_vilo_config_dense.yaml; sequence.SlidingWindow's default)
+#   c40_lb        LB|TD      hardware_go1_vilo_config.yaml: optimize_leg_bias: 0 on full 11-frame windows WITH a prior: the prior's speed /
+#                            leg-bias frame has inactive columns
+#   c40_ex_lb     LB|EX|TD   both of the above
+#   c200_ex       EX|TD      as c40_ex at the bench's size, ragged, part-mono, with outliers (field_windows.field_shape)
+#   c60_partial8  LB|EX|TD   no prior: frame_count < WINDOW_SIZE keeps the extrinsics constant (estimator.cpp:1092) — what start-up really
+#   c60_partial4             solves (the partial windows of tests/_paths_worker.py have ex free, a mask the reference never produces)
+#   c40_ex_td     EX         ESTIMATE_TD 1 on a slow robot: td free, extrinsics constant; rows of 23 columns only
+LEG = {
+    "c40_free": (40, 21, None, dict(), dict(), None),
+    "c40_ex": (40, 21, None, dict(), dict(ex_const=1), None),
+    "c40_lb": (40, 21, None, dict(), dict(leg_bias_const=1), None),
+    "c40_ex_lb": (40, 21, None, dict(), dict(leg_bias_const=1, ex_const=1), None),
+    "c200_ex": (200, 22, 22, dict(), dict(ex_const=1), None),
+    "c60_partial8": (60, 23, None, dict(), dict(ex_const=1), 8),
+    "c60_partial4": (60, 23, None, dict(), dict(ex_const=1), 4),
+    "c40_ex_td": (40, 24, None, dict(), dict(ex_const=1, td_const=0), None),
+}
+LEG_BATCH = [n for n in LEG if n != "c40_ex_td"]   # what shares a compact-row batch
+TD_NAMES, TD_POSITION = ("c40_ex_td", "v40_td"), 6  # (leg set, IMU-only set); where _paths_worker.field_batch places f40_td
+
+# IMU-only set (use_leg = 0, leg_bias_const = 1: hardware_a1_vins_config.yaml, hardware_go1_vins_config.yaml). A batch holds one IMU factor
+# kind, so these have batches of their own. Extrinsics free as the vins yaml has them (ESTIMATE_EXTRINSIC 1) unless noted.
+#   name: (landmarks, generator seed, prior: seed of the IMU-only window the oracle marginalises, or None, flags, frames, skipped intervals)
+VINS = {
+    "v40": (40, 31, 41, dict(), None, ()),
+    "v40_ex": (40, 31, 41, dict(ex_const=1), None, ()),
+    "v130_noprior": (130, 32, None, dict(), None, ()),
+    "v60_partial8": (60, 33, None, dict(ex_const=1), 8, ()),
+    "v40_skip": (40, 34, 44, dict(), None, (4,)),    # sum_dt of interval (4, 5) > 10 s: no IMU factor there
+    # ESTIMATE_TD 1: td free; only in batches of 23-column rows, at TD_POSITION. Without it an IMU-only batch of a row that gets its 23
+    # columns from a td-estimating window (row J of tests/test_kernel_paths.py) would take compact rows, another row's path.
+    "v40_td": (40, 35, 45, dict(td_const=0), None, ()),
+}
+VINS_BATCH = [n for n in VINS if n != "v40_td"]
+PRIOR_NAMES = ("c40_free", "c40_ex", "c40_lb", "c40_ex_lb", "c200_ex", "v40", "v40_ex", "v40_skip")   # the 1e-9 bound between forms
+
+# Tried and not kept, with the reason. No seed had to go: every first seed meets tests/test_const_windows.py's conditions (all steps
+# successful, step-quality ratios 0.987 .. 1.53, flag effects 5e-3 .. 0.27). Two recipes of the IMU-only prior did:
+REJECTED_RECIPES = {
+    "v40": [("the prior as marginalised, its linearisation point one frame later on the trajectory than the window it is handed to",
+             "the free extrinsics' translation moves 1.8 m in four iterations; last step-quality ratio 0.886"),
+            ("recentred, but the marginalised window without a prior of its own",
+             "the extrinsics' translation is held by one window's landmarks alone and wanders 0.27 m; the oracle's own answer moves "
+             "1.3e-10 .. 3.5e-10 under start perturbations of 1e-13, 10 times what the windows kept do")],
+}
+
+
+def _perturb_ex(w, seed):
+    """Moves both extrinsics EX_START (sigma) off their generated value: a local step on the pose, as pose_plus takes it."""
+    from oracle import oracle_py as O
+    rng = np.random.default_rng(seed)
+    for c in range(2):
+        d = np.concatenate([EX_START[0] * rng.normal(size=3), EX_START[1] * rng.normal(size=3)])
+        w.ex_pose[c] = O.pose_plus(w.ex_pose[c], d)
+
+
+def leg_window(cfg, ocfg, name):
+    L, gseed, sseed, gen, flags, frames = LEG[name]
+    w = FW._filled(cfg, ocfg, L, gseed, **gen)
+    _perturb_ex(w, 1000 + gseed)
+    if sseed is not None:
+        FW.field_shape(w, sseed, focal=cfg.focal_length)
+    if frames is not None:
+        FW._truncate(w, frames)        # (no prior, leg biases constant)
+    for k, v in flags.items():
+        setattr(w, k, v)
+    return w
+
+
+def _imu_only(cfg, ocfg, L, seed, prior=False):
+    w = FW._filled(cfg, ocfg, L, seed, prior=prior)
+    w.use_leg, w.leg_bias_const = 0, 1
+    _perturb_ex(w, 1000 + seed)
+    return w
+
+
+def imu_only_prior(cfg, ocfg, seed):
+    """The prior the oracle's MARGIN_OLD leaves of an IMU-only window (40 landmarks) at the state the oracle's solve reaches: poses 0 .. 9,
+    the 9 speed / bias dimensions of frame 0 (with pose 0 the 15-dimension frame block), extrinsics, td: 82 dimensions, no leg-bias block,
+    unlike the generator's prior (86). The marginalised window carries the generator's prior itself, as every window of a stream carries
+    its predecessor's: that is where the information on the extrinsics' translation comes from. Marginalised without one, the prior leaves
+    the free extrinsics to the landmarks of one window alone, their translation wanders 0.27 m in four iterations (measured), and the
+    oracle's own answer moves by 1.3e-10 .. 3.5e-10 under start perturbations of 1e-13 (2.0e-11 .. 6.2e-11 as built here; the leg
+    windows with a prior: 0.8e-11 .. 2.1e-11), too much for the 1e-9 the kernel forms are held to among themselves."""
+    from cerberus_amd.synth import PriorData
+    from oracle import oracle_py as O
+    w0 = _imu_only(cfg, ocfg, 40, seed, prior=True)
+    O.solve_window(ocfg, w0, O.default_opts(True, ITERS))
+    po = PriorData()
+    rc = O.marginalize(ocfg, w0, 0, po)[0]
+    assert rc == 0 and po.struct.valid == 1
+    return po
+
+
+def _recentre(prior, w):
+    """The generator's windows all start at t = 0, while the frames a marginalised window keeps are its frames 1 .. 10: one frame later
+    on the trajectory than the frames 0 .. 9 of the window the prior is handed to. So the prior's linearisation point of the poses and of
+    frame 0's speed / biases is moved onto that window's own trajectory (its true states; the start states are perturbed around them);
+    block table, J0, r0 and the linearisation point of extrinsics and td stay the marginalisation's. Left where it was, the prior pulls every pose
+    one frame's motion away from what the landmarks say and the free extrinsics absorb it (REJECTED_RECIPES)."""
+    xo = 0
+    for bid, gs, _ in prior.blocks():
+        kind, k = bid >> 4, bid & 15
+        if kind == 0:
+            prior.x0[xo:xo + 7] = w.truth_pose[k]
+        elif kind == 1:
+            prior.x0[xo:xo + 9] = w.truth_speed_bias[k]
+        xo += gs
+
+
+def vins_window(cfg, ocfg, name, priors=None):
+    L, gseed, pseed, flags, frames, skip = VINS[name]
+    w = _imu_only(cfg, ocfg, L, gseed)
+    if pseed is not None:
+        if priors is not None and pseed not in priors:
+            priors[pseed] = imu_only_prior(cfg, ocfg, pseed)
+        w.prior = (priors[pseed] if priors is not None else imu_only_prior(cfg, ocfg, pseed)).copy()
+        _recentre(w.prior, w)
+    if frames is not None:
+        FW._truncate(w, frames)
+    for k in skip:
+        w.preint[k, 0] = 11.0
+        w.preint_imu[k, 0] = 11.0
+    for k, v in flags.items():
+        setattr(w, k, v)
+    return w
+
+
+def const_set(cfg, ocfg, names=None):
+    """{name: window} of the leg set, oracle-filled, fresh objects (the oracle solves its own copies)."""
+    return {n: leg_window(cfg, ocfg, n) for n in (names or LEG)}
+
+
+def vins_set(cfg, ocfg, names=None):
+    """{name: window} of the IMU-only set, fresh objects; windows that share a prior recipe get copies of one marginalisation."""
+    priors = {}
+    return {n: vins_window(cfg, ocfg, n, priors) for n in (names or VINS)}
+
+
+def mask_of(w):
+    """(leg biases, extrinsics, td) constant: what batch_pack.hpp packs into WinMeta::const_mask."""
+    return (bool(w.leg_bias_const or not w.use_leg), bool(w.ex_const), bool(w.td_const))
+
+
+def constant_arrays(w):
+    """Indices into state_arrays() of the blocks the window's mask keeps constant (2 leg_bias, 3 ex_pose, 4 td)."""
+    lb, ex, td = mask_of(w)
+    return [i for i, c in ((2, lb), (3, ex), (4, td)) if c]
+
+
+def batch_of(S, W, with_td=False):
+    """W windows of one set in turn (field_windows.batch_of): each window at first, middle and last positions, different masks next to each
+    other in every workgroup and packed-wave neighbourhood; with_td: the set's td-estimating window at TD_POSITION. Returns (windows, names by position)."""
+    names, td = (LEG_BATCH, TD_NAMES[0]) if "c40_free" in S else (VINS_BATCH, TD_NAMES[1])
+    return FW.batch_of(S, W, names=names, extra={TD_POSITION: (td, S[td])} if with_td else None)

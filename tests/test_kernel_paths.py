@@ -22,6 +22,14 @@ tests/alt_config.py, in every row that has the field batch: huber_delta, focal_l
 visual, cost and IMU kernel form, and at their defaults (1.0 among them) a wrong launch line is bitwise right. 32 positions per row; 257
 and 2049 as well in row N, where the plan changes.
 
+A fifth and a sixth batch (worker specs "const" and "vins") hold the windows of tests/const_windows.py: the block-constancy masks the
+reference's estimator and the shipped configurations produce (extrinsics constant on every partial, slow or estimate_extrinsic: 0 window,
+leg biases constant with a prior under optimize_leg_bias: 0, both, and the IMU-only windows of the vins configurations in batches of their
+own), different masks side by side at every position. The mask is read by every visual family's landmark-coupling rows, by cd_active in
+every assembly, solver and gradient kernel and by three hand-written copies of its predicate; under the default mask a wrong one is bitwise
+invisible. On top of the field batches' checks every constant block of every returned state is bitwise the uploaded one
+(tests/test_const_windows.py holds on a CPU that each flag moves the oracle's answer by 1000 bounds or more).
+
 Checks: every special window at every position against the oracle (equal iterations / successful steps, cost 1e-8, states 1e-8; the
 far-off windows: equal decisions, states 1e-4 as tests/test_solver_forms.py holds the solver forms); bitwise where the code or the
 documents claim it; 1e-9 elsewhere on the windows with a prior (the solver forms' bound)."""
@@ -64,6 +72,22 @@ ROWS = {
     "N": ({}, {"sizes": SIZES, "few_sizes": [300], "field": 1, "alt": 1, "field_sizes": [257, 513, 2049], "alt_sizes": [32, 257, 2049]}),
 }
 FIELD_ROWS = [r for r in ROWS if "field" in ROWS[r][1]]
+# the windows of tests/const_windows.py: "const" in every row that has the field batch, "vins" (IMU-only) in these rows — each IMU form, each
+# assembly, each solver, both visual families and both row widths. They ride in the rows' own workers; row N's sizes in a worker of
+# their own under the same (empty) environment, which keeps row N's worker inside its time limit.
+CONST_ROWS = FIELD_ROWS
+VINS_ROWS = ["A", "B0", "C", "D", "E", "G", "H", "Itpar", "J", "N"]
+for _r in CONST_ROWS:
+    if _r != "N":
+        ROWS[_r][1]["const"] = 1
+        if _r in VINS_ROWS:
+            ROWS[_r][1]["vins"] = 1
+N_SIZES = [32, 257, 513, 2049]
+ALONE = ("c40_ex", "c40_lb", "c60_partial8")
+EXTRA_RUNS = {
+    "Nconst": ({}, {"sizes": [], "const": 1, "vins": 1, "const_sizes": N_SIZES, "vins_sizes": N_SIZES}),
+    "Aalone": ({}, {"sizes": [], "const_alone": list(ALONE)}),
+}
 FIELD_PRIOR = ("f40", "f200", "f70_chunks", "f40_allmono")   # the field windows with a prior and compact rows: the 1e-9 bound between forms
 
 
@@ -103,7 +127,7 @@ _cache = {}
 
 def _run(row):
     if row not in _cache:
-        env_row, spec = ROWS[row]
+        env_row, spec = ROWS[row] if row in ROWS else EXTRA_RUNS[row]
         env = {k: v for k, v in os.environ.items() if not k.startswith("VILO_") or k == "VILO_GPU_LIB"}
         env.update(env_row)
         p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_paths_worker.py"), json.dumps(spec)], cwd=ROOT, env=env,
@@ -117,7 +141,7 @@ def _run(row):
 def _sized(row):
     """(name, result of one batch) of a row: its W = 32 batch, or row N's sizes."""
     r = _run(row)
-    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith("field") and not k.startswith("alt")]
+    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith(("field", "alt", "const", "vins"))]
 
 
 def _field(row):
@@ -366,9 +390,14 @@ def test_field_descriptor(row):
             assert wo == WAVE_ORDER.get(row, 1)
 
 
-def _check_field_batches(row, batches, oracle):
+FIELD_NAMES = {"f40", "f200", "f130_noprior", "f70_chunks", "f40_allmono", "f60_partial8"}
+TD_WINDOWS = ("f40_td", "c40_ex_td", "v40_td")   # one position only (6), and only among rows of 23 columns
+
+
+def _check_field_batches(row, batches, oracle, need=FIELD_NAMES, edge=6):
     """Every field window at every position of the batches [(name, result)]: the oracle's decisions, cost 1e-8, states 1e-8 (SURVEY 8(c));
-    each window at first, middle and last positions; one window, one answer wherever it sits; replays bitwise the plain launches.
+    each window at first, middle and last positions (within `edge` of either end: one turn of the six field windows; a batch of more
+    windows in turn passes its own); one window, one answer wherever it sits; replays bitwise the plain launches.
     Returns the largest state and cost difference."""
     worst = worst_c = 0.0
     for name, res in batches:
@@ -377,12 +406,12 @@ def _check_field_batches(row, batches, oracle):
         for i in range(1, len(s)):
             assert s[i]["digest"] == s[0]["digest"] and s[i]["summ"] == s[0]["summ"], (row, name, i)
         by_name = _field_by_name(res)
-        assert set(by_name) >= {"f40", "f200", "f130_noprior", "f70_chunks", "f40_allmono", "f60_partial8"}
+        assert set(by_name) >= set(need)
         for nm, entries in by_name.items():
-            so, ost, F = oracle[nm]
-            if nm != "f40_td":
+            so, ost, F = oracle[nm][:3]
+            if nm not in TD_WINDOWS:
                 pos = [p for p, _, _ in entries]
-                assert pos[0] < 6 and pos[-1] >= res["W"] - 6 and len(pos) >= 3, (row, name, nm, pos)   # first, middle and last positions
+                assert pos[0] < edge and pos[-1] >= res["W"] - edge and len(pos) >= 3, (row, name, nm, pos)   # first, middle and last positions
             n_states = 0
             for p, st, sm in entries:
                 assert (sm["iterations"], sm["successful"]) == (so.iterations, so.num_successful), (row, name, nm, p)
@@ -505,3 +534,170 @@ def test_alt_config_field_windows_against_the_oracle(row, alt_oracle):
     worst, worst_c = _check_field_batches(row, _alt(row), alt_oracle)
     print("MEASURED test_kernel_paths[%s] alternative configuration vs oracle: states %.2e, cost %.2e; vs row A %.2e; %.2f s of the row's worker"
           % (row, worst, worst_c, worst_a, sum(res["seconds"] for _, res in _alt(row))))
+
+
+# ---- the block-constancy masks the reference produces (tests/const_windows.py): the same rows, leg and IMU-only batches ----
+CONST_EDGE = {"const": 14, "vins": 6}   # within two turns of the seven leg windows (c40_ex_td displaces one first position), one of the five IMU-only
+
+
+@pytest.fixture(scope="module")
+def const_oracle():
+    """The oracle's solve of every window of both sets, once: {name: (summary, state arrays, F, uploaded state arrays, indices of the
+    constant ones)}."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _paths_worker as P
+    import const_windows as CW
+    from cerberus_amd import synth
+    from oracle import oracle_py as O
+    cfg = synth.default_config()
+    ocfg = O.config_from(cfg)
+    out = {}
+    for name, w in list(CW.const_set(cfg, ocfg).items()) + list(CW.vins_set(cfg, ocfg).items()):
+        init = w.clone_state()
+        s = O.solve_window(ocfg, w, O.default_opts(True, P.ITERS))
+        out[name] = (s, [a.copy() for a in w.state_arrays()], w.F, init, CW.constant_arrays(w))
+    return out
+
+
+def _const_run(row):
+    return _run("Nconst" if row == "N" else row)
+
+
+def _const(row, kind):
+    """(name, result) of a row's "const" or "vins" batches: one of 32, or row N's four sizes."""
+    return [(k, v) for k, v in _const_run(row).items() if k.startswith(kind)]
+
+
+def _const_cases():
+    return [(r, "const") for r in CONST_ROWS] + [(r, "vins") for r in VINS_ROWS]
+
+
+def _const_need(kind):
+    import const_windows as CW
+    return CW.LEG_BATCH if kind == "const" else CW.VINS_BATCH
+
+
+@pytest.mark.parametrize("row,kind", _const_cases())
+def test_const_descriptor(row, kind):
+    """Each batch takes the row's forms (row N: the entry of its size), the first solve plain launches, the later ones replays; the
+    td-estimating window is in it exactly where the row runs 23-column rows."""
+    got_keys = [k for k, _ in _const(row, kind)]
+    assert got_keys == [kind + str(W) for W in (N_SIZES if row == "N" else [32])], got_keys
+    for name, res in _const(row, kind):
+        exp = EXPECT[row] if row != "N" else (EXPECT["A"] if res["W"] == 32 else EXPECT[str(res["W"])])
+        assert len(res["names"]) == res["W"] and len(res["solves"]) == 3
+        td = [p for p, nm in enumerate(res["names"]) if nm in TD_WINDOWS]
+        assert td == ([6] if row in ("J", "Itpar", "Iwalk") else []), (row, name, td)
+        for i, s in enumerate(res["solves"]):
+            got = dict(s["path"])
+            replay, wo = got.pop("replay"), got.pop("wave_order")
+            assert got == exp, (row, name, i, got)
+            assert replay == (i > 0 and row != "L"), (row, name, i)
+            assert wo == WAVE_ORDER.get(row, 1)
+
+
+def _check_constant_blocks(row, batches, oracle):
+    """Every constant block of every returned state is bitwise the uploaded one: ex_pose / leg_bias / td per the window's mask, leg_bias of
+    every IMU-only window (a back-substitution that writes a nonzero dx into a constant block, a predicate out of step with cd_active)."""
+    n = 0
+    for name, res in batches:
+        for nm, entries in _field_by_name(res).items():
+            _, _, _, init, const = oracle[nm]
+            assert const and (2 in const or nm in ("c40_free", "c40_ex", "c200_ex", "c40_ex_td")), nm
+            for p, st, _ in entries:
+                if st is None:
+                    continue
+                for i in const:
+                    assert np.array_equal(np.asarray(st[i], float).reshape(init[i].shape), init[i]), (row, name, nm, p, "state array %d moved" % i)
+                    n += 1
+    return n
+
+
+@pytest.mark.parametrize("row,kind", _const_cases())
+def test_const_windows_against_the_oracle(row, kind, const_oracle):
+    """Every window of the set at every kept position: the oracle's decisions, cost 1e-8, states 1e-8; one window, one answer wherever it
+    sits among other masks; replays bitwise the plain launches; constant blocks bitwise the uploaded ones; and, where no bitwise claim
+    exists, row A's answer to rounding (test_const_other_forms_agree_with_row_A_to_rounding holds the bound)."""
+    batches = _const(row, kind)
+    worst, worst_c = _check_field_batches(row, batches, const_oracle, need=_const_need(kind), edge=CONST_EDGE[kind])
+    n = _check_constant_blocks(row, batches, const_oracle)
+    assert n >= sum(len(const_oracle[nm][4]) for nm in _const_need(kind)) * 3
+    worst_a = _const_vs_row_A(row, kind, check=False)
+    print("MEASURED test_kernel_paths[%s] %s windows vs oracle: states %.2e, cost %.2e; vs row A %.2e; %d constant blocks bitwise; %.2f s of the row's worker"
+          % (row, kind, worst, worst_c, worst_a, n, sum(res["seconds"] for _, res in batches)))
+
+
+def _const_vs_row_A(row, kind, check):
+    """Largest state difference from row A's batch of 32 on the windows with a prior; check: equal decisions on every window, 1e-9 and
+    cost_trace at rtol 1e-9 on those."""
+    import const_windows as CW
+    ref = _field_by_name(_run("A")[kind + "32"])
+    worst = 0.0
+    for name, res in _const(row, kind):
+        for nm, entries in _field_by_name(res).items():
+            if nm not in ref:
+                continue   # (the td-estimating window: rows of 23 columns only)
+            _, st_a, sm_a = ref[nm][0]
+            for p, st, sm in entries:
+                if check:
+                    assert (sm["iterations"], sm["successful"]) == (sm_a["iterations"], sm_a["successful"]), (row, name, nm, p)
+                if nm in CW.PRIOR_NAMES and st is not None:
+                    e = _rel_states(st, st_a)
+                    worst = max(worst, e)
+                    if check:
+                        assert e < 1e-9, (row, name, nm, p, e)
+                        np.testing.assert_allclose(sm["cost_trace"], sm_a["cost_trace"], rtol=1e-9)
+    return worst
+
+
+@pytest.mark.parametrize("row,kind", [(r, k) for r, k in _const_cases() if r in ("B0", "E", "F", "G", "Itpar", "Iwalk", "N")])
+def test_const_other_forms_agree_with_row_A_to_rounding(row, kind):
+    """1e-9 relative on the windows with a prior (c40_*, c200_ex, v40, v40_ex, v40_skip), equal decisions on every one."""
+    worst = _const_vs_row_A(row, kind, check=True)
+    print("MEASURED test_kernel_paths[%s] %s windows vs row A: states %.2e (windows with a prior)" % (row, kind, worst))
+
+
+_PAIRS = [("B0", "B1"), ("C", "A"), ("D", "A"), ("H", "G"), ("K0", "B1"), ("K1", "B1"), ("K2", "B1"), ("L", "A")]
+
+
+@pytest.mark.parametrize("a,b,kind", [(a, b, "const") for a, b in _PAIRS] + [(a, b, "vins") for a, b in _PAIRS if a in VINS_ROWS and b in VINS_ROWS])
+def test_const_bitwise_pairs(a, b, kind):
+    """The pairs of test_bitwise_pairs, on the batches of mixed masks."""
+    _same(a, b, key=kind + "32")
+
+
+def test_const_frame_parallel_and_walking_forms_give_the_same_states():
+    _same("B1", "A", with_summaries=False, key="const32")
+
+
+@pytest.mark.parametrize("kind", ["const", "vins"])
+def test_const_td_estimating_window_among_23_column_rows(kind):
+    """Rows J and Itpar run the same forms on the same batch: bitwise on every window but the td-estimating one (position 6 of both)."""
+    names = _run("J")[kind + "32"]["names"]
+    td = tuple(p for p, nm in enumerate(names) if nm in TD_WINDOWS)
+    assert td == (6,) and names == _run("Itpar")[kind + "32"]["names"]
+    _same("J", "Itpar", skip=td, key=kind + "32")
+
+
+@pytest.mark.parametrize("kind", ["const", "vins"])
+def test_const_bench_kernel_set_at_small_and_full_size(kind):
+    """Row G's batch of 32 and the natural one of 2049: each window bitwise the same."""
+    g, n = _field_by_name(_run("G")[kind + "32"]), _field_by_name(_run("Nconst")[kind + "2049"])
+    assert set(g) == set(n)
+    for nm in g:
+        assert g[nm][0][1] is not None and g[nm][0][1:] == n[nm][0][1:], nm
+
+
+def test_const_window_alone_is_bitwise_the_window_among_other_masks():
+    """c40_ex, c40_lb and c60_partial8 each in a batch of their own under row A's environment: states bitwise what they are inside
+    const32, where the neighbours in the workgroup and in the packed-wave order carry other masks — no output depends on the
+    batch a window shares."""
+    alone = _run("Aalone")
+    inside = _field_by_name(_run("A")["const32"])
+    for nm in ALONE:
+        s = alone["alone_" + nm]["solves"]
+        assert s[1]["digest"] == s[0]["digest"] == s[2]["digest"]
+        _, st, sm = inside[nm][0]
+        assert st is not None and s[0]["state"]["0"] == st, nm
+        sa = s[0]["summ"][0]
+        assert (sa["iterations"], sa["successful"]) == (sm["iterations"], sm["successful"]), nm
