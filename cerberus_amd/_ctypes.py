@@ -179,6 +179,29 @@ class WindowDeadReckonRecord(C.Structure):
 DR_OK, DR_NO_FRAME, DR_NUMERIC = 0, 1, 2   # a window's status (VILO_DR_*)
 DR_STATE = 10   # P (3), quaternion x y z w, V (3)
 
+class GaugeOpts(C.Structure):
+    """vilo_gauge_opts (8 bytes)"""
+    _fields_ = [("anchor", C.c_int32), ("reserved", C.c_int32)]
+
+
+class WindowGaugeRecord(C.Structure):
+    """vilo_window_gauge_record (16 bytes)"""
+    _fields_ = [("yaw_diff_deg", C.c_double), ("singular", C.c_int32), ("status", C.c_int32)]
+
+
+GAUGE_ANCHOR = {"uploaded": 0, "given": 1}   # VILO_GAUGE_ANCHOR_UPLOADED, VILO_GAUGE_ANCHOR_GIVEN
+GAUGE_OK, GAUGE_NUMERIC = 0, 1   # a window's status (VILO_GAUGE_*)
+
+
+class WindowFailureRecord(C.Structure):
+    """vilo_window_failure_record (12 bytes)"""
+    _fields_ = [("flags", C.c_int32), ("would_reboot", C.c_int32), ("status", C.c_int32)]
+
+
+FAILURE_OK, FAILURE_NUMERIC = 0, 1   # a window's status (VILO_FAILURE_OK, VILO_FAILURE_NUMERIC)
+FAILURE_FEW_TRACKS, FAILURE_BIG_BA, FAILURE_BIG_BG, FAILURE_BIG_TRANSLATION, FAILURE_BIG_Z, FAILURE_BIG_ANGLE = 1, 2, 4, 8, 16, 32   # bits of flags
+FAILURE_VALUES = 6   # the compared quantities, in bit order
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

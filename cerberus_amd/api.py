@@ -39,6 +39,8 @@ def lib():
         L.vilo_last_gyro_align_ms.restype = C.c_double
         L.vilo_last_predict_ms.restype = C.c_double
         L.vilo_last_dead_reckon_ms.restype = C.c_double
+        L.vilo_last_gauge_fix_ms.restype = C.c_double
+        L.vilo_last_failure_detection_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -295,6 +297,61 @@ def _dead_reckon(ctx, n, samples, offsets, from_frame, write, trajectory, call):
     return DeadReckoning(state, traj, step_offsets, a["n_steps"], a["status"])
 
 
+GaugeFix = collections.namedtuple("GaugeFix", "yaw_diff_deg singular status pose0_before")
+
+
+def gauge_opts(anchor="uploaded", anchor_pose=None, n=None):
+    """(T.GaugeOpts, anchor_pose [n, 7] or None) of a gauge_fix call; needs no device. anchor: 'uploaded' (frame 0's pose of the state the
+    batch was created with) or 'given' (anchor_pose [n, 7] as [px py pz qx qy qz qw], one row per window of the call)."""
+    if anchor not in T.GAUGE_ANCHOR:
+        raise ValueError("anchor must be one of %s" % sorted(T.GAUGE_ANCHOR))
+    if anchor == "given" and anchor_pose is None:
+        raise ValueError("anchor='given' needs anchor_pose")
+    if anchor != "given" and anchor_pose is not None:
+        raise ValueError("anchor_pose needs anchor='given'")
+    if anchor_pose is not None:
+        anchor_pose = _c(anchor_pose)
+        if anchor_pose.ndim != 2 or anchor_pose.shape[1] != 7 or (n is not None and anchor_pose.shape[0] != n):
+            raise ValueError("anchor_pose must have shape (%s, 7), got %s" % ("W" if n is None else n, anchor_pose.shape))
+    o = T.GaugeOpts()
+    o.anchor, o.reserved = T.GAUGE_ANCHOR[anchor], 0
+    return o, anchor_pose
+
+
+def _gauge_fix(ctx, n, anchor, anchor_pose, pose0, call):
+    o, anchor_pose = gauge_opts(anchor, anchor_pose, n)
+    rec = (T.WindowGaugeRecord * n)()
+    before = np.zeros((n, 7)) if pose0 else None
+    ctx._check(call(C.byref(o), _p(anchor_pose), rec, _p(before)))
+    a = np.frombuffer(rec, dtype=np.dtype([("yaw_diff_deg", np.float64), ("singular", np.int32), ("status", np.int32)]), count=n).copy()
+    return GaugeFix(a["yaw_diff_deg"], a["singular"], a["status"], before)
+
+
+FailureDetection = collections.namedtuple("FailureDetection", "flags would_reboot status values")
+
+
+def failure_inputs(n, last_track_num=None, last_pose=None):
+    """(last_track_num [n] int32 or None, last_pose [n, 7] or None) of a failure_detection call, checked; needs no device."""
+    if last_track_num is not None:
+        last_track_num = np.ascontiguousarray(last_track_num, dtype=np.int32)
+        if last_track_num.shape != (n,):
+            raise ValueError("last_track_num must have shape (%d,), got %s" % (n, last_track_num.shape))
+    if last_pose is not None:
+        last_pose = _c(last_pose)
+        if last_pose.shape != (n, 7):
+            raise ValueError("last_pose must have shape (%d, 7), got %s" % (n, last_pose.shape))
+    return last_track_num, last_pose
+
+
+def _failure_detection(ctx, n, last_track_num, last_pose, call):
+    tracks, last_pose = failure_inputs(n, last_track_num, last_pose)
+    rec = (T.WindowFailureRecord * n)()
+    values = np.zeros((n, T.FAILURE_VALUES))
+    ctx._check(call(T.iptr(tracks) if tracks is not None else None, _p(last_pose), rec, _p(values)))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowFailureRecord._fields_]), count=n).copy()
+    return FailureDetection(a["flags"], a["would_reboot"], a["status"], values)
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -420,6 +477,23 @@ class Batch:
         the windows with status T.DR_OK; otherwise the batch is left as it was."""
         return _dead_reckon(self.ctx, len(self._descs), samples, offsets, from_frame, write, trajectory,
                             lambda *a: lib().vilo_batch_dead_reckon(self.ctx.h, self.handle, *a))
+
+    def gauge_fix(self, anchor="uploaded", anchor_pose=None, pose0_before=False):
+        """vilo_batch_gauge_fix, in place on the batch's device state (normally right after solve()): double2vector's re-anchoring of yaw
+        and position to frame 0 as it was before the solve, every velocity rotated, every pose and free extrinsic quaternion normalised.
+        GaugeFix(yaw_diff_deg, singular, status (T.GAUGE_*), each [W], pose0_before [W, 7] or None: the solver's frame-0 pose that was
+        replaced). anchor: 'uploaded' (frame 0 of the state the batch was created with) or 'given' (anchor_pose [W, 7]). download()
+        afterwards gives the windows' arrays the fixed state, which is what marginalize() expects."""
+        return _gauge_fix(self.ctx, len(self._descs), anchor, anchor_pose, pose0_before,
+                          lambda *a: lib().vilo_batch_gauge_fix(self.ctx.h, self.handle, *a))
+
+    def failure_detection(self, last_track_num=None, last_pose=None):
+        """vilo_batch_failure_detection at the batch's device state: FailureDetection(flags (T.FAILURE_* bits), would_reboot, status
+        (T.FAILURE_OK / T.FAILURE_NUMERIC), each [W], values [W, 6]: the compared quantities in bit order): every criterion of
+        Estimator::failureDetection on each window's last frame. last_track_num [W] (bit 0) and last_pose [W, 7] (bits 3 to 5) are the
+        caller's; None leaves their bits 0. The batch is left as it was."""
+        return _failure_detection(self.ctx, len(self._descs), last_track_num, last_pose,
+                                  lambda *a: lib().vilo_batch_failure_detection(self.ctx.h, self.handle, *a))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -785,6 +859,25 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _dead_reckon(self, n, samples, offsets, from_frame, write, trajectory,
                             lambda *a: lib().vilo_window_dead_reckon(self.h, n, descs, states, *a))
+
+    def window_gauge_fix(self, windows, anchor="given", anchor_pose=None, pose0_before=False):
+        """vilo_window_gauge_fix: the gauge fix of host windows at their current state arrays, each with its own number of frames (see
+        Batch.gauge_fix); the windows' pose, speed_bias and ex_pose arrays receive the fixed rows. anchor_pose [n, 7]: frame 0 as it was
+        before the solve."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _gauge_fix(self, n, anchor, anchor_pose, pose0_before, lambda *a: lib().vilo_window_gauge_fix(self.h, n, descs, states, *a))
+
+    def window_failure_detection(self, windows, last_track_num=None, last_pose=None):
+        """vilo_window_failure_detection: the failure criteria of host windows at their current state arrays (see Batch.failure_detection)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _failure_detection(self, n, last_track_num, last_pose,
+                                  lambda *a: lib().vilo_window_failure_detection(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

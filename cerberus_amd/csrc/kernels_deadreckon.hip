@@ -15,7 +15,7 @@
 //                  samples one step ahead the same way). With a trajectory asked for, every step writes its state row as five 16-byte stores (80-byte rows of a
 //                  256-byte aligned block: 16-byte aligned).
 //
-// The quaternion of a state row is Eigen's Quaterniond(Matrix3d) of R as it stands: neither R nor the quaternion is normalised between
+// The quaternion of a state row is Eigen's Quaterniond(Matrix3d) of R as it stands (vilo_math.hpp's quat_from_R_dev): neither R nor the quaternion is normalised between
 // steps or at the end, as the reference's Rs[j] is not. Floating-point contraction is off for the whole file, the inlined helpers of
 // vilo_math.hpp included: a trajectory's last row and state_out are the same function of the same values and must be the same bits,
 // and the numpy definition (tests/deadreckon_ref.py) rounds every operation.
@@ -46,45 +46,10 @@ struct DeadReckonArgs {
 
 namespace {
 
-// Eigen::Quaterniond(Matrix3d) (the branch structure of Eigen's quaternion-from-rotation-matrix), the arithmetic of
-// cerberus_amd/host/vilo_sliding_window.cpp's quat_from_R with the three off-trace cases written out: no register array is indexed
-// by a run-time value.
-__device__ __forceinline__ vilo::quat dr_quat_from_R(const vilo::m3 &m) {
-  vilo::quat q;
-  double t = m.a[0] + m.a[4] + m.a[8];
-  if (t > 0) {
-    t = sqrt(t + 1.0);
-    q.w = 0.5 * t;
-    t = 0.5 / t;
-    q.x = (m.a[7] - m.a[5]) * t; q.y = (m.a[2] - m.a[6]) * t; q.z = (m.a[3] - m.a[1]) * t;
-  } else {
-    int i = 0;
-    if (m.a[4] > m.a[0]) i = 1;
-    if (m.a[8] > (i == 1 ? m.a[4] : m.a[0])) i = 2;
-    if (i == 0) {          // j = 1, k = 2
-      t = sqrt(m.a[0] - m.a[4] - m.a[8] + 1.0);
-      q.x = 0.5 * t;
-      t = 0.5 / t;
-      q.w = (m.a[7] - m.a[5]) * t; q.y = (m.a[3] + m.a[1]) * t; q.z = (m.a[6] + m.a[2]) * t;
-    } else if (i == 1) {   // j = 2, k = 0
-      t = sqrt(m.a[4] - m.a[8] - m.a[0] + 1.0);
-      q.y = 0.5 * t;
-      t = 0.5 / t;
-      q.w = (m.a[2] - m.a[6]) * t; q.z = (m.a[7] + m.a[5]) * t; q.x = (m.a[1] + m.a[3]) * t;
-    } else {               // j = 0, k = 1
-      t = sqrt(m.a[8] - m.a[0] - m.a[4] + 1.0);
-      q.z = 0.5 * t;
-      t = 0.5 / t;
-      q.w = (m.a[3] - m.a[1]) * t; q.x = (m.a[2] + m.a[6]) * t; q.y = (m.a[5] + m.a[7]) * t;
-    }
-  }
-  return q;
-}
-
 struct DrRow { double2 a, b, c, d, e; };   // P.x P.y | P.z q.x | q.y q.z | q.w V.x | V.y V.z
 
 __device__ __forceinline__ DrRow dr_row(const vilo::v3 &P, const vilo::m3 &R, const vilo::v3 &V) {
-  const vilo::quat q = dr_quat_from_R(R);
+  const vilo::quat q = vilo::quat_from_R_dev(R);
   DrRow r;
   r.a = make_double2(P.x, P.y); r.b = make_double2(P.z, q.x); r.c = make_double2(q.y, q.z);
   r.d = make_double2(q.w, V.x); r.e = make_double2(V.y, V.z);

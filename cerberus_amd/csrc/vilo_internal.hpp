@@ -49,6 +49,8 @@ struct vilo_ctx {
   double last_gyro_ms = 0.0;       // GPU time of the last vilo_batch_gyro_bias_align (k_gyro_bias_align and, with samples in force, the re-integration)
   double last_predict_ms = 0.0;    // GPU time of the last vilo_batch_predict_next_frame (k_predict_next_frame + k_predict_windows)
   double last_dead_reckon_ms = 0.0;   // GPU time of the last vilo_batch_dead_reckon (k_dead_reckon)
+  double last_gauge_fix_ms = 0.0;     // GPU time of the last vilo_batch_gauge_fix (k_gauge_fix_x)
+  double last_failure_ms = 0.0;       // GPU time of the last vilo_batch_failure_detection (k_failure_detection)
   int marg_general_count = 0;    // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;

@@ -99,6 +99,40 @@ VD v3 qrot(const quat &q, const v3 &v) {
   const v3 uv = cross(u, v) * 2.0;
   return v + uv * q.w + cross(u, uv);
 }
+// Eigen::Quaterniond(Matrix3d): the branch structure of Eigen's quaternion-from-rotation-matrix, the arithmetic of
+// cerberus_amd/host/vilo_sliding_window.cpp's quat_from_R with the three off-trace cases written out: no register array is indexed by a
+// run-time value (that costs a kernel scratch memory). The gauge fix, the dead reckoning and the failure detection share it.
+VD quat quat_from_R_dev(const m3 &m) {
+  quat q;
+  double t = m.a[0] + m.a[4] + m.a[8];
+  if (t > 0) {
+    t = sqrt(t + 1.0);
+    q.w = 0.5 * t;
+    t = 0.5 / t;
+    q.x = (m.a[7] - m.a[5]) * t; q.y = (m.a[2] - m.a[6]) * t; q.z = (m.a[3] - m.a[1]) * t;
+  } else {
+    int i = 0;
+    if (m.a[4] > m.a[0]) i = 1;
+    if (m.a[8] > (i == 1 ? m.a[4] : m.a[0])) i = 2;
+    if (i == 0) {          // j = 1, k = 2
+      t = sqrt(m.a[0] - m.a[4] - m.a[8] + 1.0);
+      q.x = 0.5 * t;
+      t = 0.5 / t;
+      q.w = (m.a[7] - m.a[5]) * t; q.y = (m.a[3] + m.a[1]) * t; q.z = (m.a[6] + m.a[2]) * t;
+    } else if (i == 1) {   // j = 2, k = 0
+      t = sqrt(m.a[4] - m.a[8] - m.a[0] + 1.0);
+      q.y = 0.5 * t;
+      t = 0.5 / t;
+      q.w = (m.a[2] - m.a[6]) * t; q.z = (m.a[7] + m.a[5]) * t; q.x = (m.a[1] + m.a[3]) * t;
+    } else {               // j = 0, k = 1
+      t = sqrt(m.a[8] - m.a[0] - m.a[4] + 1.0);
+      q.z = 0.5 * t;
+      t = 0.5 / t;
+      q.w = (m.a[3] - m.a[1]) * t; q.x = (m.a[2] + m.a[6]) * t; q.y = (m.a[5] + m.a[7]) * t;
+    }
+  }
+  return q;
+}
 // Utility::deltaQ (utility.h:28-41)
 VD quat deltaQ(const v3 &t) { return mkq(1.0, t.x / 2.0, t.y / 2.0, t.z / 2.0); }
 VD m3 Qleft33(const quat &q) { return m3_eye() * q.w + skew(qvec(q)); }

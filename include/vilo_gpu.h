@@ -352,8 +352,10 @@ double vilo_last_marginalize_ms(const vilo_ctx *ctx);
  *   poses  [W][79][79]  (want_poses)     joint covariance of the 11 poses (66), ex0 ex1 (12) and td (1); rows of constant / absent blocks zero
  *   status [W]                           0 OK, 1 rank deficient / not finite, 2 window invalid (a preintegration covariance without
  *                                        sqrt_info: the window the solve fails with termination FAILURE); NaN outputs for 1 and 2
- * The covariance is that of the solver's state, not of double2vector's re-anchored output: vilo_gauge_fix rotates the window by a yaw
- * and shifts it, and Sigma is not transported through that rotation here. */
+ * The covariance is that of the state the batch holds when the call is made: the solver's state right after vilo_batch_solve,
+ * double2vector's re-anchored one once vilo_batch_gauge_fix has run on the batch. The fix rotates the window by a yaw and shifts it, and
+ * Sigma is not transported through that rotation here: to have the covariance at the re-anchored state, fix first and query then
+ * (a host-side vilo_gauge_fix of downloaded states does not change what the batch holds). */
 #define VILO_COV_GAUGE_FRAME0 0
 #define VILO_COV_GAUGE_NONE 1
 typedef struct {
@@ -387,7 +389,8 @@ double vilo_last_covariance_ms(const vilo_ctx *ctx);
  *                   d/ddp_s = I, d/ddtheta_s = -R_s [R_c f/rho + t_c]x, d/ddt_c = R_s, d/ddtheta_c = -R_s R_c [f/rho]x,
  *                   d/drho = -R_s R_c f / rho^2 (with ex_const the extrinsic rows of Sigma_PP are zero and drop out).
  * These are the landmark rows of the full inverse with the landmarks kept: N (N^T H_full N)^-1 N^T, or H_full^-1 under NONE. Like the frame
- * blocks they belong to the solver's state, not to double2vector's re-anchored output. A window with status 1 or 2 gets NaN for all its
+ * blocks they belong to the state the batch holds when the call is made: the solver's, or double2vector's re-anchored one after
+ * vilo_batch_gauge_fix. A window with status 1 or 2 gets NaN for all its
  * landmarks; the other windows are unaffected. Landmarks' cross-covariances with each other are not an output.
  * Outputs: landmarks concatenated window by window, inside a window in the caller's vilo_window_desc order (sum L = total landmarks):
  *   inv_depth_var [sum L], points [sum L][3], point_cov [sum L][3][3], status [W];
@@ -402,8 +405,9 @@ int vilo_window_landmark_covariance(vilo_ctx *ctx, int n_windows, const vilo_win
 
 /* ---- residuals at the current state (Ceres Problem::Evaluate's residuals; Estimator::outliersRejection, estimator.cpp:1741-1798) ----
  * State: the batch's current state, what vilo_batch_download returns (inverse depths included): the initial state before any solve or after
- * vilo_batch_reset, the accepted state after a solve. It is the solver's state, not double2vector's re-anchored output (reprojection errors do
- * not depend on that choice: the gauge fix moves every frame by the same rigid transform).
+ * vilo_batch_reset, the accepted state after a solve, double2vector's re-anchored one after vilo_batch_gauge_fix: whichever of them the caller last
+ * produced (reprojection errors and the factors' costs do not depend on that choice: the gauge fix moves every frame by the same rigid
+ * transform; a prior's residual does, it holds the poses it was linearised at).
  * Costs: Ceres' 1/2 sum rho(|r|^2) over the problem the solve builds, in the units of vilo_solve_summary::final_cost. The IMU-leg / IMU factor
  * counts its whitened residual; the three projection factors use sqrt_info = focal_length / 1.5, td compensation and the HuberLoss; the prior
  * is MarginalizationFactor::Evaluate's. Constant blocks change no cost. With vilo_batch_set_samples in force the IMU factors are evaluated on
@@ -817,6 +821,106 @@ int vilo_window_dead_reckon(vilo_ctx *ctx, int n_windows, const vilo_window_desc
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_dead_reckon: k_dead_reckon, without the packing and upload of the samples
  * and the copies out. */
 double vilo_last_dead_reckon_ms(const vilo_ctx *ctx);
+
+/* ---- double2vector's gauge fix on a resident batch (estimator.cpp:903-1003) ---------------------------------------------------------
+ * After vilo_batch_solve the batch's device state is the raw solver output (para_*). The reference never reads that state:
+ * Estimator::optimization() calls double2vector() right after ceres::Solve, and the marginalisation (:1247-1455), outliersRejection,
+ * predictPtsInNextFrame, failureDetection (:1005-1052), slideWindow and updateLatestStates all read the re-anchored one. This call is that
+ * step, in place on the batch's device state, so that every query of a batch (residuals, covariance, predict_next_frame, marginalize, ...)
+ * can run where the reference runs it: solve -> gauge fix -> queries -> marginalisation.
+ * Per window with F = n_frames, anchor pose (P_a, q_a) and solved frame-0 pose (P_0, q_0), literally :905-957:
+ *   y_diff   = R2ypr(R(q_a)).x - R2ypr(R(q_0)).x                       (degrees; R2ypr as utility.h:87-99 writes it)
+ *   rot      = ypr2R(y_diff, 0, 0); where | |pitch| - 90 | < 1 for either of the two R2ypr: rot = R(q_a) R(q_0)^T      (:925-934)
+ *   frame i  : q_i <- Quaterniond(rot R(q_i / |q_i|)),  P_i <- rot (P_i - P_0) + P_a,  V_i <- rot V_i                  (i < F)
+ *   camera c : q_c <- Quaterniond(R(q_c / |q_c|))  (:971-982: ric is a normalised quaternion's matrix; vector2double packs it back)
+ * Biases, leg biases, td, the extrinsic translations and the inverse depths are not touched. It is the arithmetic of vilo_gauge_fix and
+ * of vilo_optimize_windows (one device function, k_gauge_fix_body; the golden gauge_fix_edges.npz pins it at the Euler singularity).
+ * anchor: VILO_GAUGE_ANCHOR_UPLOADED (default): frame 0's pose of the state the batch was created with (Rs[0], Ps[0] of before the solve;
+ * vilo_optimize_windows uses the same). VILO_GAUGE_ANCHOR_GIVEN: anchor_pose [W][7] as [px py pz qx qy qz qw]: the reference's
+ * failure_occur branch (:908-913: last_R0, last_P0), or a batch solved more than once without a reset, where the state before the second
+ * solve is the caller's to name.
+ * Outputs (each may be NULL): records[w] = {yaw_diff_deg (y_diff above), singular (1: the :925-934 branch was taken), status};
+ * pose0_before [W][7]: the solver's frame-0 pose that was replaced (as read, whatever the status).
+ *   VILO_GAUGE_OK
+ *   VILO_GAUGE_NUMERIC  a value the window's fix reads is not finite (the anchor pose, a pose or velocity of a frame below F, an extrinsic
+ *                       quaternion that would be rewritten): nothing of that window is written, yaw_diff_deg and singular read 0
+ * Constant blocks: a window with ex_const set keeps its extrinsic rows bit for bit as uploaded (the solver never moves them; rewriting
+ * them with their normalised form would move a constant block by an ulp per call). vilo_optimize_windows and vilo_gauge_fix rewrite
+ * the extrinsic quaternions of every window, constant or not, as they always have: their results stay what they were. On windows whose
+ * extrinsics are free the two paths agree bit for bit.
+ * Side effects: the pose, velocity and extrinsic-quaternion entries of the current state, nothing else. vilo_batch_reset still restores
+ * the upload; a following vilo_batch_solve (plain launches or the captured graph) starts from the fixed state. The call's device memory
+ * is returned when it returns. Every output of a window is bitwise independent of the batch it shares and of its position in it.
+ * opts NULL: vilo_default_gauge_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched): NULL ctx or batch; an anchor other than the two; GIVEN without anchor_pose;
+ * anchor_pose without GIVEN. */
+#define VILO_GAUGE_ANCHOR_UPLOADED 0
+#define VILO_GAUGE_ANCHOR_GIVEN 1
+#define VILO_GAUGE_OK 0
+#define VILO_GAUGE_NUMERIC 1
+typedef struct {
+  int32_t anchor;           /* VILO_GAUGE_ANCHOR_* */
+  int32_t reserved;         /* 0 */
+} vilo_gauge_opts;
+void vilo_default_gauge_opts(vilo_gauge_opts *o);
+typedef struct {
+  double yaw_diff_deg;
+  int32_t singular;
+  int32_t status;           /* VILO_GAUGE_* */
+} vilo_window_gauge_record;
+int vilo_batch_gauge_fix(vilo_ctx *ctx, vilo_batch *batch, const vilo_gauge_opts *opts, const double *anchor_pose,
+                         vilo_window_gauge_record *records, double *pose0_before);
+/* The same for host windows at the given states, each with its own n_frames (vilo_gauge_fix takes one F for all): one batch is created
+ * and destroyed, the fixed pose, speed_bias and ex_pose rows are written into state[w]. The uploaded anchor is then state[w]'s own frame 0
+ * (the fix only normalises); a solver result is fixed with VILO_GAUGE_ANCHOR_GIVEN. */
+int vilo_window_gauge_fix(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state, const vilo_gauge_opts *opts,
+                          const double *anchor_pose, vilo_window_gauge_record *records, double *pose0_before);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_gauge_fix: k_gauge_fix_x, without the anchor's upload and the copies out. */
+double vilo_last_gauge_fix_ms(const vilo_ctx *ctx);
+
+/* ---- Estimator::failureDetection on a resident batch (estimator.cpp:1005-1052) -----------------------------------------------------
+ * The reference's function returns false on its first line: nothing below that line runs there and nothing reboots. This call evaluates
+ * every criterion of the text below it, literally, as a flag bit per window, at the batch's device state, with n = n_frames - 1:
+ *   bit 0  last_track_num < 2                                                  (:1008; caller's last_track_num [W], NULL: bit stays 0)
+ *   bit 1  |Ba_n| > 2.5                                                        (:1013)
+ *   bit 2  |Bg_n| > 1.0                                                        (:1018)
+ *   bit 3  |P_n - last_P| > 5                                                  (:1031; caller's last_pose)
+ *   bit 4  |P_n.z - last_P.z| > 1                                              (:1036; caller's last_pose)
+ *   bit 5  acos(Quaterniond(R_n^T last_R).w()) * 2.0 / 3.14 * 180.0 > 50       (:1041-1046; caller's last_pose)
+ * The batch holds only landmarks with used_num >= 4, so it cannot know the feature manager's last_track_num: the caller gives it.
+ * last_pose [W][7] as [px py pz qx qy qz qw] is last_P, last_R of :840-841; NULL leaves bits 3 to 5 at 0. R_n = R(q_n / |q_n|) and
+ * last_R = R(q_last / |q_last|). Bit 5 uses the reference's 3.14, not pi, and Eigen's matrix-to-quaternion conversion; an acos argument
+ * above 1 by rounding gives NaN, and the comparison is then false, as in the reference.
+ * records[w] = {flags, would_reboot, status}: would_reboot = bit 1 or bit 2, the only criteria whose branch says `return true` in the
+ * text (the others' are commented out). values_out (may be NULL) [W][6]: the six compared quantities in bit order (last_track_num as a
+ * double; 0 for those whose input array is NULL).
+ *   VILO_FAILURE_OK
+ *   VILO_FAILURE_NUMERIC  a value read is not finite (Ba_n, Bg_n; with last_pose also frame n's pose and last_pose[w]): flags,
+ *                         would_reboot and the values read 0
+ * No side effects. One launch, one code path for every batch size; every output of a window is bitwise independent of the batch it
+ * shares and of its position in it.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched): NULL ctx or batch; with windows present NULL records. */
+#define VILO_FAILURE_OK 0
+#define VILO_FAILURE_NUMERIC 1
+#define VILO_FAILURE_FEW_TRACKS 1
+#define VILO_FAILURE_BIG_BA 2
+#define VILO_FAILURE_BIG_BG 4
+#define VILO_FAILURE_BIG_TRANSLATION 8
+#define VILO_FAILURE_BIG_Z 16
+#define VILO_FAILURE_BIG_ANGLE 32
+typedef struct {
+  int32_t flags;            /* VILO_FAILURE_* bits */
+  int32_t would_reboot;     /* bit 1 or bit 2 */
+  int32_t status;           /* VILO_FAILURE_OK / VILO_FAILURE_NUMERIC */
+} vilo_window_failure_record;
+int vilo_batch_failure_detection(vilo_ctx *ctx, vilo_batch *batch, const int32_t *last_track_num, const double *last_pose,
+                                 vilo_window_failure_record *records, double *values_out);
+/* The same for host windows at the given states: one batch is created and destroyed. */
+int vilo_window_failure_detection(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                  const int32_t *last_track_num, const double *last_pose, vilo_window_failure_record *records,
+                                  double *values_out);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_failure_detection: k_failure_detection alone. */
+double vilo_last_failure_detection_ms(const vilo_ctx *ctx);
 
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
