@@ -202,6 +202,24 @@ FAILURE_OK, FAILURE_NUMERIC = 0, 1   # a window's status (VILO_FAILURE_OK, VILO_
 FAILURE_FEW_TRACKS, FAILURE_BIG_BA, FAILURE_BIG_BG, FAILURE_BIG_TRANSLATION, FAILURE_BIG_Z, FAILURE_BIG_ANGLE = 1, 2, 4, 8, 16, 32   # bits of flags
 FAILURE_VALUES = 6   # the compared quantities, in bit order
 
+class RepropOpts(C.Structure):
+    """vilo_reprop_opts (40 bytes)"""
+    _fields_ = [("point", C.c_int32), ("select", C.c_int32), ("write", C.c_int32), ("pad", C.c_int32),
+                ("ba_threshold", C.c_double), ("bg_threshold", C.c_double), ("rho_threshold", C.c_double)]
+
+
+class IntervalRepropRecord(C.Structure):
+    """vilo_interval_reprop_record (32 bytes)"""
+    _fields_ = [("drift_ba", C.c_double), ("drift_bg", C.c_double), ("drift_rho", C.c_double), ("selected", C.c_int32),
+                ("status", C.c_int32)]
+
+
+REPROP_POINT = {"state": 0, "startup": 1, "given": 2}    # VILO_REPROP_POINT_*
+REPROP_SELECT = {"all": 0, "drifted": 1, "mask": 2}      # VILO_REPROP_SELECT_*
+REPROP_OK, REPROP_NOT_SELECTED, REPROP_NO_INTERVAL, REPROP_NO_SAMPLES, REPROP_NUMERIC = 0, 1, 2, 3, 4   # an interval's status (VILO_REPROP_*)
+REPROP_THRESHOLDS = (0.10, 0.01, 0.01)   # vilo_default_reprop_opts: ba, bg, rho
+PREPARED_DOUBLES = 126 + 961   # PreintPrepared: head + sqrt_info (Batch.fetch(15))
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

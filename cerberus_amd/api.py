@@ -41,6 +41,7 @@ def lib():
         L.vilo_last_dead_reckon_ms.restype = C.c_double
         L.vilo_last_gauge_fix_ms.restype = C.c_double
         L.vilo_last_failure_detection_ms.restype = C.c_double
+        L.vilo_last_repropagate_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -352,6 +353,75 @@ def _failure_detection(ctx, n, last_track_num, last_pose, call):
     return FailureDetection(a["flags"], a["would_reboot"], a["status"], values)
 
 
+Repropagation = collections.namedtuple("Repropagation", "drift selected status")
+
+
+def reprop_opts(point="state", select="all", write=True, lin=None, mask=None, thresholds=T.REPROP_THRESHOLDS, n_windows=None):
+    """(T.RepropOpts, lin [W * 10, 10] or None, mask [W * 10] uint8 or None) of a repropagate call, checked; needs no device.
+    point: 'state' (interval k at Ba_k, Bg_k, rho_k of the current state), 'startup' (0, Bg_{k+1}, rho_{k+1}: the reference's start-up
+    loop) or 'given' with lin, one row ba bg rho per interval, [W, 10, 10] or [W * 10, 10]. select: 'all', 'drifted' (a drift above its
+    threshold) or 'mask' with mask [W, 10] or [W * 10], non-zero = selected. thresholds: (ba, bg, rho), compared with the drifts."""
+    if point not in T.REPROP_POINT:
+        raise ValueError("point must be one of %s" % sorted(T.REPROP_POINT))
+    if select not in T.REPROP_SELECT:
+        raise ValueError("select must be one of %s" % sorted(T.REPROP_SELECT))
+    if (point == "given") != (lin is not None):
+        raise ValueError("point='given' and lin go together")
+    if (select == "mask") != (mask is not None):
+        raise ValueError("select='mask' and mask go together")
+    th = np.asarray(thresholds, dtype=np.float64)
+    if th.shape != (3,) or not np.isfinite(th).all() or (th < 0).any():
+        raise ValueError("thresholds must be three finite numbers >= 0 (ba, bg, rho), got %r" % (thresholds,))
+    if lin is not None:
+        lin = _c(lin)
+        if lin.shape[-1:] != (10,) or lin.ndim not in (2, 3) or (n_windows is not None and lin.size != 100 * n_windows):
+            raise ValueError("lin must have a row of 10 per interval, 10 intervals per window%s, got shape %s"
+                             % ("" if n_windows is None else " (%d windows)" % n_windows, lin.shape))
+        lin = lin.reshape(-1, 10)
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        if mask.size % 10 or (n_windows is not None and mask.size != 10 * n_windows):
+            raise ValueError("mask must have 10 entries per window%s, got %d" % ("" if n_windows is None else " (%d windows)" % n_windows, mask.size))
+    o = T.RepropOpts()
+    o.point, o.select, o.write, o.pad = T.REPROP_POINT[point], T.REPROP_SELECT[select], 1 if write else 0, 0
+    o.ba_threshold, o.bg_threshold, o.rho_threshold = (float(x) for x in th)
+    return o, lin, mask
+
+
+def window_samples(windows):
+    """(samples [n, 35], offsets [W * 10 + 1] int32) of the windows' own samples / sample_offsets in the layout vilo_batch_set_samples and
+    vilo_batch_repropagate take: empty ranges for the intervals a window does not have."""
+    parts, offs, base = [], [0], 0
+    for w in windows:
+        n = int(w.sample_offsets[-1])
+        parts.append(w.samples[:n])
+        offs.extend((w.sample_offsets[1:] + base).tolist())
+        offs.extend([base + n] * (10 - (len(w.sample_offsets) - 1)))
+        base += n
+    return np.ascontiguousarray(np.concatenate(parts), dtype=np.float64), np.ascontiguousarray(offs, dtype=np.int32)
+
+
+def _repropagate(ctx, n, samples, offsets, point, select, write, lin, mask, thresholds, call):
+    o, lin, mask = reprop_opts(point, select, write, lin, mask, thresholds, n)
+    if (samples is None) != (offsets is None):
+        raise ValueError("samples and offsets go together")
+    sp = op = None
+    if samples is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        if offsets.shape != (10 * n + 1,):
+            raise ValueError("offsets must have 10 entries per window of the call and one more (%d), got shape %s" % (10 * n + 1, offsets.shape))
+        samples = _c(samples).reshape(-1, T.SAMPLE_DOUBLES)
+        if len(samples) < offsets.max():
+            raise ValueError("offsets reach sample %d, samples holds %d" % (offsets.max(), len(samples)))
+        sp, op = C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets)
+    rec = (T.IntervalRepropRecord * (10 * n))()
+    ctx._check(call(sp, op, C.byref(o), _p(lin), T.u8ptr(mask) if mask is not None else None, rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.IntervalRepropRecord._fields_]),
+                      count=10 * n).copy()
+    drift = np.stack([a["drift_ba"], a["drift_bg"], a["drift_rho"]], axis=1).reshape(n, 10, 3)
+    return Repropagation(drift, a["selected"].reshape(n, 10), a["status"].reshape(n, 10))
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -379,16 +449,21 @@ class Batch:
         if not on:
             self.ctx._check(lib().vilo_batch_set_samples(self.ctx.h, self.handle, None, None))
             return
-        parts, offs, base = [], [0], 0
-        for w in self.windows:
-            n = int(w.sample_offsets[-1])
-            parts.append(w.samples[:n])
-            offs.extend((w.sample_offsets[1:] + base).tolist())
-            offs.extend([base + n] * (10 - (len(w.sample_offsets) - 1)))
-            base += n
-        samples = np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)
-        offsets = np.ascontiguousarray(offs, dtype=np.int32)
+        samples, offsets = window_samples(self.windows)
         self.ctx._check(lib().vilo_batch_set_samples(self.ctx.h, self.handle, C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets)))
+
+    def repropagate(self, samples=None, offsets=None, point="state", select="all", write=True, lin=None, mask=None,
+                    thresholds=T.REPROP_THRESHOLDS):
+        """vilo_batch_repropagate: the selected intervals' preintegration records integrated again once, at the chosen point, and
+        prepared again; the solves that follow run on them. Repropagation(drift [W, 10, 3] = |point - the record's lin_ba / lin_bg /
+        lin_rho| of the records as they were, selected [W, 10], status [W, 10] (T.REPROP_*)). point / select / lin / mask / thresholds:
+        see reprop_opts. write=False is the drift query: nothing is integrated and the batch is left as it was. samples [n, 35] and
+        offsets [W * 10 + 1] as for vilo_batch_set_samples; with write and without samples they are built from the windows' samples /
+        sample_offsets, exactly as set_samples builds them."""
+        if write and samples is None and offsets is None:
+            samples, offsets = window_samples(self.windows)
+        return _repropagate(self.ctx, len(self._descs), samples, offsets, point, select, write, lin, mask, thresholds,
+                            lambda *a: lib().vilo_batch_repropagate(self.ctx.h, self.handle, *a))
 
     def marginalize(self, modes, priors_out):
         """vilo_batch_marginalize at the batch's device state (call download() first: the windows' arrays are the host copy of it).
@@ -878,6 +953,19 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _failure_detection(self, n, last_track_num, last_pose,
                                   lambda *a: lib().vilo_window_failure_detection(self.h, n, descs, states, *a))
+
+    def window_repropagate(self, windows, samples=None, offsets=None, point="state", select="all", write=True, lin=None, mask=None,
+                           thresholds=T.REPROP_THRESHOLDS):
+        """vilo_window_repropagate: the re-propagation of host windows' records at their current state arrays (see Batch.repropagate);
+        with write=True the windows' preint (use_leg == 0: preint_imu) arrays receive the selected records."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        if write and samples is None and offsets is None:
+            samples, offsets = window_samples(windows)
+        return _repropagate(self, n, samples, offsets, point, select, write, lin, mask, thresholds,
+                            lambda *a: lib().vilo_window_repropagate(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

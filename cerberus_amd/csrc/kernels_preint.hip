@@ -575,9 +575,9 @@ __device__ __forceinline__ void preint_imu_leg_body(const vilo_config &cfg, cons
 }
 
 __global__ void __launch_bounds__(PAIR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) k_preint_imu_leg(int n, const vilo_config *cfgp, const vilo_sample *samples, const int *offsets,
-                                                       const double *lin, vilo_preint *out, double *terms) {
+                                                       const double *lin, vilo_preint *out, double *terms, const int *go /* null: every interval; else [n], 0: this one is left out */) {
   const int f = blockIdx.x;
-  if (f >= n) return;
+  if (f >= n || (go && !go[f])) return;
   preint_imu_leg_body<false>(*cfgp, samples, offsets[f], offsets[f + 1], lin + 10 * f, out + f, nullptr, terms + (size_t)offsets[f] * (4 * LT_N));
 }
 
@@ -735,9 +735,9 @@ __device__ __forceinline__ void preint_imu_body(const vilo_config &cfg, const vi
 }
 
 __global__ void __launch_bounds__(64) k_preint_imu(int n, const vilo_config *cfgp, const vilo_sample *samples, const int *offsets,
-                                                   const double *lin, vilo_preint_imu *out, double * /* no leg terms */) {
+                                                   const double *lin, vilo_preint_imu *out, double * /* no leg terms */, const int *go /* as k_preint_imu_leg's */) {
   const int f = blockIdx.x;
-  if (f >= n) return;
+  if (f >= n || (go && !go[f])) return;
   preint_imu_body<false>(*cfgp, samples, offsets[f], offsets[f + 1], lin + 6 * f, out + f, nullptr);
 }
 __global__ void __launch_bounds__(64) k_preint_imu_stream_push(int n, const vilo_config *cfgp, const vilo_sample *samples, const int *offsets, const int *ids,
@@ -789,7 +789,7 @@ static int preintegrate_impl(vilo_ctx *ctx, int n, const vilo_sample *samples, c
   VILO_HIP(hipMemcpyAsync(d_o.p, offsets, sizeof(int) * (size_t)(n + 1), hipMemcpyHostToDevice, ctx->stream));
   VILO_HIP(hipMemcpyAsync(d_l.p, lin, sizeof(double) * (size_t)lin_w * n, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(kern, dim3(n), dim3(threads), 0, ctx->stream, n, (const vilo_config *)ctx->d_cfg, d_s.as<vilo_sample>(),
-                     d_o.as<int>(), d_l.as<double>(), d_out.as<OUT>(), d_t.as<double>());
+                     d_o.as<int>(), d_l.as<double>(), d_out.as<OUT>(), d_t.as<double>(), (const int *)nullptr);
   VILO_HIP(hipGetLastError());
   VILO_HIP(hipMemcpyAsync(out, d_out.p, sizeof(OUT) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   VILO_HIP(hipStreamSynchronize(ctx->stream));
@@ -803,6 +803,19 @@ extern "C" int vilo_preintegrate(vilo_ctx *ctx, int n, const vilo_sample *sample
 extern "C" int vilo_preintegrate_imu(vilo_ctx *ctx, int n, const vilo_sample *samples, const int32_t *offsets, const double *lin,
                                      vilo_preint_imu *out) {
   return preintegrate_impl(ctx, n, samples, offsets, lin, 6, out, k_preint_imu, 0, 64);
+}
+
+// vilo_batch_repropagate (kernels_reprop.hip): the same two kernels over device arrays, on the context's stream. Interval f integrates
+// d_samples [d_offsets[f], d_offsets[f + 1]) at d_lin[f] (10 doubles with leg, else 6) into d_out[f]; an interval with go[f] == 0 is left
+// out (its samples are not read, its record not written). d_terms: vilo_preint_terms_per_sample() doubles per sample (leg only).
+size_t vilo_preint_terms_per_sample(int leg) { return leg ? (size_t)(4 * LT_N) : 0; }
+int vilo_launch_preintegrate(vilo_ctx *ctx, int leg, int n, const vilo_sample *d_samples, const int *d_offsets, const double *d_lin, void *d_out,
+                             double *d_terms, const int *d_go) {
+  if (n <= 0) return VILO_OK;
+  if (leg) hipLaunchKernelGGL(k_preint_imu_leg, dim3(n), dim3(PAIR_THREADS), 0, ctx->stream, n, (const vilo_config *)ctx->d_cfg, d_samples, d_offsets, d_lin, (vilo_preint *)d_out, d_terms, d_go);
+  else hipLaunchKernelGGL(k_preint_imu, dim3(n), dim3(64), 0, ctx->stream, n, (const vilo_config *)ctx->d_cfg, d_samples, d_offsets, d_lin, (vilo_preint_imu *)d_out, d_terms, d_go);
+  VILO_HIP(hipGetLastError());
+  return VILO_OK;
 }
 
 // ---- device-resident, incrementally updated preintegration (the reference's push_back as samples arrive, estimator.cpp:619-626) ----

@@ -44,7 +44,11 @@ struct vilo_batch {
   // what vilo_batch_prepare needs to run the sqrt_info preparation again (the reference does it in every IMULegFactor::Evaluate)
   void *d_pre = nullptr;
   bool leg = true;
-  int *d_prep_bad = nullptr;   // [W * 10] covariance of this record not positive definite
+  // where the records came from (vilo_batch_repropagate): rec_pool: gathered from a vilo_preint_streams pool; rec_form: 0 full records,
+  // 1 the compact upload expanded (below), 2 that after a re-propagation which left some of them in that form
+  bool rec_pool = false;
+  int rec_form = 0;
+  int *d_prep_bad = nullptr;  // [W * 10] covariance of this record not positive definite
   // vilo_batch_residuals (kernels_resid.hip): the caller's observation row of each landmark's first observation (device order, rows
   // concatenated by window: a window without landmarks has none), uploaded into the arena at the first call
   std::vector<int> obs_row_host;
@@ -243,6 +247,17 @@ void *ArenaScope::alloc(size_t bytes) {
 
 int vilo_batch_max_window_waves(vilo_batch *bt) { return bt->max_win_waves; }
 const void *vilo_batch_records(vilo_batch *bt, int *leg) { *leg = bt->leg; return bt->d_pre; }
+BatchRecordsRW vilo_batch_records_rw(vilo_batch *bt) { return {bt->d_pre, bt->leg ? 1 : 0, bt->rec_pool ? 1 : 0, bt->rec_form}; }
+void vilo_batch_records_full(vilo_batch *bt, bool all_live) { if (bt->rec_form) bt->rec_form = all_live ? 0 : 2; }
+int vilo_batch_records_replaced(vilo_ctx *ctx, vilo_batch *bt) {
+  const int W = bt->W;
+  // (samples were in force once and may be again: the records vilo_batch_set_samples(NULL) brings back are these from here on)
+  if (bt->rp_orig) VILO_HIP(hipMemcpyAsync(bt->rp_orig, bt->d_pre, sizeof(vilo_preint) * (size_t)W * 10, hipMemcpyDeviceToDevice, ctx->stream));
+  if (!bt->d.win_bad) return VILO_OK;
+  hipLaunchKernelGGL(k_fold_win_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bt->d_prep_bad, bt->d.imu_skip, bt->d.win_bad);
+  VILO_HIP(hipGetLastError());
+  return VILO_OK;
+}
 
 // vilo_batch_residuals: the landmarks' observation rows on the device (batch data, uploaded at the first call: not in a call's scope)
 int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows) {
@@ -449,6 +464,7 @@ int upload_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, co
     void *d_comp = nullptr;
     if (dev_alloc_bytes(ctx, bt, &d_comp, per_win * (size_t)W) != VILO_OK) return VILO_ERR_HIP;
     *compact_bytes = per_win * (size_t)W;
+    bt->rec_form = 1;
     rc = upload_through_ring(ctx, (size_t)W, per_win,
         [&](size_t w, char *to) {
           const int nr = in[w].n_frames - 1;
@@ -483,6 +499,7 @@ int upload_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, co
   }
   if (rc == VILO_OK && !g_ids.empty()) {
     int *d_gi = nullptr, *d_gd = nullptr;
+    bt->rec_pool = true;
     rc = dev_upload(ctx, bt, &d_gi, g_ids);
     if (rc == VILO_OK) rc = dev_upload(ctx, bt, &d_gd, g_dst);
     if (rc == VILO_OK) rc = vilo_launch_preint_gather(ctx, refs[0].preint_pool, (int)g_ids.size(), d_gi, d_gd, d_pre);
@@ -962,7 +979,8 @@ extern "C" double vilo_last_download_ms(const vilo_ctx *ctx) { return ctx ? ctx-
 // reference's interface. what: 0 gram slots, 1 lm_E, 2 lm_g, 3 lm_w (80 x L), 4 cam_g, 5 cam_dh2, 6 cam_y,
 // 7 imu_lin, 8 lm_y, 9 lm_dh2, 10 SolverState scalars + cost trace (24 + 64 doubles), 11 landmark permutation (as doubles),
 // 13 the preintegration records (10 x vilo_preint), 14 lm_g of the buffer the current linearisation does NOT use (after an accepted last
-// step whose candidate was only costed: the gradients that go with lm_E and lm_w, which have one buffer; what 2 reads is unwritten then)
+// step whose candidate was only costed: the gradients that go with lm_E and lm_w, which have one buffer; what 2 reads is unwritten then),
+// 15 the prepared records (10 x PreintPrepared), 16 the records of an IMU-only batch (10 x vilo_preint_imu), 17 [records' form, from a pool]
 extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win, double *out, int max_n) {
   if (!ctx || !bt || win < 0 || win >= bt->W || !out) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
@@ -992,6 +1010,16 @@ extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win
     case 13:   // the window's preintegration records as they stand (vilo_preint x 10; with vilo_batch_set_samples: the last re-integration)
       if (!bt->leg || !bt->d_pre) return VILO_ERR_UNSUPPORTED;
       src = (const double *)((const vilo_preint *)bt->d_pre + (size_t)win * 10); n = 10 * sizeof(vilo_preint) / sizeof(double); break;
+    case 15:   // the window's prepared records (10 x PreintPrepared: head + sqrt_info), entries of intervals without a factor as they lie
+      src = (const double *)(bt->d.prep + (size_t)win * 10); n = 10 * sizeof(PreintPrepared) / sizeof(double); break;
+    case 16:   // what 13 is for a batch of IMU-only windows (vilo_preint_imu x 10)
+      if (bt->leg || !bt->d_pre) return VILO_ERR_UNSUPPORTED;
+      src = (const double *)((const vilo_preint_imu *)bt->d_pre + (size_t)win * 10); n = 10 * sizeof(vilo_preint_imu) / sizeof(double); break;
+    case 17: {   // vilo_batch_records_rw's form of the records (0 full, 1 compact upload, 2 mixed) and whether they came from a pool
+      if (max_n < 2) return VILO_ERR_BAD_ARG;
+      out[0] = bt->rec_form; out[1] = bt->rec_pool ? 1.0 : 0.0;
+      return 2;
+    }
     case 11: {
       n = wm.L;
       if ((int)n > max_n) return VILO_ERR_BAD_ARG;

@@ -51,6 +51,7 @@ struct vilo_ctx {
   double last_dead_reckon_ms = 0.0;   // GPU time of the last vilo_batch_dead_reckon (k_dead_reckon)
   double last_gauge_fix_ms = 0.0;     // GPU time of the last vilo_batch_gauge_fix (k_gauge_fix_x)
   double last_failure_ms = 0.0;       // GPU time of the last vilo_batch_failure_detection (k_failure_detection)
+  double last_reprop_ms = 0.0;        // GPU time of the last vilo_batch_repropagate (k_reprop_point; with write also the integration, k_reprop_commit and the preparation)
   int marg_general_count = 0;    // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
@@ -157,6 +158,10 @@ int vilo_launch_prepare_preint(vilo_ctx *ctx, int n, const vilo_preint *d_pre, P
 int vilo_launch_prepare_preint_imu(vilo_ctx *ctx, int n, const vilo_preint_imu *d_pre, PreintPrepared *d_out, int *d_status, const unsigned char *d_skip, int per_record);
 int vilo_launch_embed_sqrt15(vilo_ctx *ctx, BatchDev &b);
 int vilo_repropagate_launch(vilo_ctx *ctx, BatchDev &b, int mode, int stage);
+// kernels_preint.hip: k_preint_imu_leg / k_preint_imu over device arrays on the context's stream (go: null, or [n] with 0 = leave interval f out)
+size_t vilo_preint_terms_per_sample(int leg);
+int vilo_launch_preintegrate(vilo_ctx *ctx, int leg, int n, const vilo_sample *d_samples, const int *d_offsets, const double *d_lin, void *d_out,
+                             double *d_terms, const int *d_go);
 
 // ---- device-resident hand-over objects (include/vilo_gpu.h) ----
 struct vilo_prior_pool {
@@ -216,6 +221,16 @@ int vilo_with_batch(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo
 }
 // vilo_batch.hip: the batch's preintegration records on the device ([W * 10] vilo_preint when *leg, else vilo_preint_imu)
 const void *vilo_batch_records(vilo_batch *bt, int *leg);
+// vilo_batch.hip, for vilo_batch_repropagate: the records as the call may overwrite them and where they came from. form: 0 full records,
+// 1 uploaded in the compact 739-double form (entries no factor reads are zero, the covariance's lower triangle mirrors the upper),
+// 2 such a batch after a re-propagation that left some records in that form; pool: gathered from a vilo_preint_streams pool.
+struct BatchRecordsRW { void *d_pre; int leg, pool, form; };
+BatchRecordsRW vilo_batch_records_rw(vilo_batch *bt);
+// records were overwritten and prepared again (prep_bad of each rewritten): win_bad folded again from every live interval's flag, as
+// vilo_batch_create folds it (asynchronous on the context's stream); then, once the caller knows: all_live = no live record is left in
+// the compact form.
+int vilo_batch_records_replaced(vilo_ctx *ctx, vilo_batch *bt);
+void vilo_batch_records_full(vilo_batch *bt, bool all_live);
 BatchDev *vilo_batch_dev(vilo_batch *bt);            // vilo_batch.hip, as the next three: the batch's device tables
 int vilo_batch_max_window_waves(vilo_batch *bt);     // the most packed visual waves any of its windows has
 // the landmarks' observation rows on the device (batch data that stays with the batch, uploaded at the first call: outside any call's scope)

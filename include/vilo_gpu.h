@@ -655,7 +655,8 @@ double vilo_last_pnp_ms(const vilo_ctx *ctx);
  * Side effects: with opts->write == 0 none. With opts->write == 1, for the windows with status OK, Bg_i += delta_bg for EVERY frame
  * i < n_frames of the batch's current state (:39-40: one IEEE addition per component) and nothing else changes: vilo_batch_reset still
  * restores the uploaded state; a following vilo_batch_solve (plain launches or the captured graph) starts from the new biases.
- * The reference's trailing repropagate loops (:42-47, estimator.cpp:752-760) are not part of this call. Without samples the batch's records
+ * The reference's trailing repropagate loops (:42-47, estimator.cpp:752-760) are not part of this call: vilo_batch_repropagate (below) is
+ * that loop, once, at chosen biases (VILO_REPROP_POINT_STARTUP: estimator.cpp:752-760 literally). Without it the batch's records
  * keep their linearisation point and the factors' first-order correction takes the new bias; with vilo_batch_set_samples in force the
  * next solve integrates every interval again at the new biases anyway.
  * With samples in force the records in device memory may sit at a rejected candidate point, so the call first integrates them again at
@@ -921,6 +922,93 @@ int vilo_window_failure_detection(vilo_ctx *ctx, int n_windows, const vilo_windo
                                   double *values_out);
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_failure_detection: k_failure_detection alone. */
 double vilo_last_failure_detection_ms(const vilo_ctx *ctx);
+
+/* ---- re-propagate a resident batch's preintegration records once, at chosen biases (IMULegIntegrationBase::repropagate,
+ * imu_leg_integration_base.cpp:62-86, IntegrationBase::repropagate, integration_base.h; the start-up loop of processImage,
+ * estimator.cpp:752-760, and solveGyroscopeBias' trailing loop, initial_aligment.cpp:42-47) ----
+ * The records are integrated again from their samples ONCE and the solves that follow run on fixed records, as the reference's do;
+ * vilo_batch_set_samples instead integrates inside every iteration. Interval k of window w is f = 10 w + k; samples / offsets as for
+ * vilo_batch_set_samples ([n_windows * 10 + 1] offsets, the first sample of a range the constructor's, empty ranges for intervals a
+ * window does not have).
+ * The point of interval k (opts->point):
+ *   VILO_REPROP_POINT_STATE    (Ba_k, Bg_k, rho_k) of the batch's current state: the point the IMU factors correct towards and that
+ *                              repropagate(Bai, Bgi, rhoi) under vilo_batch_set_samples uses
+ *   VILO_REPROP_POINT_STARTUP  (0, Bg_{k+1}, rho_{k+1}): the reference's start-up loop, literally (interval k is
+ *                              il_pre_integrations[k + 1], re-propagated at Vector3d::Zero(), Bgs[k + 1], Rhos[k + 1]); use_leg == 0:
+ *                              IntegrationBase at (0, Bg_{k+1})
+ *   VILO_REPROP_POINT_GIVEN    the caller's lin [n_windows * 10][10] = ba bg rho (use_leg == 0: the first 6 of a row are read)
+ * Drift of interval k, of the record AS IT WAS: drift_ba = |point_ba - lin_ba|, drift_bg = |point_bg - lin_bg|, drift_rho =
+ * |point_rho - lin_rho| (0 when use_leg == 0), 2-norms as sqrt(((d0 d0 + d1 d1) + d2 d2) [+ d3 d3]), every operation rounded.
+ * Which intervals (opts->select):
+ *   VILO_REPROP_SELECT_ALL      every interval of every window
+ *   VILO_REPROP_SELECT_DRIFTED  those with NOT (drift_ba <= ba_threshold AND drift_bg <= bg_threshold AND drift_rho <= rho_threshold):
+ *                               a drift above its threshold, or one that is not a number (a record whose own point is not finite)
+ *   VILO_REPROP_SELECT_MASK     those with mask[f] != 0 (mask [n_windows * 10])
+ * The thresholds are compared with the drifts above, in the units of the biases (m/s^2, rad/s, m); they are the caller's to set. The
+ * defaults (0.10 / 0.01 / 0.01) are a starting point only: the reference has no such test, it re-propagates every interval at start-up
+ * and none afterwards.
+ * records[f] (may be NULL) = {drift_ba, drift_bg, drift_rho, selected, status}:
+ *   VILO_REPROP_OK            selected; with write == 1 the record was replaced
+ *   VILO_REPROP_NOT_SELECTED  the selection left it out (selected 0)
+ *   VILO_REPROP_NO_INTERVAL   k >= n_frames - 1 (selected 0, drifts 0)
+ *   VILO_REPROP_NO_SAMPLES    selected, write == 1 and the interval has fewer than two samples: the record is untouched
+ *   VILO_REPROP_NUMERIC       the point is not finite: the record is untouched, selected 0, drifts 0
+ * opts->write == 0 is the drift query: samples and offsets may be NULL, nothing is integrated, the batch is left bitwise as it was, and
+ * drift_*, selected and status (OK / NOT_SELECTED / NO_INTERVAL / NUMERIC) come back.
+ * opts->write == 1: for a selected interval with status OK the record becomes, bit for bit, what vilo_preintegrate (use_leg == 0:
+ * vilo_preintegrate_imu) returns for the same samples at the same point, and its prepared form the sqrt_info vilo_batch_prepare
+ * computes of it (under the vilo_set_sqrt_info_mode in force at this call). That is a fresh IMULegIntegrationBase object. For
+ * contact_sensor_type 0 and 1 it is also what the reference's repropagate() gives. For type 2 the reference's repropagate() keeps the
+ * contact-force filter the previous pass over the samples left in the object (imu_leg_integration_base.cpp:62-86 resets everything but
+ * foot_force_min / max / window / var); this call does NOT: a batch holds no object state between calls, and a result that depended on
+ * how often a record had been integrated before would not be reproducible. Intervals with sum_dt > 10 s, which carry no factor, are
+ * re-propagated like any other (the reference loops over all of them). Every output of an interval, the record included, is bitwise
+ * independent of the batch it shares and of its position in it.
+ * Side effects with write == 1: the selected OK records and their prepared form are overwritten, nothing else of the records; win_bad
+ * (the windows a covariance without sqrt_info fails) is rebuilt from the flags of the preparations in force, as
+ * vilo_batch_set_samples(NULL) rebuilds it. States, landmarks, observations and the prior are not touched; vilo_batch_reset still restores
+ * the states only. The device buffers keep their addresses: a captured solve graph stays valid and the next vilo_batch_solve may replay
+ * it. A batch whose records went up in the compact form (only what the factors read) holds full records where this call wrote them:
+ * both triangles of the covariance, every Jacobian entry. The call's device memory is returned when it returns.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched): NULL ctx or batch; an unknown point or select; write other than 0 or 1; GIVEN
+ * without lin; MASK without mask; write == 1 without samples and offsets; offsets that decrease or are negative; a negative or
+ * non-finite threshold. VILO_ERR_UNSUPPORTED: a batch without records on the device; records gathered from a vilo_preint_streams pool
+ * (the pool's objects own them: reset and push there); vilo_batch_set_samples in force (the solve integrates every interval again at
+ * every point anyway: switch it off first). A batch without windows: VILO_OK. opts NULL: vilo_default_reprop_opts. */
+#define VILO_REPROP_POINT_STATE 0
+#define VILO_REPROP_POINT_STARTUP 1
+#define VILO_REPROP_POINT_GIVEN 2
+#define VILO_REPROP_SELECT_ALL 0
+#define VILO_REPROP_SELECT_DRIFTED 1
+#define VILO_REPROP_SELECT_MASK 2
+#define VILO_REPROP_OK 0
+#define VILO_REPROP_NOT_SELECTED 1
+#define VILO_REPROP_NO_INTERVAL 2
+#define VILO_REPROP_NO_SAMPLES 3
+#define VILO_REPROP_NUMERIC 4
+typedef struct {
+  int32_t point;            /* VILO_REPROP_POINT_* */
+  int32_t select;           /* VILO_REPROP_SELECT_* */
+  int32_t write;            /* 0: drift query, 1: integrate the selected intervals again */
+  int32_t pad;
+  double ba_threshold, bg_threshold, rho_threshold;   /* SELECT_DRIFTED: compared with drift_ba / drift_bg / drift_rho */
+} vilo_reprop_opts;
+void vilo_default_reprop_opts(vilo_reprop_opts *o);   /* STATE, ALL, write 1, thresholds 0.10 / 0.01 / 0.01 */
+typedef struct {
+  double drift_ba, drift_bg, drift_rho;
+  int32_t selected;
+  int32_t status;           /* VILO_REPROP_* */
+} vilo_interval_reprop_record;
+int vilo_batch_repropagate(vilo_ctx *ctx, vilo_batch *batch, const vilo_sample *samples, const int32_t *offsets, const vilo_reprop_opts *opts,
+                           const double *lin, const uint8_t *mask, vilo_interval_reprop_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed; with opts->write the windows' preint (use_leg == 0:
+ * preint_imu) arrays, which the descs point at, receive the selected OK records; the others are left as they are. */
+int vilo_window_repropagate(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, const vilo_sample *samples,
+                            const int32_t *offsets, const vilo_reprop_opts *opts, const double *lin, const uint8_t *mask,
+                            vilo_interval_reprop_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_repropagate: k_reprop_point and, with write, the integration,
+ * k_reprop_commit, the preparation and the fold of win_bad, without the copies in and out. */
+double vilo_last_repropagate_ms(const vilo_ctx *ctx);
 
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
