@@ -1413,7 +1413,8 @@ int vilo_solve_launch(vilo_ctx *ctx, BatchDev &b, const vilo_solve_opts *o, cons
     switch (plan.solver) {
       case vilo::SOLVER_MW8: STEP(VILO_K_SOLVE_WAVE, vilo_launch_mw8_solver(ctx, b, sp, s)); break;
       case vilo::SOLVER_SPLIT:   // chain -> pose system -> back-substitutions + step, then the complete solver for the windows a stage flagged
-        STEP(VILO_K_CHAIN, vilo_launch_chain(ctx, b, s));
+        if (plan.chain == vilo::CHAIN_FACT) STEP(VILO_K_CHAIN_FACT, vilo_launch_chain_fact(ctx, b, s));
+        STEP(VILO_K_CHAIN, vilo_launch_chain(ctx, b, s, plan.chain));
         STEP(VILO_K_SOLVE_MID, vilo_launch_solve_mid(ctx, b, sp, s));
         STEP(VILO_K_BACKSUB, vilo_launch_backsub(ctx, b, sp, s));
         STEP(VILO_K_SOLVE_WAVE, vilo_launch_solve_wave_redo(ctx, b, sp, s));

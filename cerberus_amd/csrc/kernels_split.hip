@@ -3,8 +3,12 @@
 // yet inside k_solve_wave they run at ONE wave per SIMD because those accumulators + the Schur pass's operands need the whole register
 // file. Cut by register footprint instead:
 //
-//   k_chain      (256 registers, two waves per SIMD)  S_k, L_k, M_k = L_k^-1, T_A(k), T(k) for frames F-1 .. 0, rhs_P -= T_B^T t_g
-//                (chain_common.hpp): T_B(k) in MFMA operand order + reduced right-hand side out (Tk), M_k / T_A(k) out (Lk, TAg)
+//   k_chain_fact (two waves per SIMD, FOUR windows per wave: one per 16-lane group)  S_k, L_k, M_k = L_k^-1, T_A(k) for frames
+//                F-1 .. 0 (chain_common.hpp: chain_fact_groups): M_k / T_A(k) out (Lk, TAg), pad[1] = 1 / 0
+//   k_chain      (two waves per SIMD, no LDS)  T(k) for frames F-1 .. 0 with M_k / T_A(k+1) read back a frame ahead, rhs_P -= T_B^T t_g
+//                (chain_recur_to_global): T_B(k) in MFMA operand order + reduced right-hand side out (Tk)
+//   (k_chain_single, VILO_CHAIN_SINGLE: both of the above as the one kernel they were, one window per wave, 256 registers —
+//                chain_to_global; kept for comparisons inside one binary)
 //   k_solve_mid  (kernels_wave.hip: solve_wave_body<true>; 512 registers)  C -= T_B(k)^T T_B(k) from Tk, landmark Schur complement,
 //                blocked Cholesky-80, backward solve: y_P out
 //   k_backsub    (<= 128 registers, four waves per SIMD)  c = g_B - B y_P, the two block-bidiagonal sweeps, landmark back-substitution,
@@ -37,7 +41,38 @@
 #define BS_WPE 4
 #endif
 
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_chain(BatchDev b) {
+// (k_chain_fact at three waves per SIMD spills 4 registers, k_chain 22: occupancy bought with spills is a loss)
+#ifndef CF_WPE
+#define CF_WPE 2
+#endif
+#ifndef CH_WPE
+#define CH_WPE 2
+#endif
+
+// The factorisation of the chain, four windows per wave (chain_common.hpp: chain_fact_groups): M_k / T_A(k) out, pad[1] = 1 / 0.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CF_WPE, CF_WPE))) k_chain_fact(BatchDev b) {
+  __shared__ __attribute__((aligned(16))) double lds[CHF_TOTAL];
+  chain_fact_groups(b, 4 * (int)blockIdx.x, lds, threadIdx.x);
+}
+
+// The T recurrence of the chain for the windows k_chain_fact factorised (chain_common.hpp: chain_recur_to_global): Tk out.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH_WPE, CH_WPE))) k_chain(BatchDev b) {
+  const int win = blockIdx.x;
+  SolverState &st = b.st[win];
+  if (st.done || !st.need_lin || st.pad[1] != 1) return;   // (0: a pivot was not positive — k_solve_mid hands the window to the complete path)
+  const int lane = threadIdx.x;
+  const WinMeta wm = b.win[win];
+  const double *gin = b.cam_gin + (size_t)win * CD_N;
+  const double *bimg = b.Bimg + (size_t)win * BI_N;
+  const double *Mg = b.Lk + (size_t)win * 11 * 169, *TAg = b.TAg + (size_t)win * 11 * 169;
+  double *Tout = b.Tk + (size_t)win * TK_N;
+  PCLK(if (lane == 0) st.phase_clk[10] = clock64());
+  chain_recur_to_global(bimg, gin, Mg, TAg, Tout, Tout + TK_V, wm.n_frames, wm.pad, lane);
+  PCLK(if (lane == 0) st.phase_clk[11] = clock64());
+}
+
+// The whole chain by one wave per window (VILO_CHAIN_SINGLE: the form before the cut, kept for comparisons inside one binary).
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_chain_single(BatchDev b) {
   __shared__ __attribute__((aligned(16))) double lds[SC_TOTAL];
   const int win = blockIdx.x;
   SolverState &st = b.st[win];
@@ -309,8 +344,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BS_WPE,
   PCLK(if (lane == 0) st.phase_clk[27] = clock64());
 }
 
-int vilo_launch_chain(vilo_ctx *, BatchDev &b, hipStream_t s) {
-  hipLaunchKernelGGL(k_chain, dim3(b.W), dim3(64), 0, s, b);
+int vilo_launch_chain_fact(vilo_ctx *, BatchDev &b, hipStream_t s) {
+  hipLaunchKernelGGL(k_chain_fact, dim3((b.W + 3) / 4), dim3(64), 0, s, b);
+  return VILO_OK;
+}
+int vilo_launch_chain(vilo_ctx *, BatchDev &b, hipStream_t s, int form) {
+  if (form == vilo::CHAIN_FACT) hipLaunchKernelGGL(k_chain, dim3(b.W), dim3(64), 0, s, b);
+  else hipLaunchKernelGGL(k_chain_single, dim3(b.W), dim3(64), 0, s, b);
   return VILO_OK;
 }
 int vilo_launch_backsub(vilo_ctx *, BatchDev &b, const SolveParams &sp, hipStream_t s) {

@@ -31,6 +31,8 @@ struct Tuning {
   int split_min = 1025;        // VILO_SPLIT_MIN_WINDOWS
   int wave_order = 1;          // VILO_WAVE_ORDER: launch order of the packed waves, 0 window order, 1 by length, 2 by length, groups rotated
   int debug_redo = 0;          // VILO_DEBUG_REDO (k_backsub)
+  // the three-stage solver's chain as the one kernel it was (k_chain_single) instead of k_chain_fact + k_chain: A/B runs and the bitwise test
+  bool chain_single = false;   // VILO_CHAIN_SINGLE
   long wave_lds = -1;          // VILO_WAVE_LDS: dynamic LDS bytes of k_solve_wave / k_solve_mid (occupancy experiments); -1: what they need
   bool no_graph = false;       // VILO_NO_GRAPH: plain launches, no captured launch sequence
   bool full_record_upload = false;   // VILO_FULL_RECORD_UPLOAD: vilo_batch_create uploads whole preintegration records
@@ -49,6 +51,7 @@ struct Tuning {
     num("VILO_SPLIT_MIN_WINDOWS", t.split_min);
     num("VILO_WAVE_ORDER", t.wave_order);
     num("VILO_DEBUG_REDO", t.debug_redo);
+    t.chain_single = getenv("VILO_CHAIN_SINGLE") != nullptr;
     num("VILO_WAVE_LDS", t.wave_lds);
     t.no_graph = getenv("VILO_NO_GRAPH") != nullptr;
     t.full_record_upload = getenv("VILO_FULL_RECORD_UPLOAD") != nullptr;
@@ -66,6 +69,7 @@ enum Imu { IMU_FUSED = 0, IMU_SINGLE, IMU_PAIR };
 enum Assembly { ASM_SMALL = 0, ASM_FULL, ASM_ACCEPT_WAVE };
 enum Solver { SOLVER_WAVE = 0, SOLVER_SPLIT = 3, SOLVER_MW8 = 4 };   // VILO_SOLVER_*
 enum Cost { COST_TPAR = 0, COST_WALK };
+enum Chain { CHAIN_SINGLE = 0, CHAIN_FACT };   // SOLVER_SPLIT's chain: one kernel, or the factorisation four windows per wave + the recurrence
 
 struct BatchShape {
   int W, n_waves;     // windows, packed waves
@@ -76,14 +80,16 @@ struct BatchShape {
 // few packed waves: one workgroup per (packed wave, frame) instead of per packed wave, so that the chip is not left to 3 waves per window
 inline bool shape_takes_tpar(size_t n_waves, bool full_regime, const Tuning &t) { return n_waves <= t.tpar_max_waves && !full_regime; }
 
-// One launch sequence. The six axes vilo_debug_batch_path reports, and the kernel of the last candidate's visual cost.
+// One launch sequence. The six axes vilo_debug_batch_path reports, the kernel of the last candidate's visual cost and the form of the
+// three-stage solver's chain (NO_FORM with any other solver).
 struct SolvePlan {
-  int visual = NO_FORM, imu = NO_FORM, imu_order = NO_FORM, assembly = NO_FORM, solver = NO_FORM, rows = 0, cost = NO_FORM;
+  int visual = NO_FORM, imu = NO_FORM, imu_order = NO_FORM, assembly = NO_FORM, solver = NO_FORM, rows = 0, cost = NO_FORM, chain = NO_FORM;
   bool fuse_imu() const { return imu == IMU_FUSED; }            // extra workgroups of the visual launch linearise the IMU factors
   bool reduce_later() const { return visual == VIS_SMALL_C; }   // k_assemble_s's extra workgroups finish the frame-parallel form
   bool imu_single() const { return imu == IMU_SINGLE; }         // k_imu_linearize: one factor per wave (else a pair)
   bool operator==(const SolvePlan &o) const {
-    return visual == o.visual && imu == o.imu && imu_order == o.imu_order && assembly == o.assembly && solver == o.solver && rows == o.rows && cost == o.cost;
+    return visual == o.visual && imu == o.imu && imu_order == o.imu_order && assembly == o.assembly && solver == o.solver && rows == o.rows && cost == o.cost &&
+           chain == o.chain;
   }
   bool operator!=(const SolvePlan &o) const { return !(*this == o); }
 };
@@ -113,6 +119,7 @@ inline SolvePlan plan_solve(const BatchShape &s, int forced_solver_form, const T
   else if (p.visual == VIS_PC_IMU) p.imu_order = t.imu_first >= 0 ? t.imu_first : (s.W <= 256 ? 1 : 0);
   p.assembly = asm_small ? ASM_SMALL : (s.compact ? ASM_FULL : ASM_ACCEPT_WAVE);
   p.solver = forced_solver_form >= 0 ? forced_solver_form : (s.W <= t.mw8_max ? SOLVER_MW8 : (s.W < t.split_min ? SOLVER_WAVE : SOLVER_SPLIT));
+  if (p.solver == SOLVER_SPLIT) p.chain = t.chain_single ? CHAIN_SINGLE : CHAIN_FACT;
   return p;
 }
 // The one pass of vilo_marg_linearize (marginalisation, covariance): full 23-column rows with td, the IMU factors unfused, a pair per wave.

@@ -1020,6 +1020,11 @@ extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win
       out[0] = bt->rec_form; out[1] = bt->rec_pool ? 1.0 : 0.0;
       return 2;
     }
+    // the bias chain's hand-over buffers as the last linearisation left them: M_k, T_A(k) ([11][13][13]), T(k) in MFMA operand order + the
+    // reduced right-hand side ([TK_N]: tiles left of chain_x_lo and the padding rows are never written)
+    case 18: src = bt->d.Lk + (size_t)win * 11 * 169; n = 11 * 169; break;
+    case 19: src = bt->d.TAg + (size_t)win * 11 * 169; n = 11 * 169; break;
+    case 20: src = bt->d.Tk + (size_t)win * TK_N; n = TK_N; break;
     case 11: {
       n = wm.L;
       if ((int)n > max_n) return VILO_ERR_BAD_ARG;

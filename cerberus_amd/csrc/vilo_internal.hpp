@@ -25,6 +25,7 @@
 enum {
   VILO_K_VISUAL_LINEARIZE, VILO_K_IMU_LINEARIZE, VILO_K_ASSEMBLE_BIAS, VILO_K_VISUAL_COST, VILO_K_IMU_COST, VILO_K_ACCEPT, VILO_K_INIT_STATE,
   VILO_K_IMU_RAW, VILO_K_ASSEMBLE, VILO_K_SOLVE_WAVE, VILO_K_REPROPAGATE, VILO_K_PREPARE_PREINT, VILO_K_CHAIN, VILO_K_SOLVE_MID, VILO_K_BACKSUB,
+  VILO_K_CHAIN_FACT,
   VILO_NKERNEL
 };
 struct vilo_ctx {
@@ -148,8 +149,10 @@ int vilo_launch_assemble_wave(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp,
 int vilo_launch_solve_wave(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
 int vilo_launch_solve_wave_redo(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
 int vilo_launch_solve_mid(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
-// kernels_split.hip: the chain and the back-substitutions + step of the three-stage form
-int vilo_launch_chain(vilo_ctx *ctx, BatchDev &b, hipStream_t s);
+// kernels_split.hip: the chain (form: vilo::Chain — after k_chain_fact the recurrence alone, else the whole chain in one kernel) and the
+// back-substitutions + step of the three-stage form
+int vilo_launch_chain_fact(vilo_ctx *ctx, BatchDev &b, hipStream_t s);
+int vilo_launch_chain(vilo_ctx *ctx, BatchDev &b, hipStream_t s, int form);
 int vilo_launch_backsub(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
 // kernels_mw8.hip: eight waves per window
 int vilo_launch_mw8_solver(vilo_ctx *ctx, BatchDev &b, const SolveParams &sp, hipStream_t s);
