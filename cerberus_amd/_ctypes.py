@@ -115,6 +115,22 @@ class WindowGradient(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class MaskOpts(C.Structure):
+    """vilo_mask_opts (24 bytes)"""
+    _fields_ = [("source", C.c_int32), ("combine", C.c_int32), ("flag_bits", C.c_uint32), ("pad", C.c_int32), ("outlier_threshold_px", C.c_double)]
+
+
+class WindowMask(C.Structure):
+    """vilo_window_mask_record (24 bytes)"""
+    _fields_ = [("status", C.c_int32), ("n_landmarks", C.c_int32), ("n_masked", C.c_int32), ("n_newly_masked", C.c_int32),
+                ("n_obs_left", C.c_int32), ("pad", C.c_int32)]
+
+
+MASK_SOURCE = {"given": 0, "outlier_flags": 1, "clear": 2}   # VILO_MASK_GIVEN, _OUTLIER_FLAGS, _CLEAR
+MASK_COMBINE = {"replace": 0, "or": 1}                        # VILO_MASK_REPLACE, _OR
+MASK_OK, MASK_NO_LANDMARKS = 0, 1                             # vilo_window_mask_record.status
+
+
 class TriangulateOpts(C.Structure):
     """vilo_triangulate_opts (24 bytes)"""
     _fields_ = [("init_depth", C.c_double), ("stereo", C.c_int32), ("select", C.c_int32), ("write", C.c_int32), ("pad", C.c_int32)]

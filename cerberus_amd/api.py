@@ -42,6 +42,7 @@ def lib():
         L.vilo_last_gauge_fix_ms.restype = C.c_double
         L.vilo_last_failure_detection_ms.restype = C.c_double
         L.vilo_last_repropagate_ms.restype = C.c_double
+        L.vilo_last_mask_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -172,6 +173,44 @@ def _triangulate(ctx, descs, select, mask, write, init_depth, stereo, shift, cal
     sh = np.zeros(L) if shift else None
     ctx._check(call(C.byref(o), None if mask is None else T.u8ptr(mask), _p(depth), T.u8ptr(flags), _p(sh)))
     return Triangulation(depth, flags, offsets, sh)
+
+
+MaskRecords = collections.namedtuple("MaskRecords", "status n_landmarks n_masked n_newly_masked n_obs_left offsets")
+
+
+def mask_opts(n_landmarks, source="given", mask=None, combine="replace", flag_bits=3, outlier_threshold_px=3.0):
+    """(T.MaskOpts, mask as a contiguous uint8 array or None) of a mask_landmarks call over n_landmarks landmarks; needs no device.
+    source: 'given' with mask [n_landmarks] (non-zero: masked), 'outlier_flags' (the residual call's landmark test, flag bytes
+    intersecting flag_bits, at outlier_threshold_px) or 'clear'. combine: 'replace' or 'or' (added to the mask in force)."""
+    if source not in T.MASK_SOURCE:
+        raise ValueError("source must be one of %s" % sorted(T.MASK_SOURCE))
+    if combine not in T.MASK_COMBINE:
+        raise ValueError("combine must be one of %s" % sorted(T.MASK_COMBINE))
+    if (source == "given") != (mask is not None):
+        raise ValueError("source='given' and a mask go together")
+    thr = float(outlier_threshold_px)
+    if not (np.isfinite(thr) and thr >= 0.0):
+        raise ValueError("outlier_threshold_px must be finite and >= 0")
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape != (n_landmarks,):
+            raise ValueError("mask must have one entry per landmark of the call (%d), got shape %s" % (n_landmarks, mask.shape))
+    o = T.MaskOpts()
+    o.source, o.combine, o.flag_bits, o.pad, o.outlier_threshold_px = T.MASK_SOURCE[source], T.MASK_COMBINE[combine], int(flag_bits) & 0xFF, 0, thr
+    return o, mask
+
+
+def _mask_landmarks(ctx, descs, source, mask, combine, flag_bits, outlier_threshold_px, call):
+    n = len(descs)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    L = int(offsets[-1])
+    o, mask = mask_opts(L, source, mask, combine, flag_bits, outlier_threshold_px)
+    out = np.zeros(L, np.uint8)
+    rec = (T.WindowMask * n)()
+    ctx._check(call(C.byref(o), None if mask is None else T.u8ptr(mask), T.u8ptr(out), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowMask._fields_]), count=n).copy()
+    return out, MaskRecords(a["status"], a["n_landmarks"], a["n_masked"], a["n_newly_masked"], a["n_obs_left"], offsets)
 
 
 FramePose = collections.namedtuple("FramePose", "pose final_cost initial_cost n_points iterations status")
@@ -503,6 +542,20 @@ class Batch:
         None, imu_residuals [W, 10, 31] or None). The batch is left as it was."""
         return _residuals(self.ctx, self._descs, outlier_threshold_px, observations, imu,
                           lambda o, *out: lib().vilo_batch_residuals(self.ctx.h, self.handle, o, *out))
+
+    def mask_landmarks(self, source="given", mask=None, combine="replace", flag_bits=3, outlier_threshold_px=3.0):
+        """vilo_batch_mask_landmarks: takes landmarks out of the resident batch on the device (removeOutlier): until the mask changes,
+        solve / download / residuals / marginalize behave as on a batch built without them. Returns (mask [sum L] uint8: the mask in
+        force, window w's landmarks at offsets[w] .. offsets[w + 1] in its own order, MaskRecords(status (T.MASK_*), n_landmarks,
+        n_masked, n_newly_masked, n_obs_left, each [W], offsets [W + 1])). source / mask / combine / flag_bits: see mask_opts. A batch
+        without landmarks comes back with records of zeros. covariance, landmark_covariance, gradient, triangulate, frame_pose_pnp and
+        predict_next_frame raise (VILO_ERR_UNSUPPORTED) while a landmark is masked."""
+        return _mask_landmarks(self.ctx, self._descs, source, mask, combine, flag_bits, outlier_threshold_px,
+                               lambda *a: lib().vilo_batch_mask_landmarks(self.ctx.h, self.handle, *a))
+
+    def clear_mask(self):
+        """mask_landmarks(source='clear'): every landmark back, the flag image restored bit for bit."""
+        return self.mask_landmarks(source="clear")
 
     def gradient(self, state=True, diag=True, landmarks=True):
         """vilo_batch_gradient at the batch's device state: Gradient(per-window max_norm, norm, scaled_max, argmax_kind, argmax_index,
@@ -876,6 +929,16 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _residuals(self, descs, outlier_threshold_px, observations, imu,
                           lambda o, *out: lib().vilo_window_residuals(self.h, n, descs, states, o, *out))
+
+    def window_mask_landmarks(self, windows, source="given", mask=None, combine="replace", flag_bits=3, outlier_threshold_px=3.0):
+        """vilo_window_mask_landmarks: the mask and records of host windows at their current state arrays (see Batch.mask_landmarks);
+        what it is for is source='outlier_flags', the device's selection."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _mask_landmarks(self, descs, source, mask, combine, flag_bits, outlier_threshold_px,
+                               lambda *a: lib().vilo_window_mask_landmarks(self.h, n, descs, states, *a))
 
     def window_gradient(self, windows, state=True, diag=True, landmarks=True):
         """vilo_window_gradient: the gradient of host windows at their current state arrays (see Batch.gradient)."""

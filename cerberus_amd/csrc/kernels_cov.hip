@@ -699,6 +699,7 @@ static int batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts &
 
 extern "C" int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, int32_t *status) {
   if (!ctx || !bt || !frames || !status) return VILO_ERR_BAD_ARG;
+  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_covariance") != VILO_OK) return VILO_ERR_UNSUPPORTED;
   vilo_cov_opts o;
   if (!cov_opts(opts, &o) || (o.want_poses && !poses)) {
     ctx->err = "vilo_batch_covariance: bad options (gauge, min_reciprocal_condition >= 0, want_poses needs a poses buffer)";
@@ -716,6 +717,7 @@ extern "C" int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_w
 extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
                                               double *points, double *point_cov, int32_t *status) {
   if (!ctx || !bt || !status) return VILO_ERR_BAD_ARG;
+  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_landmark_covariance") != VILO_OK) return VILO_ERR_UNSUPPORTED;
   vilo_cov_opts o;
   if (!cov_opts(opts, &o) || (vilo_batch_dev(bt)->n_lm > 0 && (!inv_depth_var || !points || !point_cov))) {
     ctx->err = "vilo_batch_landmark_covariance: bad arguments (gauge, min_reciprocal_condition >= 0, landmark output buffers)";

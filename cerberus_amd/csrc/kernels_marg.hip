@@ -1128,6 +1128,7 @@ extern "C" int vilo_gauge_fix(vilo_ctx *ctx, int W, const vilo_window_state *bef
 static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *state,
                              const int *modes, vilo_prior *out) {
   int rc = VILO_OK;
+  if (vilo_batch_mask_stale(ctx, bt, "vilo_batch_marginalize") != VILO_OK) return VILO_ERR_HIP;
   BatchDev &bd = *vilo_batch_dev(bt);
   std::vector<MargWin> mws(W);
   std::vector<std::vector<int>> kept_ids(W), kept_cd(W), kept_gs(W), kept_soff(W);
@@ -1159,9 +1160,12 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
       if (M.has_imu)
         for (int kind = 0; kind < nkind; ++kind) { mark(kind * 16 + 0); mark(kind * 16 + 1); }
       int L; const int *perm = vilo_batch_perm(bt, w, &L);
+      // a masked landmark (vilo_batch_mask_landmarks) is the deleted one: in no residual block, so it marks no block and is not among
+      // the eliminated landmarks (its E_l is 0: the inverse k_marginalize_lds takes of it would send the window to the eigen path)
+      const unsigned char *msk = vilo_batch_mask_host(bt, w);
       for (int i = 0; i < L; ++i) {
         const int l = perm[i];
-        if (d.lm_start_frame[l] != 0) continue;
+        if (d.lm_start_frame[l] != 0 || (msk && msk[i])) continue;
         const int K = d.lm_obs_offset[l + 1] - d.lm_obs_offset[l];
         mark(VILO_BLK_POSE * 16 + 0);
         for (int t = 1; t < K; ++t) mark(VILO_BLK_POSE * 16 + t);
@@ -1170,7 +1174,7 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
       // dropped landmark list in ORIGINAL feature order (oracle: ascending parameter index)
       std::vector<std::pair<int, int>> dl;
       for (int i = 0; i < L; ++i)
-        if (d.lm_start_frame[perm[i]] == 0) dl.push_back({perm[i], i});
+        if (d.lm_start_frame[perm[i]] == 0 && !(msk && msk[i])) dl.push_back({perm[i], i});
       std::sort(dl.begin(), dl.end());
       for (auto &pr : dl) drops[w].push_back(pr.second);
       M.n_drop_lm = (int)drops[w].size();

@@ -323,6 +323,7 @@ extern "C" int vilo_batch_frame_pose_pnp(vilo_ctx *ctx, vilo_batch *bt, const vi
   vilo_pnp_opts o;
   const int rc = pnp_check_opts(ctx, opts, &o);
   if (rc != VILO_OK) return rc;
+  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_frame_pose_pnp") != VILO_OK) return VILO_ERR_UNSUPPORTED;
   BatchDev &bd = *vilo_batch_dev(bt);
   const int W = bd.W;
   if (W > 0 && !pose) {

@@ -243,6 +243,17 @@ __global__ void __launch_bounds__(128) k_resid_window(BatchDev b, ResidLm lm, co
   }
 }
 
+int vilo_resid_landmark_flags_launch(vilo_ctx *ctx, const BatchDev &b, double threshold_px, double *scratch_d3, int *scratch_i2, unsigned char *flags) {
+  if (b.n_waves <= 0) return VILO_OK;
+  ResidLm lm;
+  lm.cost = scratch_d3; lm.reproj = scratch_d3 + b.n_lm; lm.plain = scratch_d3 + 2 * (size_t)b.n_lm;
+  lm.nb = scratch_i2; lm.nh = scratch_i2 + b.n_lm; lm.flags = flags;
+  hipLaunchKernelGGL(k_resid_landmarks, dim3(b.n_waves), dim3(64), 0, ctx->stream, b, ctx->cfg.focal_length / 1.5, ctx->cfg.huber_delta, ctx->cfg.focal_length, threshold_px,
+                     (const int *)nullptr, lm, (double *)nullptr);
+  VILO_HIP(hipGetLastError());
+  return VILO_OK;
+}
+
 extern "C" void vilo_default_residual_opts(vilo_residual_opts *o) {
   if (!o) return;
   memset(o, 0, sizeof(*o));
@@ -252,6 +263,7 @@ extern "C" void vilo_default_residual_opts(vilo_residual_opts *o) {
 extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_residual_opts *opts, vilo_window_residual *windows, double *lm_cost,
                                     double *lm_reproj_px, uint8_t *lm_flags, double *obs_residuals, double *imu_residuals) {
   if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
+  if (vilo_batch_mask_stale(ctx, bt, "vilo_batch_residuals") != VILO_OK) return VILO_ERR_HIP;
   vilo_residual_opts o;
   if (opts) o = *opts; else vilo_default_residual_opts(&o);
   if (!isfinite(o.outlier_threshold_px) || !(o.outlier_threshold_px >= 0.0)) {
@@ -280,6 +292,8 @@ extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_re
   double *d_ic = call.ptr<double>(o_ic), *d_ir = imu_residuals ? call.ptr<double>(o_ir) : nullptr, *d_or = obs_residuals ? call.ptr<double>(o_or) : nullptr;
   const double sq = ctx->cfg.focal_length / 1.5, ha = ctx->cfg.huber_delta, gn = ctx->cfg.g_norm;
   VILO_HIP(call.start());
+  // a masked landmark (vilo_batch_mask_landmarks) has no valid observation: k_resid_landmarks writes none of its rows, which come back NaN
+  if (d_or && vilo_batch_mask_host(bt, 0)) VILO_HIP(hipMemsetAsync(d_or, 0xFF, sizeof(double) * 4 * (size_t)n_rows, ctx->stream));
   BatchDev b = bd;
   if (call.reintegrate(b, rp) != VILO_OK) return VILO_ERR_HIP;
   if (bd.n_waves > 0)

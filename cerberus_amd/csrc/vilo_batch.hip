@@ -54,6 +54,13 @@ struct vilo_batch {
   std::vector<int> obs_row_host;
   int n_obs_rows = 0;
   int *d_obs_row = nullptr;
+  // vilo_batch_mask_landmarks (kernels_mask.hip): the flag image as uploaded and the mask in force (device order), allocated in the arena at
+  // the first mask call; the mask's host mirror (device order; what the marginalisation's host tables read) and how many landmarks it holds
+  size_t flags_total = 0;
+  unsigned char *d_flags_orig = nullptr, *d_mask = nullptr;
+  std::vector<unsigned char> mask_host;
+  int n_masked = 0;
+  bool mask_stale = false;   // a mask call failed after its kernels were launched: the mirror may not be the device's mask
 };
 
 namespace {
@@ -270,6 +277,44 @@ int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_
   *rows = bt->d_obs_row;
   *n_rows = bt->n_obs_rows;
   return VILO_OK;
+}
+
+// vilo_batch_mask_landmarks: the second copy of the flag bytes and the mask (batch data, allocated at the first call: not in a call's scope)
+int vilo_batch_mask_store(vilo_ctx *ctx, vilo_batch *bt, BatchMaskStore *out) {
+  if (!bt->d_mask) {
+    // one block (flag copy | mask): either both exist or neither
+    const size_t mask_at = (std::max<size_t>(bt->flags_total, 1) + 255) & ~(size_t)255;
+    unsigned char *fo = nullptr;
+    const int rc = dev_alloc(ctx, bt, &fo, mask_at + std::max<size_t>((size_t)bt->d.n_lm, 1));
+    if (rc != VILO_OK) return rc;
+    unsigned char *mk = fo + mask_at;
+    VILO_HIP(hipMemcpyAsync(fo, bt->d.flags, std::max<size_t>(bt->flags_total, 1), hipMemcpyDeviceToDevice, ctx->stream));
+    VILO_HIP(hipMemsetAsync(mk, 0, std::max<size_t>((size_t)bt->d.n_lm, 1), ctx->stream));
+    bt->d_flags_orig = fo; bt->d_mask = mk;
+    bt->mask_host.assign((size_t)bt->d.n_lm, 0);
+  }
+  out->flags_orig = bt->d_flags_orig; out->mask = bt->d_mask; out->mask_host = bt->mask_host.data(); out->lm_off = bt->lm_off_host.data();
+  out->perm = bt->perm_host.data(); out->L = bt->L_host.data();
+  return VILO_OK;
+}
+void vilo_batch_mask_changed(vilo_batch *bt, bool mirror_valid) {
+  bt->mask_stale = !mirror_valid;
+  if (!mirror_valid) return;
+  int n = 0;
+  for (unsigned char m : bt->mask_host) n += m ? 1 : 0;
+  bt->n_masked = n;
+}
+const unsigned char *vilo_batch_mask_host(vilo_batch *bt, int win) { return bt->n_masked > 0 ? bt->mask_host.data() + bt->lm_off_host[win] : nullptr; }
+int vilo_batch_mask_stale(vilo_ctx *ctx, vilo_batch *bt, const char *call) {
+  if (!bt->mask_stale) return VILO_OK;
+  ctx->err = std::string(call) + ": the last vilo_batch_mask_landmarks on this batch failed after its kernels were launched, the mask in force is not known; run a mask call (VILO_MASK_CLEAR, or the mask wanted) first";
+  return VILO_ERR_HIP;
+}
+int vilo_batch_refuse_masked(vilo_ctx *ctx, vilo_batch *bt, const char *call) {
+  if (bt->mask_stale) { (void)vilo_batch_mask_stale(ctx, bt, call); return VILO_ERR_UNSUPPORTED; }
+  if (bt->n_masked <= 0) return VILO_OK;
+  ctx->err = std::string(call) + ": a landmark mask is in force on this batch (vilo_batch_mask_landmarks) and this call does not honour it; clear the mask first";
+  return VILO_ERR_UNSUPPORTED;
 }
 
 extern "C" int vilo_debug_batch_device_bytes(const vilo_batch *bt, size_t out[2]) {
@@ -566,6 +611,7 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
                    ctx->pool);   // (worker_pool.hpp: host threads parked between batches)
   bt->lm_off_host = std::move(P.lm_off); bt->L_host = std::move(P.L); bt->perm_host = std::move(P.perm);
   bt->obs_row_host = std::move(P.obs_row); bt->n_obs_rows = P.n_obs_rows;
+  bt->flags_total = P.flags_total;
   for (const WinMeta &wm : P.wins) bt->max_win_waves = std::max(bt->max_win_waves, wm.n_waves);
   const double t_packed = now();
   // a lane of vilo_solve_windows' pipeline: the uploads of the lanes go one after the other at the link's rate (side by side every lane's
@@ -716,6 +762,7 @@ extern "C" int vilo_batch_reset(vilo_ctx *ctx, vilo_batch *bt) {
 extern "C" int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *bt, const vilo_solve_opts *opts) {
   if (!ctx || !bt || !opts) return VILO_ERR_BAD_ARG;
   if (opts->max_num_iterations < 0 || opts->max_num_iterations > 63) return VILO_ERR_BAD_ARG;
+  if (vilo_batch_mask_stale(ctx, bt, "vilo_batch_solve") != VILO_OK) return VILO_ERR_HIP;
   VILO_HIP(hipSetDevice(ctx->device));
   int rc = VILO_OK;
   const vilo::SolvePlan plan = vilo::plan_solve(vilo_batch_shape(bt->d), ctx->solver_form, vilo::tuning(), opts->max_num_iterations > 0);

@@ -52,6 +52,7 @@ struct vilo_ctx {
   double last_dead_reckon_ms = 0.0;   // GPU time of the last vilo_batch_dead_reckon (k_dead_reckon)
   double last_gauge_fix_ms = 0.0;     // GPU time of the last vilo_batch_gauge_fix (k_gauge_fix_x)
   double last_failure_ms = 0.0;       // GPU time of the last vilo_batch_failure_detection (k_failure_detection)
+  double last_mask_ms = 0.0;          // GPU time of the last vilo_batch_mask_landmarks (k_mask_landmarks + k_mask_windows; with OUTLIER_FLAGS also k_resid_landmarks)
   double last_reprop_ms = 0.0;        // GPU time of the last vilo_batch_repropagate (k_reprop_point; with write also the integration, k_reprop_commit and the preparation)
   int marg_general_count = 0;    // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
@@ -239,6 +240,22 @@ int vilo_batch_max_window_waves(vilo_batch *bt);     // the most packed visual w
 // the landmarks' observation rows on the device (batch data that stays with the batch, uploaded at the first call: outside any call's scope)
 int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows);
 const int *vilo_batch_perm(vilo_batch *bt, int win, int *L);   // window win's landmark order on the host
+// vilo_batch.hip, for vilo_batch_mask_landmarks (kernels_mask.hip): the flag image as uploaded and the mask in force, both in the batch's
+// arena from the first mask call on (outside any call's scope), with the mask's host mirror (device order, as lm_perm) and the host
+// landmark tables. vilo_batch_mask_changed: the mirror was rewritten (mirror_valid), or the device's mask may have
+// been and the mirror was not (a HIP error inside a mask call): vilo_batch_mask_stale then fails (VILO_ERR_HIP, vilo_last_error set) until a
+// mask call has gone through, and so do the refusing calls. vilo_batch_mask_host: window win's part of the mirror (in the
+// order of vilo_batch_perm) while any landmark is masked, else null. vilo_batch_refuse_masked: VILO_ERR_UNSUPPORTED with vilo_last_error set while any landmark is masked (the calls that do not honour
+// a mask).
+struct BatchMaskStore { unsigned char *flags_orig, *mask, *mask_host; const int *lm_off, *perm, *L; };
+int vilo_batch_mask_store(vilo_ctx *ctx, vilo_batch *bt, BatchMaskStore *out);
+void vilo_batch_mask_changed(vilo_batch *bt, bool mirror_valid);
+int vilo_batch_mask_stale(vilo_ctx *ctx, vilo_batch *bt, const char *call);
+const unsigned char *vilo_batch_mask_host(vilo_batch *bt, int win);
+int vilo_batch_refuse_masked(vilo_ctx *ctx, vilo_batch *bt, const char *call);
+// kernels_resid.hip: k_resid_landmarks alone on the context's stream, for the landmark flags (flags [n_lm] bytes, caller order); the other
+// per-landmark outputs go to scratch the caller hands in ([n_lm] doubles x 3, ints x 2)
+int vilo_resid_landmark_flags_launch(vilo_ctx *ctx, const BatchDev &b, double threshold_px, double *scratch_d3, int *scratch_i2, unsigned char *flags);
 // vilo_batch.hip: a call on many host windows cut into sub-batches over the context's pipeline lanes (false: not a call to cut)
 bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
                        const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out);

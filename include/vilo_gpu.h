@@ -464,6 +464,78 @@ int vilo_window_residuals(vilo_ctx *ctx, int n_windows, const vilo_window_desc *
  * without the copies out. */
 double vilo_last_residuals_ms(const vilo_ctx *ctx);
 
+/* ---- landmark mask of a resident batch (Estimator::processImage's f_manager.removeOutlier(removeIndex), estimator.cpp:812-814;
+ *      FeatureManager::removeOutlier) ----
+ * Takes landmarks out of a resident batch on the device, without a new batch: while a mask is in force the batch behaves as a batch built
+ * from the same windows with the masked landmarks deleted — in vilo_batch_solve, vilo_batch_download, vilo_batch_residuals and
+ * vilo_batch_marginalize. solve -> residuals -> mask(outliers) -> solve, or -> marginalize, run on one batch with no host round trip.
+ * How: the call clears the valid bits of the masked landmarks' observations in the batch's flag image (the kernels above skip an
+ * observation without one, as they skip the tail of a short track); the image as uploaded is kept in a second copy, allocated with the mask
+ * at the first mask call (2 - 3 KB per window at 200 landmarks; a batch that is never masked holds nothing more than before).
+ * source   VILO_MASK_GIVEN          mask_in [sum L] bytes, non-zero = masked (concatenated window by window, inside a window in the caller's
+ *                                   vilo_window_desc order, as vilo_batch_triangulate's mask);
+ *          VILO_MASK_OUTLIER_FLAGS  vilo_batch_residuals' landmark test run inside this call at the batch's current state (and current
+ *                                   mask): the landmarks whose lm_flags byte intersects flag_bits (default 3: bit 0, what outliersRejection
+ *                                   hands to removeOutlier, and bit 1, what setDepth / removeFailures reject), at outlier_threshold_px;
+ *                                   byte for byte (vilo_batch_residuals' lm_flags & flag_bits) != 0 of the same batch. A landmark that is
+ *                                   already masked has no reprojection error (its bit 0 is clear): accumulate rounds with VILO_MASK_OR;
+ *          VILO_MASK_CLEAR          no landmark: removes the mask and restores the flag image bit for bit (combine is not read).
+ * combine  VILO_MASK_REPLACE the selection becomes the mask; VILO_MASK_OR it is added to the mask in force.
+ * A masked landmark: no residual block, nothing in cost, gradient, pose system or prior; its step is exactly zero, so its inverse depth
+ * comes back from the solve bitwise as it went in; vilo_batch_residuals reports lm_cost 0, no blocks, flag bit 0 clear, lm_reproj_px
+ * NaN (0 / 0 observations) and every obs_residuals row of the landmark NaN (no block exists); flag bit 1 is a property of the inverse depth alone, so a masked landmark whose inverse depth is negative keeps
+ * it and is counted in n_negative_depth. The free-running solve's ParameterToleranceReached test still counts its inverse depth in |x| (fixed-iteration
+ * solves have no such test).
+ * The mask persists across vilo_batch_reset (which restores every inverse depth, masked ones included, to the uploaded values),
+ * vilo_batch_prepare, repeated solves and replays of the captured launch sequence; only this call changes it. Without a mask call, and
+ * after VILO_MASK_CLEAR, every call gives bitwise what it gave before this call existed.
+ * The other calls on a resident batch, while at least one landmark is masked:
+ *   honour the mask   vilo_batch_solve, _download, _residuals, _marginalize (a masked landmark that starts at frame 0 is left out of the
+ *                     eliminated set, as the deleted one is: no detour through the eigen path);
+ *   do not read landmarks   vilo_batch_gauge_fix, _failure_detection, _gyro_bias_align, _dead_reckon, _repropagate, _set_samples, _prepare, _reset;
+ *   refuse            vilo_batch_covariance, _landmark_covariance, _gradient, _triangulate, _frame_pose_pnp, _predict_next_frame return
+ *                     VILO_ERR_UNSUPPORTED with vilo_last_error saying so; they work again after VILO_MASK_CLEAR (or a mask that selects nothing).
+ * records [W] (optional): status VILO_MASK_OK, or VILO_MASK_NO_LANDMARKS for a window left without a landmark (not an error: it solves as
+ * prior plus IMU factors); n_landmarks; n_masked now; n_newly_masked by this call; n_obs_left: valid observations of the unmasked landmarks.
+ * mask_out [sum L] (optional): the mask in force after the call, caller order. Mask and records do not depend on the batch a window shares
+ * or on its position.
+ * A mask call that fails with VILO_ERR_HIP after its kernels were launched leaves the mask in force unknown: vilo_batch_solve, _residuals,
+ * _marginalize and the refusing calls then fail, with vilo_last_error saying so, until a mask call has gone through.
+ * A batch without landmarks: VILO_OK, no array is touched. Bad arguments (VILO_ERR_BAD_ARG): NULL ctx or batch, an unknown source or
+ * combine, VILO_MASK_GIVEN without mask_in, a threshold that is negative or not finite; n_windows < 1 in the host-window form. */
+#define VILO_MASK_GIVEN 0
+#define VILO_MASK_OUTLIER_FLAGS 1
+#define VILO_MASK_CLEAR 2
+#define VILO_MASK_REPLACE 0
+#define VILO_MASK_OR 1
+#define VILO_MASK_OK 0
+#define VILO_MASK_NO_LANDMARKS 1
+typedef struct {
+  int32_t source;                /* VILO_MASK_GIVEN */
+  int32_t combine;               /* VILO_MASK_REPLACE */
+  uint32_t flag_bits;            /* 3 (OUTLIER_FLAGS) */
+  int32_t pad;
+  double outlier_threshold_px;   /* 3.0 (OUTLIER_FLAGS) */
+} vilo_mask_opts;
+void vilo_default_mask_opts(vilo_mask_opts *o);
+typedef struct {
+  int32_t status;           /* VILO_MASK_OK, VILO_MASK_NO_LANDMARKS */
+  int32_t n_landmarks;
+  int32_t n_masked;         /* landmarks masked after the call */
+  int32_t n_newly_masked;   /* of which were not masked before it */
+  int32_t n_obs_left;       /* valid observations of the landmarks that are not masked */
+  int32_t pad;
+} vilo_window_mask_record;
+/* opts NULL: vilo_default_mask_opts (GIVEN, REPLACE). */
+int vilo_batch_mask_landmarks(vilo_ctx *ctx, vilo_batch *batch, const vilo_mask_opts *opts, const uint8_t *mask_in, uint8_t *mask_out,
+                              vilo_window_mask_record *records);
+/* The same for host windows at the given states: one batch is created, masked, reported and destroyed (mask_out and records are what the
+ * call is for: the selection of the device's outlier test, and its counts). */
+int vilo_window_mask_landmarks(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                               const vilo_mask_opts *opts, const uint8_t *mask_in, uint8_t *mask_out, vilo_window_mask_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_mask_landmarks: its kernels, without the copies in and out. */
+double vilo_last_mask_ms(const vilo_ctx *ctx);
+
 /* ---- cost gradient and Gauss-Newton diagonal at the current state (Ceres Problem::Evaluate's gradient) ----
  * Definition. At the batch's current state, the one vilo_batch_download returns (inverse depths included), over the residual blocks of the
  * problem the solve builds:
