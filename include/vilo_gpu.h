@@ -267,6 +267,9 @@ int vilo_batch_prepare(vilo_ctx *ctx, vilo_batch *batch);
  * samples == NULL switches it off again. The records the batch was built with are overwritten. */
 int vilo_batch_set_samples(vilo_ctx *ctx, vilo_batch *batch, const vilo_sample *samples, const int32_t *offsets);
 int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *batch, const vilo_solve_opts *opts);
+/* out[w] (optional) receives window w's current state: rows 0 .. n_frames - 1 of pose, speed_bias and leg_bias, both extrinsics, td and the
+ * window's n_landmarks inverse depths. A window of fewer than 11 frames: the rows at and beyond n_frames of the caller's three per-frame
+ * arrays are absent frames, which no kernel reads as state; the call does not write them, they stay bytewise what the caller left there. */
 int vilo_batch_download(vilo_ctx *ctx, vilo_batch *batch, vilo_window_state *out, vilo_solve_summary *summaries);
 void vilo_batch_destroy(vilo_ctx *ctx, vilo_batch *batch);
 /* GPU time of the last vilo_batch_solve on ctx's stream (HIP events), and per-kernel-group breakdown. */

@@ -46,6 +46,21 @@ def mixed_windows(cfg, W):
     return out
 
 
+FRAMES_W = 2049   # the frames batch of tests/frame_windows.py at the size whose plan names the three-stage form by itself
+KEEP = {}         # {case: positions whose results are kept}; a case that is not here keeps every window
+
+
+def frames_windows(cfg, W):
+    """frame_windows.batch_of's leg batch: every frame count from 2 to 11, four different ones in every wave of k_chain_fact, (2, 11, 3, 10)
+    in the first. Kept: the first 32 positions (one turn of the placement), the last 33 (the last wave holds one window) and each window's
+    first, middle and last position."""
+    import _paths_worker as P
+    import frame_windows as FR
+    from oracle import oracle_py as O
+    ws, names = FR.batch_of(FR.leg_set(cfg, O.config_from(cfg)), W)
+    return ws, sorted(set(range(32)) | set(range(W - 33, W)) | set(P.field_keep(names))), names
+
+
 FAR = dict(sig_p=1.0, sig_theta=0.4, sig_lambda_rel=0.9, sig_v=1.0, sig_ba=0.3, sig_bg=0.05)
 
 
@@ -54,6 +69,8 @@ def cases(cfg, ctx):
     out = {}
     for W in MIXED_W:
         out["mixed%d" % W] = (mixed_windows(cfg, W), api.default_solve_opts(True, ITERS))
+    ws, KEEP["frames%d" % FRAMES_W], _ = frames_windows(cfg, FRAMES_W)
+    out["frames%d" % FRAMES_W] = (ws, api.default_solve_opts(True, ITERS))
     ws = [_gen(cfg, 42) for _ in range(8)]
     ctx.preintegrate_windows(ws)
     out["equal8"] = (ws, api.default_solve_opts(True, ITERS))
@@ -93,7 +110,8 @@ def tk_written(F):
     return m
 
 
-def solve_case(ctx, ws, opts):
+def solve_case(ctx, ws, opts, keep=None):
+    """[result of window i for i in keep (None: every window)], the batch's descriptor."""
     b = api.Batch(ctx, ws)
     try:
         b.solve(opts)
@@ -101,6 +119,8 @@ def solve_case(ctx, ws, opts):
         path = b.path()
         res = []
         for i, (w, s) in enumerate(zip(ws, summ)):
+            if keep is not None and i not in keep:
+                continue
             F = int(w.F)
             r = {"state": np.concatenate([np.asarray(a, np.float64).ravel() for a in w.state_arrays()]),
                  "cost": np.array(s.cost_trace[:s.iterations + 1]), "radius": np.array(s.radius_trace[:s.iterations + 1]),
@@ -121,9 +141,10 @@ def solve_all(form):
     flat = {}
     all_cases = cases(cfg, ctx)
     for name, (ws, opts) in all_cases.items():
-        res, path = solve_case(ctx, ws, opts)
+        keep = KEEP.get(name)
+        res, path = solve_case(ctx, ws, opts, None if keep is None else set(keep))
         assert path["solver"] == form, path
-        for i, r in enumerate(res):
+        for i, r in zip(keep if keep is not None else range(len(res)), res):
             for k, v in r.items():
                 flat["%s/%d/%s" % (name, i, k)] = v
     # which chain kernels this process launches: one more solve of a case with the per-kernel timing on (its launch counts)

@@ -14,6 +14,11 @@ produces; leg and IMU-only windows apart, a batch holds one IMU factor kind), in
 spec["vins_sizes"]), the td-estimating window of each set at position 6 where the row runs 23-column rows, reported under "const32" /
 "vins32". Spec key "const_alone": the named leg windows each in a batch of their own, under "alone_<name>".
 
+Spec keys "frames" and "vframes": two further resident batches of the windows of tests/frame_windows.py (one window for every frame count
+from 2 to 11; leg and IMU-only windows apart), placed by frame_windows.batch_of over 32 positions (or spec["frames_sizes"] /
+spec["vframes_sizes"]), reported under "frames32" / "vframes32". Spec key "frames_alone": the named leg windows each in a batch of their
+own, under "falone_<name>".
+
 Also importable (no GPU): the window set and its layout, which the test solves with the oracle."""
 import hashlib
 import json
@@ -253,6 +258,21 @@ def main():
                 t0 = time.perf_counter()
         for nm in spec.get("const_alone", []):
             res["alone_" + nm] = {"W": 1, "names": [nm], "solves": _solve_resident(ctx, [CW.leg_window(cfg, ocfg, nm)], opts, [0])}
+    if spec.get("frames") or spec.get("vframes") or spec.get("frames_alone"):
+        import time
+        import frame_windows as FR
+        for key, make in (("frames", FR.leg_set), ("vframes", FR.vins_set)):
+            if not spec.get(key):
+                continue
+            t0 = time.perf_counter()
+            GS = make(cfg, ocfg)
+            for W in spec.get(key + "_sizes", [32]):
+                ws, names = FR.batch_of(GS, W)
+                res["%s%d" % (key, W)] = {"W": W, "names": names, "solves": _solve_resident(ctx, ws, opts, field_keep(names))}
+                res["%s%d" % (key, W)]["seconds"] = time.perf_counter() - t0   # (what this batch adds to the row, window generation included)
+                t0 = time.perf_counter()
+        for nm in spec.get("frames_alone", []):
+            res["falone_" + nm] = {"W": 1, "names": [nm], "solves": _solve_resident(ctx, [FR.leg_window(cfg, ocfg, nm)], opts, [0])}
     ctx.close()
     if spec.get("alt"):
         import alt_config

@@ -31,8 +31,12 @@ EX_START = (0.004, 0.003)
 #                            leg-bias frame has inactive columns
 #   c40_ex_lb     LB|EX|TD   both of the above
 #   c200_ex       EX|TD      as c40_ex at the bench's size, ragged, part-mono, with outliers (field_windows.field_shape)
-#   c60_partial8  LB|EX|TD   no prior: frame_count < WINDOW_SIZE keeps the extrinsics constant (estimator.cpp:1092) — what start-up really
-#   c60_partial4             solves (the partial windows of tests/_paths_worker.py have ex free, a mask the reference never produces)
+#   c60_partial8  LB|EX|TD   no prior: frame_count < WINDOW_SIZE keeps the extrinsics constant (estimator.cpp:1079-1092), the mask
+#   c60_partial4             optimization() gives a partial window. The shipped stereo + IMU start-up (estimator.cpp:734-771,
+#                            vilo_sliding_window.cpp:280-296) runs initFramePoseByPnP and triangulate at every frame count and
+#                            optimization() only once the window is full; the stereo-only start-up that solved at every count is commented
+#                            out (:773-788). A partial solve is what the ABI offers any other caller (the partial windows of
+#                            tests/_paths_worker.py have ex free, a mask the reference never produces)
 #   c40_ex_td     EX         ESTIMATE_TD 1 on a slow robot: td free, extrinsics constant; rows of 23 columns only
 LEG = {
     "c40_free": (40, 21, None, dict(), dict(), None),

@@ -8,7 +8,9 @@ writes them too) and T(k) through vilo_debug_fetch.
   - eight equal windows give equal bits at every position of the two waves;
   - a window whose factorisation fails at the initial mu sits in each of the four groups in turn beside three healthy windows: it retries
     and ends as in the `wave` form, and the neighbours end as they do in a batch without it;
-  - far-off starts whose steps are rejected (the linearisation kept: the group does nothing that iteration) share a wave with plain windows.
+  - far-off starts whose steps are rejected (the linearisation kept: the group does nothing that iteration) share a wave with plain windows;
+  - the 2049-window batch of tests/frame_windows.py: every frame count from 2 to 11, four different ones in every wave, 2 frames beside 11
+    and 10 (a shorter window joins the wave's walk over the shared largest frame count at its own top frame).
 Four iterations each (twelve for the rejected steps, as tests/test_solver_forms.py needs them), with mu changing between them."""
 import os
 import subprocess
@@ -58,11 +60,14 @@ def _windows(res, case):
     return n
 
 
-def _check_case(results, case):
+def _check_case(results, case, keep=None):
     fact, wave, single = results["fact"], results["wave"], results["single"]
-    n = _windows(fact, case)
-    assert n > 0 and n == _windows(wave, case) == _windows(single, case)
-    for i in range(n):
+    n = _windows(fact, case) if keep is None else len(keep)
+    assert n > 0 and (keep is not None or n == _windows(wave, case) == _windows(single, case))
+    if keep is not None:   # the three forms kept the same windows
+        key = lambda res: sorted(k for k in res if k.startswith(case + "/") and k.endswith("/state"))   # noqa: E731
+        assert key(fact) == key(wave) == key(single) == sorted("%s/%d/state" % (case, i) for i in keep)
+    for i in (range(n) if keep is None else keep):
         for f in FIELDS:
             _same(fact, wave, "%s/%d/%s" % (case, i, f))
             _same(fact, single, "%s/%d/%s" % (case, i, f))
@@ -111,3 +116,26 @@ def test_rejected_steps_beside_fresh_linearisations_in_one_wave(results):
     assert _check_case(results, "rejected") == 4
     s = [results["fact"]["rejected/%d/summary" % i] for i in range(4)]
     assert all(s[i][1] + 2 <= s[i][0] for i in (1, 3))   # (rejected steps happened in the far-off windows)
+
+
+def test_every_frame_count_in_waves_of_four_different_ones(results):
+    """The frames batch at 2049 windows: the split form against the one-kernel chain and the `wave` form, bitwise in states, summaries and
+    the hand-over buffers under tk_written's mask, at the first 32 positions, the last 33 and each window's first, middle and last one;
+    and one window, one answer wherever it sits."""
+    import _chain_fact_worker as CF
+    import frame_windows as FR
+    case = "frames%d" % CF.FRAMES_W
+    keep = CF.KEEP[case]
+    assert len(keep) >= 65 and keep[:4] == [0, 1, 2, 3] and keep[-1] == CF.FRAMES_W - 1
+    assert _check_case(results, case, keep) == len(keep)
+    fact = results["fact"]
+    frames = {nm: rec[0] for nm, rec in FR.LEG.items()}
+    seen = {}
+    for i in keep:
+        nm = FR.LEG_ORDER[i % len(FR.LEG_ORDER)]
+        assert fact["%s/%d/M" % (case, i)].size == 169 * frames[nm] and fact["%s/%d/retries" % (case, i)][0] == 0, (i, nm)
+        first = seen.setdefault(nm, i)
+        for f in FIELDS + ("M", "TA", "T"):
+            assert fact["%s/%d/%s" % (case, i, f)].tobytes() == fact["%s/%d/%s" % (case, first, f)].tobytes(), (i, nm, f)
+    assert set(seen) == set(FR.LEG) and sorted(set(frames.values())) == list(range(2, 12))
+    assert [frames[FR.LEG_ORDER[i]] for i in range(4)] == [2, 11, 3, 10] and [frames[FR.LEG_ORDER[i]] for i in range(16, 20)] == [10, 2, 9, 3]

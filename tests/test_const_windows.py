@@ -109,7 +109,7 @@ def test_the_set_has_the_intended_shape(cfg, ocfg):
         assert S[n].prior.struct.valid == 1 and S[n].F == 11
     # the extrinsics start off the calibration the observations were generated with
     assert np.abs(S["c40_ex"].ex_pose[:, :3] - np.array([[0.10076, 0.025, 0.1114], [0.10076, -0.025, 0.1114]])).max() > 1e-3
-    # partial windows: no prior, what start-up solves
+    # partial windows: no prior, the mask optimization() gives frame_count < WINDOW_SIZE
     for n, F in (("c60_partial8", 8), ("c60_partial4", 4)):
         assert S[n].F == F and S[n].prior.struct.valid == 0 and CW.mask_of(S[n]) == (True, True, True) and S[n].L >= 8
     assert V["v60_partial8"].F == 8 and V["v60_partial8"].prior.struct.valid == 0 and V["v130_noprior"].prior.struct.valid == 0

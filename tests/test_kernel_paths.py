@@ -30,6 +30,13 @@ every assembly, solver and gradient kernel and by three hand-written copies of i
 invisible. On top of the field batches' checks every constant block of every returned state is bitwise the uploaded one
 (tests/test_const_windows.py holds on a CPU that each flag moves the oracle's answer by 1000 bounds or more).
 
+A seventh and an eighth batch (worker specs "frames" and "vframes") hold the windows of tests/frame_windows.py: one window for every frame
+count from 2 to 11 (the batches above solve 4, 8 and 11), leg and IMU-only windows apart, four different frame counts in every aligned
+group of four positions, 2 frames beside 11 and 10. The frame count decides where the 6F-wide pose system ends inside its 16-column
+tiles, the parity of the loops over frames, the blocks every assembly pads and where a window joins the four-windows-per-wave chain
+factorisation. On top of the const batches' checks the state rows of the absent frames come back bytewise as uploaded, which is what
+include/vilo_gpu.h promises of vilo_batch_download (tests/test_frame_windows.py holds the windows' properties on a CPU).
+
 Checks: every special window at every position against the oracle (equal iterations / successful steps, cost 1e-8, states 1e-8; the
 far-off windows: equal decisions, states 1e-4 as tests/test_solver_forms.py holds the solver forms); bitwise where the code or the
 documents claim it; 1e-9 elsewhere on the windows with a prior (the solver forms' bound)."""
@@ -82,9 +89,16 @@ for _r in CONST_ROWS:
         ROWS[_r][1]["const"] = 1
         if _r in VINS_ROWS:
             ROWS[_r][1]["vins"] = 1
+        ROWS[_r][1]["frames"] = 1   # the windows of tests/frame_windows.py, likewise (row N's sizes: the worker "Nframes")
+        if _r in VINS_ROWS:
+            ROWS[_r][1]["vframes"] = 1
 N_SIZES = [32, 257, 513, 2049]
+FRAMES_N_SIZES = [257, 513, 2049]
 ALONE = ("c40_ex", "c40_lb", "c60_partial8")
+FRAMES_ALONE = ("g2", "g3", "g10")
 EXTRA_RUNS = {
+    "Nframes": ({}, {"sizes": [], "frames": 1, "vframes": 1, "frames_sizes": FRAMES_N_SIZES, "vframes_sizes": FRAMES_N_SIZES}),
+    "Aframes_alone": ({}, {"sizes": [], "frames_alone": list(FRAMES_ALONE)}),
     "Nconst": ({}, {"sizes": [], "const": 1, "vins": 1, "const_sizes": N_SIZES, "vins_sizes": N_SIZES}),
     "Aalone": ({}, {"sizes": [], "const_alone": list(ALONE)}),
 }
@@ -141,7 +155,7 @@ def _run(row):
 def _sized(row):
     """(name, result of one batch) of a row: its W = 32 batch, or row N's sizes."""
     r = _run(row)
-    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith(("field", "alt", "const", "vins"))]
+    return [(k, v) for k, v in r.items() if k != "far" and not k.startswith(("field", "alt", "const", "vins", "frames", "vframes"))]
 
 
 def _field(row):
@@ -394,7 +408,7 @@ FIELD_NAMES = {"f40", "f200", "f130_noprior", "f70_chunks", "f40_allmono", "f60_
 TD_WINDOWS = ("f40_td", "c40_ex_td", "v40_td")   # one position only (6), and only among rows of 23 columns
 
 
-def _check_field_batches(row, batches, oracle, need=FIELD_NAMES, edge=6):
+def _check_field_batches(row, batches, oracle, need=FIELD_NAMES, edge=6, min_pos=3):
     """Every field window at every position of the batches [(name, result)]: the oracle's decisions, cost 1e-8, states 1e-8 (SURVEY 8(c));
     each window at first, middle and last positions (within `edge` of either end: one turn of the six field windows; a batch of more
     windows in turn passes its own); one window, one answer wherever it sits; replays bitwise the plain launches.
@@ -411,7 +425,7 @@ def _check_field_batches(row, batches, oracle, need=FIELD_NAMES, edge=6):
             so, ost, F = oracle[nm][:3]
             if nm not in TD_WINDOWS:
                 pos = [p for p, _, _ in entries]
-                assert pos[0] < edge and pos[-1] >= res["W"] - edge and len(pos) >= 3, (row, name, nm, pos)   # first, middle and last positions
+                assert pos[0] < edge and pos[-1] >= res["W"] - edge and len(pos) >= min_pos, (row, name, nm, pos)   # first, middle and last positions
             n_states = 0
             for p, st, sm in entries:
                 assert (sm["iterations"], sm["successful"]) == (so.iterations, so.num_successful), (row, name, nm, p)
@@ -696,6 +710,186 @@ def test_const_window_alone_is_bitwise_the_window_among_other_masks():
     inside = _field_by_name(_run("A")["const32"])
     for nm in ALONE:
         s = alone["alone_" + nm]["solves"]
+        assert s[1]["digest"] == s[0]["digest"] == s[2]["digest"]
+        _, st, sm = inside[nm][0]
+        assert st is not None and s[0]["state"]["0"] == st, nm
+        sa = s[0]["summ"][0]
+        assert (sa["iterations"], sa["successful"]) == (sm["iterations"], sm["successful"]), nm
+
+
+# ---- every frame count from 2 to 11 (tests/frame_windows.py): the same rows, leg and IMU-only batches ----
+# Between forms. These windows have no prior, so FIELD_PRIOR's 1e-9 does not apply: the bound is ten times the largest difference from row A
+# measured on an MI355X over every row, size and window ("Every frame count"), and never above the 1e-8 that holds against the oracle.
+FRAMES_BETWEEN_MEASURED = {"frames": 3.04e-10, "vframes": 3.83e-10}   # (rows G, H and N: the three-stage solver)
+FRAMES_BETWEEN = {k: 1e-8 if v is None else min(1e-8, 10.0 * v) for k, v in FRAMES_BETWEEN_MEASURED.items()}
+
+
+@pytest.fixture(scope="module")
+def frames_oracle():
+    """The oracle's solve of every window of both sets, once: {name: (summary, state arrays, F, uploaded state arrays, indices of the
+    constant ones)}."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _paths_worker as P
+    import const_windows as CW
+    import frame_windows as FR
+    from cerberus_amd import synth
+    from oracle import oracle_py as O
+    cfg = synth.default_config()
+    ocfg = O.config_from(cfg)
+    out = {}
+    for name, w in list(FR.leg_set(cfg, ocfg).items()) + list(FR.vins_set(cfg, ocfg).items()):
+        init = w.clone_state()
+        s = O.solve_window(ocfg, w, O.default_opts(True, P.ITERS))
+        out[name] = (s, [a.copy() for a in w.state_arrays()], w.F, init, CW.constant_arrays(w))
+    return out
+
+
+def _frames(row, kind):
+    """(name, result) of a row's "frames" or "vframes" batches: one of 32, or row N's three sizes (the worker "Nframes")."""
+    return [(k, v) for k, v in _run("Nframes" if row == "N" else row).items() if k.startswith(kind)]
+
+
+def _frames_cases():
+    return [(r, "frames") for r in CONST_ROWS] + [(r, "vframes") for r in VINS_ROWS]
+
+
+def _frames_need(kind):
+    import frame_windows as FR
+    return list(FR.LEG if kind == "frames" else FR.VINS)
+
+
+@pytest.mark.parametrize("row,kind", _frames_cases())
+def test_frames_descriptor(row, kind):
+    """Each batch takes the row's forms (row N: the entry of its size), the first solve plain launches, the later ones replays, and is
+    placed as frame_windows.batch_of places it."""
+    import frame_windows as FR
+    got_keys = [k for k, _ in _frames(row, kind)]
+    assert got_keys == [kind + str(W) for W in (FRAMES_N_SIZES if row == "N" else [32])], got_keys
+    order = FR.LEG_ORDER if kind == "frames" else FR.VINS_ORDER
+    for name, res in _frames(row, kind):
+        # row J takes 23-column rows because of its td-estimating window; these batches hold none, so there it runs row A's forms
+        exp = EXPECT[str(res["W"])] if row == "N" else EXPECT["A" if row == "J" else row]
+        assert res["names"] == [order[p % len(order)] for p in range(res["W"])] and len(res["solves"]) == 3
+        for i, s in enumerate(res["solves"]):
+            got = dict(s["path"])
+            replay, wo = got.pop("replay"), got.pop("wave_order")
+            assert got == exp, (row, name, i, got)
+            assert replay == (i > 0 and row != "L"), (row, name, i)
+            assert wo == WAVE_ORDER.get(row, 1)
+
+
+def _check_absent_frames(row, batches, oracle):
+    """include/vilo_gpu.h, vilo_batch_download: the rows at and beyond n_frames of pose, speed_bias and leg_bias are not written; they come
+    back bytewise as uploaded. Returns the number of arrays compared."""
+    n = 0
+    for name, res in batches:
+        for nm, entries in _field_by_name(res).items():
+            _, _, F, init, _ = oracle[nm]
+            for p, st, _ in entries:
+                if st is None or F == 11:
+                    continue
+                for i in (0, 1, 2):
+                    a = np.asarray(st[i], float)
+                    assert a.shape == init[i].shape and a[F:].tobytes() == init[i][F:].tobytes(), (row, name, nm, p, "absent rows of state array %d" % i)
+                    assert np.abs(init[i][F:]).max() > 0   # (the generator's later frames: not zeros a memset would also leave)
+                    n += 1
+    return n
+
+
+def _frames_vs_row_A(row, kind, bound=None):
+    """{window: largest state difference from row A's batch of 32}; bound: equal decisions, the states and the final cost within it. The
+    costs along the way are printed, not held: after the first step an IMU-only window is still falling by orders of magnitude per step
+    (v9: 4.5e7, 2.1e4, 80.5), and there two forms' costs differ by 1.6e-8 (measured, row Itpar) where their states differ by 1.4e-10."""
+    ref = _field_by_name(_run("A")[kind + "32"])
+    worst = {}
+    for name, res in _frames(row, kind):
+        for nm, entries in _field_by_name(res).items():
+            _, st_a, sm_a = ref[nm][0]
+            for p, st, sm in entries:
+                if bound is not None:
+                    assert (sm["iterations"], sm["successful"]) == (sm_a["iterations"], sm_a["successful"]), (row, name, nm, p)
+                    np.testing.assert_allclose(sm["final_cost"], sm_a["final_cost"], rtol=bound)
+                    worst["cost trace"] = max(worst.get("cost trace", 0.0), float(np.abs(np.array(sm["cost_trace"]) / np.array(sm_a["cost_trace"]) - 1).max()))
+                if st is not None:
+                    e = _rel_states(st, st_a)   # (all 11 rows: the absent frames' are the uploaded ones in both)
+                    worst[nm] = max(worst.get(nm, 0.0), e)
+                    if bound is not None:
+                        assert e < bound, (row, name, nm, p, e)
+    return worst
+
+
+@pytest.mark.parametrize("row,kind", _frames_cases())
+def test_frames_windows_against_the_oracle(row, kind, frames_oracle):
+    """Every window of the set at every kept position: the oracle's decisions, cost 1e-8, states 1e-8; one window, one answer wherever it
+    sits among other frame counts; replays bitwise the plain launches; constant blocks and the absent frames' rows bitwise the uploaded
+    ones. Positions: the leg set has 16 windows, so a batch of 32 holds each at two positions (three each would take 48: min_pos is 2 for
+    that batch alone); from 257 windows on, and in every IMU-only batch, each window sits at three positions or more, as the other
+    batches' windows do."""
+    batches = _frames(row, kind)
+    worst = worst_c = 0.0
+    for name, res in batches:
+        # 16 leg windows over a pattern of 32 positions: two positions each in a batch of 32, the last ones inside the last 33 of a longer
+        # one (a batch of 32 k + 1); the 7 IMU-only windows in turn
+        edge, min_pos = (7, 3) if kind == "vframes" else ((16, 2) if res["W"] == 32 else (33, 3))
+        e, c = _check_field_batches(row, [(name, res)], frames_oracle, need=_frames_need(kind), edge=edge, min_pos=min_pos)
+        worst, worst_c = max(worst, e), max(worst_c, c)
+    n = _check_constant_blocks(row, batches, frames_oracle)
+    assert n >= sum(len(frames_oracle[nm][4]) for nm in _frames_need(kind)) * 2
+    na = _check_absent_frames(row, batches, frames_oracle)
+    assert na >= 3 * 2 * sum(frames_oracle[nm][2] < 11 for nm in _frames_need(kind))
+    per_F = {}
+    for name, res in batches:
+        for nm, entries in _field_by_name(res).items():
+            so, ost, F = frames_oracle[nm][:3]
+            per_F[F] = max([per_F.get(F, 0.0)] + [_rel_states(st, ost, F) for _, st, _ in entries if st is not None])
+    vs_a = _frames_vs_row_A(row, kind)
+    print("MEASURED test_kernel_paths[%s] %s windows vs oracle: states %.2e, cost %.2e; per frame count %s; vs row A %.2e; %d constant blocks, %d absent-frame arrays bitwise; %.2f s of the row's worker"
+          % (row, kind, worst, worst_c, " ".join("%d: %.1e" % (F, per_F[F]) for F in sorted(per_F)), max(vs_a.values()), n, na,
+             sum(res["seconds"] for _, res in batches)))
+
+
+@pytest.mark.parametrize("row,kind", [(r, k) for r, k in _frames_cases() if r in ("B0", "E", "F", "G", "Itpar", "Iwalk", "N")])
+def test_frames_other_forms_agree_with_row_A_to_rounding(row, kind):
+    """Where no bitwise claim exists: every window within FRAMES_BETWEEN of row A's answer in states and final cost, equal decisions."""
+    worst = _frames_vs_row_A(row, kind, bound=FRAMES_BETWEEN[kind])
+    trace = worst.pop("cost trace")
+    print("MEASURED test_kernel_paths[%s] %s windows vs row A: states %.2e (bound %.1e), costs along the way %.1e; per window %s"
+          % (row, kind, max(worst.values()), FRAMES_BETWEEN[kind], trace, " ".join("%s %.1e" % kv for kv in worst.items())))
+
+
+@pytest.mark.parametrize("a,b,kind", [(a, b, "frames") for a, b in _PAIRS] + [(a, b, "vframes") for a, b in _PAIRS if a in VINS_ROWS and b in VINS_ROWS])
+def test_frames_bitwise_pairs(a, b, kind):
+    """The pairs of test_bitwise_pairs, on the batches of mixed frame counts."""
+    _same(a, b, key=kind + "32")
+
+
+def test_frames_frame_parallel_and_walking_forms_give_the_same_states():
+    _same("B1", "A", with_summaries=False, key="frames32")
+
+
+@pytest.mark.parametrize("kind", ["frames", "vframes"])
+def test_frames_same_forms_in_two_rows_are_bitwise(kind):
+    """Without a td-estimating window row J's batch takes row A's forms (test_frames_descriptor): bitwise on every window."""
+    assert _run("J")[kind + "32"]["names"] == _run("A")[kind + "32"]["names"]
+    _same("J", "A", key=kind + "32")
+
+
+@pytest.mark.parametrize("kind", ["frames", "vframes"])
+def test_frames_bench_kernel_set_at_small_and_full_size(kind):
+    """Row G's batch of 32 and the natural one of 2049: each window bitwise the same."""
+    g, n = _field_by_name(_run("G")[kind + "32"]), _field_by_name(_run("Nframes")[kind + "2049"])
+    assert set(g) == set(n)
+    for nm in g:
+        assert g[nm][0][1] is not None and g[nm][0][1:] == n[nm][0][1:], nm
+
+
+def test_frames_window_alone_is_bitwise_the_window_among_other_frame_counts():
+    """The windows of 2, 3 and 10 frames each in a batch of their own under row A's environment: states bitwise what they are inside
+    frames32, where the other windows of their aligned group of four run to 11 and 10 frames."""
+    alone = _run("Aframes_alone")
+    inside = _field_by_name(_run("A")["frames32"])
+    for nm in FRAMES_ALONE:
+        s = alone["falone_" + nm]["solves"]
         assert s[1]["digest"] == s[0]["digest"] == s[2]["digest"]
         _, st, sm = inside[nm][0]
         assert st is not None and s[0]["state"]["0"] == st, nm
