@@ -23,7 +23,7 @@ struct CallLayout {
 #ifdef __HIPCC__
 #include <optional>
 
-#include "solver_types.hpp"
+#include "batch_state.hpp"
 
 // The blocks of "the batch's records integrated again at x, on copies" (BatchCall::reintegrate). stages 1: records and contact-force
 // filters; 2: the prepared records and their flags too. Nothing is taken unless samples are in force on a leg batch.

@@ -651,7 +651,7 @@ static double *cov_chunk_view(char *p, int w0, size_t per_window) { return (doub
 // outputs (inverse-depth variance, point, point covariance) of k_landmark_covariance after each chunk, or null for no landmark pass.
 static int batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts &o, int want_poses, double *frames, double *poses, double *const *lm,
                             int32_t *status) {
-  BatchDev &bd = *vilo_batch_dev(bt);
+  BatchDev &bd = bt->d;
   const int W = bd.W, chunk = std::min(W, CV_CHUNK);
   const size_t n_lm = lm ? (size_t)bd.n_lm : 0;
   // the call's device memory: saved solver state | frames | poses | status | per-window scratch of one chunk | landmark variance, point, point covariance
@@ -699,7 +699,7 @@ static int batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts &
 
 extern "C" int vilo_batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, int32_t *status) {
   if (!ctx || !bt || !frames || !status) return VILO_ERR_BAD_ARG;
-  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_covariance") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  if (bt->mask.refuse(ctx, "vilo_batch_covariance") != VILO_OK) return VILO_ERR_UNSUPPORTED;
   vilo_cov_opts o;
   if (!cov_opts(opts, &o) || (o.want_poses && !poses)) {
     ctx->err = "vilo_batch_covariance: bad options (gauge, min_reciprocal_condition >= 0, want_poses needs a poses buffer)";
@@ -717,9 +717,9 @@ extern "C" int vilo_window_covariance(vilo_ctx *ctx, int n_windows, const vilo_w
 extern "C" int vilo_batch_landmark_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts *opts, double *frames, double *poses, double *inv_depth_var,
                                               double *points, double *point_cov, int32_t *status) {
   if (!ctx || !bt || !status) return VILO_ERR_BAD_ARG;
-  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_landmark_covariance") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  if (bt->mask.refuse(ctx, "vilo_batch_landmark_covariance") != VILO_OK) return VILO_ERR_UNSUPPORTED;
   vilo_cov_opts o;
-  if (!cov_opts(opts, &o) || (vilo_batch_dev(bt)->n_lm > 0 && (!inv_depth_var || !points || !point_cov))) {
+  if (!cov_opts(opts, &o) || (bt->d.n_lm > 0 && (!inv_depth_var || !points || !point_cov))) {
     ctx->err = "vilo_batch_landmark_covariance: bad arguments (gauge, min_reciprocal_condition >= 0, landmark output buffers)";
     return VILO_ERR_BAD_ARG;
   }

@@ -153,7 +153,7 @@ extern "C" int vilo_batch_dead_reckon(vilo_ctx *ctx, vilo_batch *bt, const vilo_
   if (!ctx || !bt) return VILO_ERR_BAD_ARG;
   vilo_dead_reckon_opts o;
   if (opts) o = *opts; else vilo_default_dead_reckon_opts(&o);
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  const BatchDev &bd = bt->d;
   const int W = bd.W;
   if (const char *what = vilo::dead_reckon_check(o, W, samples, offsets, state_out)) {
     ctx->err = what;

@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(FD_THREADS) k_failure_detection(BatchDev b, Fa
 extern "C" int vilo_batch_failure_detection(vilo_ctx *ctx, vilo_batch *bt, const int32_t *last_track_num, const double *last_pose,
                                             vilo_window_failure_record *records, double *values_out) {
   if (!ctx || !bt) return VILO_ERR_BAD_ARG;
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  const BatchDev &bd = bt->d;
   const int W = bd.W;
   if (W > 0 && !records) {
     ctx->err = "vilo_batch_failure_detection: records is NULL";

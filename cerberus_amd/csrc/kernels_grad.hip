@@ -200,8 +200,8 @@ __global__ void __launch_bounds__(GR_T) k_gradient(BatchDev b, vilo_window_gradi
 extern "C" int vilo_batch_gradient(vilo_ctx *ctx, vilo_batch *bt, vilo_window_gradient_record *windows, double *state_grad, double *state_diag,
                                    double *lm_grad, double *lm_diag) {
   if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
-  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_gradient") != VILO_OK) return VILO_ERR_UNSUPPORTED;
-  BatchDev &bd = *vilo_batch_dev(bt);
+  if (bt->mask.refuse(ctx, "vilo_batch_gradient") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  BatchDev &bd = bt->d;
   const int W = bd.W, n_lm = bd.n_lm;
   BatchCall call(ctx, bt, &vilo_ctx::last_grad_ms);
   // the call's device memory: saved solver state | window records | state gradient | state diagonal | landmark gradient | landmark diagonal

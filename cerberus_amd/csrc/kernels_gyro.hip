@@ -173,7 +173,7 @@ extern "C" int vilo_batch_gyro_bias_align(vilo_ctx *ctx, vilo_batch *bt, const v
   vilo_gyro_opts o;
   const int rc = gyro_check_opts(ctx, opts, &o);
   if (rc != VILO_OK) return rc;
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  const BatchDev &bd = bt->d;
   const int W = bd.W;
   if (W > 0 && !delta_bg) {
     ctx->err = "vilo_batch_gyro_bias_align: delta_bg is NULL";
@@ -181,8 +181,8 @@ extern "C" int vilo_batch_gyro_bias_align(vilo_ctx *ctx, vilo_batch *bt, const v
   }
   BatchCall call(ctx, bt, &vilo_ctx::last_gyro_ms);
   if (W == 0) return VILO_OK;
-  int leg = 1;
-  const void *recs = vilo_batch_records(bt, &leg);
+  const bool leg = bt->rec.leg;
+  const void *recs = bt->rec.d_pre;
   if (!recs) {
     ctx->err = "vilo_batch_gyro_bias_align: the batch has no preintegration records";
     return VILO_ERR_UNSUPPORTED;

@@ -1047,7 +1047,7 @@ extern "C" int vilo_batch_gauge_fix(vilo_ctx *ctx, vilo_batch *bt, const vilo_ga
     ctx->err = what;
     return VILO_ERR_BAD_ARG;
   }
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  const BatchDev &bd = bt->d;
   const int W = bd.W;
   BatchCall call(ctx, bt, &vilo_ctx::last_gauge_fix_ms);
   if (W == 0) return VILO_OK;
@@ -1128,8 +1128,8 @@ extern "C" int vilo_gauge_fix(vilo_ctx *ctx, int W, const vilo_window_state *bef
 static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *state,
                              const int *modes, vilo_prior *out) {
   int rc = VILO_OK;
-  if (vilo_batch_mask_stale(ctx, bt, "vilo_batch_marginalize") != VILO_OK) return VILO_ERR_HIP;
-  BatchDev &bd = *vilo_batch_dev(bt);
+  if (bt->mask.stale(ctx, "vilo_batch_marginalize") != VILO_OK) return VILO_ERR_HIP;
+  BatchDev &bd = bt->d;
   std::vector<MargWin> mws(W);
   std::vector<std::vector<int>> kept_ids(W), kept_cd(W), kept_gs(W), kept_soff(W);
   int max_l0 = 1;
@@ -1159,10 +1159,10 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
       M.has_imu = vilo_win_sum_dt(d, rf, 0) < 10.0 ? 1 : 0;
       if (M.has_imu)
         for (int kind = 0; kind < nkind; ++kind) { mark(kind * 16 + 0); mark(kind * 16 + 1); }
-      int L; const int *perm = vilo_batch_perm(bt, w, &L);
+      const int L = bt->lm.L[w], *perm = bt->lm.perm.data() + bt->lm.lm_off[w];
       // a masked landmark (vilo_batch_mask_landmarks) is the deleted one: in no residual block, so it marks no block and is not among
       // the eliminated landmarks (its E_l is 0: the inverse k_marginalize_lds takes of it would send the window to the eigen path)
-      const unsigned char *msk = vilo_batch_mask_host(bt, w);
+      const unsigned char *msk = bt->mask.host(bt->lm.lm_off[w]);
       for (int i = 0; i < L; ++i) {
         const int l = perm[i];
         if (d.lm_start_frame[l] != 0 || (msk && msk[i])) continue;
@@ -1412,7 +1412,7 @@ extern "C" int vilo_marginalize(vilo_ctx *ctx, int W, const vilo_window_desc *in
 // device state; `state` is the host copy of it (keep_block_data of the new prior). modes[w]: 0 MARGIN_OLD, 1 MARGIN_SECOND_NEW, < 0 skip.
 extern "C" int vilo_batch_marginalize(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_window_state *state, const int *modes,
                                       vilo_prior *out) {
-  if (!ctx || !bt || W <= 0 || W != vilo_batch_dev(bt)->W || !in || !state || !modes || !out) return VILO_ERR_BAD_ARG;
+  if (!ctx || !bt || W <= 0 || W != bt->d.W || !in || !state || !modes || !out) return VILO_ERR_BAD_ARG;
   for (int w = 0; w < W; ++w)
     if (modes[w] > 1) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
@@ -1439,7 +1439,7 @@ extern "C" int vilo_optimize_windows_resident(vilo_ctx *ctx, int W, const vilo_w
   const double t1 = now();
   rc = vilo_batch_solve(ctx, bt, opts);
   const double t2 = now();
-  if (rc == VILO_OK) rc = vilo_gauge_fix_batch(ctx, *vilo_batch_dev(bt));
+  if (rc == VILO_OK) rc = vilo_gauge_fix_batch(ctx, bt->d);
   if (rc == VILO_OK) rc = vilo_batch_download(ctx, bt, inout, summaries);
   const double t3 = now();
   if (rc == VILO_OK && marginalization_flag) {

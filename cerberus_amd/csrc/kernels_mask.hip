@@ -126,12 +126,12 @@ extern "C" int vilo_batch_mask_landmarks(vilo_ctx *ctx, vilo_batch *bt, const vi
   const int rc = mask_check_opts(ctx, opts, mask_in, &o);
   if (rc != VILO_OK) return rc;
   ctx->last_mask_ms = 0.0;
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  const BatchDev &bd = bt->d;
   const int W = bd.W, n_lm = bd.n_lm;
   if (n_lm <= 0 || bd.n_waves <= 0) return VILO_OK;   // nothing to mask: no array is touched
   VILO_HIP(hipSetDevice(ctx->device));
-  BatchMaskStore ms;
-  const int rs = vilo_batch_mask_store(ctx, bt, &ms);   // (batch data, allocated at the first call: before the scope opens)
+  BatchMask &ms = bt->mask;
+  const int rs = ms.store(ctx, bt->arena, bd);   // (batch data, allocated at the first call: before the scope opens)
   if (rs != VILO_OK) return rs;
   const bool outl = o.source == VILO_MASK_OUTLIER_FLAGS;
   BatchCall call(ctx, bt, &vilo_ctx::last_mask_ms);
@@ -141,7 +141,7 @@ extern "C" int vilo_batch_mask_landmarks(vilo_ctx *ctx, vilo_batch *bt, const vi
   const size_t o_d3 = call.lay.take<double>(3 * (size_t)n_lm, outl), o_i2 = call.lay.take<int>(2 * (size_t)n_lm, outl);
   if (call.begin() != VILO_OK) return VILO_ERR_HIP;
   MaskArgs a;
-  a.want = call.ptr<unsigned char>(o_want); a.orig = ms.flags_orig; a.mask = ms.mask;
+  a.want = call.ptr<unsigned char>(o_want); a.orig = ms.d_flags_orig; a.mask = ms.d_mask;
   a.out_mask = call.ptr<unsigned char>(o_mask); a.out_new = call.ptr<unsigned char>(o_new); a.n_obs = call.ptr<int>(o_nobs);
   a.source = o.source; a.combine = o.combine; a.flag_bits = o.flag_bits;
   if (o.source == VILO_MASK_GIVEN) VILO_HIP(hipMemcpyAsync(call.ptr<unsigned char>(o_want), mask_in, (size_t)n_lm, hipMemcpyHostToDevice, ctx->stream));
@@ -154,13 +154,14 @@ extern "C" int vilo_batch_mask_landmarks(vilo_ctx *ctx, vilo_batch *bt, const vi
   // From here on the device's flag image and mask may have been rewritten. The host mirror (device order: what the marginalisation's host
   // tables and the refusing calls read) follows only once the mask has come down: a HIP error in between leaves the mirror marked stale,
   // and every call that reads it fails until a mask call has gone through.
-  vilo_batch_mask_changed(bt, false);
+  ms.changed(false);
   VILO_HIP(call.finish());
   std::vector<unsigned char> now((size_t)n_lm);
   VILO_HIP(call.down(now.data(), a.out_mask, (size_t)n_lm));
+  const BatchLandmarks &lm = bt->lm;
   for (int w = 0; w < W; ++w)
-    for (int i = 0; i < ms.L[w]; ++i) ms.mask_host[ms.lm_off[w] + i] = now[ms.lm_off[w] + ms.perm[ms.lm_off[w] + i]];
-  vilo_batch_mask_changed(bt, true);
+    for (int i = 0; i < lm.L[w]; ++i) ms.mirror[lm.lm_off[w] + i] = now[lm.lm_off[w] + lm.perm[lm.lm_off[w] + i]];
+  ms.changed(true);
   if (mask_out) memcpy(mask_out, now.data(), (size_t)n_lm);
   VILO_HIP(call.down(records, call.ptr<char>(o_rec), sizeof(vilo_window_mask_record) * (size_t)W));
   return VILO_OK;

@@ -323,8 +323,8 @@ extern "C" int vilo_batch_frame_pose_pnp(vilo_ctx *ctx, vilo_batch *bt, const vi
   vilo_pnp_opts o;
   const int rc = pnp_check_opts(ctx, opts, &o);
   if (rc != VILO_OK) return rc;
-  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_frame_pose_pnp") != VILO_OK) return VILO_ERR_UNSUPPORTED;
-  BatchDev &bd = *vilo_batch_dev(bt);
+  if (bt->mask.refuse(ctx, "vilo_batch_frame_pose_pnp") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  BatchDev &bd = bt->d;
   const int W = bd.W;
   if (W > 0 && !pose) {
     ctx->err = "vilo_batch_frame_pose_pnp: pose is NULL";
@@ -333,7 +333,7 @@ extern "C" int vilo_batch_frame_pose_pnp(vilo_ctx *ctx, vilo_batch *bt, const vi
   BatchCall call(ctx, bt, &vilo_ctx::last_pnp_ms);
   if (W == 0) return VILO_OK;
   // a lane's points beyond its first live in LDS: one slot per further trip over the window's packed waves
-  const int trips = (vilo_batch_max_window_waves(bt) + PNP_WAVES - 1) / PNP_WAVES;
+  const int trips = (bt->lm.max_win_waves + PNP_WAVES - 1) / PNP_WAVES;
   if (trips > PNP_MAX_TRIPS) {
     ctx->err = "vilo_batch_frame_pose_pnp: a window has more packed waves than VILO_NUM_OF_F landmarks can make";
     return VILO_ERR_UNSUPPORTED;

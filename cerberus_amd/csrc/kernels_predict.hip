@@ -183,8 +183,8 @@ extern "C" int vilo_batch_predict_next_frame(vilo_ctx *ctx, vilo_batch *bt, cons
   vilo_predict_opts o;
   const int rc = predict_check_opts(ctx, opts, next_pose_in, &o);
   if (rc != VILO_OK) return rc;
-  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_predict_next_frame") != VILO_OK) return VILO_ERR_UNSUPPORTED;
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  if (bt->mask.refuse(ctx, "vilo_batch_predict_next_frame") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  const BatchDev &bd = bt->d;
   const int W = bd.W, n_lm = bd.n_lm;
   if (n_lm > 0 && !pts_cam) {
     ctx->err = "vilo_batch_predict_next_frame: pts_cam is NULL";

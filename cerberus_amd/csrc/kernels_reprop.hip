@@ -143,7 +143,7 @@ extern "C" int vilo_batch_repropagate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
   vilo_reprop_opts o;
   int rc = reprop_check_opts(ctx, opts, samples, offsets, lin, mask, &o);
   if (rc != VILO_OK) return rc;
-  BatchDev &bd = *vilo_batch_dev(bt);
+  BatchDev &bd = bt->d;
   const int W = bd.W;
   const size_t NF = (size_t)W * 10;
   if (offsets) {
@@ -156,12 +156,12 @@ extern "C" int vilo_batch_repropagate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
   }
   BatchCall call(ctx, bt, &vilo_ctx::last_reprop_ms);
   if (W == 0) return VILO_OK;
-  const BatchRecordsRW R = vilo_batch_records_rw(bt);
+  BatchRecords &R = bt->rec;
   if (!R.d_pre) {
     ctx->err = "vilo_batch_repropagate: the batch has no preintegration records on the device";
     return VILO_ERR_UNSUPPORTED;
   }
-  if (R.pool) {
+  if (R.from_pool) {
     ctx->err = "vilo_batch_repropagate: the batch's records were gathered from a vilo_preint_streams pool, whose objects own them";
     return VILO_ERR_UNSUPPORTED;
   }
@@ -169,7 +169,7 @@ extern "C" int vilo_batch_repropagate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
     ctx->err = "vilo_batch_repropagate: vilo_batch_set_samples is in force, the solve integrates every interval again at every point anyway (switch it off first)";
     return VILO_ERR_UNSUPPORTED;
   }
-  const bool wr = o.write != 0, leg = R.leg != 0;
+  const bool wr = o.write != 0, leg = R.leg;
   const int nl = leg ? 10 : 6;
   const size_t rec_bytes = leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu), rec_dbl = rec_bytes / sizeof(double);
   const size_t ns = wr ? (size_t)offsets[NF] : 0, tps = vilo_preint_terms_per_sample(R.leg);
@@ -214,7 +214,7 @@ extern "C" int vilo_batch_repropagate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
       hipLaunchKernelGGL(k_reprop_commit, dim3((unsigned)NF), dim3(RP_THREADS), 0, ctx->stream, (int)NF, (int)(sizeof(PreintPrepared) / sizeof(double)), (const double *)bs.prep,
                          (double *)bd.prep, (const int *)a.go, (int *)nullptr);
     }
-    if (vilo_batch_records_replaced(ctx, bt) != VILO_OK) return VILO_ERR_HIP;
+    if (R.replaced(ctx, bd) != VILO_OK) return VILO_ERR_HIP;
   }
   VILO_HIP(call.finish());
   std::vector<vilo_interval_reprop_record> host(NF);
@@ -223,7 +223,7 @@ extern "C" int vilo_batch_repropagate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
   if (wr) {
     bool all_live = true;
     for (const vilo_interval_reprop_record &r : host) all_live = all_live && (r.status == VILO_REPROP_OK || r.status == VILO_REPROP_NO_INTERVAL);
-    vilo_batch_records_full(bt, all_live);
+    R.full(all_live);
   }
   return VILO_OK;
 }
@@ -243,7 +243,7 @@ extern "C" int vilo_window_repropagate(vilo_ctx *ctx, int n_windows, const vilo_
     if (records) memcpy(records, rec.data(), sizeof(vilo_interval_reprop_record) * NF);
     if (!o.write) return rc;
     // the records this call wrote, and only those (the others are on the device in the form they went up in), into the caller's arrays
-    const BatchRecordsRW R = vilo_batch_records_rw(bt);
+    const BatchRecords &R = bt->rec;
     const size_t rec_bytes = R.leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu);
     for (size_t f = 0; f < NF; ++f) {
       if (rec[f].status != VILO_REPROP_OK || !rec[f].selected) continue;

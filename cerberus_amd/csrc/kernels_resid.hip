@@ -263,7 +263,7 @@ extern "C" void vilo_default_residual_opts(vilo_residual_opts *o) {
 extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_residual_opts *opts, vilo_window_residual *windows, double *lm_cost,
                                     double *lm_reproj_px, uint8_t *lm_flags, double *obs_residuals, double *imu_residuals) {
   if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
-  if (vilo_batch_mask_stale(ctx, bt, "vilo_batch_residuals") != VILO_OK) return VILO_ERR_HIP;
+  if (bt->mask.stale(ctx, "vilo_batch_residuals") != VILO_OK) return VILO_ERR_HIP;
   vilo_residual_opts o;
   if (opts) o = *opts; else vilo_default_residual_opts(&o);
   if (!isfinite(o.outlier_threshold_px) || !(o.outlier_threshold_px >= 0.0)) {
@@ -271,11 +271,11 @@ extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_re
     return VILO_ERR_BAD_ARG;
   }
   VILO_HIP(hipSetDevice(ctx->device));
-  const BatchDev &bd = *vilo_batch_dev(bt);
+  const BatchDev &bd = bt->d;
   const int W = bd.W, n_lm = bd.n_lm, NF = W * 10;
   const int *obs_row = nullptr;
-  int n_rows = 0;
-  const int rc = vilo_batch_obs_rows(ctx, bt, &obs_row, &n_rows);   // (batch data, uploaded at the first call: before the scope opens)
+  const int n_rows = bt->lm.n_obs_rows;
+  const int rc = bt->lm.obs_rows(ctx, bt->arena, &obs_row);   // (batch data, uploaded at the first call: before the scope opens)
   if (rc != VILO_OK) return rc;
   BatchCall call(ctx, bt, &vilo_ctx::last_resid_ms);
   // the call's device memory: window records | per-landmark values | interval costs, residuals | observation residuals | re-integration copies
@@ -293,7 +293,7 @@ extern "C" int vilo_batch_residuals(vilo_ctx *ctx, vilo_batch *bt, const vilo_re
   const double sq = ctx->cfg.focal_length / 1.5, ha = ctx->cfg.huber_delta, gn = ctx->cfg.g_norm;
   VILO_HIP(call.start());
   // a masked landmark (vilo_batch_mask_landmarks) has no valid observation: k_resid_landmarks writes none of its rows, which come back NaN
-  if (d_or && vilo_batch_mask_host(bt, 0)) VILO_HIP(hipMemsetAsync(d_or, 0xFF, sizeof(double) * 4 * (size_t)n_rows, ctx->stream));
+  if (d_or && bt->mask.n_masked > 0) VILO_HIP(hipMemsetAsync(d_or, 0xFF, sizeof(double) * 4 * (size_t)n_rows, ctx->stream));
   BatchDev b = bd;
   if (call.reintegrate(b, rp) != VILO_OK) return VILO_ERR_HIP;
   if (bd.n_waves > 0)

@@ -204,8 +204,8 @@ extern "C" int vilo_batch_triangulate(vilo_ctx *ctx, vilo_batch *bt, const vilo_
   vilo_triangulate_opts o;
   int rc = tri_check_opts(ctx, opts, mask, &o);
   if (rc != VILO_OK) return rc;
-  if (vilo_batch_refuse_masked(ctx, bt, "vilo_batch_triangulate") != VILO_OK) return VILO_ERR_UNSUPPORTED;
-  BatchDev &bd = *vilo_batch_dev(bt);
+  if (bt->mask.refuse(ctx, "vilo_batch_triangulate") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  BatchDev &bd = bt->d;
   const int n_lm = bd.n_lm;
   if (n_lm > 0 && !depth) {
     ctx->err = "vilo_batch_triangulate: depth is NULL";

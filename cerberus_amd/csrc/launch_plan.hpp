@@ -1,6 +1,6 @@
 // Which kernels a batch runs: the tuning switches, and the one function that turns a batch's shape into the forms of a Gauss-Newton
-// iteration. Plain C++17, no HIP: vilo_batch.hip asks it at create (frame-parallel form or not), for the lane rule and for the key of a
-// captured launch sequence; vilo_solve_launch executes the plan it returns; tests/host_check/launch_plan_check.cpp pins it on a CPU.
+// iteration. Plain C++17, no HIP: vilo_batch.hip asks it at create (frame-parallel form or not) and for the key of a captured
+// launch sequence, host_pipeline.hip for the lane rule; vilo_solve_launch executes the plan it returns; tests/host_check/launch_plan_check.cpp pins it on a CPU.
 // The codes are those of vilo_debug_batch_path (include/vilo_gpu.h).
 #pragma once
 #include <cstddef>

@@ -5,67 +5,12 @@
 //   double2vector  estimator.cpp:903-1003  (gauge fix: vilo_gauge_fix)
 #include <algorithm>
 #include <chrono>
-#include <cmath>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
 
 #include "batch_pack.hpp"
-#include "solver_types.hpp"
-#include "worker_pool.hpp"
-
-struct vilo_batch {
-  BatchDev d;
-  std::vector<std::pair<void *, size_t>> chunks_dev;   // arena chunks (from / back to ctx->pool_free)
-  char *cur = nullptr;
-  size_t cur_left = 0;
-  size_t used = 0;                  // bytes handed out of the chunks (vilo_debug_batch_device_bytes)
-  std::vector<int> lm_off_host;     // per window
-  std::vector<int> perm_host;       // device order -> original landmark index (per window, concatenated)
-  std::vector<int> L_host;
-  int max_win_waves = 0;            // most packed visual waves of one window (vilo_batch_frame_pose_pnp sizes its LDS by it)
-  int W;
-  // the launch sequence of one solve (5 + 7 x max_num_iterations kernels) as a hipGraph, captured when the same resident batch is
-  // solved a second time with the same options (vilo_batch_reset + vilo_batch_solve loops: replays, Monte-Carlo seeds, bench)
-  hipGraphExec_t gexec = nullptr;
-  vilo_solve_opts gopts;
-  int g_sqrt_info_mode = 0, g_rp_on = 0;   // context / batch state the captured launch sequence depends on (part of the cache key)
-  vilo::SolvePlan gplan;                   // the forms it was captured with
-  double g_initial_mu = 1e-8;
-  // re-propagation buffers (vilo_batch_set_samples): reused by later calls while they are large enough (the arena cannot free)
-  vilo_sample *rp_s = nullptr; int *rp_o = nullptr; double *rp_t = nullptr; size_t rp_cap = 0;
-  double *rp_ff = nullptr;          // [W * 10][VILO_FF_N]
-  double *rp_ff0 = nullptr;         // the same right after the objects' first integration: what vilo_batch_reset brings back (contact_sensor_type 2)
-  vilo_preint *rp_orig = nullptr;   // [W * 10] the records as created, kept from the first vilo_batch_set_samples on
-  int n_solves = 0;
-  bool graph_failed = false;
-  int32_t path[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // vilo_debug_batch_path: the plan of the last solve, replay or not, the wave order
-  // what vilo_batch_prepare needs to run the sqrt_info preparation again (the reference does it in every IMULegFactor::Evaluate)
-  void *d_pre = nullptr;
-  bool leg = true;
-  // where the records came from (vilo_batch_repropagate): rec_pool: gathered from a vilo_preint_streams pool; rec_form: 0 full records,
-  // 1 the compact upload expanded (below), 2 that after a re-propagation which left some of them in that form
-  bool rec_pool = false;
-  int rec_form = 0;
-  int *d_prep_bad = nullptr;  // [W * 10] covariance of this record not positive definite
-  // vilo_batch_residuals (kernels_resid.hip): the caller's observation row of each landmark's first observation (device order, rows
-  // concatenated by window: a window without landmarks has none), uploaded into the arena at the first call
-  std::vector<int> obs_row_host;
-  int n_obs_rows = 0;
-  int *d_obs_row = nullptr;
-  // vilo_batch_mask_landmarks (kernels_mask.hip): the flag image as uploaded and the mask in force (device order), allocated in the arena at
-  // the first mask call; the mask's host mirror (device order; what the marginalisation's host tables read) and how many landmarks it holds
-  size_t flags_total = 0;
-  unsigned char *d_flags_orig = nullptr, *d_mask = nullptr;
-  std::vector<unsigned char> mask_host;
-  int n_masked = 0;
-  bool mask_stale = false;   // a mask call failed after its kernels were launched: the mirror may not be the device's mask
-};
+#include "batch_state.hpp"
 
 namespace {
 
-// win_bad[w] = any live interval of window w whose covariance had no sqrt_info (prep_bad, written by the preparation)
 // What the solver reads of an IMULegIntegrationBase record (vilo_preint, 1955 doubles): the 33 scalars, the bias columns 21 .. 30 of the
 // Jacobian's rows 0 .. 20 (PreintHead, factors.hpp) and ONE triangle of the covariance (k_prepare_preint's Cholesky of the index-reversed
 // matrix takes the source's upper triangle; the literal inverse() route reads all of it and keeps the full upload). Host windows bring
@@ -100,6 +45,7 @@ __global__ void __launch_bounds__(256) k_expand_records(int n, const double *com
   }
 }
 
+// win_bad[w] = any live interval of window w whose covariance had no sqrt_info (prep_bad, written by the preparation)
 __global__ void k_fold_win_bad(int W, const int *prep_bad, const unsigned char *imu_skip, int *win_bad) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= W) return;
@@ -108,47 +54,6 @@ __global__ void k_fold_win_bad(int W, const int *prep_bad, const unsigned char *
   win_bad[w] = bad;
 }
 
-// bump allocation out of 64 MB (or larger) arena chunks; chunks are recycled through the context's free list
-int dev_alloc_bytes(vilo_ctx *ctx, vilo_batch *bt, void **p, size_t bytes) {
-  *p = nullptr;
-  bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-  if (bt->cur_left < bytes) {
-    const size_t want = std::max<size_t>(bytes, (size_t)64 << 20);
-    int best = -1;
-    for (int i = 0; i < (int)ctx->pool_free.size(); ++i)
-      if (ctx->pool_free[i].second >= bytes && (best < 0 || ctx->pool_free[i].second < ctx->pool_free[best].second)) best = i;
-    std::pair<void *, size_t> ch;
-    if (best >= 0) {
-      ch = ctx->pool_free[best];
-      ctx->pool_free.erase(ctx->pool_free.begin() + best);
-    } else {
-      void *q = nullptr;
-      VILO_HIP(hipMalloc(&q, want));
-      ch = {q, want};
-    }
-    bt->chunks_dev.push_back(ch);
-    bt->cur = (char *)ch.first; bt->cur_left = ch.second;
-  }
-  *p = bt->cur;
-  bt->cur += bytes; bt->cur_left -= bytes; bt->used += bytes;
-  return VILO_OK;
-}
-template <class T>
-int dev_alloc(vilo_ctx *ctx, vilo_batch *bt, T **p, size_t n) {
-  void *q = nullptr;
-  int rc = dev_alloc_bytes(ctx, bt, &q, std::max<size_t>(n, 1) * sizeof(T));
-  *p = (T *)q;
-  return rc;
-}
-template <class T>
-int dev_upload_raw(vilo_ctx *ctx, vilo_batch *bt, T **p, const T *h, size_t n) {
-  int rc = dev_alloc(ctx, bt, p, n);
-  if (rc != VILO_OK) return rc;
-  if (n) VILO_HIP(hipMemcpy(*p, h, n * sizeof(T), hipMemcpyHostToDevice));
-  return VILO_OK;
-}
-template <class T>
-int dev_upload(vilo_ctx *ctx, vilo_batch *bt, T **p, const std::vector<T> &h) { return dev_upload_raw(ctx, bt, p, h.data(), h.size()); }
 // The tables of a batch are a dozen and a half small arrays: uploaded one by one, a window's batch pays a blocking copy for each (what a
 // frame-by-frame caller pays per image). They are laid out in ONE host blob at the offsets of one device allocation and go up in one copy;
 // the device pointers are set when the blob is flushed (nothing may read them before). Arrays of 256 KB and more keep their own copy
@@ -158,9 +63,9 @@ struct UploadBlob {
   std::vector<char> host;
   std::vector<Item> items;
   template <class T>
-  int add(vilo_ctx *ctx, vilo_batch *bt, T **p, const T *h, size_t n) {
+  int add(vilo_ctx *ctx, BatchArena &arena, T **p, const T *h, size_t n) {
     const size_t bytes = n * sizeof(T);
-    if (bytes >= ((size_t)256 << 10)) return dev_upload_raw(ctx, bt, p, h, n);
+    if (bytes >= ((size_t)256 << 10)) return arena.upload_raw(ctx, p, h, n);
     const size_t off = (host.size() + 255) & ~(size_t)255;
     host.resize(off + std::max<size_t>(bytes, sizeof(T)));
     if (bytes) memcpy(host.data() + off, h, bytes);
@@ -168,10 +73,10 @@ struct UploadBlob {
     items.push_back({(void **)p, off});
     return VILO_OK;
   }
-  int flush(vilo_ctx *ctx, vilo_batch *bt) {
+  int flush(vilo_ctx *ctx, BatchArena &arena) {
     if (items.empty()) return VILO_OK;
     void *base = nullptr;
-    int rc = dev_alloc_bytes(ctx, bt, &base, host.size());
+    int rc = arena.alloc_bytes(ctx, &base, host.size());
     if (rc != VILO_OK) return rc;
     VILO_HIP(hipMemcpy(base, host.data(), host.size(), hipMemcpyHostToDevice));
     for (const Item &it : items) *it.pp = (char *)base + it.off;
@@ -234,85 +139,93 @@ __global__ void __launch_bounds__(256) k_prior_pack(int W, const WinMeta *win, c
 
 }  // namespace
 
-BatchDev *vilo_batch_dev(vilo_batch *bt) { return &bt->d; }
-const int *vilo_batch_perm(vilo_batch *bt, int win, int *L) {
-  *L = bt->L_host[win];
-  return bt->perm_host.data() + bt->lm_off_host[win];
+// ---- the parts of a batch (batch_state.hpp) ----
+int BatchArena::alloc_bytes(vilo_ctx *ctx, void **p, size_t bytes) {
+  *p = nullptr;
+  bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+  if (cur_left < bytes) {
+    const size_t want = std::max<size_t>(bytes, (size_t)64 << 20);
+    int best = -1;
+    for (int i = 0; i < (int)ctx->pool_free.size(); ++i)
+      if (ctx->pool_free[i].second >= bytes && (best < 0 || ctx->pool_free[i].second < ctx->pool_free[best].second)) best = i;
+    std::pair<void *, size_t> ch;
+    if (best >= 0) {
+      ch = ctx->pool_free[best];
+      ctx->pool_free.erase(ctx->pool_free.begin() + best);
+    } else {
+      void *q = nullptr;
+      VILO_HIP(hipMalloc(&q, want));
+      ch = {q, want};
+    }
+    chunks.push_back(ch);
+    cur = (char *)ch.first; cur_left = ch.second;
+  }
+  *p = cur;
+  cur += bytes; cur_left -= bytes; used += bytes;
+  return VILO_OK;
 }
 
-ArenaScope::ArenaScope(vilo_ctx *c, vilo_batch *b) : ctx(c), bt(b), n_chunks(b->chunks_dev.size()), cur_left(b->cur_left), used(b->used), cur(b->cur) {}
+ArenaScope::ArenaScope(vilo_ctx *c, vilo_batch *b) : ctx(c), bt(b), n_chunks(b->arena.chunks.size()), cur_left(b->arena.cur_left), used(b->arena.used), cur(b->arena.cur) {}
 ArenaScope::~ArenaScope() {
   (void)hipStreamSynchronize(ctx->stream);   // nothing of this call may still run when its memory is handed on
-  for (size_t i = n_chunks; i < bt->chunks_dev.size(); ++i) ctx->pool_free.push_back(bt->chunks_dev[i]);
-  bt->chunks_dev.resize(n_chunks);
-  bt->cur = cur; bt->cur_left = cur_left; bt->used = used;
+  BatchArena &a = bt->arena;
+  for (size_t i = n_chunks; i < a.chunks.size(); ++i) ctx->pool_free.push_back(a.chunks[i]);
+  a.chunks.resize(n_chunks);
+  a.cur = cur; a.cur_left = cur_left; a.used = used;
 }
 void *ArenaScope::alloc(size_t bytes) {
   void *p = nullptr;
-  return dev_alloc_bytes(ctx, bt, &p, bytes) == VILO_OK ? p : nullptr;
+  return bt->arena.alloc_bytes(ctx, &p, bytes) == VILO_OK ? p : nullptr;
 }
 
-int vilo_batch_max_window_waves(vilo_batch *bt) { return bt->max_win_waves; }
-const void *vilo_batch_records(vilo_batch *bt, int *leg) { *leg = bt->leg; return bt->d_pre; }
-BatchRecordsRW vilo_batch_records_rw(vilo_batch *bt) { return {bt->d_pre, bt->leg ? 1 : 0, bt->rec_pool ? 1 : 0, bt->rec_form}; }
-void vilo_batch_records_full(vilo_batch *bt, bool all_live) { if (bt->rec_form) bt->rec_form = all_live ? 0 : 2; }
-int vilo_batch_records_replaced(vilo_ctx *ctx, vilo_batch *bt) {
-  const int W = bt->W;
-  // (samples were in force once and may be again: the records vilo_batch_set_samples(NULL) brings back are these from here on)
-  if (bt->rp_orig) VILO_HIP(hipMemcpyAsync(bt->rp_orig, bt->d_pre, sizeof(vilo_preint) * (size_t)W * 10, hipMemcpyDeviceToDevice, ctx->stream));
-  if (!bt->d.win_bad) return VILO_OK;
-  hipLaunchKernelGGL(k_fold_win_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bt->d_prep_bad, bt->d.imu_skip, bt->d.win_bad);
+int BatchLandmarks::obs_rows(vilo_ctx *ctx, BatchArena &arena, const int **rows) {
+  if (!d_obs_row) {
+    int *d = nullptr;
+    int rc = arena.upload(ctx, &d, obs_row);
+    if (rc != VILO_OK) return rc;
+    d_obs_row = d;
+  }
+  *rows = d_obs_row;
+  return VILO_OK;
+}
+
+int BatchRecords::fold_win_bad(vilo_ctx *ctx, BatchDev &d) {
+  hipLaunchKernelGGL(k_fold_win_bad, dim3((d.W + 255) / 256), dim3(256), 0, ctx->stream, d.W, d_prep_bad, d.imu_skip, d.win_bad);
   VILO_HIP(hipGetLastError());
   return VILO_OK;
 }
-
-// vilo_batch_residuals: the landmarks' observation rows on the device (batch data, uploaded at the first call: not in a call's scope)
-int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows) {
-  if (!bt->d_obs_row) {
-    int *d = nullptr;
-    int rc = dev_upload(ctx, bt, &d, bt->obs_row_host);
-    if (rc != VILO_OK) return rc;
-    bt->d_obs_row = d;
-  }
-  *rows = bt->d_obs_row;
-  *n_rows = bt->n_obs_rows;
-  return VILO_OK;
+int BatchRecords::replaced(vilo_ctx *ctx, BatchDev &d) {
+  // (samples were in force once and may be again: the records vilo_batch_set_samples(NULL) brings back are these from here on)
+  if (orig) VILO_HIP(hipMemcpyAsync(orig, d_pre, sizeof(vilo_preint) * (size_t)d.W * 10, hipMemcpyDeviceToDevice, ctx->stream));
+  return d.win_bad ? fold_win_bad(ctx, d) : VILO_OK;
 }
 
-// vilo_batch_mask_landmarks: the second copy of the flag bytes and the mask (batch data, allocated at the first call: not in a call's scope)
-int vilo_batch_mask_store(vilo_ctx *ctx, vilo_batch *bt, BatchMaskStore *out) {
-  if (!bt->d_mask) {
-    // one block (flag copy | mask): either both exist or neither
-    const size_t mask_at = (std::max<size_t>(bt->flags_total, 1) + 255) & ~(size_t)255;
-    unsigned char *fo = nullptr;
-    const int rc = dev_alloc(ctx, bt, &fo, mask_at + std::max<size_t>((size_t)bt->d.n_lm, 1));
-    if (rc != VILO_OK) return rc;
-    unsigned char *mk = fo + mask_at;
-    VILO_HIP(hipMemcpyAsync(fo, bt->d.flags, std::max<size_t>(bt->flags_total, 1), hipMemcpyDeviceToDevice, ctx->stream));
-    VILO_HIP(hipMemsetAsync(mk, 0, std::max<size_t>((size_t)bt->d.n_lm, 1), ctx->stream));
-    bt->d_flags_orig = fo; bt->d_mask = mk;
-    bt->mask_host.assign((size_t)bt->d.n_lm, 0);
-  }
-  out->flags_orig = bt->d_flags_orig; out->mask = bt->d_mask; out->mask_host = bt->mask_host.data(); out->lm_off = bt->lm_off_host.data();
-  out->perm = bt->perm_host.data(); out->L = bt->L_host.data();
+int BatchMask::store(vilo_ctx *ctx, BatchArena &arena, const BatchDev &d) {
+  if (d_mask) return VILO_OK;
+  // one block (flag copy | mask): either both exist or neither
+  const size_t mask_at = (std::max<size_t>(flags_total, 1) + 255) & ~(size_t)255;
+  unsigned char *fo = nullptr;
+  const int rc = arena.alloc(ctx, &fo, mask_at + std::max<size_t>((size_t)d.n_lm, 1));
+  if (rc != VILO_OK) return rc;
+  unsigned char *mk = fo + mask_at;
+  VILO_HIP(hipMemcpyAsync(fo, d.flags, std::max<size_t>(flags_total, 1), hipMemcpyDeviceToDevice, ctx->stream));
+  VILO_HIP(hipMemsetAsync(mk, 0, std::max<size_t>((size_t)d.n_lm, 1), ctx->stream));
+  d_flags_orig = fo; d_mask = mk;
+  mirror.assign((size_t)d.n_lm, 0);
   return VILO_OK;
 }
-void vilo_batch_mask_changed(vilo_batch *bt, bool mirror_valid) {
-  bt->mask_stale = !mirror_valid;
-  if (!mirror_valid) return;
-  int n = 0;
-  for (unsigned char m : bt->mask_host) n += m ? 1 : 0;
-  bt->n_masked = n;
+void BatchMask::changed(bool mirror_valid) {
+  mirror_stale = !mirror_valid;
+  if (mirror_valid) n_masked = (int)(mirror.size() - std::count(mirror.begin(), mirror.end(), 0));
 }
-const unsigned char *vilo_batch_mask_host(vilo_batch *bt, int win) { return bt->n_masked > 0 ? bt->mask_host.data() + bt->lm_off_host[win] : nullptr; }
-int vilo_batch_mask_stale(vilo_ctx *ctx, vilo_batch *bt, const char *call) {
-  if (!bt->mask_stale) return VILO_OK;
+int BatchMask::stale(vilo_ctx *ctx, const char *call) const {
+  if (!mirror_stale) return VILO_OK;
   ctx->err = std::string(call) + ": the last vilo_batch_mask_landmarks on this batch failed after its kernels were launched, the mask in force is not known; run a mask call (VILO_MASK_CLEAR, or the mask wanted) first";
   return VILO_ERR_HIP;
 }
-int vilo_batch_refuse_masked(vilo_ctx *ctx, vilo_batch *bt, const char *call) {
-  if (bt->mask_stale) { (void)vilo_batch_mask_stale(ctx, bt, call); return VILO_ERR_UNSUPPORTED; }
-  if (bt->n_masked <= 0) return VILO_OK;
+int BatchMask::refuse(vilo_ctx *ctx, const char *call) const {
+  if (mirror_stale) { (void)stale(ctx, call); return VILO_ERR_UNSUPPORTED; }
+  if (n_masked <= 0) return VILO_OK;
   ctx->err = std::string(call) + ": a landmark mask is in force on this batch (vilo_batch_mask_landmarks) and this call does not honour it; clear the mask first";
   return VILO_ERR_UNSUPPORTED;
 }
@@ -320,20 +233,20 @@ int vilo_batch_refuse_masked(vilo_ctx *ctx, vilo_batch *bt, const char *call) {
 extern "C" int vilo_debug_batch_device_bytes(const vilo_batch *bt, size_t out[2]) {
   if (!bt || !out) return VILO_ERR_BAD_ARG;
   out[0] = 0;
-  for (const auto &c : bt->chunks_dev) out[0] += c.second;
-  out[1] = bt->used;
+  for (const auto &c : bt->arena.chunks) out[0] += c.second;
+  out[1] = bt->arena.used;
   return VILO_OK;
 }
 
 extern "C" void vilo_batch_destroy(vilo_ctx *ctx, vilo_batch *bt) {
   if (!bt) return;
   if (ctx) (void)hipSetDevice(ctx->device);
-  if (bt->gexec) (void)hipGraphExecDestroy(bt->gexec);
+  bt->graph.drop();
   if (ctx) {
     (void)hipStreamSynchronize(ctx->stream);   // nothing of this batch may still be running when its memory is handed on
-    for (auto &c : bt->chunks_dev) ctx->pool_free.push_back(c);
+    for (auto &c : bt->arena.chunks) ctx->pool_free.push_back(c);
   } else {
-    for (auto &c : bt->chunks_dev) (void)hipFree(c.first);
+    for (auto &c : bt->arena.chunks) (void)hipFree(c.first);
   }
   delete bt;
 }
@@ -393,15 +306,15 @@ int create_device_buffers(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h) {
   const bool CLEAR = true;
   UploadBlob blob;
   int rc = VILO_OK;
-  auto up = [&](auto **p, const auto *src, size_t n) { if (rc == VILO_OK) rc = blob.add(ctx, bt, p, src, n); };
+  auto up = [&](auto **p, const auto *src, size_t n) { if (rc == VILO_OK) rc = blob.add(ctx, bt->arena, p, src, n); };
   auto upv = [&](auto **p, const auto &v) { up(p, v.data(), v.size()); };
   auto dev = [&](auto **p, size_t n, bool clear = false) {
-    if (rc == VILO_OK) rc = dev_alloc(ctx, bt, p, n);
+    if (rc == VILO_OK) rc = bt->arena.alloc(ctx, p, n);
     if (rc == VILO_OK && clear && hipMemsetAsync(*p, 0, sizeof(**p) * std::max<size_t>(n, 1), ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
   };
   upv(&D.win, P.wins); upv(&D.chunk, P.chunks); upv(&D.wave, P.waves); upv(&D.wave_order, P.wave_order);
   up(&D.obs, h.obs, P.obs_total); up(&D.flags, h.flags, P.flags_total);
-  upv(&D.x0, h.x0); upv(&D.lam0, P.lam0); upv(&D.lm_s, P.lm_s); upv(&D.lm_perm, bt->perm_host);
+  upv(&D.x0, h.x0); upv(&D.lam0, P.lam0); upv(&D.lm_s, P.lm_s); upv(&D.lm_perm, bt->lm.perm);
   dev(&D.x, W * XSTRIDE); dev(&D.xc, W * XSTRIDE);
   dev(&D.lam, lm); dev(&D.lamc, lm); dev(&D.lm_E, lm); dev(&D.lm_gbuf[0], lm); dev(&D.lm_gbuf[1], lm);
   dev(&D.lm_dh2, lm); dev(&D.lm_y, lm); dev(&D.lm_scale, lm); dev(&D.lm_einv, lm);
@@ -424,7 +337,7 @@ int create_device_buffers(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h) {
   dev(&D.prior_b0, W * 96, CLEAR); dev(&D.prior_c0, W, CLEAR);
   upv(&D.prior_x0, h.px0); upv(&D.prior_map, h.pmap);
   upv(&D.prior_bsize, h.pbs); upv(&D.prior_bidx, h.pbi); upv(&D.prior_bxoff, h.pbx); upv(&D.prior_bstate, h.pbst);
-  if (rc == VILO_OK) rc = blob.flush(ctx, bt);   // D.win ... D.prior_bstate are device pointers from here on
+  if (rc == VILO_OK) rc = blob.flush(ctx, bt->arena);   // D.win ... D.prior_bstate are device pointers from here on
   dev(&D.cam_g, W * CD_N); dev(&D.cam_dh2, W * CD_N); dev(&D.cam_y, W * CD_N); dev(&D.cam_scale, W * CD_N);
   dev(&D.Lk, W * 11 * 169); dev(&D.TAg, W * 11 * 169); dev(&D.Cimg, W * 3840); dev(&D.Tk, W * TK_N);
   dev(&D.cam_gin, W * CD_N); dev(&D.Bimg, W * BI_N);
@@ -437,8 +350,8 @@ int upload_priors(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h, const vilo_r
   BatchDev &D = bt->d;
   const int W = D.W;
   double *d_J = nullptr, *d_r = nullptr;
-  int rc = dev_alloc(ctx, bt, &d_J, (size_t)W * 96 * 96);
-  if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &d_r, (size_t)W * 96);
+  int rc = bt->arena.alloc(ctx, &d_J, (size_t)W * 96 * 96);
+  if (rc == VILO_OK) rc = bt->arena.alloc(ctx, &d_r, (size_t)W * 96);
   if (rc != VILO_OK) return rc;
   if (hipMemcpyAsync(d_J, h.pJ, sizeof(double) * (size_t)W * 96 * 96, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
       hipMemcpyAsync(d_r, h.pr0, sizeof(double) * (size_t)W * 96, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
@@ -447,7 +360,7 @@ int upload_priors(vilo_ctx *ctx, vilo_batch *bt, const HostPack &h, const vilo_r
     for (int w = 0; w < W; ++w)
       if (refs[w].prior_pool && refs[w].prior_slot >= 0 && refs[w].prior_slot < refs[w].prior_pool->n && h.plan.wins[w].prior_n > 0) slot[w] = refs[w].prior_slot;
     int *d_slot = nullptr;
-    rc = dev_upload(ctx, bt, &d_slot, slot);
+    rc = bt->arena.upload(ctx, &d_slot, slot);
     if (rc != VILO_OK) return rc;
     hipLaunchKernelGGL(k_prior_gather, dim3(W), dim3(256), 0, ctx->stream, W, D.win, d_slot, refs[0].prior_pool->dJ, refs[0].prior_pool->dr, d_J, d_r);
   }
@@ -488,7 +401,7 @@ int upload_through_ring(vilo_ctx *ctx, size_t n_items, size_t per_item, Gather g
 // gathered there. *compact_bytes: bytes that crossed the bus when not the full records'.
 int upload_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, const vilo_resident_refs *refs, void *d_pre, size_t *compact_bytes) {
   const int W = bt->W;
-  const bool leg = bt->leg;
+  const bool leg = bt->rec.leg;
   const size_t rec = leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu);
   bool partial = false;
   for (int w = 0; w < W; ++w) partial = partial || in[w].n_frames < VILO_MAX_FRAMES;
@@ -507,9 +420,9 @@ int upload_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, co
     // every window's records from host memory, default sqrt_info route: the compact form (above); the device expands each chunk behind its copy
     const size_t per_win = sizeof(double) * REC_C_N * 10;
     void *d_comp = nullptr;
-    if (dev_alloc_bytes(ctx, bt, &d_comp, per_win * (size_t)W) != VILO_OK) return VILO_ERR_HIP;
+    if (bt->arena.alloc_bytes(ctx, &d_comp, per_win * (size_t)W) != VILO_OK) return VILO_ERR_HIP;
     *compact_bytes = per_win * (size_t)W;
-    bt->rec_form = 1;
+    bt->rec.form = 1;
     rc = upload_through_ring(ctx, (size_t)W, per_win,
         [&](size_t w, char *to) {
           const int nr = in[w].n_frames - 1;
@@ -544,9 +457,9 @@ int upload_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, co
   }
   if (rc == VILO_OK && !g_ids.empty()) {
     int *d_gi = nullptr, *d_gd = nullptr;
-    bt->rec_pool = true;
-    rc = dev_upload(ctx, bt, &d_gi, g_ids);
-    if (rc == VILO_OK) rc = dev_upload(ctx, bt, &d_gd, g_dst);
+    bt->rec.from_pool = true;
+    rc = bt->arena.upload(ctx, &d_gi, g_ids);
+    if (rc == VILO_OK) rc = bt->arena.upload(ctx, &d_gd, g_dst);
     if (rc == VILO_OK) rc = vilo_launch_preint_gather(ctx, refs[0].preint_pool, (int)g_ids.size(), d_gi, d_gd, d_pre);
   }
   return rc;
@@ -559,20 +472,17 @@ int create_records(vilo_ctx *ctx, vilo_batch *bt, const vilo_window_desc *in, co
   const int W = bt->W;
   const bool leg = in[0].use_leg != 0;
   void *d_pre = nullptr;
-  if (dev_alloc_bytes(ctx, bt, &d_pre, (leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu)) * (size_t)W * 10) != VILO_OK) return VILO_ERR_HIP;   // arena: lives as long as the batch
-  bt->d_pre = d_pre; bt->leg = leg;
+  if (bt->arena.alloc_bytes(ctx, &d_pre, (leg ? sizeof(vilo_preint) : sizeof(vilo_preint_imu)) * (size_t)W * 10) != VILO_OK) return VILO_ERR_HIP;   // arena: lives as long as the batch
+  bt->rec.d_pre = d_pre; bt->rec.leg = leg;
   int rc = upload_records(ctx, bt, in, refs, d_pre, compact_bytes);
-  if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &bt->d_prep_bad, (size_t)W * 10);
-  D.prep_bad = bt->d_prep_bad;   // (per-interval flags of the records in force: the marginalisation looks at the intervals it uses)
+  if (rc == VILO_OK) rc = bt->arena.alloc(ctx, &bt->rec.d_prep_bad, (size_t)W * 10);
+  D.prep_bad = bt->rec.d_prep_bad;   // (per-interval flags of the records in force: the marginalisation looks at the intervals it uses)
   if (rc == VILO_OK) rc = vilo_batch_prepare(ctx, bt);
   // a covariance that is not positive definite has no sqrt_info: that window alone fails (termination FAILURE, like a non-finite
   // IterationZero); the flag is looked at for live intervals only — folded per window on the device (no round trip through the host:
   // a one-window batch is built for every image of a replay)
-  if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &D.win_bad, (size_t)W);
-  if (rc == VILO_OK) {
-    hipLaunchKernelGGL(k_fold_win_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bt->d_prep_bad, D.imu_skip, D.win_bad);
-    if (hipGetLastError() != hipSuccess) rc = VILO_ERR_HIP;
-  }
+  if (rc == VILO_OK) rc = bt->arena.alloc(ctx, &D.win_bad, (size_t)W);
+  if (rc == VILO_OK) rc = bt->rec.fold_win_bad(ctx, D);
   // (the uploads above came out of this call's host memory and the context's reusable staging: they are complete when it returns)
   if (rc == VILO_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = VILO_ERR_HIP;
   return rc;
@@ -609,10 +519,10 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
   if (!h.pJ || !h.pr0 || !h.obs || !h.flags) return VILO_ERR_HIP;
   vilo::fill_batch(W, in, init, h.res.data(), P, {h.obs, h.flags, h.x0.data(), h.pmap.data(), h.pbs.data(), h.pbi.data(), h.pbx.data(), h.pbst.data(), h.px0.data(), h.pJ, h.pr0, h.iskip.data()},
                    ctx->pool);   // (worker_pool.hpp: host threads parked between batches)
-  bt->lm_off_host = std::move(P.lm_off); bt->L_host = std::move(P.L); bt->perm_host = std::move(P.perm);
-  bt->obs_row_host = std::move(P.obs_row); bt->n_obs_rows = P.n_obs_rows;
-  bt->flags_total = P.flags_total;
-  for (const WinMeta &wm : P.wins) bt->max_win_waves = std::max(bt->max_win_waves, wm.n_waves);
+  bt->lm.lm_off = std::move(P.lm_off); bt->lm.L = std::move(P.L); bt->lm.perm = std::move(P.perm);
+  bt->lm.obs_row = std::move(P.obs_row); bt->lm.n_obs_rows = P.n_obs_rows;
+  bt->mask.flags_total = P.flags_total;
+  for (const WinMeta &wm : P.wins) bt->lm.max_win_waves = std::max(bt->lm.max_win_waves, wm.n_waves);
   const double t_packed = now();
   // a lane of vilo_solve_windows' pipeline: the uploads of the lanes go one after the other at the link's rate (side by side every lane's
   // solve would start when ALL uploads are through); held until this batch's uploads are complete, i.e. to the end of the call
@@ -643,22 +553,31 @@ int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, con
 
 // sqrt_info = chol(cov^-1)^T of every live interval of the batch (asynchronous, on the context's stream)
 extern "C" int vilo_batch_prepare(vilo_ctx *ctx, vilo_batch *bt) {
-  if (!ctx || !bt || !bt->d_pre) return VILO_ERR_BAD_ARG;
+  if (!ctx || !bt || !bt->rec.d_pre) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
   BatchDev &D = bt->d;
-  VILO_HIP(hipMemsetAsync(bt->d_prep_bad, 0, sizeof(int) * (size_t)bt->W * 10, ctx->stream));
+  const BatchRecords &R = bt->rec;
+  VILO_HIP(hipMemsetAsync(R.d_prep_bad, 0, sizeof(int) * (size_t)bt->W * 10, ctx->stream));
   const bool timed = ctx->profile == 1 || ctx->profile == 2 + 11;   // (kind 11 = k_prepare_preint, vilo_kernel_name)
   if (timed) {
     for (hipEvent_t &e : ctx->prep_ev) if (!e) VILO_HIP(hipEventCreate(&e));
     VILO_HIP(hipEventRecord(ctx->prep_ev[0], ctx->stream));
   }
-  int rc = bt->leg ? vilo_launch_prepare_preint(ctx, bt->W * 10, (const vilo_preint *)bt->d_pre, D.prep, bt->d_prep_bad, D.imu_skip, 1)
-                   : vilo_launch_prepare_preint_imu(ctx, bt->W * 10, (const vilo_preint_imu *)bt->d_pre, D.prep, bt->d_prep_bad, D.imu_skip, 1);
-  if (rc == VILO_OK && !bt->leg) rc = vilo_launch_embed_sqrt15(ctx, D);
+  int rc = R.leg ? vilo_launch_prepare_preint(ctx, bt->W * 10, (const vilo_preint *)R.d_pre, D.prep, R.d_prep_bad, D.imu_skip, 1)
+                 : vilo_launch_prepare_preint_imu(ctx, bt->W * 10, (const vilo_preint_imu *)R.d_pre, D.prep, R.d_prep_bad, D.imu_skip, 1);
+  if (rc == VILO_OK && !R.leg) rc = vilo_launch_embed_sqrt15(ctx, D);
   if (timed) {
     VILO_HIP(hipEventRecord(ctx->prep_ev[1], ctx->stream));
     ctx->prep_pending = true;
   }
+  return rc;
+}
+
+// a vilo_batch_set_samples that fails: nothing of a set of samples may stay referenced by the launch sequence, captured or not
+static int samples_failed(vilo_batch *bt, int rc) {
+  BatchDev &D = bt->d;
+  D.rp_on = 0; D.rp_samples = nullptr; D.rp_terms = nullptr; D.rp_offsets = nullptr;
+  bt->graph.drop();
   return rc;
 }
 
@@ -667,32 +586,26 @@ extern "C" int vilo_batch_prepare(vilo_ctx *ctx, vilo_batch *bt) {
 extern "C" int vilo_batch_set_samples(vilo_ctx *ctx, vilo_batch *bt, const vilo_sample *samples, const int32_t *offsets) {
   if (!ctx || !bt) return VILO_ERR_BAD_ARG;
   BatchDev &D = bt->d;
+  BatchRecords &R = bt->rec;
+  const size_t n = (size_t)bt->W * 10;
   if (!samples) {   // back to records integrated once
     if (!D.rp_on) return VILO_OK;
     D.rp_on = 0;
-    if (bt->gexec) { (void)hipGraphExecDestroy(bt->gexec); bt->gexec = nullptr; }
+    bt->graph.drop();
     // d_pre holds what the last re-integration left (the records at the last candidate point): the records the batch was created with come
-    // back from their copy, their sqrt_info is prepared again and win_bad is rebuilt from the flags of that preparation — a covariance
-    // without sqrt_info fails its window again, as it did before the samples were set
+    // back from their copy, their sqrt_info is prepared again and win_bad is folded again from the flags of that preparation — a covariance
+    // without sqrt_info fails its window again, as it did before the samples were set. All of it is complete when the call returns.
     VILO_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)bt->W * 10;
-    if (bt->rp_orig) VILO_HIP(hipMemcpyAsync(bt->d_pre, bt->rp_orig, sizeof(vilo_preint) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    if (R.orig) VILO_HIP(hipMemcpyAsync(R.d_pre, R.orig, sizeof(vilo_preint) * n, hipMemcpyDeviceToDevice, ctx->stream));
     int rc = vilo_batch_prepare(ctx, bt);
+    if (rc == VILO_OK && D.win_bad) rc = R.fold_win_bad(ctx, D);
     if (rc != VILO_OK) return rc;
-    std::vector<int> bad(n, 0), winbad(bt->W, 0);
-    std::vector<unsigned char> skip(n);
     VILO_HIP(hipStreamSynchronize(ctx->stream));
-    VILO_HIP(hipMemcpy(bad.data(), bt->d_prep_bad, sizeof(int) * n, hipMemcpyDeviceToHost));
-    VILO_HIP(hipMemcpy(skip.data(), D.imu_skip, n, hipMemcpyDeviceToHost));
-    for (size_t f = 0; f < n; ++f)
-      if (!skip[f] && bad[f]) winbad[f / 10] = 1;
-    if (D.win_bad) VILO_HIP(hipMemcpy(D.win_bad, winbad.data(), sizeof(int) * (size_t)bt->W, hipMemcpyHostToDevice));
     return VILO_OK;
   }
   if (!offsets) return VILO_ERR_BAD_ARG;
-  if (!bt->leg || !bt->d_pre) { ctx->err = "vilo_batch_set_samples: the batch has no IMU-leg preintegration records"; return VILO_ERR_UNSUPPORTED; }
+  if (!R.leg || !R.d_pre) { ctx->err = "vilo_batch_set_samples: the batch has no IMU-leg preintegration records"; return VILO_ERR_UNSUPPORTED; }
   VILO_HIP(hipSetDevice(ctx->device));
-  const size_t n = (size_t)bt->W * 10;
   std::vector<unsigned char> skip(n);
   VILO_HIP(hipMemcpy(skip.data(), D.imu_skip, n, hipMemcpyDeviceToHost));
   if (offsets[0] < 0) return VILO_ERR_BAD_ARG;
@@ -702,49 +615,44 @@ extern "C" int vilo_batch_set_samples(vilo_ctx *ctx, vilo_batch *bt, const vilo_
       ctx->err = "vilo_batch_set_samples: a live interval needs at least two samples";
       return VILO_ERR_BAD_ARG;
     }
-  if (!bt->rp_s || bt->rp_cap < (size_t)offsets[n]) {
-    bt->rp_cap = (size_t)offsets[n];
-    int rc = dev_alloc(ctx, bt, &bt->rp_s, bt->rp_cap);
-    if (rc == VILO_OK && !bt->rp_o) rc = dev_alloc(ctx, bt, &bt->rp_o, n + 1);
-    if (rc == VILO_OK) rc = dev_alloc(ctx, bt, &bt->rp_t, bt->rp_cap * (size_t)(4 * VILO_LEG_REC));   // 4 legs x one record per sample
-    if (rc != VILO_OK) {   // (nothing of a previous set of samples may stay referenced by the launch sequence)
-      bt->rp_s = nullptr; bt->rp_cap = 0;
-      D.rp_on = 0; D.rp_samples = nullptr; D.rp_terms = nullptr; D.rp_offsets = nullptr;
-      if (bt->gexec) { (void)hipGraphExecDestroy(bt->gexec); bt->gexec = nullptr; }
-      return rc;
+  if (!R.rp_s || R.rp_cap < (size_t)offsets[n]) {
+    R.rp_cap = (size_t)offsets[n];
+    int rc = bt->arena.alloc(ctx, &R.rp_s, R.rp_cap);
+    if (rc == VILO_OK && !R.rp_o) rc = bt->arena.alloc(ctx, &R.rp_o, n + 1);
+    if (rc == VILO_OK) rc = bt->arena.alloc(ctx, &R.rp_t, R.rp_cap * (size_t)(4 * VILO_LEG_REC));   // 4 legs x one record per sample
+    if (rc != VILO_OK) {
+      R.rp_s = nullptr; R.rp_cap = 0;
+      return samples_failed(bt, rc);
     }
   }
-  if (!bt->rp_orig) {   // the records the batch was created with (vilo_batch_set_samples(NULL) brings them back)
-    int rc = dev_alloc(ctx, bt, &bt->rp_orig, n);
+  if (!R.orig) {   // the records the batch was created with (vilo_batch_set_samples(NULL) brings them back)
+    int rc = bt->arena.alloc(ctx, &R.orig, n);
     if (rc != VILO_OK) return rc;
-    VILO_HIP(hipMemcpyAsync(bt->rp_orig, bt->d_pre, sizeof(vilo_preint) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    VILO_HIP(hipMemcpyAsync(R.orig, R.d_pre, sizeof(vilo_preint) * n, hipMemcpyDeviceToDevice, ctx->stream));
     VILO_HIP(hipStreamSynchronize(ctx->stream));
   }
-  vilo_sample *d_s = bt->rp_s;
-  int *d_o = bt->rp_o;
-  double *d_t = bt->rp_t;
   // the records are integrated again before every linearisation from here on: the flags of the records the batch was created with no
   // longer describe them (k_accept / the marginalisation read prep_bad of the records in force)
-  if (bt->d.win_bad) VILO_HIP(hipMemset(bt->d.win_bad, 0, sizeof(int) * (size_t)bt->W));
-  VILO_HIP(hipMemcpy(d_s, samples, sizeof(vilo_sample) * (size_t)offsets[n], hipMemcpyHostToDevice));
-  VILO_HIP(hipMemcpy(d_o, offsets, sizeof(int) * (n + 1), hipMemcpyHostToDevice));
-  D.rp_samples = d_s; D.rp_terms = d_t; D.rp_offsets = d_o; D.rp_pre = bt->d_pre; D.prep_bad = bt->d_prep_bad; D.leg = 1; D.rp_on = 1;
+  if (D.win_bad) VILO_HIP(hipMemset(D.win_bad, 0, sizeof(int) * (size_t)bt->W));
+  VILO_HIP(hipMemcpy(R.rp_s, samples, sizeof(vilo_sample) * (size_t)offsets[n], hipMemcpyHostToDevice));
+  VILO_HIP(hipMemcpy(R.rp_o, offsets, sizeof(int) * (n + 1), hipMemcpyHostToDevice));
+  D.rp_samples = R.rp_s; D.rp_terms = R.rp_t; D.rp_offsets = R.rp_o; D.rp_pre = R.d_pre; D.prep_bad = R.d_prep_bad; D.leg = 1; D.rp_on = 1;
   // Every interval is one IMULegIntegrationBase object that integrated its samples once (the record the batch was created with); the
   // solver's re-integrations are repropagate() calls on it, and repropagate() leaves the contact-force filter of contact_sensor_type 2 as
   // the previous pass left it (imu_leg_integration_base.cpp:62-86). The filter state after the original integration depends on the
   // samples only: that pass is run here once (mode 2: at the records' own linearisation point, which reproduces the records).
-  if (!bt->rp_ff) { int rc = dev_alloc(ctx, bt, &bt->rp_ff, n * VILO_FF_N); if (rc != VILO_OK) { D.rp_on = 0; return rc; } }
-  D.rp_ff = bt->rp_ff;
-  VILO_HIP(hipMemsetAsync(bt->rp_ff, 0, sizeof(double) * n * VILO_FF_N, ctx->stream));
+  if (!R.rp_ff) { int rc = bt->arena.alloc(ctx, &R.rp_ff, n * VILO_FF_N); if (rc != VILO_OK) return samples_failed(bt, rc); }
+  D.rp_ff = R.rp_ff;
+  VILO_HIP(hipMemsetAsync(R.rp_ff, 0, sizeof(double) * n * VILO_FF_N, ctx->stream));
   if (ctx->cfg.contact_sensor_type == 2) {
     int rc = vilo_repropagate_launch(ctx, D, 2, 0);
-    if (rc != VILO_OK) { D.rp_on = 0; return rc; }
+    if (rc != VILO_OK) return samples_failed(bt, rc);
     // a reset batch is the batch as it was after this call: the filter state the first integration left, not the one the last solve's
     // re-integrations left (reset + solve is then repeatable bit for bit: bench steps, Monte-Carlo restarts, graph replays)
-    if (!bt->rp_ff0) { rc = dev_alloc(ctx, bt, &bt->rp_ff0, n * VILO_FF_N); if (rc != VILO_OK) { D.rp_on = 0; return rc; } }
-    VILO_HIP(hipMemcpyAsync(bt->rp_ff0, bt->rp_ff, sizeof(double) * n * VILO_FF_N, hipMemcpyDeviceToDevice, ctx->stream));
+    if (!R.rp_ff0) { rc = bt->arena.alloc(ctx, &R.rp_ff0, n * VILO_FF_N); if (rc != VILO_OK) return samples_failed(bt, rc); }
+    VILO_HIP(hipMemcpyAsync(R.rp_ff0, R.rp_ff, sizeof(double) * n * VILO_FF_N, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  if (bt->gexec) { (void)hipGraphExecDestroy(bt->gexec); bt->gexec = nullptr; }   // the captured launch sequence changes
+  bt->graph.drop();   // the captured launch sequence changes
   return VILO_OK;
 }
 
@@ -754,37 +662,38 @@ extern "C" int vilo_batch_reset(vilo_ctx *ctx, vilo_batch *bt) {
   VILO_HIP(hipMemcpyAsync(bt->d.x, bt->d.x0, sizeof(double) * (size_t)bt->W * XSTRIDE, hipMemcpyDeviceToDevice, ctx->stream));
   if (bt->d.n_lm > 0)
     VILO_HIP(hipMemcpyAsync(bt->d.lam, bt->d.lam0, sizeof(double) * (size_t)bt->d.n_lm, hipMemcpyDeviceToDevice, ctx->stream));
-  if (bt->d.rp_on && bt->rp_ff0 && ctx->cfg.contact_sensor_type == 2)   // the contact-force filters of the intervals' objects as set_samples left them
-    VILO_HIP(hipMemcpyAsync(bt->rp_ff, bt->rp_ff0, sizeof(double) * (size_t)bt->W * 10 * VILO_FF_N, hipMemcpyDeviceToDevice, ctx->stream));
+  if (bt->d.rp_on && bt->rec.rp_ff0 && ctx->cfg.contact_sensor_type == 2)   // the contact-force filters of the intervals' objects as set_samples left them
+    VILO_HIP(hipMemcpyAsync(bt->rec.rp_ff, bt->rec.rp_ff0, sizeof(double) * (size_t)bt->W * 10 * VILO_FF_N, hipMemcpyDeviceToDevice, ctx->stream));
   return VILO_OK;
 }
 
 extern "C" int vilo_batch_solve(vilo_ctx *ctx, vilo_batch *bt, const vilo_solve_opts *opts) {
   if (!ctx || !bt || !opts) return VILO_ERR_BAD_ARG;
   if (opts->max_num_iterations < 0 || opts->max_num_iterations > 63) return VILO_ERR_BAD_ARG;
-  if (vilo_batch_mask_stale(ctx, bt, "vilo_batch_solve") != VILO_OK) return VILO_ERR_HIP;
+  if (bt->mask.stale(ctx, "vilo_batch_solve") != VILO_OK) return VILO_ERR_HIP;
   VILO_HIP(hipSetDevice(ctx->device));
   int rc = VILO_OK;
   const vilo::SolvePlan plan = vilo::plan_solve(vilo_batch_shape(bt->d), ctx->solver_form, vilo::tuning(), opts->max_num_iterations > 0);
-  const bool want_graph = !ctx->profile && !bt->graph_failed && bt->n_solves >= 1 && !vilo::tuning().no_graph;
+  SolveGraph &G = bt->graph;
+  const bool want_graph = !ctx->profile && !G.failed && bt->n_solves >= 1 && !vilo::tuning().no_graph;
   if (opts->max_solver_time_us < 0) { ctx->err = "vilo_solve_opts.max_solver_time_us < 0 (fill the struct with vilo_default_solve_opts)"; return VILO_ERR_BAD_ARG; }
-  if (want_graph && (!bt->gexec || memcmp(&bt->gopts, opts, sizeof(*opts)) != 0 || bt->g_sqrt_info_mode != ctx->sqrt_info_mode || bt->g_rp_on != bt->d.rp_on ||
-                     bt->g_initial_mu != ctx->initial_mu || bt->gplan != plan)) {
-    if (bt->gexec) { (void)hipGraphExecDestroy(bt->gexec); bt->gexec = nullptr; }
+  const SolveGraph::Key key{*opts, ctx->sqrt_info_mode, bt->d.rp_on, ctx->initial_mu, plan};   // what the launch sequence depends on
+  if (want_graph && !(G.exec && G.key == key)) {
+    G.drop();
     hipGraph_t g = nullptr;
     if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
       rc = vilo_solve_launch(ctx, bt->d, opts, plan);
       const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
-      if (rc != VILO_OK || e != hipSuccess || !g || hipGraphInstantiate(&bt->gexec, g, nullptr, nullptr, 0) != hipSuccess) bt->gexec = nullptr;
+      if (rc != VILO_OK || e != hipSuccess || !g || hipGraphInstantiate(&G.exec, g, nullptr, nullptr, 0) != hipSuccess) G.exec = nullptr;
       if (g) (void)hipGraphDestroy(g);
     }
-    if (!bt->gexec) { bt->graph_failed = true; (void)hipGetLastError(); ctx->err.clear(); }
-    else { bt->gopts = *opts; bt->g_sqrt_info_mode = ctx->sqrt_info_mode; bt->g_rp_on = bt->d.rp_on; bt->g_initial_mu = ctx->initial_mu; bt->gplan = plan; }
+    if (!G.exec) { G.failed = true; (void)hipGetLastError(); ctx->err.clear(); }
+    else G.key = key;
     rc = VILO_OK;
   }
   VILO_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  if (want_graph && bt->gexec) {
-    VILO_HIP(hipGraphLaunch(bt->gexec, ctx->stream));
+  if (want_graph && G.exec) {
+    VILO_HIP(hipGraphLaunch(G.exec, ctx->stream));
     bt->path[6] = 1;
   } else {
     rc = vilo_solve_launch(ctx, bt->d, opts, plan);
@@ -844,7 +753,7 @@ extern "C" int vilo_batch_download(vilo_ctx *ctx, vilo_batch *bt, vilo_window_st
       memcpy(out[w].leg_bias, xw + XO_LB, sizeof(double) * 4 * F);
       memcpy(out[w].ex_pose, xw + XO_EX, sizeof(double) * 14);
       out[w].td[0] = xw[XO_TD];
-      for (int i = 0; i < bt->L_host[w]; ++i) out[w].inv_depth[bt->perm_host[bt->lm_off_host[w] + i]] = lam[bt->lm_off_host[w] + i];
+      for (int i = 0; i < bt->lm.L[w]; ++i) out[w].inv_depth[bt->lm.perm[bt->lm.lm_off[w] + i]] = lam[bt->lm.lm_off[w] + i];
     }
   }
   if (summ) {
@@ -859,156 +768,6 @@ extern "C" int vilo_batch_download(vilo_ctx *ctx, vilo_batch *bt, vilo_window_st
       memcpy(s.radius_trace, st[w].radius_trace, sizeof(s.radius_trace));
     }
   }
-  return VILO_OK;
-}
-
-// one batch of host windows through create / solve / download on context c
-static int solve_host_batch(vilo_ctx *c, int n, const vilo_window_desc *in, vilo_window_state *inout, const vilo_solve_opts *opts, vilo_solve_summary *out) {
-  vilo_batch *bt = nullptr;
-  int rc = vilo_batch_create(c, n, in, inout, &bt);
-  if (rc != VILO_OK) return rc;
-  rc = vilo_batch_solve(c, bt, opts);
-  if (rc == VILO_OK) rc = vilo_batch_download(c, bt, inout, out);
-  if (rc == VILO_OK && out) {
-    for (int w = 0; w < n; ++w)
-      if (out[w].termination == 2) rc = VILO_ERR_NUMERIC;
-  }
-  vilo_batch_destroy(c, bt);
-  return rc;
-}
-static void snapshot_host_states(int n, const vilo_window_desc *in, const vilo_window_state *st, std::vector<double> &keep) {
-  size_t tot = 0;
-  for (int w = 0; w < n; ++w) tot += (size_t)20 * in[w].n_frames + 15 + (size_t)std::max(0, in[w].n_landmarks);
-  keep.resize(tot);
-  double *q = keep.data();
-  for (int w = 0; w < n; ++w) {
-    const int F = in[w].n_frames, L = std::max(0, in[w].n_landmarks);
-    const vilo_window_state &s = st[w];
-    memcpy(q, s.pose, sizeof(double) * 7 * F); q += 7 * F;
-    memcpy(q, s.speed_bias, sizeof(double) * 9 * F); q += 9 * F;
-    memcpy(q, s.leg_bias, sizeof(double) * 4 * F); q += 4 * F;
-    memcpy(q, s.ex_pose, sizeof(double) * 14); q += 14;
-    *q++ = s.td[0];
-    if (L > 0) { memcpy(q, s.inv_depth, sizeof(double) * L); q += L; }
-  }
-}
-static void restore_host_states(int n, const vilo_window_desc *in, vilo_window_state *inout, const std::vector<double> &keep) {
-  const double *q = keep.data();
-  for (int w = 0; w < n; ++w) {
-    const int F = in[w].n_frames, L = std::max(0, in[w].n_landmarks);
-    vilo_window_state &s = inout[w];
-    memcpy(s.pose, q, sizeof(double) * 7 * F); q += 7 * F;
-    memcpy(s.speed_bias, q, sizeof(double) * 9 * F); q += 9 * F;
-    memcpy(s.leg_bias, q, sizeof(double) * 4 * F); q += 4 * F;
-    memcpy(s.ex_pose, q, sizeof(double) * 14); q += 14;
-    s.td[0] = *q++;
-    if (L > 0) { memcpy(s.inv_depth, q, sizeof(double) * L); q += L; }
-  }
-}
-
-// A call on many HOST windows (vilo_solve_windows, vilo_optimize_windows), cut into sub-batches that go through `lanes` internal contexts
-// of the same device, one host thread each (vilo_set_host_pipeline; default 4 lanes of 1024 windows, from two sub-batches' worth of windows
-// up): while one lane's windows are on the DMA engines or in the solver, the other lanes pack theirs — the three resources a hand-over of
-// host windows needs (host cores, PCIe, GPU) work at the same time instead of one after the other. The windows are independent and every
-// lane solves with the form the whole call would take as ONE batch, so the answer is the one batch's bit for bit
-// (tests/test_gpu_parity.py::test_host_pipeline_...). `inout` comes back changed only if every sub-batch came through (or failed
-// numerically, which is a per-window outcome): the states a finished sub-batch overwrote are put back.
-// Returns false when the call is not one to cut (few windows, pipeline off, per-kernel profiling on): the caller runs it as one batch.
-bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
-                       const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out) {
-  const int sub = ctx->pipe_sub, lanes_want = ctx->pipe_lanes;
-  if (lanes_want < 2 || sub <= 0 || n_windows < 2 * sub || ctx->profile) return false;
-  for (int w = 0; w < n_windows; ++w) {   // (what the snapshots below index with; the sub-batches' own checks say why)
-    const vilo_window_state &s = inout[w];
-    if (in[w].n_frames < 2 || in[w].n_frames > VILO_MAX_FRAMES || in[w].n_landmarks < 0 || in[w].n_landmarks > VILO_NUM_OF_F || !s.pose || !s.speed_bias || !s.leg_bias ||
-        !s.ex_pose || !s.td || (in[w].n_landmarks && !s.inv_depth)) return false;
-  }
-  // The kernel set of a batch depends on its size and those forms agree to rounding, not bitwise. The lanes run the kernel set of a FULL
-  // batch whatever their share (BatchDev::full_regime) with the row form and the solver of the whole call, so a call is cut only if as
-  // ONE batch it would certainly be a full one too.
-  int with_lm = 0, all_td_const = 1;
-  for (int w = 0; w < n_windows; ++w) { with_lm += in[w].n_landmarks > 0 ? 1 : 0; if (!in[w].td_const) all_td_const = 0; }
-  if (!vilo::call_is_full_as_one_batch(n_windows, with_lm, vilo::tuning())) return false;
-  const bool compact = ctx->compact_rows && all_td_const;
-  const int form = vilo::plan_solve({n_windows, with_lm, compact, false, true}, ctx->solver_form, vilo::tuning()).solver;   // what ONE batch of all the windows would be solved with
-  const int n_sub = (n_windows + sub - 1) / sub, per = (n_windows + n_sub - 1) / n_sub;   // equal shares: no small tail batch
-  const int n_lanes = std::min(lanes_want, n_sub);
-  while ((int)ctx->lanes.size() < n_lanes) {
-    vilo_ctx *l = nullptr;
-    const int rc = vilo_create(&l, &ctx->cfg, ctx->device);
-    if (rc != VILO_OK) { ctx->err = "no context for a pipeline lane"; *rc_out = rc; return true; }
-    // the lanes pack side by side: each brings its own share of the host's threads (at most the shared pool's 16, at least 2)
-    const int hw = (int)std::thread::hardware_concurrency();
-    l->dma_turn = &ctx->dma_m;
-    l->pool = new vilo::WorkerPool(std::max(2, std::min(16, (hw > 0 ? hw : 1) / std::max(1, lanes_want))) - 1);
-    ctx->lanes.push_back(l);
-  }
-  std::vector<int> rcs(n_sub, VILO_OK);
-  std::vector<char> ran(n_sub, 0);
-  std::vector<std::vector<double>> keep(n_sub);
-  std::vector<double> solve_ms(n_lanes, 0.0), marg_ms(n_lanes, 0.0);
-  std::vector<int> general(n_lanes, 0);
-  std::vector<std::thread> th;
-  for (int li = 0; li < n_lanes; ++li) {
-    vilo_ctx *l = ctx->lanes[li];
-    l->sqrt_info_mode = ctx->sqrt_info_mode; l->solver_form = form; l->compact_rows = compact ? 1 : 0; l->regime_full = 1;
-    l->initial_mu = ctx->initial_mu; l->prior_form = ctx->prior_form; l->err.clear();
-  }
-  auto lane_work = [&](int li) {
-    vilo_ctx *l = ctx->lanes[li];
-    for (int i = li; i < n_sub; i += n_lanes) {
-      const int w0 = i * per, n = std::min(per, n_windows - w0);
-      if (n <= 0) break;
-      try {
-        snapshot_host_states(n, in + w0, inout + w0, keep[i]);
-        l->last_solve_ms = 0.0; l->last_marg_ms = 0.0; l->marg_general_count = 0;
-        ran[i] = 1;
-        rcs[i] = fn(l, w0, n);
-      } catch (...) {   // (host allocation failure inside a lane's thread: reported, not thrown across the C boundary)
-        rcs[i] = VILO_ERR_HIP; l->err = "host allocation failed in a pipeline lane";
-      }
-      solve_ms[li] += l->last_solve_ms; marg_ms[li] += l->last_marg_ms; general[li] += l->marg_general_count;
-      if (rcs[i] != VILO_OK && rcs[i] != VILO_ERR_NUMERIC) break;
-    }
-  };
-  std::vector<int> inline_lanes;   // (a lane whose thread the process could not start is worked on this one)
-  for (int li = 0; li < n_lanes; ++li) {
-    try { th.emplace_back(lane_work, li); } catch (...) { inline_lanes.push_back(li); }
-  }
-  for (int li : inline_lanes) lane_work(li);
-  for (std::thread &t : th) t.join();
-  int rc = VILO_OK;
-  for (int i = 0; i < n_sub; ++i)
-    if (rcs[i] != VILO_OK && rcs[i] != VILO_ERR_NUMERIC) { rc = rcs[i]; ctx->err = ctx->lanes[i % n_lanes]->err; break; }
-  if (rc != VILO_OK) {   // a sub-batch was refused or lost its device: the call as a whole did not happen
-    for (int i = 0; i < n_sub; ++i) {
-      const int w0 = i * per, n = std::min(per, n_windows - w0);
-      if (n > 0 && ran[i]) restore_host_states(n, in + w0, inout + w0, keep[i]);
-    }
-    *rc_out = rc;
-    return true;
-  }
-  ctx->last_solve_ms = 0.0; ctx->last_marg_ms = 0.0; ctx->marg_general_count = 0;
-  for (int li = 0; li < n_lanes; ++li) { ctx->last_solve_ms += solve_ms[li]; ctx->last_marg_ms += marg_ms[li]; ctx->marg_general_count += general[li]; }
-  for (int i = 0; i < n_sub; ++i) if (rcs[i] == VILO_ERR_NUMERIC) rc = VILO_ERR_NUMERIC;
-  *rc_out = rc;
-  return true;
-}
-
-// Estimator::optimization()'s solve half on host windows (estimator.cpp:1054-1245)
-extern "C" int vilo_solve_windows(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
-                                  const vilo_solve_opts *opts, vilo_solve_summary *out) {
-  if (!ctx || !in || !inout || !opts || n_windows <= 0) return VILO_ERR_BAD_ARG;
-  int rc = VILO_OK;
-  if (vilo_run_on_lanes(ctx, n_windows, in, inout, [&](vilo_ctx *l, int w0, int n) { return solve_host_batch(l, n, in + w0, inout + w0, opts, out ? out + w0 : nullptr); }, &rc))
-    return rc;
-  return solve_host_batch(ctx, n_windows, in, inout, opts, out);
-}
-
-// lanes < 2 or sub_windows <= 0: every vilo_solve_windows call is one batch
-extern "C" int vilo_set_host_pipeline(vilo_ctx *ctx, int lanes, int sub_windows) {
-  if (!ctx || lanes < 0 || lanes > 8 || sub_windows < 0) return VILO_ERR_BAD_ARG;
-  ctx->pipe_lanes = lanes; ctx->pipe_sub = sub_windows;
   return VILO_OK;
 }
 
@@ -1055,16 +814,16 @@ extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win
     case 10: src = (const double *)(bt->d.st + win); n = 24 + 64; break;
     case 12: src = (const double *)(bt->d.st + win) + 24 + 128 + 1; n = 63; break;   // phase_clk (int64 bit patterns)
     case 13:   // the window's preintegration records as they stand (vilo_preint x 10; with vilo_batch_set_samples: the last re-integration)
-      if (!bt->leg || !bt->d_pre) return VILO_ERR_UNSUPPORTED;
-      src = (const double *)((const vilo_preint *)bt->d_pre + (size_t)win * 10); n = 10 * sizeof(vilo_preint) / sizeof(double); break;
+      if (!bt->rec.leg || !bt->rec.d_pre) return VILO_ERR_UNSUPPORTED;
+      src = (const double *)((const vilo_preint *)bt->rec.d_pre + (size_t)win * 10); n = 10 * sizeof(vilo_preint) / sizeof(double); break;
     case 15:   // the window's prepared records (10 x PreintPrepared: head + sqrt_info), entries of intervals without a factor as they lie
       src = (const double *)(bt->d.prep + (size_t)win * 10); n = 10 * sizeof(PreintPrepared) / sizeof(double); break;
     case 16:   // what 13 is for a batch of IMU-only windows (vilo_preint_imu x 10)
-      if (bt->leg || !bt->d_pre) return VILO_ERR_UNSUPPORTED;
-      src = (const double *)((const vilo_preint_imu *)bt->d_pre + (size_t)win * 10); n = 10 * sizeof(vilo_preint_imu) / sizeof(double); break;
-    case 17: {   // vilo_batch_records_rw's form of the records (0 full, 1 compact upload, 2 mixed) and whether they came from a pool
+      if (bt->rec.leg || !bt->rec.d_pre) return VILO_ERR_UNSUPPORTED;
+      src = (const double *)((const vilo_preint_imu *)bt->rec.d_pre + (size_t)win * 10); n = 10 * sizeof(vilo_preint_imu) / sizeof(double); break;
+    case 17: {   // BatchRecords::form of the records (0 full, 1 compact upload, 2 mixed) and whether they came from a pool
       if (max_n < 2) return VILO_ERR_BAD_ARG;
-      out[0] = bt->rec_form; out[1] = bt->rec_pool ? 1.0 : 0.0;
+      out[0] = bt->rec.form; out[1] = bt->rec.from_pool ? 1.0 : 0.0;
       return 2;
     }
     // the bias chain's hand-over buffers as the last linearisation left them: M_k, T_A(k) ([11][13][13]), T(k) in MFMA operand order + the
@@ -1075,7 +834,7 @@ extern "C" int vilo_debug_fetch(vilo_ctx *ctx, vilo_batch *bt, int what, int win
     case 11: {
       n = wm.L;
       if ((int)n > max_n) return VILO_ERR_BAD_ARG;
-      for (size_t i = 0; i < n; ++i) out[i] = bt->perm_host[bt->lm_off_host[win] + i];
+      for (size_t i = 0; i < n; ++i) out[i] = bt->lm.perm[bt->lm.lm_off[win] + i];
       return (int)n;
     }
     default: return VILO_ERR_BAD_ARG;

@@ -195,24 +195,7 @@ inline double vilo_win_sum_dt(const vilo_window_desc &d, const vilo_resident_ref
   if (r && r->preint_pool) return r->preint_sum_dt[k];
   return d.use_leg ? d.preint[k].sum_dt : d.preint_imu[k].sum_dt;
 }
-struct vilo_batch;
-// Per-call device memory of a batch call (vilo_batch.hip): bump-allocated out of the batch's arena, all of it given back when the scope
-// closes, on every return path. Closing waits for the context's stream first (batch uploads are null-stream copies, which do not wait for
-// it), then hands the arena chunks taken since opening back to ctx->pool_free and rewinds the bump pointer. Bump allocation never moves
-// what it has handed out, so a buffer may be sized partway through a call. The rule: nothing that must outlive the call is allocated
-// inside a scope. The calls that query a resident batch do not open one by hand: batch_call.hpp's BatchCall owns the scope, allocates the
-// blocks its CallLayout lists in one piece, and carries the timed region and the downloads around the call's kernels.
-struct ArenaScope {
-  ArenaScope(vilo_ctx *ctx, vilo_batch *bt);
-  ~ArenaScope();
-  ArenaScope(const ArenaScope &) = delete;
-  ArenaScope &operator=(const ArenaScope &) = delete;
-  void *alloc(size_t bytes);   // 256-byte aligned; null (ctx->err set) when the device has no memory left
-  vilo_ctx *ctx;
-  vilo_batch *bt;
-  size_t n_chunks, cur_left, used;
-  char *cur;
-};
+struct vilo_batch;   // batch_state.hpp
 // The host-window form of a batch call: a batch of the windows at the given states, fn(batch) on it, the batch destroyed.
 template <class Fn>
 int vilo_with_batch(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_window_state *state, Fn &&fn) {
@@ -223,40 +206,10 @@ int vilo_with_batch(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo
   vilo_batch_destroy(ctx, bt);
   return rc;
 }
-// vilo_batch.hip: the batch's preintegration records on the device ([W * 10] vilo_preint when *leg, else vilo_preint_imu)
-const void *vilo_batch_records(vilo_batch *bt, int *leg);
-// vilo_batch.hip, for vilo_batch_repropagate: the records as the call may overwrite them and where they came from. form: 0 full records,
-// 1 uploaded in the compact 739-double form (entries no factor reads are zero, the covariance's lower triangle mirrors the upper),
-// 2 such a batch after a re-propagation that left some records in that form; pool: gathered from a vilo_preint_streams pool.
-struct BatchRecordsRW { void *d_pre; int leg, pool, form; };
-BatchRecordsRW vilo_batch_records_rw(vilo_batch *bt);
-// records were overwritten and prepared again (prep_bad of each rewritten): win_bad folded again from every live interval's flag, as
-// vilo_batch_create folds it (asynchronous on the context's stream); then, once the caller knows: all_live = no live record is left in
-// the compact form.
-int vilo_batch_records_replaced(vilo_ctx *ctx, vilo_batch *bt);
-void vilo_batch_records_full(vilo_batch *bt, bool all_live);
-BatchDev *vilo_batch_dev(vilo_batch *bt);            // vilo_batch.hip, as the next three: the batch's device tables
-int vilo_batch_max_window_waves(vilo_batch *bt);     // the most packed visual waves any of its windows has
-// the landmarks' observation rows on the device (batch data that stays with the batch, uploaded at the first call: outside any call's scope)
-int vilo_batch_obs_rows(vilo_ctx *ctx, vilo_batch *bt, const int **rows, int *n_rows);
-const int *vilo_batch_perm(vilo_batch *bt, int win, int *L);   // window win's landmark order on the host
-// vilo_batch.hip, for vilo_batch_mask_landmarks (kernels_mask.hip): the flag image as uploaded and the mask in force, both in the batch's
-// arena from the first mask call on (outside any call's scope), with the mask's host mirror (device order, as lm_perm) and the host
-// landmark tables. vilo_batch_mask_changed: the mirror was rewritten (mirror_valid), or the device's mask may have
-// been and the mirror was not (a HIP error inside a mask call): vilo_batch_mask_stale then fails (VILO_ERR_HIP, vilo_last_error set) until a
-// mask call has gone through, and so do the refusing calls. vilo_batch_mask_host: window win's part of the mirror (in the
-// order of vilo_batch_perm) while any landmark is masked, else null. vilo_batch_refuse_masked: VILO_ERR_UNSUPPORTED with vilo_last_error set while any landmark is masked (the calls that do not honour
-// a mask).
-struct BatchMaskStore { unsigned char *flags_orig, *mask, *mask_host; const int *lm_off, *perm, *L; };
-int vilo_batch_mask_store(vilo_ctx *ctx, vilo_batch *bt, BatchMaskStore *out);
-void vilo_batch_mask_changed(vilo_batch *bt, bool mirror_valid);
-int vilo_batch_mask_stale(vilo_ctx *ctx, vilo_batch *bt, const char *call);
-const unsigned char *vilo_batch_mask_host(vilo_batch *bt, int win);
-int vilo_batch_refuse_masked(vilo_ctx *ctx, vilo_batch *bt, const char *call);
 // kernels_resid.hip: k_resid_landmarks alone on the context's stream, for the landmark flags (flags [n_lm] bytes, caller order); the other
 // per-landmark outputs go to scratch the caller hands in ([n_lm] doubles x 3, ints x 2)
 int vilo_resid_landmark_flags_launch(vilo_ctx *ctx, const BatchDev &b, double threshold_px, double *scratch_d3, int *scratch_i2, unsigned char *flags);
-// vilo_batch.hip: a call on many host windows cut into sub-batches over the context's pipeline lanes (false: not a call to cut)
+// host_pipeline.hip: a call on many host windows cut into sub-batches over the context's pipeline lanes (false: not a call to cut)
 bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
                        const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out);
 int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *init, vilo_batch **out);

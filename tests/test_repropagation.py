@@ -123,6 +123,43 @@ def test_gpu_solve_with_repropagation_vs_oracle(ctx, cfg, ocfg, seed, L):
 
 
 @pytest.mark.gpu
+def test_gpu_samples_off_again_restores_records_and_failed_windows(ctx, cfg, ocfg):
+    """vilo_batch_set_samples(NULL) after a re-propagated solve: the records the batch was created with, their preparation and the
+    per-window "a covariance has no sqrt_info" flag are back, and the launch sequence captured with the samples in force is not
+    replayed: the plain solve again, bit for bit, for a window that solves and for one that fails."""
+    import ctypes
+    from cerberus_amd import api
+    good = _window(cfg, ocfg, n_landmarks=40, seed=5)
+    bad = good.twin()
+    bad.preint = bad.preint.copy()
+    bad.preint[2][33 + 961] = -1.0   # covariance (0, 0) of interval 2: not positive definite, no sqrt_info
+    ws = [good, bad]
+    opts = api.default_solve_opts(True, 4)
+
+    def result(b):
+        summ = b.download()
+        return [bytes(ctypes.string_at(ctypes.addressof(s), ctypes.sizeof(s))) for s in summ], [w.clone_state() for w in ws], summ
+    b = api.Batch(ctx, ws)
+    try:
+        b.solve(opts)
+        plain_bytes, plain_states, summ = result(b)
+        assert summ[1].termination == 2 and summ[0].termination != 2
+        b.set_samples()
+        b.reset()
+        b.solve(opts)
+        b.set_samples(False)
+        b.reset()
+        b.solve(opts)
+        back_bytes, back_states, _ = result(b)
+    finally:
+        b.close()
+    for i in range(2):
+        assert back_bytes[i] == plain_bytes[i], i
+        for a, bb in zip(back_states[i], plain_states[i]):
+            np.testing.assert_array_equal(a, bb)
+
+
+@pytest.mark.gpu
 def test_gpu_repropagated_batch_of_windows_equals_the_single_solves(ctx, cfg, ocfg):
     """Interval offsets of a batch are global: every window integrates its own samples."""
     from cerberus_amd import api
