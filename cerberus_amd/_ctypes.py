@@ -236,6 +236,19 @@ REPROP_OK, REPROP_NOT_SELECTED, REPROP_NO_INTERVAL, REPROP_NO_SAMPLES, REPROP_NU
 REPROP_THRESHOLDS = (0.10, 0.01, 0.01)   # vilo_default_reprop_opts: ba, bg, rho
 PREPARED_DOUBLES = 126 + 961   # PreintPrepared: head + sqrt_info (Batch.fetch(15))
 
+class RetractOpts(C.Structure):
+    """vilo_retract_opts (8 bytes)"""
+    _fields_ = [("base", C.c_int32), ("reserved", C.c_int32)]
+
+
+class WindowRetractRecord(C.Structure):
+    """vilo_window_retract_record (24 bytes)"""
+    _fields_ = [("status", C.c_int32), ("n_applied", C.c_int32), ("step_norm", C.c_double), ("step_max", C.c_double)]
+
+
+RETRACT_BASE = {"current": 0, "uploaded": 1}   # VILO_RETRACT_BASE_CURRENT, VILO_RETRACT_BASE_UPLOADED
+RETRACT_OK, RETRACT_NUMERIC = 0, 1   # a window's status (VILO_RETRACT_*)
+
 GRAD_STATE = 222  # pose 11 x 6, speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td
 IMU_RESIDUAL = 31  # entries of an interval's whitened residual (IMULegFactor; IMUFactor fills 0..14)
 

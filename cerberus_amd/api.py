@@ -6,6 +6,11 @@ The methods mirror the reference's operator interface for the hot path:
   preintegrate .. IMULegIntegrationBase ctor + push_back (imu_leg_integration_base.cpp:7-136)
   solve_windows . Estimator::optimization() solve half (estimator.cpp:1054-1245)
   marginalize ... Estimator::optimization() marginalisation half (estimator.cpp:1247-1455)
+  Batch.retract ........ PoseLocalParameterization::Plus / Ceres' Euclidean Plus over a whole resident batch (vilo_batch_retract)
+  window_retract ....... the same on host windows (vilo_window_retract)
+  Batch.set_state ...... Estimator::vector2double for chosen windows of a resident batch (vilo_batch_set_state)
+  Batch.save_state ..... the current state into the batch's snapshot slot (vilo_batch_save_state)
+  Batch.restore_state .. the snapshot back, bit for bit (vilo_batch_restore_state)
 """
 import collections
 import ctypes as C
@@ -43,6 +48,8 @@ def lib():
         L.vilo_last_failure_detection_ms.restype = C.c_double
         L.vilo_last_repropagate_ms.restype = C.c_double
         L.vilo_last_mask_ms.restype = C.c_double
+        L.vilo_last_retract_ms.restype = C.c_double
+        L.vilo_last_set_state_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -461,6 +468,43 @@ def _repropagate(ctx, n, samples, offsets, point, select, write, lin, mask, thre
     return Repropagation(drift, a["selected"].reshape(n, 10), a["status"].reshape(n, 10))
 
 
+Retraction = collections.namedtuple("Retraction", "status n_applied step_norm step_max")
+
+
+def retract_opts(n_windows, n_landmarks, base="current", state_step=None, lm_step=None, alpha=None):
+    """(T.RetractOpts, state_step [n_windows, 222] or None, lm_step [n_landmarks] or None, alpha [n_windows] or None) of a retract call,
+    checked and made contiguous float64; needs no device. base: 'current' (the step is applied to the current state) or 'uploaded' (to the
+    state the batch was created with). state_step: vilo_batch_gradient's state_grad layout; lm_step: one entry per landmark of the call,
+    window by window, in each window's own order; alpha: one step length per window, None for 1. A step that is None is a zero step."""
+    if base not in T.RETRACT_BASE:
+        raise ValueError("base must be one of %s" % sorted(T.RETRACT_BASE))
+    if state_step is not None:
+        state_step = _c(state_step)
+        if state_step.shape != (n_windows, T.GRAD_STATE):
+            raise ValueError("state_step must have shape (%d, %d), got %s" % (n_windows, T.GRAD_STATE, state_step.shape))
+    if lm_step is not None:
+        lm_step = _c(lm_step)
+        if lm_step.shape != (n_landmarks,):
+            raise ValueError("lm_step must have one entry per landmark of the call (%d), got shape %s" % (n_landmarks, lm_step.shape))
+    if alpha is not None:
+        alpha = _c(alpha)
+        if alpha.shape != (n_windows,):
+            raise ValueError("alpha must have one entry per window of the call (%d), got shape %s" % (n_windows, alpha.shape))
+    o = T.RetractOpts()
+    o.base, o.reserved = T.RETRACT_BASE[base], 0
+    return o, state_step, lm_step, alpha
+
+
+def _retract(ctx, descs, base, state_step, lm_step, alpha, call):
+    n = len(descs)
+    o, state_step, lm_step, alpha = retract_opts(n, sum(d.n_landmarks for d in descs), base, state_step, lm_step, alpha)
+    rec = (T.WindowRetractRecord * n)()
+    ctx._check(call(C.byref(o), _p(state_step), _p(lm_step), _p(alpha), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.WindowRetractRecord._fields_]),
+                      count=n).copy()
+    return Retraction(a["status"], a["n_applied"], a["step_norm"], a["step_max"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -622,6 +666,36 @@ class Batch:
         caller's; None leaves their bits 0. The batch is left as it was."""
         return _failure_detection(self.ctx, len(self._descs), last_track_num, last_pose,
                                   lambda *a: lib().vilo_batch_failure_detection(self.ctx.h, self.handle, *a))
+
+    def retract(self, state_step=None, lm_step=None, alpha=None, base="current"):
+        """vilo_batch_retract, in place on the batch's device state: x <- x [+] alpha * step in the local coordinates gradient() reports
+        (state_step [W, 222] as state_grad, lm_step [sum L] as lm_grad, alpha [W] or None for 1; see retract_opts). Pose and extrinsic
+        blocks take PoseLocalParameterization::Plus (bit for bit Context.pose_plus), the others x + alpha * step, each product and sum
+        rounded once. Constant blocks, the rows of absent frames and masked landmarks are not stepped and their step entries not read. A
+        window with a non-finite alpha or applied step entry is left as it is (status T.RETRACT_NUMERIC). base='uploaded' steps the state
+        the batch was created with (reset() and the step in one launch). Retraction(status (T.RETRACT_*), n_applied, step_norm, step_max,
+        each [W]). reset(), the records, the mask and the summaries are not affected."""
+        return _retract(self.ctx, self._descs, base, state_step, lm_step, alpha,
+                        lambda *a: lib().vilo_batch_retract(self.ctx.h, self.handle, *a))
+
+    def set_state(self, window_ids, windows):
+        """vilo_batch_set_state: the state arrays of windows[i] (synth.Window, or anything with desc()) replace the current device state
+        of window window_ids[i]; the windows that are not named, and what reset() restores, stay as they are."""
+        ids = np.ascontiguousarray(window_ids, dtype=np.int32)
+        if ids.ndim != 1 or len(ids) != len(windows):
+            raise ValueError("window_ids and windows must have the same length, got %s and %d" % (ids.shape, len(windows)))
+        states = (T.WindowState * max(len(windows), 1))()
+        for i, w in enumerate(windows):
+            states[i] = w.desc(T)[1]
+        self.ctx._check(lib().vilo_batch_set_state(self.ctx.h, self.handle, len(ids), T.iptr(ids), states))
+
+    def save_state(self):
+        """vilo_batch_save_state: the current device state into the batch's one snapshot slot (allocated at the first call)."""
+        self.ctx._check(lib().vilo_batch_save_state(self.ctx.h, self.handle))
+
+    def restore_state(self):
+        """vilo_batch_restore_state: the saved state back, bit for bit; raises (VILO_ERR_UNSUPPORTED) before any save_state()."""
+        self.ctx._check(lib().vilo_batch_restore_state(self.ctx.h, self.handle))
 
     def solve(self, opts):
         self.ctx._check(lib().vilo_batch_solve(self.ctx.h, self.handle, C.byref(opts)))
@@ -1029,6 +1103,15 @@ class Context:
             samples, offsets = window_samples(windows)
         return _repropagate(self, n, samples, offsets, point, select, write, lin, mask, thresholds,
                             lambda *a: lib().vilo_window_repropagate(self.h, n, descs, states, *a))
+
+    def window_retract(self, windows, state_step=None, lm_step=None, alpha=None, base="current"):
+        """vilo_window_retract: the step of host windows at their current state arrays (see Batch.retract); the windows' state arrays
+        receive the stepped state."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _retract(self, descs, base, state_step, lm_step, alpha, lambda *a: lib().vilo_window_retract(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -1,4 +1,4 @@
-// The resident batch (vilo_batch) as every .hip file of the library sees it: the device tables the kernels read (BatchDev) and five parts,
+// The resident batch (vilo_batch) as every .hip file of the library sees it: the device tables the kernels read (BatchDev) and six parts,
 // each with the state of one concern and the few operations on it. State that outlives a call goes into a part; state of one call goes
 // into its BatchCall (batch_call.hpp). Members without a body here live in vilo_batch.hip.
 #pragma once
@@ -102,6 +102,16 @@ struct BatchMask {
   const unsigned char *host(int lm_off) const { return n_masked > 0 ? mirror.data() + lm_off : nullptr; }
 };
 
+// vilo_batch_save_state / vilo_batch_restore_state (kernels_retract.hip): the one snapshot slot of a batch, a second copy of x and lam,
+// one arena block from the first save() on (batch data, outside any call's scope)
+struct BatchSnapshot {
+  double *d_x = nullptr, *d_lam = nullptr;   // [W][XSTRIDE], [n_lm]
+  bool saved = false;                        // a save has gone through: the slot holds a state
+  int save(vilo_ctx *ctx, BatchArena &arena, const BatchDev &d);
+  // VILO_ERR_UNSUPPORTED with vilo_last_error set before the first save
+  int restore(vilo_ctx *ctx, const BatchDev &d) const;
+};
+
 // The launch sequence of one solve (5 + 7 x max_num_iterations kernels) as a hipGraph, captured when the same resident batch is solved a
 // second time (vilo_batch_reset + vilo_batch_solve loops: replays, Monte-Carlo seeds, bench), and everything that sequence depends on
 struct SolveGraph {
@@ -125,5 +135,6 @@ struct vilo_batch {
   BatchLandmarks lm;
   BatchRecords rec;
   BatchMask mask;
+  BatchSnapshot snap;
   SolveGraph graph;
 };

@@ -230,6 +230,32 @@ int BatchMask::refuse(vilo_ctx *ctx, const char *call) const {
   return VILO_ERR_UNSUPPORTED;
 }
 
+int BatchSnapshot::save(vilo_ctx *ctx, BatchArena &arena, const BatchDev &d) {
+  const size_t nx = (size_t)d.W * XSTRIDE, nl = std::max<size_t>((size_t)std::max(d.n_lm, 0), 1);
+  if (!d_x) {
+    // one block (x | lam): either both exist or neither
+    const size_t lam_at = (nx * sizeof(double) + 255) & ~(size_t)255;
+    char *blk = nullptr;
+    const int rc = arena.alloc(ctx, &blk, lam_at + nl * sizeof(double));
+    if (rc != VILO_OK) return rc;
+    d_x = (double *)blk; d_lam = (double *)(blk + lam_at);
+  }
+  saved = false;   // (a copy that fails leaves the slot without a state)
+  VILO_HIP(hipMemcpyAsync(d_x, d.x, nx * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  if (d.n_lm > 0) VILO_HIP(hipMemcpyAsync(d_lam, d.lam, (size_t)d.n_lm * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  saved = true;
+  return VILO_OK;
+}
+int BatchSnapshot::restore(vilo_ctx *ctx, const BatchDev &d) const {
+  if (!saved) {
+    ctx->err = "vilo_batch_restore_state: no state has been saved on this batch (vilo_batch_save_state first)";
+    return VILO_ERR_UNSUPPORTED;
+  }
+  VILO_HIP(hipMemcpyAsync(d.x, d_x, (size_t)d.W * XSTRIDE * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  if (d.n_lm > 0) VILO_HIP(hipMemcpyAsync(d.lam, d_lam, (size_t)d.n_lm * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  return VILO_OK;
+}
+
 extern "C" int vilo_debug_batch_device_bytes(const vilo_batch *bt, size_t out[2]) {
   if (!bt || !out) return VILO_ERR_BAD_ARG;
   out[0] = 0;

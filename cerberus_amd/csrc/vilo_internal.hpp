@@ -54,7 +54,9 @@ struct vilo_ctx {
   double last_failure_ms = 0.0;       // GPU time of the last vilo_batch_failure_detection (k_failure_detection)
   double last_mask_ms = 0.0;          // GPU time of the last vilo_batch_mask_landmarks (k_mask_landmarks + k_mask_windows; with OUTLIER_FLAGS also k_resid_landmarks)
   double last_reprop_ms = 0.0;        // GPU time of the last vilo_batch_repropagate (k_reprop_point; with write also the integration, k_reprop_commit and the preparation)
-  int marg_general_count = 0;    // windows of the last vilo_marginalize that took the global-memory eigen path
+  double last_retract_ms = 0.0;       // GPU time of the last vilo_batch_retract (k_retract)
+  double last_set_state_ms = 0.0;     // GPU time of the last vilo_batch_set_state (k_set_state)
+  int marg_general_count = 0;   // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
   vilo_config *d_cfg;
   // per-kernel HIP-event timing of the solve pipeline (vilo_set_profiling)

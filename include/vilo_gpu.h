@@ -1085,6 +1085,75 @@ int vilo_window_repropagate(vilo_ctx *ctx, int n_windows, const vilo_window_desc
  * k_reprop_commit, the preparation and the fold of win_bad, without the copies in and out. */
 double vilo_last_repropagate_ms(const vilo_ctx *ctx);
 
+/* ---- caller-given local steps on a resident batch's state (PoseLocalParameterization::Plus, pose_local_parameterization.cpp:12-27, on the
+ *      7-dimensional blocks; Ceres' Plus of a Euclidean block, x + delta, on the others; Estimator::vector2double, estimator.cpp:848-901,
+ *      for the host states a batch takes) ----
+ * vilo_batch_retract computes x <- x [+] alpha * delta in place on the device state of every window, in the local coordinates
+ * vilo_batch_gradient reports g and h in: what a line search, a gradient or preconditioned step of the caller's own, a teacher-forced
+ * trajectory or a Monte-Carlo restart needs, without a new batch.
+ * Inputs. state_step [W][222], or NULL for a zero step: exactly vilo_batch_gradient's state_grad layout (pose 11 x 6 (dp dtheta),
+ * speed-bias 11 x 9, leg bias 11 x 4, extrinsics 2 x 6, td). lm_step [sum L], or NULL: the inverse depths' steps, window w's landmarks
+ * concatenated window by window, inside a window in the caller's vilo_window_desc order (as every per-landmark array of this header).
+ * alpha [W], or NULL for 1. opts->base: VILO_RETRACT_BASE_CURRENT (default) steps the current state; VILO_RETRACT_BASE_UPLOADED steps the
+ * state the batch was created with, bit for bit what vilo_batch_reset followed by the call with CURRENT gives, in the same launch.
+ * Arithmetic, fixed so that a host restatement agrees to the bit: s = alpha * delta, rounded once; a Euclidean coordinate becomes x + s,
+ * rounded once (no fused multiply-add across the two); a pose or extrinsic block becomes vilo_pose_plus(x, s) — p + dp, q * deltaQ(dtheta)
+ * normalised — through the device function vilo_pose_plus runs, so bit for bit its result.
+ * Not stepped, whatever the step holds there (it is not read: NaN is harmless): the constant blocks (leg_bias_const, ex_const, td_const; the
+ * leg biases of a use_leg == 0 window), the rows of frames a window does not have (n_frames < 11) and masked landmarks
+ * (vilo_batch_mask_landmarks). Their bytes stay (with UPLOADED: become the uploaded ones, as after vilo_batch_reset).
+ * Non-finite entries: a window with a non-finite alpha, or whose s is not finite in a coordinate that would be stepped, is not stepped at
+ * all (the check comes before the window's first store; with UPLOADED it is reset) and reports VILO_RETRACT_NUMERIC; the other windows are
+ * unaffected.
+ * records [W] (optional): status; n_applied, the coordinates stepped (vilo_batch_gradient's n_free, less the masked landmarks); step_norm =
+ * sqrt(sum s^2) and step_max = max |s| over them. A NUMERIC window reads 0 in all three.
+ * What the call leaves alone: the uploaded copy (vilo_batch_reset and VILO_GAUGE_ANCHOR_UPLOADED still mean the state given at creation),
+ * the preintegration records, the landmark mask, the solve summaries vilo_batch_download reports. A vilo_batch_solve after it starts from
+ * the stepped state and may replay the captured launch sequence. One launch, one code path for every batch size; a window's state and
+ * record are bitwise independent of the batch it shares and of its position in it. The call's device memory is returned when it returns.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing written): NULL ctx or batch; a base other than the two; a reserved field that is not 0. */
+#define VILO_RETRACT_BASE_CURRENT 0
+#define VILO_RETRACT_BASE_UPLOADED 1
+#define VILO_RETRACT_OK 0
+#define VILO_RETRACT_NUMERIC 1
+typedef struct {
+  int32_t base;             /* VILO_RETRACT_BASE_* */
+  int32_t reserved;         /* 0 */
+} vilo_retract_opts;
+void vilo_default_retract_opts(vilo_retract_opts *o);
+typedef struct {
+  int32_t status;           /* VILO_RETRACT_* */
+  int32_t n_applied;        /* local coordinates stepped, inverse depths included */
+  double step_norm;         /* sqrt(sum s_i^2) over them */
+  double step_max;          /* max |s_i| over them */
+} vilo_window_retract_record;
+/* opts NULL: vilo_default_retract_opts (CURRENT). */
+int vilo_batch_retract(vilo_ctx *ctx, vilo_batch *batch, const vilo_retract_opts *opts, const double *state_step, const double *lm_step,
+                       const double *alpha, vilo_window_retract_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed, the stepped state is written into state[w] (the
+ * uploaded state is then state[w] itself: the two bases agree). */
+int vilo_window_retract(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state, const vilo_retract_opts *opts,
+                        const double *state_step, const double *lm_step, const double *alpha, vilo_window_retract_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_retract: k_retract alone, without the copies in and out. */
+double vilo_last_retract_ms(const vilo_ctx *ctx);
+
+/* vector2double (estimator.cpp:848-901) for chosen windows of a resident batch: the host states state[i] replace the current device state
+ * of window window_ids[i], i < n, as vilo_batch_create packs them (the inverse depths scattered through the batch's landmark order; rows
+ * beyond a window's n_frames are not read). Windows that are not named stay bytewise as they were; the uploaded copy, the records, the mask
+ * and the summaries are not touched. Bad arguments (VILO_ERR_BAD_ARG, nothing written): NULL ctx, batch, window_ids or state, n < 1, an id
+ * outside 0 .. W - 1, an id named twice. */
+int vilo_batch_set_state(vilo_ctx *ctx, vilo_batch *batch, int n, const int32_t *window_ids, const vilo_window_state *state);
+/* GPU time of the last vilo_batch_set_state: k_set_state alone, without the upload. */
+double vilo_last_set_state_ms(const vilo_ctx *ctx);
+
+/* One snapshot slot per batch, for trial steps: save copies the current state (every window's 240 doubles and every inverse depth, masked
+ * ones like any other) into the slot on the device, restore copies it back, bit for bit. The slot is allocated at the first save (2 KB per
+ * window plus 8 B per landmark; a batch that never saves holds nothing more) and overwritten by every later one. State only: records, mask
+ * and summaries are neither saved nor restored. vilo_batch_restore_state before any save returns VILO_ERR_UNSUPPORTED with vilo_last_error
+ * saying so. Both are asynchronous on the context's stream, as vilo_batch_reset is. */
+int vilo_batch_save_state(vilo_ctx *ctx, vilo_batch *batch);
+int vilo_batch_restore_state(vilo_ctx *ctx, vilo_batch *batch);
+
 /* ---- measurement / test hooks (no counterpart in the reference) -------------------------------------- */
 /* Windows of the last vilo_marginalize whose Amm was not certified positive definite beyond eps = 1e-8 and therefore went
  * through the eigen-thresholded pseudo-inverse of the full Amm (marginalization_factor.cpp:281-286) instead of block
