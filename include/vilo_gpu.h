@@ -254,7 +254,7 @@ int vilo_set_host_pipeline(vilo_ctx *ctx, int lanes, int sub_windows);
 /* Device-resident form of the same call, for batches (independent windows: robots / replays / seeds). */
 int vilo_batch_create(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *init,
                       vilo_batch **batch);
-int vilo_batch_reset(vilo_ctx *ctx, vilo_batch *batch);  /* restore the uploaded initial states (device-side copy) */
+int vilo_batch_reset(vilo_ctx *ctx, vilo_batch *batch);  /* restore the uploaded initial states (device-side copy); the landmark mask and the snapshot slot stay as they are */
 /* sqrt_info = LLT(cov^-1)^T of the batch's preintegration records again (asynchronous): vilo_batch_create runs it once; the reference
  * recomputes it in every IMULegFactor::Evaluate (imu_leg_factor.cpp:197-198), a caller that replays a resident batch can charge it per solve */
 int vilo_batch_prepare(vilo_ctx *ctx, vilo_batch *batch);
@@ -293,7 +293,9 @@ int vilo_marginalize(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, c
 /* The same on a batch that is already resident, linearised at its device state (after vilo_batch_solve + vilo_batch_download; `state` is
  * the host copy of that state, `in` the descriptors the batch was created from). modes[w]: 0, 1 as above, < 0: leave window w alone.
  * With vilo_batch_set_samples in force the intervals are integrated again at the accepted state first. The call's device memory is
- * returned to the context's pool when it returns. */
+ * returned to the context's pool when it returns. The batch's states, uploaded copy, mask, snapshot and (without samples) records are
+ * left as they were; the solve summaries are NOT kept: a vilo_batch_download after this call reports zeroed summaries, so read them
+ * before it. */
 int vilo_batch_marginalize(vilo_ctx *ctx, vilo_batch *batch, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
                            const int *modes, vilo_prior *out);
 
@@ -1150,7 +1152,8 @@ double vilo_last_set_state_ms(const vilo_ctx *ctx);
  * ones like any other) into the slot on the device, restore copies it back, bit for bit. The slot is allocated at the first save (2 KB per
  * window plus 8 B per landmark; a batch that never saves holds nothing more) and overwritten by every later one. State only: records, mask
  * and summaries are neither saved nor restored. vilo_batch_restore_state before any save returns VILO_ERR_UNSUPPORTED with vilo_last_error
- * saying so. Both are asynchronous on the context's stream, as vilo_batch_reset is. */
+ * saying so. Restore replaces the whole current state: a window named in a vilo_batch_set_state since the save comes back as saved like
+ * any other. Both are asynchronous on the context's stream, as vilo_batch_reset is. */
 int vilo_batch_save_state(vilo_ctx *ctx, vilo_batch *batch);
 int vilo_batch_restore_state(vilo_ctx *ctx, vilo_batch *batch);
 
