@@ -115,6 +115,18 @@ class WindowGradient(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class StepOpts(C.Structure):
+    """vilo_step_opts (32 bytes)"""
+    _fields_ = [("gauge", C.c_int32), ("pad0", C.c_int32), ("min_lm_diagonal", C.c_double), ("max_lm_diagonal", C.c_double),
+                ("min_pivot", C.c_double)]
+
+
+class WindowStepRecord(C.Structure):
+    """vilo_window_step_record (40 bytes)"""
+    _fields_ = [("model_cost_change", C.c_double), ("scaled_norm", C.c_double), ("norm", C.c_double), ("grad_dot_step", C.c_double),
+                ("n_free", C.c_int32), ("status", C.c_int32)]
+
+
 class MaskOpts(C.Structure):
     """vilo_mask_opts (24 bytes)"""
     _fields_ = [("source", C.c_int32), ("combine", C.c_int32), ("flag_bits", C.c_uint32), ("pad", C.c_int32), ("outlier_threshold_px", C.c_double)]

@@ -11,6 +11,7 @@ The methods mirror the reference's operator interface for the hot path:
   Batch.set_state ...... Estimator::vector2double for chosen windows of a resident batch (vilo_batch_set_state)
   Batch.save_state ..... the current state into the batch's snapshot slot (vilo_batch_save_state)
   Batch.restore_state .. the snapshot back, bit for bit (vilo_batch_restore_state)
+  Batch.gauss_newton_step  the step Ceres' linear solver computes, (H + mu D^2) delta = -g, per window (vilo_batch_gauss_newton_step)
 """
 import collections
 import ctypes as C
@@ -50,6 +51,7 @@ def lib():
         L.vilo_last_mask_ms.restype = C.c_double
         L.vilo_last_retract_ms.restype = C.c_double
         L.vilo_last_set_state_ms.restype = C.c_double
+        L.vilo_last_gn_step_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -505,6 +507,49 @@ def _retract(ctx, descs, base, state_step, lm_step, alpha, call):
     return Retraction(a["status"], a["n_applied"], a["step_norm"], a["step_max"])
 
 
+GaussNewtonStep = collections.namedtuple("GaussNewtonStep", "state_step lm_step offsets model_cost_change scaled_norm norm grad_dot_step "
+                                                            "n_free status")
+
+
+def gn_step_opts(n_windows, mu=None, gauge="none", min_lm_diagonal=1e-6, max_lm_diagonal=1e32, min_pivot=1e-14):
+    """(T.StepOpts, mu [n_windows] contiguous float64 or None) of a gauss_newton_step call, checked; needs no device. mu: None (0), a scalar
+    or one value per window, finite and >= 0. gauge: 'none' (the full system, what the solver solves) or 'frame0' (frame 0's position and
+    its rotation about gravity held). The diagonal bounds are Ceres' min_lm_diagonal / max_lm_diagonal."""
+    if gauge not in T.COV_GAUGES:
+        raise ValueError("gauge must be one of %s" % sorted(T.COV_GAUGES))
+    lo, hi, piv = float(min_lm_diagonal), float(max_lm_diagonal), float(min_pivot)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo <= hi):
+        raise ValueError("0 <= min_lm_diagonal <= max_lm_diagonal < inf is required")
+    if not (np.isfinite(piv) and piv >= 0.0):
+        raise ValueError("min_pivot must be finite and >= 0")
+    if mu is not None:
+        mu = np.asarray(mu, dtype=np.float64)
+        if mu.ndim == 0:
+            mu = np.full(n_windows, float(mu))
+        mu = _c(mu)
+        if mu.shape != (n_windows,):
+            raise ValueError("mu must be a scalar or have one entry per window of the call (%d), got shape %s" % (n_windows, mu.shape))
+        if not np.isfinite(mu).all() or (mu < 0.0).any():
+            raise ValueError("mu must be finite and >= 0")
+    o = T.StepOpts()
+    o.gauge, o.pad0, o.min_lm_diagonal, o.max_lm_diagonal, o.min_pivot = T.COV_GAUGES[gauge], 0, lo, hi, piv
+    return o, mu
+
+
+def _gn_step(ctx, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot, call):
+    n = len(descs)
+    o, mu = gn_step_opts(n, mu, gauge, min_lm_diagonal, max_lm_diagonal, min_pivot)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    rec = (T.WindowStepRecord * n)()
+    ss = np.zeros((n, T.GRAD_STATE)) if state else None
+    ls = np.zeros(int(offsets[-1])) if landmarks else None
+    ctx._check(call(C.byref(o), _p(mu), rec, _p(ss), _p(ls)))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.WindowStepRecord._fields_]),
+                      count=n).copy()
+    return GaussNewtonStep(ss, ls, offsets, a["model_cost_change"], a["scaled_norm"], a["norm"], a["grad_dot_step"], a["n_free"], a["status"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -678,6 +723,16 @@ class Batch:
         return _retract(self.ctx, self._descs, base, state_step, lm_step, alpha,
                         lambda *a: lib().vilo_batch_retract(self.ctx.h, self.handle, *a))
 
+    def gauss_newton_step(self, mu=None, gauge="none", state=True, landmarks=True, min_lm_diagonal=1e-6, max_lm_diagonal=1e32,
+                          min_pivot=1e-14):
+        """vilo_batch_gauss_newton_step at the batch's device state: the solution delta of (H + mu D^2 / s^2) delta = -g (Ceres' Jacobi
+        scale s and clamped D^2; see gn_step_opts and include/vilo_gpu.h), inverse depths included, in gradient()'s layouts, so that
+        retract(r.state_step, r.lm_step) applies it. GaussNewtonStep(state_step [W, 222], lm_step [sum L], offsets, and per window
+        model_cost_change, scaled_norm, norm, grad_dot_step, n_free, status). A window of status 1 or 2 reads NaN. The batch is left as
+        it was."""
+        return _gn_step(self.ctx, self._descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
+                        lambda *a: lib().vilo_batch_gauss_newton_step(self.ctx.h, self.handle, *a))
+
     def set_state(self, window_ids, windows):
         """vilo_batch_set_state: the state arrays of windows[i] (synth.Window, or anything with desc()) replace the current device state
         of window window_ids[i]; the windows that are not named, and what reset() restores, stay as they are."""
@@ -842,6 +897,11 @@ class Context:
     def set_solver_form(self, form):
         """vilo_set_solver_form: 'auto' (by batch size), 'wave', 'split' (bitwise equal to 'wave'), 'mw8'."""
         self._check(lib().vilo_set_solver_form(self.h, self.SOLVER_FORMS[form]))
+
+    def set_gn_step_form(self, form):
+        """vilo_set_gn_step_form: 'streamed' (default: the coupling through global memory, two workgroups per CU) or 'resident' (in LDS,
+        one workgroup per CU); the same definition, kept for measurement."""
+        self._check(lib().vilo_set_gn_step_form(self.h, {"streamed": 0, "resident": 1}[form]))
 
     def set_prior_form(self, form):
         """vilo_set_prior_form: 'eigen' (J0 = sqrt(S) V^T like the reference, default) or 'factor' (pivoted Cholesky factor where no
@@ -1112,6 +1172,16 @@ class Context:
         for i, w in enumerate(windows):
             descs[i], states[i] = w.desc(T)
         return _retract(self, descs, base, state_step, lm_step, alpha, lambda *a: lib().vilo_window_retract(self.h, n, descs, states, *a))
+
+    def window_gauss_newton_step(self, windows, mu=None, gauge="none", state=True, landmarks=True, min_lm_diagonal=1e-6,
+                                 max_lm_diagonal=1e32, min_pivot=1e-14):
+        """vilo_window_gauss_newton_step: the step of host windows at their current state arrays (see Batch.gauss_newton_step)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _gn_step(self, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
+                        lambda *a: lib().vilo_window_gauss_newton_step(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -587,6 +587,57 @@ int vilo_window_gradient(vilo_ctx *ctx, int n_windows, const vilo_window_desc *i
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_gradient: linearisation + k_gradient, without the copies out. */
 double vilo_last_gradient_ms(const vilo_ctx *ctx);
 
+/* ---- Gauss-Newton / damped step at the current state (the linear system of Ceres 1.14's dogleg and Levenberg-Marquardt strategies) ----
+ * Definition. State and problem as for the cost gradient above: g and H = sum_blocks rho'(s) J^T J are exactly vilo_batch_gradient's and
+ * vilo_batch_covariance's (whitened, Huber corrector applied, PoseLocalParameterization's local coordinates; constant blocks and absent
+ * frames left out; the inverse depths part of the system). With h = diag(H), what state_diag / lm_diag report:
+ *   s_i   = 1 / (1 + sqrt(h_i))                                   Ceres' Jacobi scale,
+ *   D^2_i = clamp(s_i^2 h_i, min_lm_diagonal, max_lm_diagonal),
+ *   delta = s o y,  (S H S + mu diag(D^2)) y = -S g,  S = diag(s),
+ * which is (H + mu diag(D^2_i / s_i^2)) delta = -g: the Gauss-Newton system the solver forms build (mu = 0: the plain Gauss-Newton step).
+ * The inverse depths are eliminated first, with E~_l = E_l + mu D^2_l / s_l^2, and their step is returned.
+ * Gauge (opts->gauge, VILO_COV_GAUGE_*). NONE solves the full system: meaningful only where a prior or mu > 0 fixes it. FRAME0 restricts
+ * the step to frame 0's dp = 0 and (R_0^T e_z) . dtheta_0 = 0: delta = N z with N^T (H + mu diag(D^2 / s^2)) N z = -N^T g, N the
+ * orthonormal basis vilo_batch_covariance uses ([e1 e2 u], u = R_0^T e_z, on frame 0's rotation); those four directions of the step are zero.
+ * mu [W], or NULL for 0. A window whose mu is negative or not finite gets status 1.
+ * Outputs. state_step [W][222], lm_step [sum L]: exactly state_grad's / lm_grad's layouts, so that they go straight into
+ * vilo_batch_retract; entries of constant blocks, absent frames and gauge-held directions are zero. The record:
+ *   model_cost_change = -(g^T delta + delta^T H delta / 2) with the undamped H (= -g^T delta / 2 + mu sum_i (D^2_i / s_i^2) delta_i^2 / 2),
+ *   scaled_norm = |D o y|, the quantity the dogleg compares with the trust-region radius,  norm = |delta|,  grad_dot_step = g^T delta,
+ *   n_free: the coordinates solved for (vilo_batch_gradient's n_free, less 4 under FRAME0).
+ * Status 0 OK; 1 an input is not finite, or a pivot of the equilibrated system (unit diagonal) is at or below min_pivot: every output of
+ * the window is NaN, the other windows are untouched; 2 window invalid (a record without sqrt_info), as vilo_batch_gradient.
+ * Side effects: vilo_batch_gradient's — the SolverStates are copied aside and back, records are integrated again in place when samples are
+ * in force, a following vilo_batch_solve is bitwise what it would have been. While a landmark is masked the call returns
+ * VILO_ERR_UNSUPPORTED. Its device memory is returned when the call returns. Every output of a window is bitwise independent of the batch
+ * it shares and of its position in it. Bad arguments (VILO_ERR_BAD_ARG): NULL ctx, batch or windows, an unknown gauge, pad0 != 0, diagonal
+ * bounds that are negative, unordered or not finite, a negative or non-finite min_pivot, n_windows < 1. */
+typedef struct {
+  int32_t gauge;                           /* VILO_COV_GAUGE_* */
+  int32_t pad0;                            /* 0 */
+  double min_lm_diagonal, max_lm_diagonal; /* the clamp of D^2 (Ceres: 1e-6, 1e32) */
+  double min_pivot;                        /* smallest accepted Cholesky pivot of the equilibrated system */
+} vilo_step_opts;   /* 32 bytes */
+/* VILO_COV_GAUGE_NONE (what the solver solves), 1e-6, 1e32, 1e-14 */
+void vilo_default_step_opts(vilo_step_opts *o);
+typedef struct {
+  double model_cost_change, scaled_norm, norm, grad_dot_step;
+  int32_t n_free, status;
+} vilo_window_step_record;   /* 40 bytes */
+/* windows [W] is required; state_step and lm_step may each be NULL to leave it out. opts NULL: vilo_default_step_opts. */
+int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *batch, const vilo_step_opts *opts, const double *mu,
+                                 vilo_window_step_record *windows, double *state_step, double *lm_step);
+/* The same for host windows at the given states: one batch is created, queried once and destroyed. */
+int vilo_window_gauss_newton_step(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                  const vilo_step_opts *opts, const double *mu, vilo_window_step_record *windows, double *state_step,
+                                  double *lm_step);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_gauss_newton_step: linearisation + k_gn_step, without the copies. */
+double vilo_last_gn_step_ms(const vilo_ctx *ctx);
+/* The kernel form of vilo_batch_gauss_newton_step on this context: 0 (default) streams the 143 x 80 coupling through per-call global memory,
+ * two workgroups per CU; 1 keeps it in LDS, one workgroup per CU. The same definition and bounds; the two differ in rounding only (the split
+ * of the landmark passes). Kept for measurement (tools/time_gn_step.py). VILO_ERR_BAD_ARG for any other value. */
+int vilo_set_gn_step_form(vilo_ctx *ctx, int form);
+
 /* ---- landmark depths from the current poses (FeatureManager::triangulate, feature_manager.cpp:302-382 with triangulatePoint :198-212; the
  * arithmetic of FeatureManager::removeBackShiftDepth :450-479) ----
  * State: the batch's current state, what vilo_batch_download returns. Rotation matrices are taken from the normalised quaternions, as
