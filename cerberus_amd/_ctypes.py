@@ -127,6 +127,14 @@ class WindowStepRecord(C.Structure):
                 ("n_free", C.c_int32), ("status", C.c_int32)]
 
 
+HV_MAX_VECTORS = 16  # VILO_HV_MAX_VECTORS
+
+
+class HessVecRecord(C.Structure):
+    """vilo_hess_vec_record (32 bytes)"""
+    _fields_ = [("vHv", C.c_double), ("g_dot_v", C.c_double), ("model_cost_change", C.c_double), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 class MaskOpts(C.Structure):
     """vilo_mask_opts (24 bytes)"""
     _fields_ = [("source", C.c_int32), ("combine", C.c_int32), ("flag_bits", C.c_uint32), ("pad", C.c_int32), ("outlier_threshold_px", C.c_double)]

@@ -52,6 +52,7 @@ def lib():
         L.vilo_last_retract_ms.restype = C.c_double
         L.vilo_last_set_state_ms.restype = C.c_double
         L.vilo_last_gn_step_ms.restype = C.c_double
+        L.vilo_last_hess_vec_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -550,6 +551,64 @@ def _gn_step(ctx, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_di
     return GaussNewtonStep(ss, ls, offsets, a["model_cost_change"], a["scaled_norm"], a["norm"], a["grad_dot_step"], a["n_free"], a["status"])
 
 
+HessianVector = collections.namedtuple("HessianVector", "state_out lm_out offsets n_vec vHv g_dot_v model_cost_change status")
+
+
+def hess_vec_args(descs, state_vec=None, lm_vec=None):
+    """(K, squeeze, state_vec [W, K, 222] or None, lm_vec [K sum L] or None, offsets) of a hessian_vector call, checked; needs no device.
+    state_vec: [W, 222] (one vector) or [W, K, 222]. lm_vec: the call's layout, 1-D of K * sum L entries — window w's block starts at
+    K * offsets[w], vector k at + k * L_w inside it (hess_vec_lm_block views it) —, so [sum L] for one vector. At least one is needed."""
+    n = len(descs)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    n_lm = int(offsets[-1])
+    if state_vec is None and lm_vec is None:
+        raise ValueError("state_vec or lm_vec is needed")
+    K, squeeze = None, False
+    if state_vec is not None:
+        state_vec = _c(state_vec)
+        if state_vec.ndim == 2:
+            state_vec, squeeze = state_vec[:, None, :], True
+        if state_vec.ndim != 3 or state_vec.shape[0] != n or state_vec.shape[2] != T.GRAD_STATE:
+            raise ValueError("state_vec must be [%d, %d] or [%d, K, %d], got %s" % (n, T.GRAD_STATE, n, T.GRAD_STATE, state_vec.shape))
+        K = state_vec.shape[1]
+        state_vec = _c(state_vec)
+    if lm_vec is not None:
+        lm_vec = _c(lm_vec)
+        if lm_vec.ndim != 1:
+            raise ValueError("lm_vec must be 1-D in the call's layout (K * sum L entries), got shape %s" % (lm_vec.shape,))
+        if K is None:
+            if n_lm == 0 or lm_vec.size % n_lm:
+                raise ValueError("lm_vec must have K * sum L = K * %d entries, got %d" % (n_lm, lm_vec.size))
+            K, squeeze = lm_vec.size // n_lm, lm_vec.size == n_lm
+        elif lm_vec.size != K * n_lm:
+            raise ValueError("lm_vec must have K * sum L = %d * %d entries, got %d" % (K, n_lm, lm_vec.size))
+    if not 1 <= K <= T.HV_MAX_VECTORS:
+        raise ValueError("1 <= K <= %d vectors per window are supported, got %d" % (T.HV_MAX_VECTORS, K))
+    return K, squeeze, state_vec, lm_vec, offsets
+
+
+def hess_vec_lm_block(lm, offsets, n_vec, w):
+    """window w's [K, L_w] block of an lm_vec / lm_out array of a hessian_vector call (a view)"""
+    a, b = n_vec * int(offsets[w]), n_vec * int(offsets[w + 1])
+    return lm[a:b].reshape(n_vec, -1) if b > a else lm[a:b].reshape(n_vec, 0)
+
+
+def _hess_vec(ctx, descs, state_vec, lm_vec, state, landmarks, call):
+    n = len(descs)
+    K, squeeze, sv, lv, offsets = hess_vec_args(descs, state_vec, lm_vec)
+    rec = (T.HessVecRecord * (n * K))()
+    so = np.zeros((n, K, T.GRAD_STATE)) if state else None
+    lo = np.zeros(K * int(offsets[-1])) if landmarks else None
+    ctx._check(call(K, _p(sv), _p(lv), rec, _p(so), _p(lo)))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.HessVecRecord._fields_]),
+                      count=n * K).copy().reshape(n, K)
+    if squeeze:
+        a = a[:, 0]
+        so = so[:, 0] if so is not None else None
+    return HessianVector(so, lo, offsets, K, a["vHv"], a["g_dot_v"], a["model_cost_change"], a["status"])
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -732,6 +791,16 @@ class Batch:
         it was."""
         return _gn_step(self.ctx, self._descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
                         lambda *a: lib().vilo_batch_gauss_newton_step(self.ctx.h, self.handle, *a))
+
+    def hessian_vector(self, state_vec=None, lm_vec=None, state=True, landmarks=True):
+        """vilo_batch_hessian_vector at the batch's device state: y = H v for K vectors per window, H the Gauss-Newton Hessian of
+        gradient() and gauss_newton_step() (inverse depths part of the system, undamped, no gauge). state_vec [W, 222] or [W, K, 222],
+        lm_vec [K sum L] (see hess_vec_args; None: zero). HessianVector(state_out [W, K, 222], lm_out [K sum L] (hess_vec_lm_block),
+        offsets, n_vec, and per (window, vector) vHv, g_dot_v, model_cost_change = -g.v - vHv / 2, status); one vector given as
+        [W, 222] returns [W, 222] and [W]. Entries of constant blocks and absent frames are not read and read 0 in the output. A
+        vector with a non-finite read entry reads NaN (status 1), the others are untouched. The batch is left as it was."""
+        return _hess_vec(self.ctx, self._descs, state_vec, lm_vec, state, landmarks,
+                         lambda *a: lib().vilo_batch_hessian_vector(self.ctx.h, self.handle, *a))
 
     def set_state(self, window_ids, windows):
         """vilo_batch_set_state: the state arrays of windows[i] (synth.Window, or anything with desc()) replace the current device state
@@ -1182,6 +1251,15 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _gn_step(self, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
                         lambda *a: lib().vilo_window_gauss_newton_step(self.h, n, descs, states, *a))
+
+    def window_hessian_vector(self, windows, state_vec=None, lm_vec=None, state=True, landmarks=True):
+        """vilo_window_hessian_vector: the products of host windows at their current state arrays (see Batch.hessian_vector)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _hess_vec(self, descs, state_vec, lm_vec, state, landmarks,
+                         lambda *a: lib().vilo_window_hessian_vector(self.h, n, descs, states, *a))
 
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)

@@ -638,6 +638,39 @@ double vilo_last_gn_step_ms(const vilo_ctx *ctx);
  * of the landmark passes). Kept for measurement (tools/time_gn_step.py). VILO_ERR_BAD_ARG for any other value. */
 int vilo_set_gn_step_form(vilo_ctx *ctx, int form);
 
+/* ---- Gauss-Newton Hessian-vector products at the current state (what a Cauchy point, a predicted decrease of a caller's own step, the
+ * curvature along a search direction, conjugate gradients or a few Lanczos steps need) ----
+ * Definition. State and problem as for the cost gradient above: g and H = sum_blocks rho'(s) J^T J are exactly vilo_batch_gradient's,
+ * vilo_batch_covariance's and vilo_batch_gauss_newton_step's (whitened, Huber corrector applied, PoseLocalParameterization's local
+ * coordinates; constant blocks and absent frames left out; the inverse depths part of the system: not eliminated, not damped, no gauge).
+ * For every window w and each of its K = n_vec vectors v_k over the 222 state coordinates and the window's L_w inverse depths:
+ *   y_k = H v_k,   record[w][k]: vHv = v_k^T H v_k,  g_dot_v = g^T v_k,  model_cost_change = -g_dot_v - vHv / 2,  status.
+ * Layouts. state_vec, state_out [W][K][222]: every row in state_grad's layout. lm_vec, lm_out [K sum L]: window w's block starts at
+ * K * (sum of L of the windows before it); vector k starts at k * L_w inside it, in the caller's vilo_window_desc order. records [W][K].
+ * state_vec or lm_vec NULL: zero; state_out or lm_out NULL: not wanted. K is the same for all windows, 1 <= K <= VILO_HV_MAX_VECTORS (16:
+ * the K vectors are the columns of one 16-column matrix-core tile, and one pass over the landmarks' coupling rows serves them all).
+ * Entries of v on constant blocks (ex_const, td_const, leg_bias_const; the leg biases when use_leg == 0) and on absent frames are not
+ * read — NaN there is harmless — and the outputs at those entries are 0.
+ * Status per (window, vector): 0 OK; 1 a read entry of v_k (or a sum) is not finite: that vector's outputs (at the entries that are
+ * read) and record are NaN, the window's other vectors and the other windows are untouched; 2 window invalid (a record without sqrt_info), as vilo_batch_gradient: NaN.
+ * Side effects: vilo_batch_gradient's — the SolverStates are copied aside and back, records are integrated again in place when samples are
+ * in force, a following vilo_batch_solve is bitwise what it would have been. While a landmark is masked the call returns
+ * VILO_ERR_UNSUPPORTED. Its device memory is returned when the call returns. Every output of a (window, vector) pair is bitwise
+ * independent of the batch it shares and of its position in it, and of K and of k: column 0 of a K = 5 call is the K = 1 call on that vector.
+ * Bad arguments (VILO_ERR_BAD_ARG): NULL ctx, batch or records, n_vec out of range, n_windows < 1. */
+#define VILO_HV_MAX_VECTORS 16
+typedef struct {
+  double vHv, g_dot_v, model_cost_change;
+  int32_t status, pad;
+} vilo_hess_vec_record;   /* 32 bytes */
+int vilo_batch_hessian_vector(vilo_ctx *ctx, vilo_batch *batch, int n_vec, const double *state_vec, const double *lm_vec,
+                              vilo_hess_vec_record *records, double *state_out, double *lm_out);
+/* The same for host windows at the given states: one batch is created, queried once and destroyed. */
+int vilo_window_hessian_vector(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, int n_vec,
+                               const double *state_vec, const double *lm_vec, vilo_hess_vec_record *records, double *state_out, double *lm_out);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_hessian_vector: linearisation + k_hess_vec, without the copies. */
+double vilo_last_hess_vec_ms(const vilo_ctx *ctx);
+
 /* ---- landmark depths from the current poses (FeatureManager::triangulate, feature_manager.cpp:302-382 with triangulatePoint :198-212; the
  * arithmetic of FeatureManager::removeBackShiftDepth :450-479) ----
  * State: the batch's current state, what vilo_batch_download returns. Rotation matrices are taken from the normalised quaternions, as
