@@ -215,6 +215,15 @@ class WindowDeadReckonRecord(C.Structure):
 DR_OK, DR_NO_FRAME, DR_NUMERIC = 0, 1, 2   # a window's status (VILO_DR_*)
 DR_STATE = 10   # P (3), quaternion x y z w, V (3)
 
+
+class DrCovOpts(C.Structure):
+    """vilo_dr_cov_opts (8 bytes)"""
+    _fields_ = [("from_frame", C.c_int32), ("reserved", C.c_int32)]
+
+
+DR_COV_N = 15     # error-state coordinates of a dead-reckoned covariance: dp, dtheta, dv, dba, dbg
+DR_COV_POSE = 6   # the pose block of a trajectory row: dp, dtheta
+
 class GaugeOpts(C.Structure):
     """vilo_gauge_opts (8 bytes)"""
     _fields_ = [("anchor", C.c_int32), ("reserved", C.c_int32)]

@@ -11,6 +11,7 @@ The methods mirror the reference's operator interface for the hot path:
   Batch.set_state ...... Estimator::vector2double for chosen windows of a resident batch (vilo_batch_set_state)
   Batch.save_state ..... the current state into the batch's snapshot slot (vilo_batch_save_state)
   Batch.restore_state .. the snapshot back, bit for bit (vilo_batch_restore_state)
+  Batch.dead_reckon_covariance  IntegrationBase::midPointIntegration's F, V covariance recurrence beside dead_reckon's state (vilo_batch_dead_reckon_covariance)
   Batch.gauss_newton_step  the step Ceres' linear solver computes, (H + mu D^2) delta = -g, per window (vilo_batch_gauss_newton_step)
 """
 import collections
@@ -45,6 +46,7 @@ def lib():
         L.vilo_last_gyro_align_ms.restype = C.c_double
         L.vilo_last_predict_ms.restype = C.c_double
         L.vilo_last_dead_reckon_ms.restype = C.c_double
+        L.vilo_last_dr_cov_ms.restype = C.c_double
         L.vilo_last_gauge_fix_ms.restype = C.c_double
         L.vilo_last_failure_detection_ms.restype = C.c_double
         L.vilo_last_repropagate_ms.restype = C.c_double
@@ -345,6 +347,60 @@ def _dead_reckon(ctx, n, samples, offsets, from_frame, write, trajectory, call):
     ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(state), _p(traj), rec))
     a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowDeadReckonRecord._fields_]), count=n).copy()
     return DeadReckoning(state, traj, step_offsets, a["n_steps"], a["status"])
+
+
+DeadReckonedCovariance = collections.namedtuple("DeadReckonedCovariance", "state cov pose_cov_trajectory step_offsets n_steps status")
+
+
+def dr_cov_opts(from_frame=-1):
+    """T.DrCovOpts of a dead_reckon_covariance call; needs no device. from_frame: -1 (each window's last frame) or 0 .. T.MAX_FRAMES - 1."""
+    if int(from_frame) != from_frame or not -1 <= from_frame <= T.MAX_FRAMES - 1:
+        raise ValueError("from_frame must be -1 (the last frame) or 0 .. %d" % (T.MAX_FRAMES - 1))
+    o = T.DrCovOpts()
+    o.from_frame, o.reserved = int(from_frame), 0
+    return o
+
+
+def dr_cov_in(frames, n_frames, from_frame=-1):
+    """cov_in [W, 15, 15] of a dead_reckon_covariance call, cut out of Batch.covariance()'s frames [W, 11, 19, 19]: for every window the
+    leading 15 x 15 (dp, dtheta, dv, dba, dbg; the leg bias does not enter the IMU recurrence) of the block of frame from_frame, -1: the
+    window's last, n_frames[w] - 1. Needs no device. A window that has no such frame gets zeros (the call reports it as NO_FRAME)."""
+    frames = np.asarray(frames, dtype=np.float64)
+    if frames.ndim != 4 or frames.shape[1:] != (T.F, T.COV_FRAME, T.COV_FRAME):
+        raise ValueError("frames must have shape (W, %d, %d, %d), got %s" % (T.F, T.COV_FRAME, T.COV_FRAME, frames.shape))
+    n_frames = np.asarray(n_frames)
+    if n_frames.shape != (frames.shape[0],) or n_frames.dtype.kind not in "iu" or (n_frames < 1).any() or (n_frames > T.MAX_FRAMES).any():
+        raise ValueError("n_frames must hold one frame count in 1 .. %d per window (%d)" % (T.MAX_FRAMES, frames.shape[0]))
+    dr_cov_opts(from_frame)
+    f = n_frames - 1 if from_frame == -1 else np.full(len(n_frames), int(from_frame))
+    out = np.zeros((len(n_frames), T.DR_COV_N, T.DR_COV_N))
+    have = f < n_frames
+    out[have] = frames[np.nonzero(have)[0], f[have], :T.DR_COV_N, :T.DR_COV_N]
+    return out
+
+
+def _dead_reckon_covariance(ctx, n, samples, offsets, cov_in, from_frame, pose_trajectory, call):
+    o = dr_cov_opts(from_frame)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    if offsets.shape != (n + 1,):
+        raise ValueError("offsets must have one entry per window of the call and one more (%d), got shape %s" % (n + 1, offsets.shape))
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must start at 0 and must not decrease")
+    samples = _c(samples).reshape(-1, T.SAMPLE_DOUBLES)
+    if len(samples) < offsets[-1]:
+        raise ValueError("offsets reach sample %d, samples holds %d" % (offsets[-1], len(samples)))
+    if cov_in is not None:
+        cov_in = _c(cov_in)
+        if cov_in.shape != (n, T.DR_COV_N, T.DR_COV_N):
+            raise ValueError("cov_in must have shape (%d, %d, %d), got %s" % (n, T.DR_COV_N, T.DR_COV_N, cov_in.shape))
+    step_offsets = np.zeros(n + 1, np.int64)
+    step_offsets[1:] = np.cumsum(np.maximum(np.diff(offsets) - 1, 0))
+    state, cov = np.zeros((n, T.DR_STATE)), np.zeros((n, T.DR_COV_N, T.DR_COV_N))
+    traj = np.zeros((int(step_offsets[-1]), T.DR_COV_POSE, T.DR_COV_POSE)) if pose_trajectory else None
+    rec = (T.WindowDeadReckonRecord * n)()
+    ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(cov_in), _p(state), _p(cov), _p(traj), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowDeadReckonRecord._fields_]), count=n).copy()
+    return DeadReckonedCovariance(state, cov, traj, step_offsets, a["n_steps"], a["status"])
 
 
 GaugeFix = collections.namedtuple("GaugeFix", "yaw_diff_deg singular status pose0_before")
@@ -753,6 +809,15 @@ class Batch:
         the windows with status T.DR_OK; otherwise the batch is left as it was."""
         return _dead_reckon(self.ctx, len(self._descs), samples, offsets, from_frame, write, trajectory,
                             lambda *a: lib().vilo_batch_dead_reckon(self.ctx.h, self.handle, *a))
+
+    def dead_reckon_covariance(self, samples, offsets, cov_in=None, from_frame=-1, pose_trajectory=False):
+        """vilo_batch_dead_reckon_covariance at the batch's device state: DeadReckonedCovariance(state [W, 10], bit for bit
+        dead_reckon()'s; cov [W, 15, 15] over (dp, dtheta, dv, dba, dbg), bitwise symmetric; pose_cov_trajectory [sum n_steps, 6, 6] or
+        None, the pose block after every step; step_offsets [W + 1]; n_steps and status (T.DR_*), each [W]): the covariance cov_in
+        [W, 15, 15] (None: zero; only its upper triangle is read; dr_cov_in() cuts it out of covariance()'s frames) of frame from_frame
+        (-1: each window's last) carried through the window's samples by Sigma <- F Sigma F^T + V Q V^T. The batch is left as it was."""
+        return _dead_reckon_covariance(self.ctx, len(self._descs), samples, offsets, cov_in, from_frame, pose_trajectory,
+                                       lambda *a: lib().vilo_batch_dead_reckon_covariance(self.ctx.h, self.handle, *a))
 
     def gauge_fix(self, anchor="uploaded", anchor_pose=None, pose0_before=False):
         """vilo_batch_gauge_fix, in place on the batch's device state (normally right after solve()): double2vector's re-anchoring of yaw
@@ -1200,6 +1265,15 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _dead_reckon(self, n, samples, offsets, from_frame, write, trajectory,
                             lambda *a: lib().vilo_window_dead_reckon(self.h, n, descs, states, *a))
+
+    def window_dead_reckon_covariance(self, windows, samples, offsets, cov_in=None, from_frame=-1, pose_trajectory=False):
+        """vilo_window_dead_reckon_covariance: Batch.dead_reckon_covariance of host windows at their current state arrays."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _dead_reckon_covariance(self, n, samples, offsets, cov_in, from_frame, pose_trajectory,
+                                       lambda *a: lib().vilo_window_dead_reckon_covariance(self.h, n, descs, states, *a))
 
     def window_gauge_fix(self, windows, anchor="given", anchor_pose=None, pose0_before=False):
         """vilo_window_gauge_fix: the gauge fix of host windows at their current state arrays, each with its own number of frames (see

@@ -1,5 +1,5 @@
 // The host frame of a call that queries a resident batch (marginalisation, covariance, residuals, gradient, triangulation, PnP, gyroscope-
-// bias alignment, next-frame prediction, dead reckoning, gauge fix, failure detection, retraction, set_state, Gauss-Newton step): BatchCall call(ctx, bt, &vilo_ctx::last_X_ms); the call's blocks of device memory, call.lay.take<T>(n); call.begin()
+// bias alignment, next-frame prediction, dead reckoning and its covariance, gauge fix, failure detection, retraction, set_state, Gauss-Newton step): BatchCall call(ctx, bt, &vilo_ctx::last_X_ms); the call's blocks of device memory, call.lay.take<T>(n); call.begin()
 // (one allocation out of the batch's arena, given back when `call` dies); uploads that are not to be timed; call.start(); the copies and
 // launches on ctx->stream, at call.ptr<T>(offset); call.finish() (launch errors, the stream drained, last_X_ms written);
 // call.down(host, dev, bytes) for every output the caller may have asked for.

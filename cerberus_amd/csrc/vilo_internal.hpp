@@ -50,7 +50,8 @@ struct vilo_ctx {
   double last_gyro_ms = 0.0;       // GPU time of the last vilo_batch_gyro_bias_align (k_gyro_bias_align and, with samples in force, the re-integration)
   double last_predict_ms = 0.0;    // GPU time of the last vilo_batch_predict_next_frame (k_predict_next_frame + k_predict_windows)
   double last_dead_reckon_ms = 0.0;   // GPU time of the last vilo_batch_dead_reckon (k_dead_reckon)
-  double last_gauge_fix_ms = 0.0;     // GPU time of the last vilo_batch_gauge_fix (k_gauge_fix_x)
+  double last_dr_cov_ms = 0.0;        // GPU time of the last vilo_batch_dead_reckon_covariance (k_dr_covariance)
+  double last_gauge_fix_ms = 0.0;    // GPU time of the last vilo_batch_gauge_fix (k_gauge_fix_x)
   double last_failure_ms = 0.0;       // GPU time of the last vilo_batch_failure_detection (k_failure_detection)
   double last_mask_ms = 0.0;          // GPU time of the last vilo_batch_mask_landmarks (k_mask_landmarks + k_mask_windows; with OUTLIER_FLAGS also k_resid_landmarks)
   double last_reprop_ms = 0.0;        // GPU time of the last vilo_batch_repropagate (k_reprop_point; with write also the integration, k_reprop_commit and the preparation)

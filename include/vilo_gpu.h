@@ -497,7 +497,7 @@ double vilo_last_residuals_ms(const vilo_ctx *ctx);
  * The other calls on a resident batch, while at least one landmark is masked:
  *   honour the mask   vilo_batch_solve, _download, _residuals, _marginalize (a masked landmark that starts at frame 0 is left out of the
  *                     eliminated set, as the deleted one is: no detour through the eigen path);
- *   do not read landmarks   vilo_batch_gauge_fix, _failure_detection, _gyro_bias_align, _dead_reckon, _repropagate, _set_samples, _prepare, _reset;
+ *   do not read landmarks   vilo_batch_gauge_fix, _failure_detection, _gyro_bias_align, _dead_reckon, _dead_reckon_covariance, _repropagate, _set_samples, _prepare, _reset;
  *   refuse            vilo_batch_covariance, _landmark_covariance, _gradient, _triangulate, _frame_pose_pnp, _predict_next_frame return
  *                     VILO_ERR_UNSUPPORTED with vilo_last_error saying so; they work again after VILO_MASK_CLEAR (or a mask that selects nothing).
  * records [W] (optional): status VILO_MASK_OK, or VILO_MASK_NO_LANDMARKS for a window left without a landmark (not an error: it solves as
@@ -983,6 +983,63 @@ int vilo_window_dead_reckon(vilo_ctx *ctx, int n_windows, const vilo_window_desc
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_dead_reckon: k_dead_reckon, without the packing and upload of the samples
  * and the copies out. */
 double vilo_last_dead_reckon_ms(const vilo_ctx *ctx);
+
+/* ---- covariance of a frame's state carried through IMU samples (the error-state recurrence of IntegrationBase::midPointIntegration,
+ * integration_base.h:103-137, written in the world frame beside vilo_batch_dead_reckon's nominal state) ----
+ * The IMU-rate odometry vilo_batch_dead_reckon produces, with its uncertainty: per window, f = opts->from_frame (-1: the window's last
+ * frame) and the samples [offsets[w], offsets[w + 1]) in vilo_batch_dead_reckon's convention (the first sample of the range plays
+ * (acc_0, gyr_0), its dt is not read; every later sample is one step).
+ *   nominal  P, R, V, Ba, Bg are vilo_batch_dead_reckon's: the same start, the same step in the same order of operations, the
+ *            un-normalised R(deltaQ(.)). state_out[w][10] is bit for bit what vilo_batch_dead_reckon returns for the same arguments.
+ *   error    15 coordinates, in the order and meaning of the leading 15 entries of vilo_batch_covariance's frame block: dp (world),
+ *            dtheta (body frame, right perturbation), dv (world), dba, dbg: IntegrationBase's O_P, O_R, O_V, O_BA, O_BG.
+ *   start    Sigma = cov_in[w] (15 x 15, row-major). Only the upper triangle with the diagonal is read; the lower is taken as its mirror.
+ *            cov_in NULL: zero. (The leg bias does not enter the IMU recurrence: the leading 15 x 15 of a 19 x 19 frame block is the
+ *            marginal to pass.)
+ *   step     with sample s after s0, dt = s.dt, R0 the nominal R before the step's update and R1 after it:
+ *              Sigma <- F Sigma F^T + V Q V^T
+ *            F (15 x 15) and V (15 x 18) are the blocks of integration_base.h:103-132 with delta_q.toRotationMatrix() -> R0,
+ *            result_delta_q.toRotationMatrix() -> R1, linearized_ba / bg -> the frame's Ba, Bg, and R_w_x, R_a_0_x, R_a_1_x the skew
+ *            matrices of the nominal step's un_gyr, s0.acc - Ba, s.acc - Ba. With a = dt^2 / 4, h = dt / 2, A = R0 R_a_0_x,
+ *            C = R1 R_a_1_x, K = I - R_w_x dt:
+ *              F = [ I   -a (A + C K)   dt I   -a (R0 + R1)    a dt C ]      V = [ a R0   -a h C   a R1   -a h C   0      0    ]
+ *                  [ 0    K             0       0             -dt I   ]          [ 0       h I     0       h I     0      0    ]
+ *                  [ 0   -h (A + C K)   I      -h (R0 + R1)    h dt C ]          [ h R0   -h h C   h R1   -h h C   0      0    ]
+ *                  [ 0    0             0       I              0      ]          [ 0       0       0       0       dt I   0    ]
+ *                  [ 0    0             0       0              I      ]          [ 0       0       0       0       0      dt I ]
+ *            Gravity does not appear: it is constant.
+ *   Q        the 18 x 18 diagonal exactly as vilo_preintegrate_imu builds it (kernels_preint.hip, preint_imu_body, the line marked
+ *            integration_base.h:31-37): cfg.acc_n^2 (3), gyr_n^2 (3), acc_n^2 (3), gyr_n^2 (3), acc_w^2 (3), gyr_w^2 (3). ACC_N on all
+ *            three axes: cfg.acc_n_z belongs to the leg record and does not enter.
+ * Outputs: cov_out[w][15][15], full, stored from the upper triangle so that it is bitwise symmetric; pose_cov_trajectory (may be NULL)
+ * [sum n_steps][6][6], the pose block (dp, dtheta) after every step in vilo_batch_dead_reckon's trajectory order, what an odometry
+ * message's covariance field holds (a window's last row is the pose block of cov_out[w] bit for bit); state_out[w][10]; records[w] (may
+ * be NULL) = {n_steps, status}. A range of 0 or 1 samples makes no step: cov_out[w] is then the mirrored cov_in[w] (or zeros), bit for bit.
+ * Statuses: VILO_DR_OK / VILO_DR_NO_FRAME / VILO_DR_NUMERIC with vilo_batch_dead_reckon's meaning; NUMERIC also for a value that is not
+ * finite in the triangle of cov_in[w] that is read, or in the resulting covariance. For a failed window state_out[w], cov_out[w] and
+ * its trajectory rows are zeros; the other windows of the batch are not affected.
+ * Side effects: none; there is no write option (the call is no state-changing call). The call's device memory is returned when it
+ * returns. Every output of a window is bitwise independent of the batch it shares and of its position in it. opts NULL:
+ * vilo_default_dr_cov_opts.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched, the caller's arrays untouched): as for vilo_batch_dead_reckon, and with windows
+ * present a NULL cov_out; reserved other than 0. */
+typedef struct {
+  int32_t from_frame;       /* -1: each window's last frame; else 0 .. VILO_MAX_FRAMES - 1 */
+  int32_t reserved;         /* 0 */
+} vilo_dr_cov_opts;
+void vilo_default_dr_cov_opts(vilo_dr_cov_opts *o);
+
+int vilo_batch_dead_reckon_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_dr_cov_opts *opts, const vilo_sample *samples,
+                                      const int32_t *offsets, const double *cov_in, double *state_out, double *cov_out,
+                                      double *pose_cov_trajectory, vilo_window_dead_reckon_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed. */
+int vilo_window_dead_reckon_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                       const vilo_dr_cov_opts *opts, const vilo_sample *samples, const int32_t *offsets, const double *cov_in,
+                                       double *state_out, double *cov_out, double *pose_cov_trajectory,
+                                       vilo_window_dead_reckon_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_dead_reckon_covariance: k_dr_covariance, without the packing and upload
+ * of the samples and of cov_in and the copies out. */
+double vilo_last_dr_cov_ms(const vilo_ctx *ctx);
 
 /* ---- double2vector's gauge fix on a resident batch (estimator.cpp:903-1003) ---------------------------------------------------------
  * After vilo_batch_solve the batch's device state is the raw solver output (para_*). The reference never reads that state:
