@@ -135,6 +135,16 @@ class HessVecRecord(C.Structure):
     _fields_ = [("vHv", C.c_double), ("g_dot_v", C.c_double), ("model_cost_change", C.c_double), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+TRIAL_MAX_STEPS = 16  # VILO_TRIAL_MAX_STEPS
+TRIAL_OK, TRIAL_NUMERIC, TRIAL_INVALID, TRIAL_NOT_FINITE = 0, 1, 2, 3   # vilo_trial_record.status
+
+
+class TrialRecord(C.Structure):
+    """vilo_trial_record (48 bytes)"""
+    _fields_ = [("cost", C.c_double), ("visual_cost", C.c_double), ("imu_cost", C.c_double), ("prior_cost", C.c_double),
+                ("cost_change", C.c_double), ("n_negative_depth", C.c_int32), ("status", C.c_int32)]
+
+
 class MaskOpts(C.Structure):
     """vilo_mask_opts (24 bytes)"""
     _fields_ = [("source", C.c_int32), ("combine", C.c_int32), ("flag_bits", C.c_uint32), ("pad", C.c_int32), ("outlier_threshold_px", C.c_double)]

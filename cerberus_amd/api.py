@@ -55,6 +55,7 @@ def lib():
         L.vilo_last_set_state_ms.restype = C.c_double
         L.vilo_last_gn_step_ms.restype = C.c_double
         L.vilo_last_hess_vec_ms.restype = C.c_double
+        L.vilo_last_trial_cost_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
     return _lib
@@ -665,6 +666,46 @@ def _hess_vec(ctx, descs, state_vec, lm_vec, state, landmarks, call):
     return HessianVector(so, lo, offsets, K, a["vHv"], a["g_dot_v"], a["model_cost_change"], a["status"])
 
 
+TrialCost = collections.namedtuple("TrialCost", "cost visual_cost imu_cost prior_cost cost_change n_negative_depth status base best n_steps offsets")
+TrialBase = collections.namedtuple("TrialBase", "cost visual_cost imu_cost prior_cost cost_change n_negative_depth status")
+
+
+def trial_cost_args(descs, state_step=None, lm_step=None, alpha=None):
+    """(K, squeeze, state_step [W, K, 222] or None, lm_step [K sum L] or None, alpha [W, K] or None, offsets) of a trial_cost call,
+    checked; needs no device. state_step and lm_step as hess_vec_args takes its vectors ([W, 222] or [sum L]: one step); alpha [W, K], or
+    [W] for one step, or None for 1."""
+    n = len(descs)
+    K, squeeze, sv, lv, offsets = hess_vec_args(descs, state_step, lm_step)
+    if alpha is not None:
+        alpha = _c(alpha)
+        if alpha.ndim == 1 and K == 1:
+            alpha = alpha[:, None]
+        if alpha.shape != (n, K):
+            raise ValueError("alpha must be [%d, %d]%s, got %s" % (n, K, " or [%d]" % n if K == 1 else "", alpha.shape))
+        alpha = _c(alpha)
+    return K, squeeze, sv, lv, alpha, offsets
+
+
+def _trial_fields(rec, count):
+    return np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.TrialRecord._fields_]),
+                         count=count).copy()
+
+
+def _trial_cost(ctx, descs, state_step, lm_step, alpha, base, best, call):
+    n = len(descs)
+    K, squeeze, sv, lv, al, offsets = trial_cost_args(descs, state_step, lm_step, alpha)
+    rec = (T.TrialRecord * (n * K))()
+    brec = (T.TrialRecord * n)() if base else None
+    bk = np.full(n, -2, np.int32) if best else None
+    ctx._check(call(K, _p(sv), _p(lv), _p(al), brec, rec, T.iptr(bk) if best else None))
+    a = _trial_fields(rec, n * K).reshape(n, K)
+    if squeeze:
+        a = a[:, 0]
+    names = [f for f, _ in T.TrialRecord._fields_]
+    b = TrialBase(*[_trial_fields(brec, n)[f] for f in names]) if base else None
+    return TrialCost(*[a[f] for f in names], b, bk, K, offsets)
+
+
 class Batch:
     """Device-resident batch of windows (vilo_batch)."""
 
@@ -877,6 +918,16 @@ class Batch:
         for i, w in enumerate(windows):
             states[i] = w.desc(T)[1]
         self.ctx._check(lib().vilo_batch_set_state(self.ctx.h, self.handle, len(ids), T.iptr(ids), states))
+
+    def trial_cost(self, state_step=None, lm_step=None, alpha=None, base=True, best=True):
+        """vilo_batch_trial_cost: the cost at x [+] alpha[w][k] * step_k for K <= 16 steps per window, the batch left exactly as it is.
+        state_step [W, K, 222] (or [W, 222]: one step), lm_step [K sum L] in hessian_vector's layout (hess_vec_lm_block views it), alpha
+        [W, K] or None for 1 (see trial_cost_args). TrialCost(cost, visual_cost, imu_cost (the intervals' sum), prior_cost, cost_change
+        (base cost - cost), n_negative_depth, status (T.TRIAL_*) [W, K] ([W] for one step given as [W, 222] / [sum L]), base (TrialBase
+        of [W] arrays: the same at x itself) or None, best [W] (the lowest-cost OK step that lowers the cost, -1: none) or None, n_steps,
+        offsets). The trial states are bit for bit what retract() would leave; commit a step with retract()."""
+        return _trial_cost(self.ctx, self._descs, state_step, lm_step, alpha, base, best,
+                           lambda *a: lib().vilo_batch_trial_cost(self.ctx.h, self.handle, *a))
 
     def save_state(self):
         """vilo_batch_save_state: the current device state into the batch's one snapshot slot (allocated at the first call)."""
@@ -1326,6 +1377,15 @@ class Context:
         return _gn_step(self, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
                         lambda *a: lib().vilo_window_gauss_newton_step(self.h, n, descs, states, *a))
 
+    def window_trial_cost(self, windows, state_step=None, lm_step=None, alpha=None, base=True, best=True):
+        """vilo_window_trial_cost: the trial costs of host windows at their current state arrays (see Batch.trial_cost)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _trial_cost(self, descs, state_step, lm_step, alpha, base, best,
+                           lambda *a: lib().vilo_window_trial_cost(self.h, n, descs, states, *a))
+
     def window_hessian_vector(self, windows, state_vec=None, lm_vec=None, state=True, landmarks=True):
         """vilo_window_hessian_vector: the products of host windows at their current state arrays (see Batch.hessian_vector)."""
         n = len(windows)
@@ -1338,3 +1398,8 @@ class Context:
     def marginalize(self, w, mode, prior_out):
         d, s = w.desc(T)
         self._check(lib().vilo_marginalize(self.h, 1, C.byref(d), C.byref(s), mode, C.byref(prior_out.struct)))
+
+
+def window_trial_cost(ctx, windows, state_step=None, lm_step=None, alpha=None, base=True, best=True):
+    """Context.window_trial_cost as a function: the host-window form of Batch.trial_cost."""
+    return ctx.window_trial_cost(windows, state_step, lm_step, alpha, base, best)

@@ -12,6 +12,7 @@
 //                and out per window: the kernel is paced by memory latency, not by arithmetic.
 //   k_set_state  one wave per named window: its packed 240-double row and its inverse depths (device order) copied over the current ones.
 //
+// The two passes are retract_step.hpp's rt_scan / rt_store, which k_trial_states (kernels_trial.hip) runs too.
 // Rounding. s = alpha * delta and x + s are each rounded once (rt_mul / rt_add: contraction off), so numpy restates them to the bit
 // (tests/retract_ref.py); pose_plus is compiled as kernels_eval.hip compiles it (the file's default contraction, a function of its own:
 // rt_pose_plus), so a pose block is bit for bit vilo_pose_plus(x, s). step_norm's sum of squares is carried in two doubles (TwoSum): the lanes' order of summation leaves no trace
@@ -21,17 +22,11 @@
 #include <vector>
 
 #include "batch_call.hpp"
+#include "retract_step.hpp"
 #include "vilo_math.hpp"
 
 static_assert(sizeof(vilo_retract_opts) == 8, "vilo_retract_opts: 8 bytes (include/vilo_gpu.h)");
 static_assert(sizeof(vilo_window_retract_record) == 24, "vilo_window_retract_record: 24 bytes (include/vilo_gpu.h)");
-
-#define RT_STATE 222                      // vilo_batch_gradient's state_grad row
-#define RT_SB 66                          // its speed-bias, leg-bias, extrinsic and td entries
-#define RT_LB 165
-#define RT_EX 209
-#define RT_TD 221
-#define RT_EUCLID (99 + 44 + 1)           // Euclidean coordinates of a window: speed-bias, leg bias, td
 
 struct RetractArgs {
   const double *state_step;               // [W][RT_STATE], or null
@@ -42,81 +37,19 @@ struct RetractArgs {
   int uploaded;                           // 1: the step is applied to x0 / lam0
 };
 
-namespace {
-
-__device__ __forceinline__ double rt_mul(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ double rt_add(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-// vilo::pose_plus as a function of its own, memory to memory, the way k_pose_plus (kernels_eval.hip) runs it. Which of a quaternion
-// product's multiplies the compiler fuses into the following addition depends on what surrounds the expression: inlined here on steps that
-// are themselves products in registers, it fuses qw * bz instead of qx * by in the z component and the result is an ulp off
-// vilo_pose_plus's. Compiled on its own it is instruction for instruction k_pose_plus's arithmetic (tests/test_retract_gpu.py holds the
-// bytes). The 13 lanes that call it pass the step and take the result through private memory.
-__device__ __noinline__ void rt_pose_plus(const double *x, const double *s, double *out) { vilo::pose_plus(x, s, out); }
-
-// count, max |s| and sum s^2 (hi + lo, TwoSum) of the steps a lane applies
-struct StepStats {
-  double hi, lo, mx;
-  int n, bad;
-};
-__device__ __forceinline__ void rt_two_sum(double &hi, double &lo, double v, double vlo) {
-#pragma clang fp contract(off)
-  const double t = hi + v, bb = t - hi, e = (hi - (t - bb)) + (v - bb);
-  hi = t;
-  lo = (lo + vlo) + e;
-}
-__device__ __forceinline__ void rt_count(StepStats &st, double s) {
-  st.bad |= !isfinite(s);
-  st.n += 1;
-  st.mx = fmax(st.mx, fabs(s));
-  rt_two_sum(st.hi, st.lo, rt_mul(s, s), 0.0);
-}
-
-// Euclidean coordinate e < RT_EUCLID of a window: its entry of the state row, of the step row, and whether it is stepped
-__device__ __forceinline__ bool rt_euclid(int e, int F, int use_leg, int cmask, int &xo, int &so) {
-  if (e < 99) { xo = XO_SB + e; so = RT_SB + e; return e / 9 < F; }
-  if (e < 143) { xo = XO_LB + (e - 99); so = RT_LB + (e - 99); return (e - 99) / 4 < F && use_leg && !(cmask & CONST_LB); }
-  xo = XO_TD; so = RT_TD;
-  return !(cmask & CONST_TD);
-}
-// pose-type block blk < 13 (11 frames, 2 extrinsics)
-__device__ __forceinline__ bool rt_block(int blk, int F, int cmask, int &xo, int &so) {
-  if (blk < 11) { xo = XO_POSE + 7 * blk; so = 6 * blk; return blk < F; }
-  xo = XO_EX + 7 * (blk - 11); so = RT_EX + 6 * (blk - 11);
-  return !(cmask & CONST_EX);
-}
-
-}  // namespace
-
 __global__ void __launch_bounds__(64) k_retract(BatchDev b, RetractArgs a) {
   const int win = blockIdx.x, lane = threadIdx.x;
   const WinMeta wm = b.win[win];
-  const int F = wm.n_frames, cmask = wm.const_mask, L = wm.L;
-  const double al = a.alpha ? a.alpha[win] : 1.0;
-  const double *step = a.state_step ? a.state_step + (size_t)win * RT_STATE : nullptr;
-  const double *src = (a.uploaded ? b.x0 : b.x) + (size_t)win * XSTRIDE, *lsrc = a.uploaded ? b.lam0 : b.lam;
-  double *x = b.x + (size_t)win * XSTRIDE;
+  const double *src = (a.uploaded ? b.x0 : b.x) + (size_t)win * XSTRIDE, *lsrc = (a.uploaded ? b.lam0 : b.lam) + wm.lm_off;
+  StepView v;
+  v.step = a.state_step ? a.state_step + (size_t)win * RT_STATE : nullptr;
+  v.lm_step = a.lm_step ? a.lm_step + wm.lm_off : nullptr;
+  v.mask = a.mask;
+  v.perm = b.lm_perm;
+  v.al = a.alpha ? a.alpha[win] : 1.0;
 
   // pass 1: every s that would be applied, tested and summed; nothing is stored
-  StepStats st = {0.0, 0.0, 0.0, 0, !isfinite(al)};
-  int bxo = 0, bso = 0;
-  const bool blk_on = lane < 13 && rt_block(lane, F, cmask, bxo, bso);
-  if (blk_on)
-    for (int c = 0; c < 6; ++c) rt_count(st, rt_mul(al, step ? step[bso + c] : 0.0));
-  for (int e = lane; e < RT_EUCLID; e += 64) {
-    int xo, so;
-    if (rt_euclid(e, F, wm.use_leg, cmask, xo, so)) rt_count(st, rt_mul(al, step ? step[so] : 0.0));
-  }
-  for (int l = lane; l < L; l += 64) {
-    const int gi = wm.lm_off + l;
-    if (!(a.mask && a.mask[gi])) rt_count(st, rt_mul(al, a.lm_step ? a.lm_step[wm.lm_off + b.lm_perm[gi]] : 0.0));
-  }
+  StepStats st = rt_scan(wm, v, lane);
   const bool numeric = __any(st.bad);   // (wave-wide: the same for every lane, before the window's first store)
   for (int off = 32; off > 0; off >>= 1) {
     const double ph = __shfl_xor(st.hi, off, 64), pl = __shfl_xor(st.lo, off, 64);
@@ -135,31 +68,7 @@ __global__ void __launch_bounds__(64) k_retract(BatchDev b, RetractArgs a) {
   if (numeric && !a.uploaded) return;   // the window stays as it is
 
   // pass 2: the same items again, stored. What is not stepped is written only with UPLOADED (the reset's copy).
-  if (lane < 13) {
-    double out[7];
-    if (blk_on && !numeric) {
-      double s6[6];
-      for (int c = 0; c < 6; ++c) s6[c] = rt_mul(al, step ? step[bso + c] : 0.0);
-      rt_pose_plus(src + bxo, s6, out);
-    } else {
-      for (int c = 0; c < 7; ++c) out[c] = src[bxo + c];
-    }
-    if ((blk_on && !numeric) || a.uploaded)
-      for (int c = 0; c < 7; ++c) x[bxo + c] = out[c];
-  }
-  for (int e = lane; e < RT_EUCLID; e += 64) {
-    int xo, so;
-    const bool on = rt_euclid(e, F, wm.use_leg, cmask, xo, so) && !numeric;
-    if (on) x[xo] = rt_add(src[xo], rt_mul(al, step ? step[so] : 0.0));
-    else if (a.uploaded) x[xo] = src[xo];
-  }
-  if (a.uploaded && lane < XSTRIDE - (XO_TD + 1)) x[XO_TD + 1 + lane] = src[XO_TD + 1 + lane];   // (the row's padding)
-  for (int l = lane; l < L; l += 64) {
-    const int gi = wm.lm_off + l;
-    const bool on = !(a.mask && a.mask[gi]) && !numeric;
-    if (on) b.lam[gi] = rt_add(lsrc[gi], rt_mul(al, a.lm_step ? a.lm_step[wm.lm_off + b.lm_perm[gi]] : 0.0));
-    else if (a.uploaded) b.lam[gi] = lsrc[gi];
-  }
+  rt_store(wm, v, lane, src, lsrc, b.x + (size_t)win * XSTRIDE, b.lam + wm.lm_off, !numeric, a.uploaded != 0);
 }
 
 struct SetStateArgs {

@@ -671,6 +671,49 @@ int vilo_window_hessian_vector(vilo_ctx *ctx, int n_windows, const vilo_window_d
 /* GPU time (HIP events on ctx's stream) of the last vilo_batch_hessian_vector: linearisation + k_hess_vec, without the copies. */
 double vilo_last_hess_vec_ms(const vilo_ctx *ctx);
 
+/* ---- the cost at up to 16 trial steps from the current state, without moving it (the actual decrease of a trust-region gain ratio, a
+ * backtracking line search, a ladder of damped steps; TrustRegionMinimizer's candidate evaluation opened to the caller) ----
+ * Definition. For every window w and each of its K = n_steps steps delta_k the trial state is x_k = x [+] alpha[w][k] * delta_k, exactly
+ * vilo_batch_retract with base CURRENT: s = alpha * delta rounded once, x + s rounded once, pose and extrinsic blocks through
+ * vilo_pose_plus — the two calls run one device function. The same coordinates are not read (constant blocks, absent frames, masked
+ * landmarks): NaN there is harmless. records[w][k] holds the costs vilo_batch_residuals would report at x_k: visual_cost, the sum of its
+ * ten imu_cost, prior_cost (k_accept's normal-equation form), and cost, their sum in that call's order (prior, intervals 0 .. 9, visual);
+ * cost_change = base cost - cost; n_negative_depth counts the unmasked landmarks whose trial inverse depth is < 0.
+ * base (optional) [W]: the same record at x itself — x as it stands, not a zero-step retract, which would normalise the quaternions
+ * again — with cost_change 0. best (optional) [W]: the smallest k of status OK with the lowest cost among those with cost_change > 0, or -1.
+ * Layouts, as vilo_batch_hessian_vector: state_step [W][K][222], every row in state_grad's layout; lm_step [K sum L], window w's block at
+ * K * (sum of L of the windows before it), step k at k * L_w inside it, in the caller's vilo_window_desc order; alpha [W][K] or NULL for
+ * 1; records [W][K]. state_step or lm_step NULL: zero. Masked landmarks (vilo_batch_mask_landmarks) are honoured as vilo_batch_residuals
+ * and vilo_batch_retract honour them: they contribute nothing and their steps are not read.
+ * Status per (window, step): OK; NUMERIC alpha or a read entry of the step is not finite: the record's doubles are NaN, its counts 0, the
+ * window's other steps and the other windows are untouched; INVALID a live preintegration record of the window has no sqrt_info (as
+ * vilo_batch_residuals' status 2): imu_cost, cost and cost_change are NaN, in base too; NOT_FINITE the step is finite, the cost at the
+ * trial state is not: the values as computed.
+ * No side effects: current and uploaded state, snapshot slot, records, mask, solve summaries and SolverStates are not written; a
+ * vilo_batch_solve after the call is bit for bit the solve without it. With vilo_batch_set_samples in force the call returns
+ * VILO_ERR_UNSUPPORTED and writes nothing (K re-integrations at K bias sets are another matter). Its device memory is returned when the
+ * call returns. Every record is bitwise independent of the batch the window shares, of its position in it, of K and of k: column 0 of
+ * a K = 5 call is the K = 1 call on that step. No floating-point atomics; every sum has a fixed order.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing written): NULL ctx, batch or records, n_steps outside 1 .. VILO_TRIAL_MAX_STEPS, n_windows < 1. */
+#define VILO_TRIAL_MAX_STEPS 16
+#define VILO_TRIAL_OK 0
+#define VILO_TRIAL_NUMERIC 1      /* alpha or a read entry of the step not finite: record NaN */
+#define VILO_TRIAL_INVALID 2      /* a live record of the window has no sqrt_info (as vilo_batch_residuals' status 2): NaN */
+#define VILO_TRIAL_NOT_FINITE 3   /* the step is finite, the cost at the trial state is not: the values as computed */
+typedef struct {
+  double cost, visual_cost, imu_cost, prior_cost;   /* as vilo_window_residual's, at the trial state; imu_cost = the sum over the intervals */
+  double cost_change;                               /* base cost - cost: positive = the step lowers the cost */
+  int32_t n_negative_depth, status;                 /* unmasked landmarks whose trial inverse depth is < 0; VILO_TRIAL_* */
+} vilo_trial_record;   /* 48 bytes */
+int vilo_batch_trial_cost(vilo_ctx *ctx, vilo_batch *batch, int n_steps, const double *state_step, const double *lm_step,
+                          const double *alpha, vilo_trial_record *base, vilo_trial_record *records, int32_t *best);
+/* The same for host windows at the given states: one batch is created, queried once and destroyed. */
+int vilo_window_trial_cost(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state, int n_steps,
+                           const double *state_step, const double *lm_step, const double *alpha, vilo_trial_record *base,
+                           vilo_trial_record *records, int32_t *best);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_trial_cost: its four kernels, without the copies. */
+double vilo_last_trial_cost_ms(const vilo_ctx *ctx);
+
 /* ---- landmark depths from the current poses (FeatureManager::triangulate, feature_manager.cpp:302-382 with triangulatePoint :198-212; the
  * arithmetic of FeatureManager::removeBackShiftDepth :450-479) ----
  * State: the batch's current state, what vilo_batch_download returns. Rotation matrices are taken from the normalised quaternions, as
