@@ -9,9 +9,10 @@
 //   P  (79, LDS)      poses 6k..6k+5, ex0 66..71, ex1 72..77, td 78 (79: padding, treated as a constant dimension)
 //   B  (11 x 13)      speed / bias / leg bias of frame k: block tridiagonal (the IMU factors couple consecutive frames only)
 //   BP (143 x 80)     coupling of B with P (IMU factors: poses k-1, k, k+1; the prior: any pose / extrinsic / td)
-// Steps:
-//   1. Assemble H = J^T J without damping: visual Gram slots into P, the landmarks' Schur complement P -= w w^T / E, IMU Grams, prior.
-//   2. FRAME0 gauge: frame 0's rotation rows / columns in the basis [e1 e2 u] (u = R0^T e_z): the u direction and frame 0's position
+// The reading of the linearisation (assembly, gauge, scaling, 13 x 13 Cholesky) is gn_system.hpp's, shared with k_gn_step. Steps:
+//   1. Assemble H = J^T J without damping: visual Gram slots into P (assemble_visual_pose_block), IMU Grams (assemble_imu_grams), prior
+//      (assemble_prior), the landmarks' Schur complement P -= w w^T / E.
+//   2. FRAME0 gauge (gauge_basis, gauge_rotate): frame 0's rotation rows / columns in the basis [e1 e2 u] (u = R0^T e_z): the u direction and frame 0's position
 //      become constant dimensions; Sigma = N (N^T H N)^-1 N^T is the inverse with those rows and columns left out.
 //   3. Jacobi equilibration (unit diagonal of the reduced camera system); a constant or absent dimension gets scale 0 (its rows come out
 //      zero) and a unit pivot.
@@ -27,14 +28,11 @@
 #include <algorithm>
 
 #include "batch_call.hpp"
-#include "solve_common.hpp"
-#include "vilo_math.hpp"
+#include "gn_system.hpp"
 
 static_assert(sizeof(vilo_cov_opts) == 24, "vilo_cov_opts layout (cerberus_amd/_ctypes.py mirrors it)");
 
-#define CV_T 256            // threads per window
 #define CV_NB 13
-#define CV_NP 80
 #define CV_FR 19
 #define CV_FRN (VILO_MAX_FRAMES * CV_FR * CV_FR)   // 3971 doubles of frame blocks per window
 #define CV_PN (VILO_NPU * VILO_NPU)                // 6241 doubles of the pose system per window
@@ -45,13 +43,13 @@ static_assert(sizeof(vilo_cov_opts) == 24, "vilo_cov_opts layout (cerberus_amd/_
 #define CS_LI (CS_AO + 11 * 169)             // [11][13][13] L_k^-1
 #define CS_T (CS_LI + 11 * 169)              // [11][13][13] T_k = A_{k,k-1} L_{k-1}^-T
 #define CS_BP (CS_T + 11 * 169)              // [143][80] BP, then Y, then G
-#define CS_N (CS_BP + 143 * CV_NP)
+#define CS_N (CS_BP + 143 * GN_NP)
 // LDS (doubles)
 #define CL_P 0                               // [80][80] pose system, then Sigma_PP (scaled)
-#define CL_S (CL_P + CV_NP * CV_NP)          // [80][80] landmark staging / L_P^-1 / output staging
-#define CL_Z (CL_S + CV_NP * CV_NP)          // [13][80]
-#define CL_M (CL_Z + CV_NB * CV_NP)          // [13][80]
-#define CL_SM (CL_M + CV_NB * CV_NP)         // six 13 x 13: ss, lc, lp, tn, vs, xs
+#define CL_S (CL_P + GN_NP * GN_NP)          // [80][80] landmark staging / L_P^-1 / output staging
+#define CL_Z (CL_S + GN_NP * GN_NP)          // [13][80]
+#define CL_M (CL_Z + CV_NB * GN_NP)          // [13][80]
+#define CL_SM (CL_M + CV_NB * GN_NP)         // six 13 x 13: ss, lc, lp, tn, vs, xs
 #define CL_D (CL_SM + 6 * 169)               // [224] scale of every camera dimension (0: constant / absent)
 #define CL_Q (CL_D + CD_N)                   // [9] Q = [e1 e2 u] (column-major: Q[3 m + i] = i-th entry of column m)
 #define CL_N (CL_Q + 16)
@@ -71,24 +69,10 @@ __device__ __forceinline__ bool cov_active(int cd, const WinMeta &wm, int gauge)
   return true;
 }
 
-// in-place Cholesky of the 13 x 13 block ss (lower triangle), then li = L^-1 (lower, upper zeroed). *bad when a pivot <= thr.
-__device__ void cov_chol13(double *ss, double *li, double thr, int *bad) {
+// in-place Cholesky of the 13 x 13 block ss (chol13, gn_system.hpp), then li = L^-1 (lower, upper zeroed). *bad when a pivot <= thr.
+__device__ __forceinline__ void cov_chol13(double *ss, double *li, double thr, int *bad) {
   const int tid = threadIdx.x;
-  for (int j = 0; j < CV_NB; ++j) {
-    if (tid == 0) {
-      double p = ss[j * 13 + j];
-      if (!(p > thr)) { *bad = 1; p = 1.0; }
-      ss[j * 13 + j] = sqrt(p);
-    }
-    __syncthreads();
-    if (tid > j && tid < CV_NB) ss[tid * 13 + j] /= ss[j * 13 + j];
-    __syncthreads();
-    for (int e = tid; e < 169; e += CV_T) {
-      const int r = e / 13, c = e % 13;
-      if (c > j && r >= c) ss[e] -= ss[r * 13 + j] * ss[c * 13 + j];
-    }
-    __syncthreads();
-  }
+  chol13(ss, thr, bad);
   if (tid < CV_NB) {
     const int c = tid;
     for (int r = 0; r < c; ++r) li[r * 13 + c] = 0.0;
@@ -101,7 +85,7 @@ __device__ void cov_chol13(double *ss, double *li, double thr, int *bad) {
   __syncthreads();
 }
 
-__global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gauge, double thr, int want_poses, double *scr, double *frames_out,
+__global__ void __launch_bounds__(GN_T) k_covariance(BatchDev b, int w0, int gauge, double thr, int want_poses, double *scr, double *frames_out,
                                                     double *poses_out, int *status_out) {
   extern __shared__ double lds[];
   __shared__ int bad_s;
@@ -116,100 +100,35 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
   const bool invalid = b.win_bad && b.win_bad[w];
   if (tid == 0) bad_s = 0;
   if (invalid) {   // a preintegration covariance without sqrt_info: the window is not linearised (k_init_state marks it done)
-    for (int e = tid; e < CV_FRN; e += CV_T) fo[e] = NAN;
-    if (po) for (int e = tid; e < CV_PN; e += CV_T) po[e] = NAN;
+    for (int e = tid; e < CV_FRN; e += GN_T) fo[e] = NAN;
+    if (po) for (int e = tid; e < CV_PN; e += GN_T) po[e] = NAN;
     if (tid == 0) status_out[w] = 2;
     return;
   }
-  for (int e = tid; e < CV_NP * CV_NP; e += CV_T) Pm[e] = 0.0;
-  for (int e = tid; e < CS_N; e += CV_T) G[e] = 0.0;
+  for (int e = tid; e < GN_NP * GN_NP; e += GN_T) Pm[e] = 0.0;
+  for (int e = tid; e < CS_N; e += GN_T) G[e] = 0.0;
   __syncthreads();
 
   // ---- 1. assembly ----
-  // visual Gram slots (the 26-column view: pose s, pose s + t, ex0, ex1, td, r) of every chunk of the window's landmarks
-  for (int ch = 0; ch < wm.n_chunks; ++ch) {
-    const ChunkMeta cm = b.chunk[wm.chunk_off + ch];
-    for (int t = 0; t < cm.kmax; ++t) {
-      const double *gs = b.gram + (size_t)(cm.gram_off + t) * VILO_GRAM;
-      for (int e = tid; e < VILO_GRAM26; e += CV_T) {
-        int a = 0, rem = e;
-        while (rem >= 26 - a) { rem -= 26 - a; ++a; }
-        const int bc = a + rem;
-        if (bc == 25) continue;
-        if (t == 0 && ((a >= 6 && a < 12) || (bc >= 6 && bc < 12))) continue;
-        auto cdof = [&](int c) { return c < 6 ? 6 * cm.s + c : (c < 12 ? 6 * (cm.s + t) + (c - 6) : (c < 18 ? CD_EX0 + c - 12 : (c < 24 ? CD_EX1 + c - 18 : CD_TD))); };
-        double sg;
-        const double v = gs[gram26_index(a, bc, sg)];
-        const int i = cdof(a), j = cdof(bc);
-        Pm[i * CV_NP + j] += sg * v;
-        if (i != j) Pm[j * CV_NP + i] += sg * v;
-      }
-      __syncthreads();
-    }
-  }
-  // IMU(-leg) factors: [pose_i 6 | B_i 13 | pose_j 6 | B_j 13 | r] upper triangle
-  for (int k = 0; k + 1 < wm.n_frames && k < VILO_WINDOW_SIZE; ++k) {
-    const int f = w * 10 + k;
-    if (!b.imu_skip[f]) {
-      const double *gr = b.imu_gram + (size_t)f * 780;
-      for (int e = tid; e < 780; e += CV_T) {
-        int a = 0, rem = e;
-        while (rem >= 39 - a) { rem -= 39 - a; ++a; }
-        const int bc = a + rem;   // (tri39(a, bc) == e)
-        if (bc >= 38) continue;
-        const double v = gr[e];
-        auto map = [&](int c, bool &isP, int &fr) {   // P dimension or (frame, B dimension)
-          if (c < 6) { isP = true; return 6 * k + c; }
-          if (c < 19) { isP = false; fr = k; return c - 6; }
-          if (c < 25) { isP = true; return 6 * (k + 1) + (c - 19); }
-          isP = false; fr = k + 1; return c - 25;
-        };
-        bool pa, pb; int fa = 0, fb = 0;
-        const int ia = map(a, pa, fa), ib = map(bc, pb, fb);
-        if (pa && pb) { Pm[ia * CV_NP + ib] += v; if (ia != ib) Pm[ib * CV_NP + ia] += v; }
-        else if (!pa && !pb) {
-          if (fa == fb) { Bd[fa * 169 + ia * 13 + ib] += v; if (ia != ib) Bd[fa * 169 + ib * 13 + ia] += v; }
-          else Ao[fb * 169 + ib * 13 + ia] += v;   // (a < bc: a in frame k, bc in frame k + 1)
-        } else if (pa) BP[(fb * 13 + ib) * CV_NP + ia] += v;
-        else BP[(fa * 13 + ia) * CV_NP + ib] += v;
-      }
-    }
-    __syncthreads();
-  }
-  // prior: H_prior on its camera dimensions (the whole n x n matrix: every target once)
-  if (wm.prior_n > 0) {
-    const int pn = wm.prior_n;
-    const double *Hp = b.prior_H + (size_t)w * 96 * 96;
-    const int *pmap = b.prior_map + (size_t)w * 96;
-    for (int e = tid; e < pn * pn; e += CV_T) {
-      const int ci = pmap[e / pn], cj = pmap[e % pn];
-      const double v = Hp[e];
-      if (ci < CD_B0 && cj < CD_B0) Pm[ci * CV_NP + cj] += v;
-      else if (ci >= CD_B0 && cj >= CD_B0) {
-        const int fi = (ci - CD_B0) / 13, di = (ci - CD_B0) % 13, fj = (cj - CD_B0) / 13, dj = (cj - CD_B0) % 13;
-        if (fi == fj) Bd[fi * 169 + di * 13 + dj] += v;
-        else if (fi == fj + 1) Ao[fi * 169 + di * 13 + dj] += v;
-        else if (fj != fi + 1 && v != 0.0) bad_s = 1;   // (the speed / bias part would not be block tridiagonal; no prior of the reference does this)
-      } else if (ci >= CD_B0) BP[(ci - CD_B0) * CV_NP + cj] += v;
-    }
-    __syncthreads();
-  }
+  assemble_visual_pose_block(b, wm, Pm);
+  assemble_imu_grams(b, wm, w, Pm, Bd, Ao, BP);
+  assemble_prior(b, wm, w, Pm, Bd, Ao, BP, &bad_s);
   // landmarks: P -= w_l w_l^T / E_l, the coupling rows staged CL_LMC landmarks at a time (scaled by E_l^-1/2)
   {
     const double *wl = b.lm_w + 80 * (size_t)wm.lm_off;
     for (int l0 = 0; l0 < wm.L; l0 += CL_LMC) {
       const int nl = min(CL_LMC, wm.L - l0);
-      for (int e = tid; e < nl * CV_NP; e += CV_T) {
-        const int li = e / CV_NP, a = e % CV_NP;
+      for (int e = tid; e < nl * GN_NP; e += GN_T) {
+        const int li = e / GN_NP, a = e % GN_NP;
         const double E = b.lm_E[wm.lm_off + l0 + li];
         if (a == 0 && !(E > 0.0)) bad_s = 1;
-        Sg[li * CV_NP + a] = (a < VILO_NPU) ? wl[(size_t)a * wm.L + l0 + li] / sqrt(E) : 0.0;
+        Sg[li * GN_NP + a] = (a < VILO_NPU) ? wl[(size_t)a * wm.L + l0 + li] / sqrt(E) : 0.0;
       }
       __syncthreads();
-      for (int e = tid; e < CV_NP * CV_NP; e += CV_T) {
-        const int i = e / CV_NP, j = e % CV_NP;
+      for (int e = tid; e < GN_NP * GN_NP; e += GN_T) {
+        const int i = e / GN_NP, j = e % GN_NP;
         double s = 0.0;
-        for (int li = 0; li < nl; ++li) s += Sg[li * CV_NP + i] * Sg[li * CV_NP + j];
+        for (int li = 0; li < nl; ++li) s += Sg[li * GN_NP + i] * Sg[li * GN_NP + j];
         Pm[e] -= s;
       }
       __syncthreads();
@@ -219,77 +138,32 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
   // ---- 2. gauge: frame 0's rotation in the basis Q = [e1 e2 u], u = R0^T e_z ----
   const bool frame0 = gauge == VILO_COV_GAUGE_FRAME0;
   if (frame0) {
-    if (tid == 0) {
-      const double *q = b.x + (size_t)w * XSTRIDE + XO_POSE + 3;   // qx qy qz qw
-      const double qx = q[0], qy = q[1], qz = q[2], qw = q[3], nq = 1.0 / sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-      const double x = qx * nq, y = qy * nq, z = qz * nq, s = qw * nq;
-      // u = third row of R0
-      double u[3] = {2.0 * (x * z - s * y), 2.0 * (y * z + s * x), 1.0 - 2.0 * (x * x + y * y)};
-      const double nu = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-      for (int i = 0; i < 3; ++i) u[i] *= nu;
-      // e1 = normalise(u x a), a = the axis along which u is smallest; e2 = u x e1
-      int m = 0;
-      for (int i = 1; i < 3; ++i) if (fabs(u[i]) < fabs(u[m])) m = i;
-      double a3[3] = {0.0, 0.0, 0.0}; a3[m] = 1.0;
-      double e1[3] = {u[1] * a3[2] - u[2] * a3[1], u[2] * a3[0] - u[0] * a3[2], u[0] * a3[1] - u[1] * a3[0]};
-      const double n1 = 1.0 / sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-      for (int i = 0; i < 3; ++i) e1[i] *= n1;
-      const double e2[3] = {u[1] * e1[2] - u[2] * e1[1], u[2] * e1[0] - u[0] * e1[2], u[0] * e1[1] - u[1] * e1[0]};
-      for (int i = 0; i < 3; ++i) { Q[i] = e1[i]; Q[3 + i] = e2[i]; Q[6 + i] = u[i]; }
-    }
+    if (tid == 0) gauge_basis(b.x + (size_t)w * XSTRIDE + XO_POSE + 3, Q);
     __syncthreads();
-    // rows 3..5 of P and columns 3..5 of BP: H' = Q^T H Q
-    if (tid < CV_NP) {
-      double r[3];
-      for (int m = 0; m < 3; ++m) r[m] = Q[3 * m] * Pm[3 * CV_NP + tid] + Q[3 * m + 1] * Pm[4 * CV_NP + tid] + Q[3 * m + 2] * Pm[5 * CV_NP + tid];
-      for (int m = 0; m < 3; ++m) Pm[(3 + m) * CV_NP + tid] = r[m];
-    }
-    __syncthreads();
-    if (tid < CV_NP) {
-      double r[3];
-      for (int m = 0; m < 3; ++m) r[m] = Q[3 * m] * Pm[tid * CV_NP + 3] + Q[3 * m + 1] * Pm[tid * CV_NP + 4] + Q[3 * m + 2] * Pm[tid * CV_NP + 5];
-      for (int m = 0; m < 3; ++m) Pm[tid * CV_NP + 3 + m] = r[m];
-    }
-    for (int rw = tid; rw < 143; rw += CV_T) {
-      double *row = BP + (size_t)rw * CV_NP;
-      double r[3];
-      for (int m = 0; m < 3; ++m) r[m] = Q[3 * m] * row[3] + Q[3 * m + 1] * row[4] + Q[3 * m + 2] * row[5];
-      for (int m = 0; m < 3; ++m) row[3 + m] = r[m];
-    }
-    __syncthreads();
+    gauge_rotate(Pm, BP, Q);
   }
 
   // ---- 3. equilibration; constant / absent dimensions: scale 0, unit diagonal ----
-  for (int cd = tid; cd < CD_N; cd += CV_T) {
+  for (int cd = tid; cd < CD_N; cd += GN_T) {
     bool act = cov_active(cd, wm, gauge) && !(frame0 && cd == 5);
     double d = 0.0;
     if (act) {
-      const double h = cd < CD_B0 ? Pm[cd * CV_NP + cd] : Bd[((cd - CD_B0) / 13) * 169 + ((cd - CD_B0) % 13) * 14];
+      const double h = cd < CD_B0 ? Pm[cd * GN_NP + cd] : Bd[((cd - CD_B0) / 13) * 169 + ((cd - CD_B0) % 13) * 14];
       if (!(h > 0.0) || !isfinite(h)) bad_s = 1;
       else d = 1.0 / sqrt(h);
     }
     dsc[cd] = d;
   }
   __syncthreads();
-  auto scaled = [&](double v, int ci, int cj) { const double di = dsc[ci], dj = dsc[cj]; return (di == 0.0 || dj == 0.0) ? (ci == cj ? 1.0 : 0.0) : v * di * dj; };
-  for (int e = tid; e < CV_NP * CV_NP; e += CV_T) Pm[e] = scaled(Pm[e], e / CV_NP, e % CV_NP);
-  for (int e = tid; e < 11 * 169; e += CV_T) {
-    const int k = e / 169, i = (e % 169) / 13, j = e % 13;
-    Bd[e] = scaled(Bd[e], CD_B0 + 13 * k + i, CD_B0 + 13 * k + j);
-    Ao[e] = k == 0 ? 0.0 : scaled(Ao[e], CD_B0 + 13 * k + i, CD_B0 + 13 * (k - 1) + j);
-  }
-  for (int e = tid; e < 143 * CV_NP; e += CV_T) {
-    const double di = dsc[CD_B0 + e / CV_NP], dj = dsc[e % CV_NP];
-    BP[e] = (di == 0.0 || dj == 0.0) ? 0.0 : BP[e] * di * dj;
-  }
+  scale_system(Pm, Bd, Ao, BP, dsc);
   __syncthreads();
 
   // ---- 4. forward over the chain: L_k^-1, T_k, Y_k; S_P = P - sum Y_k^T Y_k ----
   for (int k = 0; k < VILO_F; ++k) {
-    for (int e = tid; e < 169; e += CV_T) ss[e] = Bd[k * 169 + e];
+    for (int e = tid; e < 169; e += GN_T) ss[e] = Bd[k * 169 + e];
     __syncthreads();
     if (k > 0) {
-      for (int e = tid; e < 169; e += CV_T) {   // T = A_{k,k-1} L_{k-1}^-T
+      for (int e = tid; e < 169; e += GN_T) {   // T = A_{k,k-1} L_{k-1}^-T
         const int r = e / 13, c = e % 13;
         double s = 0.0;
         for (int m = 0; m <= c; ++m) s += Ao[k * 169 + r * 13 + m] * lp[c * 13 + m];
@@ -297,7 +171,7 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
         Tg[k * 169 + e] = s;
       }
       __syncthreads();
-      for (int e = tid; e < 169; e += CV_T) {
+      for (int e = tid; e < 169; e += GN_T) {
         const int r = e / 13, c = e % 13;
         double s = 0.0;
         for (int m = 0; m < 13; ++m) s += tn[r * 13 + m] * tn[c * 13 + m];
@@ -306,65 +180,65 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
       __syncthreads();
     }
     cov_chol13(ss, lc, thr, &bad_s);
-    for (int e = tid; e < 169; e += CV_T) Li[k * 169 + e] = lc[e];
+    for (int e = tid; e < 169; e += GN_T) Li[k * 169 + e] = lc[e];
     // Z = BP_k - T Y_{k-1};  Y_k = L_k^-1 Z (into BP_k and Mg)
-    for (int e = tid; e < CV_NB * CV_NP; e += CV_T) {
-      const int r = e / CV_NP, p = e % CV_NP;
-      double s = BP[(size_t)(13 * k + r) * CV_NP + p];
+    for (int e = tid; e < CV_NB * GN_NP; e += GN_T) {
+      const int r = e / GN_NP, p = e % GN_NP;
+      double s = BP[(size_t)(13 * k + r) * GN_NP + p];
       if (k > 0)
-        for (int m = 0; m < 13; ++m) s -= tn[r * 13 + m] * Mg[m * CV_NP + p];
+        for (int m = 0; m < 13; ++m) s -= tn[r * 13 + m] * Mg[m * GN_NP + p];
       Z[e] = s;
     }
     __syncthreads();
-    for (int e = tid; e < CV_NB * CV_NP; e += CV_T) {
-      const int r = e / CV_NP, p = e % CV_NP;
+    for (int e = tid; e < CV_NB * GN_NP; e += GN_T) {
+      const int r = e / GN_NP, p = e % GN_NP;
       double s = 0.0;
-      for (int m = 0; m <= r; ++m) s += lc[r * 13 + m] * Z[m * CV_NP + p];
+      for (int m = 0; m <= r; ++m) s += lc[r * 13 + m] * Z[m * GN_NP + p];
       Mg[e] = s;
-      BP[(size_t)(13 * k + r) * CV_NP + p] = s;
+      BP[(size_t)(13 * k + r) * GN_NP + p] = s;
     }
     __syncthreads();
-    for (int e = tid; e < CV_NP * CV_NP; e += CV_T) {
-      const int i = e / CV_NP, j = e % CV_NP;
+    for (int e = tid; e < GN_NP * GN_NP; e += GN_T) {
+      const int i = e / GN_NP, j = e % GN_NP;
       double s = 0.0;
-      for (int r = 0; r < 13; ++r) s += Mg[r * CV_NP + i] * Mg[r * CV_NP + j];
+      for (int r = 0; r < 13; ++r) s += Mg[r * GN_NP + i] * Mg[r * GN_NP + j];
       Pm[e] -= s;
     }
-    for (int e = tid; e < 169; e += CV_T) lp[e] = lc[e];
+    for (int e = tid; e < 169; e += GN_T) lp[e] = lc[e];
     __syncthreads();
   }
   // Cholesky of S_P (lower, in place), L_P^-1 into Sg, Sigma_PP = L_P^-T L_P^-1 into Pm
-  for (int j = 0; j < CV_NP; ++j) {
+  for (int j = 0; j < GN_NP; ++j) {
     if (tid == 0) {
-      double p = Pm[j * CV_NP + j];
+      double p = Pm[j * GN_NP + j];
       if (!(p > thr)) { bad_s = 1; p = 1.0; }
-      Pm[j * CV_NP + j] = sqrt(p);
+      Pm[j * GN_NP + j] = sqrt(p);
     }
     __syncthreads();
-    const double piv = Pm[j * CV_NP + j];
-    for (int r = j + 1 + tid; r < CV_NP; r += CV_T) Pm[r * CV_NP + j] /= piv;
+    const double piv = Pm[j * GN_NP + j];
+    for (int r = j + 1 + tid; r < GN_NP; r += GN_T) Pm[r * GN_NP + j] /= piv;
     __syncthreads();
-    const int n = CV_NP - j - 1;
-    for (int e = tid; e < n * n; e += CV_T) {
+    const int n = GN_NP - j - 1;
+    for (int e = tid; e < n * n; e += GN_T) {
       const int r = j + 1 + e / n, c = j + 1 + e % n;
-      if (c <= r) Pm[r * CV_NP + c] -= Pm[r * CV_NP + j] * Pm[c * CV_NP + j];
+      if (c <= r) Pm[r * GN_NP + c] -= Pm[r * GN_NP + j] * Pm[c * GN_NP + j];
     }
     __syncthreads();
   }
-  if (tid < CV_NP) {
+  if (tid < GN_NP) {
     const int c = tid;
-    for (int r = 0; r < c; ++r) Sg[r * CV_NP + c] = 0.0;
-    for (int r = c; r < CV_NP; ++r) {
+    for (int r = 0; r < c; ++r) Sg[r * GN_NP + c] = 0.0;
+    for (int r = c; r < GN_NP; ++r) {
       double s = (r == c) ? 1.0 : 0.0;
-      for (int m = c; m < r; ++m) s -= Pm[r * CV_NP + m] * Sg[m * CV_NP + c];
-      Sg[r * CV_NP + c] = s / Pm[r * CV_NP + r];
+      for (int m = c; m < r; ++m) s -= Pm[r * GN_NP + m] * Sg[m * GN_NP + c];
+      Sg[r * GN_NP + c] = s / Pm[r * GN_NP + r];
     }
   }
   __syncthreads();
-  for (int e = tid; e < CV_NP * CV_NP; e += CV_T) {
-    const int i = e / CV_NP, j = e % CV_NP;
+  for (int e = tid; e < GN_NP * GN_NP; e += GN_T) {
+    const int i = e / GN_NP, j = e % GN_NP;
     double s = 0.0;
-    for (int m = max(i, j); m < CV_NP; ++m) s += Sg[m * CV_NP + i] * Sg[m * CV_NP + j];
+    for (int m = max(i, j); m < GN_NP; ++m) s += Sg[m * GN_NP + i] * Sg[m * GN_NP + j];
     Pm[e] = s;
   }
   __syncthreads();
@@ -372,19 +246,19 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
 
   // ---- 5. backward over the chain: G_k, X_kk, the frame blocks ----
   for (int k = VILO_F - 1; k >= 0; --k) {
-    for (int e = tid; e < 169; e += CV_T) { lc[e] = Li[k * 169 + e]; if (k + 1 < VILO_F) tn[e] = Tg[(k + 1) * 169 + e]; }
+    for (int e = tid; e < 169; e += GN_T) { lc[e] = Li[k * 169 + e]; if (k + 1 < VILO_F) tn[e] = Tg[(k + 1) * 169 + e]; }
     __syncthreads();
     // Z = Y_k - T_{k+1}^T G_{k+1}  (G_{k+1} in Mg)
-    for (int e = tid; e < CV_NB * CV_NP; e += CV_T) {
-      const int r = e / CV_NP, p = e % CV_NP;
-      double s = BP[(size_t)(13 * k + r) * CV_NP + p];
+    for (int e = tid; e < CV_NB * GN_NP; e += GN_T) {
+      const int r = e / GN_NP, p = e % GN_NP;
+      double s = BP[(size_t)(13 * k + r) * GN_NP + p];
       if (k + 1 < VILO_F)
-        for (int m = 0; m < 13; ++m) s -= tn[m * 13 + r] * Mg[m * CV_NP + p];
+        for (int m = 0; m < 13; ++m) s -= tn[m * 13 + r] * Mg[m * GN_NP + p];
       Z[e] = s;
     }
     // X_kk: V = T_{k+1} L_k^-1, X = L_k^-T L_k^-1 + V^T X_{k+1} V
     if (k + 1 < VILO_F)
-      for (int e = tid; e < 169; e += CV_T) {
+      for (int e = tid; e < 169; e += GN_T) {
         const int r = e / 13, c = e % 13;
         double s = 0.0;
         for (int m = c; m < 13; ++m) s += tn[r * 13 + m] * lc[m * 13 + c];
@@ -392,21 +266,21 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
       }
     __syncthreads();
     // G_k = L_k^-T Z  (into Mg);  ss = V^T X_{k+1}
-    for (int e = tid; e < CV_NB * CV_NP; e += CV_T) {
-      const int r = e / CV_NP, p = e % CV_NP;
+    for (int e = tid; e < CV_NB * GN_NP; e += GN_T) {
+      const int r = e / GN_NP, p = e % GN_NP;
       double s = 0.0;
-      for (int m = r; m < 13; ++m) s += lc[m * 13 + r] * Z[m * CV_NP + p];
+      for (int m = r; m < 13; ++m) s += lc[m * 13 + r] * Z[m * GN_NP + p];
       Mg[e] = s;
     }
     if (k + 1 < VILO_F)
-      for (int e = tid; e < 169; e += CV_T) {
+      for (int e = tid; e < 169; e += GN_T) {
         const int r = e / 13, c = e % 13;
         double s = 0.0;
         for (int m = 0; m < 13; ++m) s += vs[m * 13 + r] * xs[m * 13 + c];
         ss[e] = s;
       }
     __syncthreads();
-    for (int e = tid; e < 169; e += CV_T) {
+    for (int e = tid; e < 169; e += GN_T) {
       const int r = e / 13, c = e % 13;
       double s = 0.0;
       for (int m = max(r, c); m < 13; ++m) s += lc[m * 13 + r] * lc[m * 13 + c];
@@ -415,25 +289,25 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
       lp[e] = s;
     }
     // Z = G_k Sigma_PP
-    for (int e = tid; e < CV_NB * CV_NP; e += CV_T) {
-      const int r = e / CV_NP, p = e % CV_NP;
+    for (int e = tid; e < CV_NB * GN_NP; e += GN_T) {
+      const int r = e / GN_NP, p = e % GN_NP;
       double s = 0.0;
-      for (int q = 0; q < CV_NP; ++q) s += Mg[r * CV_NP + q] * Pm[q * CV_NP + p];
+      for (int q = 0; q < GN_NP; ++q) s += Mg[r * GN_NP + q] * Pm[q * GN_NP + p];
       Z[e] = s;
     }
     __syncthreads();
-    for (int e = tid; e < 169; e += CV_T) xs[e] = lp[e];
+    for (int e = tid; e < 169; e += GN_T) xs[e] = lp[e];
     __syncthreads();
     // frame block (scaled) into Sg[0 .. 361): [dp dtheta | v ba bg rho]
-    for (int e = tid; e < CV_FR * CV_FR; e += CV_T) {
+    for (int e = tid; e < CV_FR * CV_FR; e += GN_T) {
       const int a = e / CV_FR, c = e % CV_FR;
       double v;
-      if (a < 6 && c < 6) v = Pm[(6 * k + a) * CV_NP + 6 * k + c];
-      else if (a < 6) v = -Z[(c - 6) * CV_NP + 6 * k + a];
-      else if (c < 6) v = -Z[(a - 6) * CV_NP + 6 * k + c];
+      if (a < 6 && c < 6) v = Pm[(6 * k + a) * GN_NP + 6 * k + c];
+      else if (a < 6) v = -Z[(c - 6) * GN_NP + 6 * k + a];
+      else if (c < 6) v = -Z[(a - 6) * GN_NP + 6 * k + c];
       else {
         double s = xs[(a - 6) * 13 + (c - 6)];
-        for (int p = 0; p < CV_NP; ++p) s += Z[(a - 6) * CV_NP + p] * Mg[(c - 6) * CV_NP + p];
+        for (int p = 0; p < GN_NP; ++p) s += Z[(a - 6) * GN_NP + p] * Mg[(c - 6) * GN_NP + p];
         v = s;
       }
       const int ca = a < 6 ? 6 * k + a : CD_B0 + 13 * k + (a - 6), cc = c < 6 ? 6 * k + c : CD_B0 + 13 * k + (c - 6);
@@ -454,32 +328,32 @@ __global__ void __launch_bounds__(CV_T) k_covariance(BatchDev b, int w0, int gau
       }
       __syncthreads();
     }
-    for (int e = tid; e < CV_FR * CV_FR; e += CV_T) {   // (symmetric to the bit: the two triangles went through different rounding)
+    for (int e = tid; e < CV_FR * CV_FR; e += GN_T) {   // (symmetric to the bit: the two triangles went through different rounding)
       const int a = e / CV_FR, c = e % CV_FR;
       fo[k * CV_FR * CV_FR + e] = bad ? NAN : 0.5 * (Sg[e] + Sg[c * CV_FR + a]);
     }
     __syncthreads();
   }
   if (po) {
-    for (int e = tid; e < CV_NP * CV_NP; e += CV_T) Sg[e] = Pm[e] * dsc[e / CV_NP] * dsc[e % CV_NP];
+    for (int e = tid; e < GN_NP * GN_NP; e += GN_T) Sg[e] = Pm[e] * dsc[e / GN_NP] * dsc[e % GN_NP];
     __syncthreads();
     if (frame0) {
-      if (tid < CV_NP) {
+      if (tid < GN_NP) {
         double r[3];
-        for (int i = 0; i < 3; ++i) r[i] = Q[i] * Sg[3 * CV_NP + tid] + Q[3 + i] * Sg[4 * CV_NP + tid] + Q[6 + i] * Sg[5 * CV_NP + tid];
-        for (int i = 0; i < 3; ++i) Sg[(3 + i) * CV_NP + tid] = r[i];
+        for (int i = 0; i < 3; ++i) r[i] = Q[i] * Sg[3 * GN_NP + tid] + Q[3 + i] * Sg[4 * GN_NP + tid] + Q[6 + i] * Sg[5 * GN_NP + tid];
+        for (int i = 0; i < 3; ++i) Sg[(3 + i) * GN_NP + tid] = r[i];
       }
       __syncthreads();
-      if (tid < CV_NP) {
+      if (tid < GN_NP) {
         double r[3];
-        for (int i = 0; i < 3; ++i) r[i] = Q[i] * Sg[tid * CV_NP + 3] + Q[3 + i] * Sg[tid * CV_NP + 4] + Q[6 + i] * Sg[tid * CV_NP + 5];
-        for (int i = 0; i < 3; ++i) Sg[tid * CV_NP + 3 + i] = r[i];
+        for (int i = 0; i < 3; ++i) r[i] = Q[i] * Sg[tid * GN_NP + 3] + Q[3 + i] * Sg[tid * GN_NP + 4] + Q[6 + i] * Sg[tid * GN_NP + 5];
+        for (int i = 0; i < 3; ++i) Sg[tid * GN_NP + 3 + i] = r[i];
       }
       __syncthreads();
     }
-    for (int e = tid; e < CV_PN; e += CV_T) {
+    for (int e = tid; e < CV_PN; e += GN_T) {
       const int a = e / VILO_NPU, c = e % VILO_NPU;
-      po[e] = bad ? NAN : 0.5 * (Sg[a * CV_NP + c] + Sg[c * CV_NP + a]);
+      po[e] = bad ? NAN : 0.5 * (Sg[a * GN_NP + c] + Sg[c * GN_NP + a]);
     }
   }
   if (tid == 0) status_out[w] = bad ? 1 : 0;
@@ -507,7 +381,7 @@ extern "C" double vilo_last_covariance_ms(const vilo_ctx *ctx) { return ctx ? ct
 // Sigma_p = J Sigma_13 J^T.
 #define LC_T 256
 #define LC_S 0                        // [80][80] Sigma_PP
-#define LC_U (LC_S + CV_NP * CV_NP)   // [4 waves][16][12] U at pose s (dp dtheta) and ex0 (dt dtheta)
+#define LC_U (LC_S + GN_NP * GN_NP)   // [4 waves][16][12] U at pose s (dp dtheta) and ex0 (dt dtheta)
 #define LC_N (LC_U + 4 * 16 * 12)     // 57 344 bytes: two workgroups per CU
 
 // pp: Sigma_PP of window w0 + blockIdx.x at pp + blockIdx.x * 6241; status: k_covariance's, by window. Outputs in the caller's landmark
@@ -530,8 +404,8 @@ __global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0
   }
   double *S = lds + LC_S, *Uw = lds + LC_U + wave * 16 * 12;
   const double *src = pp + (size_t)blockIdx.x * CV_PN;
-  for (int e = tid; e < CV_NP * CV_NP; e += LC_T) {
-    const int i = e / CV_NP, j = e % CV_NP;
+  for (int e = tid; e < GN_NP * GN_NP; e += LC_T) {
+    const int i = e / GN_NP, j = e % GN_NP;
     S[e] = (i < VILO_NPU && j < VILO_NPU) ? src[i * VILO_NPU + j] : 0.0;
   }
   __syncthreads();
@@ -556,7 +430,7 @@ __global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0
 #pragma unroll
       for (int ks = 0; ks < 20; ++ks)
 #pragma unroll
-        for (int X = 0; X < 5; ++X) U[X] = __builtin_amdgcn_mfma_f64_16x16x4f64(S[(4 * ks + lk) * CV_NP + 16 * X + lr], B[ks], U[X], 0, 0, 0);
+        for (int X = 0; X < 5; ++X) U[X] = __builtin_amdgcn_mfma_f64_16x16x4f64(S[(4 * ks + lk) * GN_NP + 16 * X + lr], B[ks], U[X], 0, 0, 0);
 #pragma unroll
       for (int X = 0; X < 5; ++X)
 #pragma unroll
@@ -614,7 +488,7 @@ __global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0
           const int dj = j < 6 ? 6 * s + j : CD_EX0 + j - 6;
           double t = 0.0;
 #pragma unroll
-          for (int m = 0; m < 12; ++m) t += JP[r][m] * S[(m < 6 ? 6 * s + m : CD_EX0 + m - 6) * CV_NP + dj];
+          for (int m = 0; m < 12; ++m) t += JP[r][m] * S[(m < 6 ? 6 * s + m : CD_EX0 + m - 6) * GN_NP + dj];
           T[j] = t;
           Jc += JP[r][j] * cv[j];
         }
@@ -677,7 +551,7 @@ static int batch_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_cov_opts &
     const int n = std::min(chunk, W - w0);
     double *fr = frames ? call.ptr<double>(o_fr) : cov_chunk_view(call.ptr<char>(o_fr), w0, CV_FRN);
     double *po = poses ? call.ptr<double>(o_po) : want_poses ? cov_chunk_view(call.ptr<char>(o_po), w0, CV_PN) : nullptr;
-    hipLaunchKernelGGL(k_covariance, dim3(n), dim3(CV_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, want_poses,
+    hipLaunchKernelGGL(k_covariance, dim3(n), dim3(GN_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_reciprocal_condition, want_poses,
                        call.ptr<double>(o_scr), fr, po, d_stat);
     if (lm)
       hipLaunchKernelGGL(k_landmark_covariance, dim3(n), dim3(LC_T), sizeof(double) * LC_N, ctx->stream, bd, w0, po + (size_t)w0 * CV_PN,

@@ -8,9 +8,9 @@
 // absent frames are zero and never read from the caller's arrays. H is never assembled beyond the 80 x 80 pose block of the visual factors:
 // every other source is applied to its own slice of V. Steps, every product on v_mfma_f64_16x16x4f64 (operand placement of step_syrk_wave /
 // k_landmark_covariance: lane (lr, lk) gives A[row lr][k lk] and B[k lk][column lr], accumulator r is row lk + 4 r, column lr):
-//   1. g of the 222 state entries by their owners, in k_gradient's order of the sums (the record's g . v).
+//   1. g of the 222 state entries by their owners (state_entry_gh of gn_system.hpp, without the diagonal; the record's g . v).
 //   2. V into LDS by camera dimension; a read entry that is not finite marks its column (status 1) and is taken as 0.
-//   3. P = the visual Gram slots' 80 x 80 block, assembled as k_gn_step assembles it; Y_P = P V_P (5 row tiles, 20 k-steps).
+//   3. P = the visual Gram slots' 80 x 80 block (assemble_visual_pose_block of gn_system.hpp); Y_P = P V_P (5 row tiles, 20 k-steps).
 //   4. the IMU Gram of every interval k, 38 x 38 over [pose_k 6 | B_k 13 | pose_k+1 6 | B_k+1 13], applied to those rows of V and added to
 //      those rows of Y (3 row tiles, 10 k-steps; intervals in ascending order, a barrier between them): the speed / bias chain and the
 //      143 x 80 coupling are never materialised.
@@ -27,40 +27,27 @@
 #include <math.h>
 
 #include "batch_call.hpp"
-#include "solve_common.hpp"
-#include "vilo_math.hpp"
+#include "gn_system.hpp"
 
 static_assert(sizeof(vilo_hess_vec_record) == 32, "vilo_hess_vec_record: 32 bytes (cerberus_amd/_ctypes.py mirrors it)");
 static_assert(VILO_HV_MAX_VECTORS == 16, "k_hess_vec: one 16-column tile of v_mfma_f64_16x16x4f64");
 
-#define HV_T 256            // threads per window
-#define HV_NP 80
-#define HV_NS 222           // state entries per window (VILO_NCAM)
 #define HV_K 16             // columns of a tile (VILO_HV_MAX_VECTORS)
 #define HV_LMC 32           // landmarks per pass
 #define HV_WS 33            // row stride of the staged coupling rows (a pad of one: the tile's 16 rows fall into 16 banks)
 // LDS (doubles)
 #define HL_P 0                                // [80][80] visual pose block; then: staging | partial sums
 #define HL_WT HL_P                            //   [80][33] w_l of a pass, by camera dimension
-#define HL_VL (HL_WT + HV_NP * HV_WS)         //   [32][16] v_l of a pass
+#define HL_VL (HL_WT + GN_NP * HV_WS)         //   [32][16] v_l of a pass
 #define HL_RED HL_P                           //   [2][16][33] partial sums of v . Hv and g . v
-#define HL_V (HL_P + HV_NP * HV_NP)           // [224][16] V by camera dimension
+#define HL_V (HL_P + GN_NP * GN_NP)           // [224][16] V by camera dimension
 #define HL_Y (HL_V + CD_N * HV_K)             // [224][16] Y
 #define HL_G (HL_Y + CD_N * HV_K)             // [224] g by camera dimension
 #define HL_DX (HL_G + CD_N)                   // [96] prior dx
 #define HL_MAP (HL_DX + VILO_MAX_PRIOR_DIM)   // int pmap[96], short inv_pmap[224], int badk[16]
 #define HL_N (HL_MAP + (96 * 4 + 224 * 2 + 16 * 4 + 7) / 8)
-static_assert(HL_VL + HV_LMC * HV_K <= HL_V && 2 * HV_K * HV_WS <= HV_NP * HV_NP, "k_hess_vec: what reuses P's place");
+static_assert(HL_VL + HV_LMC * HV_K <= HL_V && 2 * HV_K * HV_WS <= GN_NP * GN_NP, "k_hess_vec: what reuses P's place");
 static_assert(sizeof(double) * HL_N <= 160 * 1024, "k_hess_vec: the CU's LDS");
-
-// camera dimension (solver_types.hpp) of entry d of the caller's layout
-__device__ __forceinline__ int hv_cd(int d) {
-  if (d < 66) return d;
-  if (d < 165) { const int k = (d - 66) / 9; return CD_B0 + 13 * k + (d - 66 - 9 * k); }
-  if (d < 209) { const int k = (d - 165) / 4; return CD_B0 + 13 * k + 9 + (d - 165 - 4 * k); }
-  if (d < 221) return CD_EX0 + (d - 209);
-  return CD_TD;
-}
 
 // camera dimension of column c < 38 of interval k's IMU Gram [pose_k 6 | B_k 13 | pose_k+1 6 | B_k+1 13]
 __device__ __forceinline__ int hv_imu_cd(int k, int c) {
@@ -81,7 +68,7 @@ __device__ __forceinline__ mfma_d4 hv_tile(int row0, int nk, int lr, int lk, FA 
   return acc;
 }
 
-__global__ void __launch_bounds__(HV_T) k_hess_vec(BatchDev b, int K, const double *sv_in, const double *lv_in, vilo_hess_vec_record *rec, double *ss_out,
+__global__ void __launch_bounds__(GN_T) k_hess_vec(BatchDev b, int K, const double *sv_in, const double *lv_in, vilo_hess_vec_record *rec, double *ss_out,
                                                   double *ls_out) {
   using namespace vilo;
   extern __shared__ double lds[];
@@ -93,11 +80,11 @@ __global__ void __launch_bounds__(HV_T) k_hess_vec(BatchDev b, int K, const doub
   int *pmap = (int *)(lds + HL_MAP);
   short *inv_pmap = (short *)(pmap + 96);
   int *badk = (int *)(inv_pmap + CD_N);
-  double *so = ss_out ? ss_out + (size_t)w * K * HV_NS : nullptr, *lo = ls_out ? ls_out + (size_t)K * wm.lm_off : nullptr;
-  const double *sv = sv_in ? sv_in + (size_t)w * K * HV_NS : nullptr, *lv = lv_in ? lv_in + (size_t)K * wm.lm_off : nullptr;
+  double *so = ss_out ? ss_out + (size_t)w * K * GN_NS : nullptr, *lo = ls_out ? ls_out + (size_t)K * wm.lm_off : nullptr;
+  const double *sv = sv_in ? sv_in + (size_t)w * K * GN_NS : nullptr, *lv = lv_in ? lv_in + (size_t)K * wm.lm_off : nullptr;
   if (b.win_bad && b.win_bad[w]) {   // a record without sqrt_info: the window is not linearised
-    if (so) for (int e = tid; e < K * HV_NS; e += HV_T) so[e] = NAN;
-    if (lo) for (int e = tid; e < K * L; e += HV_T) lo[e] = NAN;
+    if (so) for (int e = tid; e < K * GN_NS; e += GN_T) so[e] = NAN;
+    if (lo) for (int e = tid; e < K * L; e += GN_T) lo[e] = NAN;
     if (rec && tid < K) {
       vilo_hess_vec_record r;
       r.vHv = NAN; r.g_dot_v = NAN; r.model_cost_change = NAN; r.status = 2; r.pad = 0;
@@ -106,56 +93,19 @@ __global__ void __launch_bounds__(HV_T) k_hess_vec(BatchDev b, int K, const doub
     return;
   }
   const int pn = wm.prior_n;
-  for (int e = tid; e < HV_NP * HV_NP; e += HV_T) Pm[e] = 0.0;
-  for (int e = tid; e < CD_N * HV_K; e += HV_T) { Vs[e] = 0.0; Ys[e] = 0.0; }
-  for (int e = tid; e < CD_N; e += HV_T) { inv_pmap[e] = -1; gs[e] = 0.0; }
+  for (int e = tid; e < GN_NP * GN_NP; e += GN_T) Pm[e] = 0.0;
+  for (int e = tid; e < CD_N * HV_K; e += GN_T) { Vs[e] = 0.0; Ys[e] = 0.0; }
+  for (int e = tid; e < CD_N; e += GN_T) gs[e] = 0.0;
   if (tid < HV_K) badk[tid] = 0;
   if (tid < 96) pmap[tid] = tid < pn ? b.prior_map[(size_t)w * 96 + tid] : 0;
-  if (pn > 0 && tid < wm.prior_nb)
-    prior_dx(b.x + (size_t)w * XSTRIDE + b.prior_bstate[w * 40 + tid], b.prior_x0 + (size_t)w * 280 + b.prior_bxoff[w * 40 + tid],
-             b.prior_bsize[w * 40 + tid], dxs + b.prior_bidx[w * 40 + tid]);
-  __syncthreads();
-  if (tid < pn) inv_pmap[pmap[tid]] = (short)tid;
-  __syncthreads();
+  prior_view_init(b, wm, w, pmap, dxs, inv_pmap);
 
-  // ---- 1. g of the 222 state entries (k_gradient's walk) ----
-  if (tid < HV_NS) {
-    const int cd = hv_cd(tid);
+  // ---- 1. g of the 222 state entries ----
+  if (tid < GN_NS) {
+    const int cd = caller_cd(tid);
     if (cd_active(cd, F, wm.const_mask)) {
-      double g = 0.0;
-      if (cd < CD_B0) {
-        const int f = cd / 6, a = cd - 6 * f;
-        const int crest = cd < 66 ? -1 : (cd < CD_TD ? 12 + (cd - CD_EX0) : 24);
-        for (int ch = 0; ch < wm.n_chunks; ++ch) {
-          const ChunkMeta cm = b.chunk[wm.chunk_off + ch];
-          int t0 = 0, t1 = cm.kmax, c = crest;
-          if (cd < 66) {
-            if (f == cm.s) c = a;
-            else if (f > cm.s && f - cm.s < cm.kmax) { c = 6 + a; t0 = f - cm.s; t1 = t0 + 1; }
-            else continue;
-          }
-          double sgn;
-          const int eg = gram26_index(c, 25, sgn);
-          for (int t = t0; t < t1; ++t) g += sgn * b.gram[(size_t)(cm.gram_off + t) * VILO_GRAM + eg];
-        }
-      }
-      {
-        int f, ci;
-        if (cd < 66) { f = cd / 6; ci = cd - 6 * f; }
-        else if (cd >= CD_B0) { f = (cd - CD_B0) / 13; ci = 6 + (cd - CD_B0 - 13 * f); }
-        else { f = -1; ci = 0; }
-        if (f >= 0) {
-          if (f >= 1 && !b.imu_skip[w * 10 + f - 1]) g += b.imu_gram[(size_t)(w * 10 + f - 1) * 780 + tri39(19 + ci, 38)];
-          if (f + 1 < F && f < VILO_WINDOW_SIZE && !b.imu_skip[w * 10 + f]) g += b.imu_gram[(size_t)(w * 10 + f) * 780 + tri39(ci, 38)];
-        }
-      }
-      const int pi = inv_pmap[cd];
-      if (pn > 0 && pi >= 0) {
-        const double *Hp = b.prior_H + (size_t)w * 96 * 96;
-        double s = b.prior_b0[(size_t)w * 96 + pi];
-        for (int q = 0; q < pn; ++q) s += Hp[(size_t)q * pn + pi] * dxs[q];
-        g += s;
-      }
+      double g = 0.0, h = 0.0;   // (h: not formed)
+      state_entry_gh<false>(b, wm, w, cd, inv_pmap, dxs, g, h);
       gs[cd] = g;
     }
   }
@@ -164,41 +114,22 @@ __global__ void __launch_bounds__(HV_T) k_hess_vec(BatchDev b, int K, const doub
   // (badk[k] = 1 is stored by many threads, and again in step 7: benign, every writer stores the same value and barriers separate
   // the stores from the reads)
   if (sv)
-    for (int e = tid; e < K * HV_NS; e += HV_T) {
-      const int k = e / HV_NS, cd = hv_cd(e - k * HV_NS);
+    for (int e = tid; e < K * GN_NS; e += GN_T) {
+      const int k = e / GN_NS, cd = caller_cd(e - k * GN_NS);
       if (!cd_active(cd, F, wm.const_mask)) continue;
       const double v = sv[e];
       if (isfinite(v)) Vs[cd * HV_K + k] = v;
       else badk[k] = 1;
     }
   if (lv)
-    for (int e = tid; e < K * L; e += HV_T)
+    for (int e = tid; e < K * L; e += GN_T)
       if (!isfinite(lv[e])) badk[e / L] = 1;
 
-  // ---- 3. P of the visual factors (k_gn_step's assembly), Y_P = P V_P ----
-  for (int ch = 0; ch < wm.n_chunks; ++ch) {
-    const ChunkMeta cm = b.chunk[wm.chunk_off + ch];
-    for (int t = 0; t < cm.kmax; ++t) {
-      const double *gr = b.gram + (size_t)(cm.gram_off + t) * VILO_GRAM;
-      for (int e = tid; e < VILO_GRAM26; e += HV_T) {
-        int a = 0, rem = e;
-        while (rem >= 26 - a) { rem -= 26 - a; ++a; }
-        const int bc = a + rem;
-        if (bc == 25) continue;
-        if (t == 0 && ((a >= 6 && a < 12) || (bc >= 6 && bc < 12))) continue;
-        auto cdof = [&](int c) { return c < 6 ? 6 * cm.s + c : (c < 12 ? 6 * (cm.s + t) + (c - 6) : (c < 18 ? CD_EX0 + c - 12 : (c < 24 ? CD_EX1 + c - 18 : CD_TD))); };
-        double sg;
-        const double v = gr[gram26_index(a, bc, sg)];
-        const int i = cdof(a), j = cdof(bc);
-        Pm[i * HV_NP + j] += sg * v;
-        if (i != j) Pm[j * HV_NP + i] += sg * v;
-      }
-      __syncthreads();
-    }
-  }
+  // ---- 3. P of the visual factors, Y_P = P V_P ----
+  assemble_visual_pose_block(b, wm, Pm);
   __syncthreads();
   for (int X = wave; X < 5; X += 4) {   // (wave-uniform; P is symmetric: read down a column, lane by lane)
-    const mfma_d4 acc = hv_tile(16 * X, HV_NP / 4, lr, lk, [&](int i, int kk) { return Pm[kk * HV_NP + i]; }, [&](int kk, int c) { return Vs[kk * HV_K + c]; });
+    const mfma_d4 acc = hv_tile(16 * X, GN_NP / 4, lr, lk, [&](int i, int kk) { return Pm[kk * GN_NP + i]; }, [&](int kk, int c) { return Vs[kk * HV_K + c]; });
 #pragma unroll
     for (int r = 0; r < 4; ++r) Ys[(16 * X + lk + 4 * r) * HV_K + lr] = acc[r];
   }
@@ -245,11 +176,11 @@ __global__ void __launch_bounds__(HV_T) k_hess_vec(BatchDev b, int K, const doub
     mfma_d4 accP[2] = {mfma_d4{0.0, 0.0, 0.0, 0.0}, mfma_d4{0.0, 0.0, 0.0, 0.0}};   // tile `wave` of Y_P; wave 0: tile 4 too
     for (int l0 = 0; l0 < L; l0 += HV_LMC) {
       const int nl = min(HV_LMC, L - l0);
-      for (int e = tid; e < HV_NP * HV_LMC; e += HV_T) {
+      for (int e = tid; e < GN_NP * HV_LMC; e += GN_T) {
         const int l = e % HV_LMC, a = e / HV_LMC;
         Wt[a * HV_WS + l] = (l < nl && a < VILO_NPU) ? wl[(size_t)a * L + l0 + l] : 0.0;
       }
-      for (int e = tid; e < HV_LMC * HV_K; e += HV_T) {
+      for (int e = tid; e < HV_LMC * HV_K; e += GN_T) {
         const int l = e / HV_K, c = e % HV_K;
         double v = 0.0;
         if (lv && l < nl && c < K) {
@@ -331,12 +262,12 @@ __global__ void __launch_bounds__(HV_T) k_hess_vec(BatchDev b, int K, const doub
   }
   __syncthreads();
   if (so)
-    for (int e = tid; e < K * HV_NS; e += HV_T) {
-      const int k = e / HV_NS, cd = hv_cd(e - k * HV_NS);
+    for (int e = tid; e < K * GN_NS; e += GN_T) {
+      const int k = e / GN_NS, cd = caller_cd(e - k * GN_NS);
       so[e] = !cd_active(cd, F, wm.const_mask) ? 0.0 : (badk[k] ? NAN : Ys[cd * HV_K + k]);
     }
   if (lo)
-    for (int e = tid; e < K * L; e += HV_T)
+    for (int e = tid; e < K * L; e += GN_T)
       if (badk[e / L]) lo[e] = NAN;
 }
 
@@ -352,7 +283,7 @@ extern "C" int vilo_batch_hessian_vector(vilo_ctx *ctx, vilo_batch *bt, int n_ve
   if (bt->mask.refuse(ctx, "vilo_batch_hessian_vector") != VILO_OK) return VILO_ERR_UNSUPPORTED;
   BatchDev &bd = bt->d;
   const int W = bd.W, n_lm = bd.n_lm, K = n_vec;
-  const size_t n_ss = (size_t)W * K * HV_NS, n_ls = (size_t)K * n_lm;
+  const size_t n_ss = (size_t)W * K * GN_NS, n_ls = (size_t)K * n_lm;
   BatchCall call(ctx, bt, &vilo_ctx::last_hess_vec_ms);
   // the call's device memory: saved solver state | records | state vectors | landmark vectors | state products | landmark products
   const size_t o_st = call.lay.take<SolverState>(W), o_rec = call.lay.take<vilo_hess_vec_record>((size_t)W * K);
@@ -370,7 +301,7 @@ extern "C" int vilo_batch_hessian_vector(vilo_ctx *ctx, vilo_batch *bt, int n_ve
   VILO_HIP(keep.saved);
   const int rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
-  hipLaunchKernelGGL(k_hess_vec, dim3(W), dim3(HV_T), sizeof(double) * HL_N, ctx->stream, bd, K, state_vec ? call.ptr<double>(o_sv) : (const double *)nullptr,
+  hipLaunchKernelGGL(k_hess_vec, dim3(W), dim3(GN_T), sizeof(double) * HL_N, ctx->stream, bd, K, state_vec ? call.ptr<double>(o_sv) : (const double *)nullptr,
                      (lm_vec && n_ls) ? call.ptr<double>(o_lv) : (const double *)nullptr, call.ptr<vilo_hess_vec_record>(o_rec),
                      state_out ? call.ptr<double>(o_ss) : (double *)nullptr, (lm_out && n_ls) ? call.ptr<double>(o_ls) : (double *)nullptr);
   VILO_HIP(hipGetLastError());

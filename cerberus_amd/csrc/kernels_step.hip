@@ -3,13 +3,14 @@
 // Linearisation: the marginalisation's pass (vilo_marg_linearize, mode 0), exactly as vilo_batch_gradient and vilo_batch_covariance run it:
 // the windows' SolverStates are copied aside before and back after; x, lambda and the prior are only read.
 //
-// k_gn_step, one workgroup per window, one code path for every batch size, all FP64. The camera-side dimensions split as k_covariance
-// splits them: P (79 + 1 padding, LDS), B (11 x 13, block tridiagonal), BP (143 x 80, global scratch or LDS: the forms below). Steps:
-//   1. owner-computes g and h = diag(H) of the 222 state entries, in k_gradient's order of the sums; dd_i = D^2_i / s_i^2 from h_i.
-//   2. assembly of H as k_covariance assembles it (visual Gram slots, IMU Grams, prior), mu dd on the diagonal; the landmarks are
+// k_gn_step, one workgroup per window, one code path for every batch size, all FP64. The camera-side dimensions split as gn_system.hpp
+// splits them: P (79 + 1 padding, LDS), B (11 x 13, block tridiagonal), BP (143 x 80, global scratch or LDS: the forms below). The reading
+// of the linearisation (owner walk, assembly, gauge, scaling, 13 x 13 Cholesky) is gn_system.hpp's. Steps:
+//   1. owner-computes g and h = diag(H) of the 222 state entries (state_entry_gh); dd_i = D^2_i / s_i^2 from h_i.
+//   2. assembly of H (assemble_visual_pose_block, assemble_imu_grams, assemble_prior), mu dd on the diagonal; the landmarks are
 //      eliminated with the damped E~_l = E_l + mu dd_l: P -= W^T W on the FP64 matrix cores (W = w_l^T / sqrt(E~_l), 32 or 16 landmarks per
 //      pass staged in LDS), g_P -= sum w_l g_l / E~_l.
-//   3. FRAME0 gauge: frame 0's rotation rows / columns and right-hand side in k_covariance's basis [e1 e2 u]; u and frame 0's position
+//   3. FRAME0 gauge: frame 0's rotation rows / columns and right-hand side in the basis [e1 e2 u] (gauge_basis); u and frame 0's position
 //      become constant dimensions.
 //   4. Jacobi equilibration (unit diagonal of the damped, reduced camera system); a constant or absent dimension gets scale 0, a unit
 //      pivot and a zero right-hand side.
@@ -34,15 +35,11 @@
 #include <algorithm>
 
 #include "batch_call.hpp"
-#include "solve_common.hpp"
-#include "vilo_math.hpp"
+#include "gn_system.hpp"
 
 static_assert(sizeof(vilo_step_opts) == 32, "vilo_step_opts: 32 bytes (cerberus_amd/_ctypes.py mirrors it)");
 static_assert(sizeof(vilo_window_step_record) == 40, "vilo_window_step_record: 40 bytes (cerberus_amd/_ctypes.py mirrors it)");
 
-#define ST_T 256            // threads per window
-#define ST_NP 80
-#define ST_NS 222           // state entries per window (VILO_NCAM)
 #define ST_CHUNK 4096       // windows per scratch pass
 // global scratch per window (doubles)
 #define SS_BD 0                              // [11][13][13] diagonal blocks of B
@@ -50,10 +47,10 @@ static_assert(sizeof(vilo_window_step_record) == 40, "vilo_window_step_record: 4
 #define SS_L (SS_AO + 11 * 169)              // [11][13][13] L_k (lower triangle)
 #define SS_T (SS_L + 11 * 169)               // [11][13][13] T_k = A_{k,k-1} L_{k-1}^-T
 #define SS_BP (SS_T + 11 * 169)              // [143][80] BP, then Y
-#define SS_N (SS_BP + 143 * ST_NP)
+#define SS_N (SS_BP + 143 * GN_NP)
 // LDS (doubles)
 #define SL_P 0                               // [80][80] pose system, then its Cholesky factor
-#define SL_SM (SL_P + ST_NP * ST_NP)         // three 13 x 13: lc, lp, tn (lc also: 1 / sqrt(E~) and g_l / sqrt(E~) of a staging pass)
+#define SL_SM (SL_P + GN_NP * GN_NP)         // three 13 x 13: lc, lp, tn (lc also: 1 / sqrt(E~) and g_l / sqrt(E~) of a staging pass)
 #define SL_D (SL_SM + 3 * 169)               // [224] scale of every camera dimension (0: constant / absent)
 #define SL_B (SL_D + CD_N)                   // [224] g, then the scaled right-hand side, then the solution, by camera dimension
 #define SL_Q (SL_B + CD_N)                   // [16] Q = [e1 e2 u] (column-major, 9 used)
@@ -61,22 +58,13 @@ static_assert(sizeof(vilo_window_step_record) == 40, "vilo_window_step_record: 4
 // landmarks per staging pass, LDS doubles and the place of BP of a form (resident: BP / Y behind the shared region)
 template <bool YL> struct StepForm {
   static constexpr int LMC = YL ? 16 : 32;
-  static constexpr int Y = SL_R + LMC * ST_NP;
-  static constexpr int N = Y + (YL ? 143 * ST_NP : 0);
+  static constexpr int Y = SL_R + LMC * GN_NP;
+  static constexpr int N = Y + (YL ? 143 * GN_NP : 0);
 };
 static_assert(sizeof(double) * StepForm<false>::N + 64 <= 80 * 1024, "k_gn_step, streamed: two workgroups per CU");
 static_assert(sizeof(double) * StepForm<true>::N + 64 <= 160 * 1024, "k_gn_step, resident: the CU's LDS");
-static_assert(16 * ST_NP <= StepForm<true>::LMC * ST_NP && 4 * ST_T <= StepForm<true>::LMC * ST_NP && VILO_MAX_PRIOR_DIM + CD_N / 4 <= 16 * ST_NP,
+static_assert(16 * GN_NP <= StepForm<true>::LMC * GN_NP && 4 * GN_T <= StepForm<true>::LMC * GN_NP && VILO_MAX_PRIOR_DIM + CD_N / 4 <= 16 * GN_NP,
               "k_gn_step: the shared region");
-
-// camera dimension (solver_types.hpp) of entry d of the caller's layout
-__device__ __forceinline__ int step_cd(int d) {
-  if (d < 66) return d;
-  if (d < 165) { const int k = (d - 66) / 9; return CD_B0 + 13 * k + (d - 66 - 9 * k); }
-  if (d < 209) { const int k = (d - 165) / 4; return CD_B0 + 13 * k + 9 + (d - 165 - 4 * k); }
-  if (d < 221) return CD_EX0 + (d - 209);
-  return CD_TD;
-}
 
 // D^2 / s^2 of a coordinate with Gauss-Newton diagonal h: s = 1 / (1 + sqrt(h)), D^2 = clamp(s^2 h, lo, hi)
 __device__ __forceinline__ double step_dd(double h, double lo, double hi) {
@@ -94,7 +82,7 @@ __device__ __forceinline__ void step_syrk_wave(double *Pm, const double *A, int 
 #pragma unroll
   for (int i = 0; i < NT; ++i) acc[i] = mfma_d4{0.0, 0.0, 0.0, 0.0};
   for (int ks = 0; ks < nk; ++ks) {
-    const double *row = A + (4 * ks + lk) * ST_NP + lr;
+    const double *row = A + (4 * ks + lk) * GN_NP + lr;
     double v[5];
 #pragma unroll
     for (int X = 0; X < 5; ++X) v[X] = row[16 * X];
@@ -108,7 +96,7 @@ __device__ __forceinline__ void step_syrk_wave(double *Pm, const double *A, int 
   for (int i = 0; i < NT; ++i) {
     const int t = WV + 4 * i, X = t / 5, Y = t % 5;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) Pm[(16 * X + lk + 4 * r) * ST_NP + 16 * Y + lr] -= acc[i][r];
+    for (int r = 0; r < 4; ++r) Pm[(16 * X + lk + 4 * r) * GN_NP + 16 * Y + lr] -= acc[i][r];
   }
 }
 __device__ __forceinline__ void step_syrk(double *Pm, const double *A, int nk) {
@@ -121,28 +109,8 @@ __device__ __forceinline__ void step_syrk(double *Pm, const double *A, int nk) {
   }
 }
 
-// in-place Cholesky of the 13 x 13 block ss (lower triangle; the upper one is not read afterwards). *bad when a pivot <= thr.
-__device__ void step_chol13(double *ss, double thr, int *bad) {
-  const int tid = threadIdx.x;
-  for (int j = 0; j < 13; ++j) {
-    if (tid == 0) {
-      double p = ss[j * 13 + j];
-      if (!(p > thr)) { *bad = 1; p = 1.0; }
-      ss[j * 13 + j] = sqrt(p);
-    }
-    __syncthreads();
-    if (tid > j && tid < 13) ss[tid * 13 + j] /= ss[j * 13 + j];
-    __syncthreads();
-    for (int e = tid; e < 169; e += ST_T) {
-      const int r = e / 13, c = e % 13;
-      if (c > j && r >= c) ss[e] -= ss[r * 13 + j] * ss[c * 13 + j];
-    }
-    __syncthreads();
-  }
-}
-
 template <bool YL>
-__global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge, double lo, double hi, double thr, const double *mu_in, double *scr,
+__global__ void __launch_bounds__(GN_T) k_gn_step(BatchDev b, int w0, int gauge, double lo, double hi, double thr, const double *mu_in, double *scr,
                                                  vilo_window_step_record *rec, double *ss_out, double *ls_out) {
   using namespace vilo;
   extern __shared__ double lds[];
@@ -155,12 +123,12 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
   double *lc = lds + SL_SM, *lp = lc + 169, *tn = lp + 169;
   double *G = scr + (size_t)blockIdx.x * SS_N;
   double *Bd = G + SS_BD, *Ao = G + SS_AO, *Lg = G + SS_L, *Tg = G + SS_T, *BP = YL ? lds + StepForm<YL>::Y : G + SS_BP;
-  double *so = ss_out + (size_t)w * ST_NS, *lo_out = ls_out + wm.lm_off;
+  double *so = ss_out + (size_t)w * GN_NS, *lo_out = ls_out + wm.lm_off;
   const double mu = mu_in ? mu_in[w] : 0.0;
   const bool invalid = b.win_bad && b.win_bad[w];
   if (invalid || !(mu >= 0.0) || !isfinite(mu)) {   // a record without sqrt_info (the window is not linearised), or a bad mu: NaN for this window
-    for (int e = tid; e < ST_NS; e += ST_T) so[e] = NAN;
-    for (int l = tid; l < L; l += ST_T) lo_out[l] = NAN;
+    for (int e = tid; e < GN_NS; e += GN_T) so[e] = NAN;
+    for (int l = tid; l < L; l += GN_T) lo_out[l] = NAN;
     if (tid == 0) {
       vilo_window_step_record r;
       r.model_cost_change = NAN; r.scaled_norm = NAN; r.norm = NAN; r.grad_dot_step = NAN;
@@ -170,74 +138,23 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
     return;
   }
   const bool frame0 = gauge == VILO_COV_GAUGE_FRAME0;
-  const int pn = wm.prior_n;
   double *dxs = Rg;                                            // [96] prior dx
   short *inv_pmap = (short *)(Rg + VILO_MAX_PRIOR_DIM);        // [224] prior row of a camera dimension
   if (tid == 0) bad_s = 0;
-  for (int e = tid; e < ST_NP * ST_NP; e += ST_T) Pm[e] = 0.0;
-  for (int e = tid; e < SS_L; e += ST_T) G[e] = 0.0;   // (Bd, Ao; every L_k and T_k that is read is written first)
-  for (int e = tid; e < 143 * ST_NP; e += ST_T) BP[e] = 0.0;
-  for (int e = tid; e < CD_N; e += ST_T) { inv_pmap[e] = -1; bv[e] = 0.0; dsc[e] = 0.0; }
-  if (pn > 0 && tid < wm.prior_nb)
-    prior_dx(b.x + (size_t)w * XSTRIDE + b.prior_bstate[w * 40 + tid], b.prior_x0 + (size_t)w * 280 + b.prior_bxoff[w * 40 + tid],
-             b.prior_bsize[w * 40 + tid], dxs + b.prior_bidx[w * 40 + tid]);
-  __syncthreads();
-  if (tid < pn) inv_pmap[b.prior_map[(size_t)w * 96 + tid]] = (short)tid;
-  __syncthreads();
+  for (int e = tid; e < GN_NP * GN_NP; e += GN_T) Pm[e] = 0.0;
+  for (int e = tid; e < SS_L; e += GN_T) G[e] = 0.0;   // (Bd, Ao; every L_k and T_k that is read is written first)
+  for (int e = tid; e < 143 * GN_NP; e += GN_T) BP[e] = 0.0;
+  for (int e = tid; e < CD_N; e += GN_T) { bv[e] = 0.0; dsc[e] = 0.0; }
+  prior_view_init(b, wm, w, b.prior_map + (size_t)w * 96, dxs, inv_pmap);
 
-  // ---- 1. g, h and dd of the 222 state entries (k_gradient's walk) ----
+  // ---- 1. g, h and dd of the 222 state entries ----
   double g = 0.0, h = 0.0, dd = 0.0;
   bool act = false;
-  const int cd = tid < ST_NS ? step_cd(tid) : CD_N - 1;
-  if (tid < ST_NS) {
+  const int cd = tid < GN_NS ? caller_cd(tid) : CD_N - 1;
+  if (tid < GN_NS) {
     act = cd_active(cd, F, wm.const_mask);
     if (act) {
-      if (cd < CD_B0) {
-        const int f = cd / 6, a = cd - 6 * f;
-        const int crest = cd < 66 ? -1 : (cd < CD_TD ? 12 + (cd - CD_EX0) : 24);
-        for (int ch = 0; ch < wm.n_chunks; ++ch) {
-          const ChunkMeta cm = b.chunk[wm.chunk_off + ch];
-          int t0 = 0, t1 = cm.kmax, c = crest;
-          if (cd < 66) {
-            if (f == cm.s) c = a;
-            else if (f > cm.s && f - cm.s < cm.kmax) { c = 6 + a; t0 = f - cm.s; t1 = t0 + 1; }
-            else continue;
-          }
-          double sgn, one;
-          const int eg = gram26_index(c, 25, sgn), eh = gram26_index(c, c, one);
-          for (int t = t0; t < t1; ++t) {
-            const double *gs = b.gram + (size_t)(cm.gram_off + t) * VILO_GRAM;
-            g += sgn * gs[eg];
-            h += gs[eh];
-          }
-        }
-      }
-      {
-        int f, ci;
-        if (cd < 66) { f = cd / 6; ci = cd - 6 * f; }
-        else if (cd >= CD_B0) { f = (cd - CD_B0) / 13; ci = 6 + (cd - CD_B0 - 13 * f); }
-        else { f = -1; ci = 0; }
-        if (f >= 0) {
-          if (f >= 1 && !b.imu_skip[w * 10 + f - 1]) {
-            const double *gr = b.imu_gram + (size_t)(w * 10 + f - 1) * 780;
-            g += gr[tri39(19 + ci, 38)];
-            h += gr[tri39(19 + ci, 19 + ci)];
-          }
-          if (f + 1 < F && f < VILO_WINDOW_SIZE && !b.imu_skip[w * 10 + f]) {
-            const double *gr = b.imu_gram + (size_t)(w * 10 + f) * 780;
-            g += gr[tri39(ci, 38)];
-            h += gr[tri39(ci, ci)];
-          }
-        }
-      }
-      const int pi = inv_pmap[cd];
-      if (pn > 0 && pi >= 0) {
-        const double *Hp = b.prior_H + (size_t)w * 96 * 96;
-        double s = b.prior_b0[(size_t)w * 96 + pi];
-        for (int q = 0; q < pn; ++q) s += Hp[(size_t)q * pn + pi] * dxs[q];
-        g += s;
-        h += Hp[(size_t)pi * pn + pi];
-      }
+      state_entry_gh<true>(b, wm, w, cd, inv_pmap, dxs, g, h);
       if (!isfinite(g) || !isfinite(h) || h < 0.0) bad_s = 1;
       else dd = step_dd(h, lo, hi);
       bv[cd] = g;
@@ -245,74 +162,13 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
   }
   __syncthreads();   // (dxs / inv_pmap are done with: the region is the landmark staging below)
 
-  // ---- 2. assembly (k_covariance's) ----
-  for (int ch = 0; ch < wm.n_chunks; ++ch) {
-    const ChunkMeta cm = b.chunk[wm.chunk_off + ch];
-    for (int t = 0; t < cm.kmax; ++t) {
-      const double *gs = b.gram + (size_t)(cm.gram_off + t) * VILO_GRAM;
-      for (int e = tid; e < VILO_GRAM26; e += ST_T) {
-        int a = 0, rem = e;
-        while (rem >= 26 - a) { rem -= 26 - a; ++a; }
-        const int bc = a + rem;
-        if (bc == 25) continue;
-        if (t == 0 && ((a >= 6 && a < 12) || (bc >= 6 && bc < 12))) continue;
-        auto cdof = [&](int c) { return c < 6 ? 6 * cm.s + c : (c < 12 ? 6 * (cm.s + t) + (c - 6) : (c < 18 ? CD_EX0 + c - 12 : (c < 24 ? CD_EX1 + c - 18 : CD_TD))); };
-        double sg;
-        const double v = gs[gram26_index(a, bc, sg)];
-        const int i = cdof(a), j = cdof(bc);
-        Pm[i * ST_NP + j] += sg * v;
-        if (i != j) Pm[j * ST_NP + i] += sg * v;
-      }
-      __syncthreads();
-    }
-  }
-  for (int k = 0; k + 1 < F && k < VILO_WINDOW_SIZE; ++k) {
-    const int f = w * 10 + k;
-    if (!b.imu_skip[f]) {
-      const double *gr = b.imu_gram + (size_t)f * 780;
-      for (int e = tid; e < 780; e += ST_T) {
-        int a = 0, rem = e;
-        while (rem >= 39 - a) { rem -= 39 - a; ++a; }
-        const int bc = a + rem;   // (tri39(a, bc) == e)
-        if (bc >= 38) continue;
-        const double v = gr[e];
-        auto map = [&](int c, bool &isP, int &fr) {   // P dimension or (frame, B dimension)
-          if (c < 6) { isP = true; return 6 * k + c; }
-          if (c < 19) { isP = false; fr = k; return c - 6; }
-          if (c < 25) { isP = true; return 6 * (k + 1) + (c - 19); }
-          isP = false; fr = k + 1; return c - 25;
-        };
-        bool pa, pb; int fa = 0, fb = 0;
-        const int ia = map(a, pa, fa), ib = map(bc, pb, fb);
-        if (pa && pb) { Pm[ia * ST_NP + ib] += v; if (ia != ib) Pm[ib * ST_NP + ia] += v; }
-        else if (!pa && !pb) {
-          if (fa == fb) { Bd[fa * 169 + ia * 13 + ib] += v; if (ia != ib) Bd[fa * 169 + ib * 13 + ia] += v; }
-          else Ao[fb * 169 + ib * 13 + ia] += v;   // (a < bc: a in frame k, bc in frame k + 1)
-        } else if (pa) BP[(fb * 13 + ib) * ST_NP + ia] += v;
-        else BP[(fa * 13 + ia) * ST_NP + ib] += v;
-      }
-    }
-    __syncthreads();
-  }
-  if (pn > 0) {
-    const double *Hp = b.prior_H + (size_t)w * 96 * 96;
-    const int *pmap = b.prior_map + (size_t)w * 96;
-    for (int e = tid; e < pn * pn; e += ST_T) {
-      const int ci = pmap[e / pn], cj = pmap[e % pn];
-      const double v = Hp[e];
-      if (ci < CD_B0 && cj < CD_B0) Pm[ci * ST_NP + cj] += v;
-      else if (ci >= CD_B0 && cj >= CD_B0) {
-        const int fi = (ci - CD_B0) / 13, di = (ci - CD_B0) % 13, fj = (cj - CD_B0) / 13, dj = (cj - CD_B0) % 13;
-        if (fi == fj) Bd[fi * 169 + di * 13 + dj] += v;
-        else if (fi == fj + 1) Ao[fi * 169 + di * 13 + dj] += v;
-        else if (fj != fi + 1 && v != 0.0) bad_s = 1;   // (the speed / bias part would not be block tridiagonal; no prior of the reference does this)
-      } else if (ci >= CD_B0) BP[(ci - CD_B0) * ST_NP + cj] += v;
-    }
-    __syncthreads();
-  }
+  // ---- 2. assembly ----
+  assemble_visual_pose_block(b, wm, Pm);
+  assemble_imu_grams(b, wm, w, Pm, Bd, Ao, BP);
+  assemble_prior(b, wm, w, Pm, Bd, Ao, BP, &bad_s);
   // damping: mu D^2 / s^2 on the diagonal, by the entry's owner
   if (act) {
-    if (cd < CD_B0) Pm[cd * ST_NP + cd] += mu * dd;
+    if (cd < CD_B0) Pm[cd * GN_NP + cd] += mu * dd;
     else Bd[((cd - CD_B0) / 13) * 169 + ((cd - CD_B0) % 13) * 14] += mu * dd;
   }
   __syncthreads();
@@ -335,69 +191,39 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
         gls[tid] = gl * s;
       }
       __syncthreads();
-      for (int e = tid; e < ST_LMC * ST_NP; e += ST_T) {
+      for (int e = tid; e < ST_LMC * GN_NP; e += GN_T) {
         const int li = e % ST_LMC, a = e / ST_LMC;
-        if (li < nr) Rg[li * ST_NP + a] = (li < nl && a < VILO_NPU) ? wl[(size_t)a * L + l0 + li] * sl[li] : 0.0;
+        if (li < nr) Rg[li * GN_NP + a] = (li < nl && a < VILO_NPU) ? wl[(size_t)a * L + l0 + li] * sl[li] : 0.0;
       }
       __syncthreads();
       step_syrk(Pm, Rg, nr / 4);
-      if (tid < ST_NP) {
+      if (tid < GN_NP) {
         double s = 0.0;
-        for (int li = 0; li < nl; ++li) s += Rg[li * ST_NP + tid] * gls[li];
+        for (int li = 0; li < nl; ++li) s += Rg[li * GN_NP + tid] * gls[li];
         bv[tid] -= s;
       }
       __syncthreads();
     }
   }
 
-  // ---- 3. gauge: frame 0's rotation in the basis Q = [e1 e2 u], u = R0^T e_z (k_covariance's) ----
+  // ---- 3. gauge: frame 0's rotation in the basis Q = [e1 e2 u], u = R0^T e_z ----
   if (frame0) {
     if (tid == 0) {
-      const double *q = b.x + (size_t)w * XSTRIDE + XO_POSE + 3;   // qx qy qz qw
-      const double qx = q[0], qy = q[1], qz = q[2], qw = q[3], nq = 1.0 / sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-      const double x = qx * nq, y = qy * nq, z = qz * nq, s = qw * nq;
-      double u[3] = {2.0 * (x * z - s * y), 2.0 * (y * z + s * x), 1.0 - 2.0 * (x * x + y * y)};
-      const double nu = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-      for (int i = 0; i < 3; ++i) u[i] *= nu;
-      int m = 0;
-      for (int i = 1; i < 3; ++i) if (fabs(u[i]) < fabs(u[m])) m = i;
-      double a3[3] = {0.0, 0.0, 0.0}; a3[m] = 1.0;
-      double e1[3] = {u[1] * a3[2] - u[2] * a3[1], u[2] * a3[0] - u[0] * a3[2], u[0] * a3[1] - u[1] * a3[0]};
-      const double n1 = 1.0 / sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-      for (int i = 0; i < 3; ++i) e1[i] *= n1;
-      const double e2[3] = {u[1] * e1[2] - u[2] * e1[1], u[2] * e1[0] - u[0] * e1[2], u[0] * e1[1] - u[1] * e1[0]};
-      for (int i = 0; i < 3; ++i) { Q[i] = e1[i]; Q[3 + i] = e2[i]; Q[6 + i] = u[i]; }
+      gauge_basis(b.x + (size_t)w * XSTRIDE + XO_POSE + 3, Q);
       double r[3];
       for (int m2 = 0; m2 < 3; ++m2) r[m2] = Q[3 * m2] * bv[3] + Q[3 * m2 + 1] * bv[4] + Q[3 * m2 + 2] * bv[5];
       for (int m2 = 0; m2 < 3; ++m2) bv[3 + m2] = r[m2];
     }
     __syncthreads();
-    if (tid < ST_NP) {
-      double r[3];
-      for (int m = 0; m < 3; ++m) r[m] = Q[3 * m] * Pm[3 * ST_NP + tid] + Q[3 * m + 1] * Pm[4 * ST_NP + tid] + Q[3 * m + 2] * Pm[5 * ST_NP + tid];
-      for (int m = 0; m < 3; ++m) Pm[(3 + m) * ST_NP + tid] = r[m];
-    }
-    __syncthreads();
-    if (tid < ST_NP) {
-      double r[3];
-      for (int m = 0; m < 3; ++m) r[m] = Q[3 * m] * Pm[tid * ST_NP + 3] + Q[3 * m + 1] * Pm[tid * ST_NP + 4] + Q[3 * m + 2] * Pm[tid * ST_NP + 5];
-      for (int m = 0; m < 3; ++m) Pm[tid * ST_NP + 3 + m] = r[m];
-    }
-    for (int rw = tid; rw < 143; rw += ST_T) {
-      double *row = BP + (size_t)rw * ST_NP;
-      double r[3];
-      for (int m = 0; m < 3; ++m) r[m] = Q[3 * m] * row[3] + Q[3 * m + 1] * row[4] + Q[3 * m + 2] * row[5];
-      for (int m = 0; m < 3; ++m) row[3 + m] = r[m];
-    }
-    __syncthreads();
+    gauge_rotate(Pm, BP, Q);
   }
 
   // ---- 4. equilibration; constant / absent / gauge-held dimensions: scale 0, unit diagonal, zero right-hand side ----
-  for (int c = tid; c < CD_N; c += ST_T) {
+  for (int c = tid; c < CD_N; c += GN_T) {
     const bool on = cd_active(c, F, wm.const_mask) && !(frame0 && (c < 3 || c == 5));
     double d = 0.0;
     if (on) {
-      const double hh = c < CD_B0 ? Pm[c * ST_NP + c] : Bd[((c - CD_B0) / 13) * 169 + ((c - CD_B0) % 13) * 14];
+      const double hh = c < CD_B0 ? Pm[c * GN_NP + c] : Bd[((c - CD_B0) / 13) * 169 + ((c - CD_B0) % 13) * 14];
       if (!(hh > 0.0) || !isfinite(hh)) bad_s = 1;
       else d = 1.0 / sqrt(hh);
     }
@@ -406,24 +232,14 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
     if (d == 0.0) bv[c] = 0.0;
   }
   __syncthreads();
-  auto scaled = [&](double v, int ci, int cj) { const double di = dsc[ci], dj = dsc[cj]; return (di == 0.0 || dj == 0.0) ? (ci == cj ? 1.0 : 0.0) : v * di * dj; };
-  for (int e = tid; e < ST_NP * ST_NP; e += ST_T) Pm[e] = scaled(Pm[e], e / ST_NP, e % ST_NP);
-  for (int e = tid; e < 11 * 169; e += ST_T) {
-    const int k = e / 169, i = (e % 169) / 13, j = e % 13;
-    Bd[e] = scaled(Bd[e], CD_B0 + 13 * k + i, CD_B0 + 13 * k + j);
-    Ao[e] = k == 0 ? 0.0 : scaled(Ao[e], CD_B0 + 13 * k + i, CD_B0 + 13 * (k - 1) + j);
-  }
-  for (int e = tid; e < 143 * ST_NP; e += ST_T) {
-    const double di = dsc[CD_B0 + e / ST_NP], dj = dsc[e % ST_NP];
-    BP[e] = (di == 0.0 || dj == 0.0) ? 0.0 : BP[e] * di * dj;
-  }
-  for (int e = tid; e < ST_LMC * ST_NP; e += ST_T) Rg[e] = 0.0;   // (rows 13 .. 15 of Mg stay zero)
+  scale_system(Pm, Bd, Ao, BP, dsc);
+  for (int e = tid; e < ST_LMC * GN_NP; e += GN_T) Rg[e] = 0.0;   // (rows 13 .. 15 of Mg stay zero)
   __syncthreads();
 
   // ---- 5. forward over the chain ----
   double *yB = bv + CD_B0;
   for (int k = 0; k < VILO_F; ++k) {
-    for (int e = tid; e < 169; e += ST_T) lc[e] = Bd[k * 169 + e];
+    for (int e = tid; e < 169; e += GN_T) lc[e] = Bd[k * 169 + e];
     if (k > 0 && tid < 13) {   // row tid of T = A_{k,k-1} L_{k-1}^-T
       const double *a = Ao + k * 169 + tid * 13;
       double t[13];
@@ -439,7 +255,7 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
     }
     __syncthreads();
     if (k > 0) {
-      for (int e = tid; e < 169; e += ST_T) {
+      for (int e = tid; e < 169; e += GN_T) {
         const int r = e / 13, c = e % 13;
         double s = 0.0;
         for (int m = 0; m < 13; ++m) s += tn[r * 13 + m] * tn[c * 13 + m];
@@ -447,11 +263,11 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
       }
       __syncthreads();
     }
-    step_chol13(lc, thr, &bad_s);
-    for (int e = tid; e < 169; e += ST_T) Lg[k * 169 + e] = lc[e];
+    chol13(lc, thr, &bad_s);
+    for (int e = tid; e < 169; e += GN_T) Lg[k * 169 + e] = lc[e];
     // the right-hand side z = b_k - T y_{k-1} (in place)
-    if (k > 0 && tid >= ST_T - 13) {
-      const int r = tid - (ST_T - 13);
+    if (k > 0 && tid >= GN_T - 13) {
+      const int r = tid - (GN_T - 13);
       double s = yB[13 * k + r];
       for (int m = 0; m < 13; ++m) s -= tn[r * 13 + m] * yB[13 * (k - 1) + m];
       yB[13 * k + r] = s;
@@ -459,14 +275,14 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
     __syncthreads();
     // Y_k = L_k^-1 (BP_k - T Y_{k-1}), column p by thread p (Y_{k-1}'s column p read out of Mg, Y_k's written into Mg and BP_k);
     // y_k = L_k^-1 z by thread 80
-    if (tid < ST_NP) {
+    if (tid < GN_NP) {
       double y[13];
 #pragma unroll
-      for (int r = 0; r < 13; ++r) y[r] = BP[(size_t)(13 * k + r) * ST_NP + tid];
+      for (int r = 0; r < 13; ++r) y[r] = BP[(size_t)(13 * k + r) * GN_NP + tid];
       if (k > 0) {
 #pragma unroll 1
         for (int m = 0; m < 13; ++m) {   // (rolled: 169 hoisted loads of T would cost the second workgroup its registers)
-          const double ym = Mg[m * ST_NP + tid];
+          const double ym = Mg[m * GN_NP + tid];
 #pragma unroll
           for (int r = 0; r < 13; ++r) y[r] -= tn[r * 13 + m] * ym;
         }
@@ -479,8 +295,8 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
         y[r] = s / lc[r * 13 + r];
       }
 #pragma unroll
-      for (int r = 0; r < 13; ++r) { Mg[r * ST_NP + tid] = y[r]; BP[(size_t)(13 * k + r) * ST_NP + tid] = y[r]; }
-    } else if (tid == ST_NP) {
+      for (int r = 0; r < 13; ++r) { Mg[r * GN_NP + tid] = y[r]; BP[(size_t)(13 * k + r) * GN_NP + tid] = y[r]; }
+    } else if (tid == GN_NP) {
       double y[13];
 #pragma unroll
       for (int r = 0; r < 13; ++r) {
@@ -494,57 +310,57 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
     }
     __syncthreads();
     step_syrk(Pm, Mg, 4);   // S_P -= Y_k^T Y_k
-    if (tid < ST_NP) {
+    if (tid < GN_NP) {
       double s = 0.0;
-      for (int r = 0; r < 13; ++r) s += Mg[r * ST_NP + tid] * yB[13 * k + r];
+      for (int r = 0; r < 13; ++r) s += Mg[r * GN_NP + tid] * yB[13 * k + r];
       bv[tid] -= s;
     }
-    for (int e = tid; e < 169; e += ST_T) lp[e] = lc[e];
+    for (int e = tid; e < 169; e += GN_T) lp[e] = lc[e];
     __syncthreads();
   }
   // Cholesky of S_P (lower, in place); the forward substitution of the right-hand side rides along as one more row
-  for (int j = 0; j < ST_NP; ++j) {
+  for (int j = 0; j < GN_NP; ++j) {
     if (tid == 0) {
-      double p = Pm[j * ST_NP + j];
+      double p = Pm[j * GN_NP + j];
       if (!(p > thr)) { bad_s = 1; p = 1.0; }
-      Pm[j * ST_NP + j] = sqrt(p);
+      Pm[j * GN_NP + j] = sqrt(p);
     }
     __syncthreads();
-    const double piv = Pm[j * ST_NP + j];
-    for (int r = j + 1 + tid; r < ST_NP; r += ST_T) Pm[r * ST_NP + j] /= piv;
-    if (tid == ST_T - 1) bv[j] /= piv;
+    const double piv = Pm[j * GN_NP + j];
+    for (int r = j + 1 + tid; r < GN_NP; r += GN_T) Pm[r * GN_NP + j] /= piv;
+    if (tid == GN_T - 1) bv[j] /= piv;
     __syncthreads();
-    const int n = ST_NP - j - 1;
-    for (int e = tid; e < n * n; e += ST_T) {
+    const int n = GN_NP - j - 1;
+    for (int e = tid; e < n * n; e += GN_T) {
       const int r = j + 1 + e / n, c = j + 1 + e % n;
-      if (c <= r) Pm[r * ST_NP + c] -= Pm[r * ST_NP + j] * Pm[c * ST_NP + j];
+      if (c <= r) Pm[r * GN_NP + c] -= Pm[r * GN_NP + j] * Pm[c * GN_NP + j];
     }
-    if (tid >= ST_T - ST_NP) {
-      const int c = j + 1 + (tid - (ST_T - ST_NP));
-      if (c < ST_NP) bv[c] -= Pm[c * ST_NP + j] * bv[j];
+    if (tid >= GN_T - GN_NP) {
+      const int c = j + 1 + (tid - (GN_T - GN_NP));
+      if (c < GN_NP) bv[c] -= Pm[c * GN_NP + j] * bv[j];
     }
     __syncthreads();
   }
   // L_P^T x_P = y_P: thread r keeps y_r, thread j publishes x_j
   {
-    double yr = tid < ST_NP ? bv[tid] : 0.0;
-    for (int j = ST_NP - 1; j >= 0; --j) {
-      if (tid == j) bv[j] = yr / Pm[j * ST_NP + j];
+    double yr = tid < GN_NP ? bv[tid] : 0.0;
+    for (int j = GN_NP - 1; j >= 0; --j) {
+      if (tid == j) bv[j] = yr / Pm[j * GN_NP + j];
       __syncthreads();
-      if (tid < j) yr -= Pm[j * ST_NP + tid] * bv[j];
+      if (tid < j) yr -= Pm[j * GN_NP + tid] * bv[j];
     }
     __syncthreads();
   }
   // u = y_B - Y x_P, then backward over the chain: L_k^T x_k = u_k - T_{k+1}^T x_{k+1}
   if (tid < 143) {
-    const double *row = BP + (size_t)tid * ST_NP;
+    const double *row = BP + (size_t)tid * GN_NP;
     double s = 0.0;
-    for (int p = 0; p < ST_NP; ++p) s += row[p] * bv[p];
+    for (int p = 0; p < GN_NP; ++p) s += row[p] * bv[p];
     yB[tid] -= s;
   }
   __syncthreads();
   for (int k = VILO_F - 1; k >= 0; --k) {
-    for (int e = tid; e < 169; e += ST_T) { lc[e] = Lg[k * 169 + e]; if (k + 1 < VILO_F) tn[e] = Tg[(k + 1) * 169 + e]; }
+    for (int e = tid; e < 169; e += GN_T) { lc[e] = Lg[k * 169 + e]; if (k + 1 < VILO_F) tn[e] = Tg[(k + 1) * 169 + e]; }
     __syncthreads();
     double v = 0.0;
     if (tid < 13) {
@@ -561,7 +377,7 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
   }
 
   // ---- 6. the step in the caller's coordinates ----
-  for (int c = tid; c < CD_N; c += ST_T) bv[c] *= dsc[c];
+  for (int c = tid; c < CD_N; c += GN_T) bv[c] *= dsc[c];
   __syncthreads();
   if (frame0 && tid == 0) {   // back from the basis Q (the u component is zero)
     double r[3];
@@ -582,7 +398,7 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
   {
     const double *wl = b.lm_w + 80 * (size_t)wm.lm_off, *lmg = b.lm_gbuf[0] + wm.lm_off, *lmE = b.lm_E + wm.lm_off;
     const int *perm = b.lm_perm + wm.lm_off;
-    for (int l = tid; l < L; l += ST_T) {
+    for (int l = tid; l < L; l += GN_T) {
       const double E = lmE[l], gl = lmg[l];
       const double ddl = (isfinite(E) && E >= 0.0) ? step_dd(E, lo, hi) : NAN;
       double s = gl;
@@ -596,11 +412,11 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
   }
 
   // ---- 7. the window record ----
-  double *r_gd = Rg, *r_dd = Rg + ST_T, *r_sq = Rg + 2 * ST_T;
-  int *r_nf = (int *)(Rg + 3 * ST_T), *r_bad = r_nf + ST_T;
+  double *r_gd = Rg, *r_dd = Rg + GN_T, *r_sq = Rg + 2 * GN_T;
+  int *r_nf = (int *)(Rg + 3 * GN_T), *r_bad = r_nf + GN_T;
   r_gd[tid] = a_gd; r_dd[tid] = a_dd; r_sq[tid] = a_sq; r_nf[tid] = a_nf; r_bad[tid] = a_bad;
   __syncthreads();
-  for (int st = ST_T / 2; st > 0; st >>= 1) {
+  for (int st = GN_T / 2; st > 0; st >>= 1) {
     if (tid < st) {
       const int o = tid + st;
       r_gd[tid] += r_gd[o];
@@ -612,9 +428,9 @@ __global__ void __launch_bounds__(ST_T) k_gn_step(BatchDev b, int w0, int gauge,
     __syncthreads();
   }
   const bool bad = bad_s != 0 || r_bad[0] != 0;
-  if (tid < ST_NS) so[tid] = bad ? NAN : ds;
+  if (tid < GN_NS) so[tid] = bad ? NAN : ds;
   if (bad)
-    for (int l = tid; l < L; l += ST_T) lo_out[l] = NAN;
+    for (int l = tid; l < L; l += GN_T) lo_out[l] = NAN;
   if (tid == 0) {
     vilo_window_step_record r;
     const double gd = r_gd[0], sdd = r_dd[0];
@@ -661,7 +477,7 @@ extern "C" int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *bt, const
   BatchCall call(ctx, bt, &vilo_ctx::last_gn_step_ms);
   // the call's device memory: saved solver state | window records | mu | state step | landmark step | per-window scratch of one chunk
   const size_t o_st = call.lay.take<SolverState>(W), o_rec = call.lay.take<vilo_window_step_record>(W), o_mu = call.lay.take<double>(W, mu != nullptr);
-  const size_t o_ss = call.lay.take<double>(ST_NS * (size_t)W), o_ls = call.lay.take<double>(n_lm), o_scr = call.lay.take<double>((size_t)chunk * SS_N);
+  const size_t o_ss = call.lay.take<double>(GN_NS * (size_t)W), o_ls = call.lay.take<double>(n_lm), o_scr = call.lay.take<double>((size_t)chunk * SS_N);
   if (call.begin() != VILO_OK) return VILO_ERR_HIP;
   const bool resident = ctx->gn_step_form == 1;
   const size_t lds_bytes = sizeof(double) * (resident ? StepForm<true>::N : StepForm<false>::N);
@@ -678,7 +494,7 @@ extern "C" int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *bt, const
   if (rc != VILO_OK) return rc;
   for (int w0 = 0; w0 < W; w0 += chunk) {
     const int n = std::min(chunk, W - w0);
-    hipLaunchKernelGGL(resident ? k_gn_step<true> : k_gn_step<false>, dim3(n), dim3(ST_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_lm_diagonal, o.max_lm_diagonal, o.min_pivot,
+    hipLaunchKernelGGL(resident ? k_gn_step<true> : k_gn_step<false>, dim3(n), dim3(GN_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_lm_diagonal, o.max_lm_diagonal, o.min_pivot,
                        mu ? call.ptr<double>(o_mu) : (const double *)nullptr, call.ptr<double>(o_scr), call.ptr<vilo_window_step_record>(o_rec),
                        call.ptr<double>(o_ss), call.ptr<double>(o_ls));
   }
@@ -686,7 +502,7 @@ extern "C" int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *bt, const
   VILO_HIP(keep.restore());
   VILO_HIP(call.finish());
   VILO_HIP(call.down(windows, call.ptr<char>(o_rec), sizeof(vilo_window_step_record) * (size_t)W));
-  VILO_HIP(call.down(state_step, call.ptr<char>(o_ss), sizeof(double) * ST_NS * (size_t)W));
+  VILO_HIP(call.down(state_step, call.ptr<char>(o_ss), sizeof(double) * GN_NS * (size_t)W));
   VILO_HIP(call.down(lm_step, call.ptr<char>(o_ls), sizeof(double) * (size_t)n_lm));
   return VILO_OK;
 }
