@@ -2,9 +2,9 @@
 // Handle{Successful,Unsuccessful,Invalid}Step, DoglegStrategy::Step{Accepted,Rejected,IsInvalid}, the tolerances, max_solver_time): the body
 // of k_accept, callable from k_assemble as well (the two are consecutive one-workgroup-per-window launches; fused, an iteration of a small
 // batch loses a launch and its latency). Written for 128 threads; the other threads of a larger workgroup pass through its barriers.
+// The prior's dx and row term are cost_eval.hpp's; the two forms of the H dx loop, with their unroll factors, are this file's.
 #pragma once
-#include "solve_common.hpp"
-#include "factors.hpp"
+#include "cost_eval.hpp"
 
 using namespace vilo;
 
@@ -114,9 +114,7 @@ __device__ __forceinline__ void accept_body(BatchDev &b, const AcceptParams &ap,
   for (int k = t128; k + 1 < wm.n_frames; k += 128) imu += b.imu_cost[(size_t)win * 10 + k];
   if (wm.prior_n > 0) {
     const int n = wm.prior_n;
-    if (tid < wm.prior_nb)
-      prior_dx(xc + b.prior_bstate[win * 40 + tid], b.prior_x0 + (size_t)win * 280 + b.prior_bxoff[win * 40 + tid],
-               b.prior_bsize[win * 40 + tid], dxs + b.prior_bidx[win * 40 + tid]);
+    if (tid < wm.prior_nb) prior_dx_block(b, win, tid, xc, dxs);
     __syncthreads();
     const double *Hp = b.prior_H + (size_t)win * 96 * 96, *b0 = b.prior_b0 + (size_t)win * 96;
     if (part) {
@@ -134,14 +132,14 @@ __device__ __forceinline__ void accept_body(BatchDev &b, const AcceptParams &ap,
       if (tid < n) {
         double sacc = 0.0;
         for (int s2 = 0; s2 < ns; ++s2) sacc += part[s2 * 96 + tid];
-        pri = dxs[tid] * (sacc + 2.0 * b0[tid]);
+        pri = prior_row_term(dxs[tid], sacc, b0[tid]);
         my_hd = sacc;
       }
     } else if (tid < n) {   // n <= 96 < 128: one row per thread
       double sacc = 0.0;
 #pragma unroll 16
       for (int q = 0; q < n; ++q) sacc += Hp[(size_t)q * n + tid] * dxs[q];
-      pri = dxs[tid] * (sacc + 2.0 * b0[tid]);
+      pri = prior_row_term(dxs[tid], sacc, b0[tid]);
       my_hd = sacc;
     }
   }

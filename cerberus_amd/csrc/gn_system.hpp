@@ -17,6 +17,7 @@
 // every sum is fixed (owner-computes or one target per thread and barrier interval): no floating-point atomics.
 #pragma once
 #include "batch_state.hpp"
+#include "cost_eval.hpp"
 #include "solve_common.hpp"
 #include "vilo_math.hpp"
 
@@ -39,9 +40,7 @@ __device__ __forceinline__ int caller_cd(int d) {
 __device__ __forceinline__ void prior_view_init(const BatchDev &b, const WinMeta &wm, int w, const int *pmap, double *dxs, short *inv_pmap) {
   const int tid = threadIdx.x, pn = wm.prior_n;
   for (int e = tid; e < CD_N; e += GN_T) inv_pmap[e] = -1;
-  if (pn > 0 && tid < wm.prior_nb)
-    vilo::prior_dx(b.x + (size_t)w * XSTRIDE + b.prior_bstate[w * 40 + tid], b.prior_x0 + (size_t)w * 280 + b.prior_bxoff[w * 40 + tid],
-                   b.prior_bsize[w * 40 + tid], dxs + b.prior_bidx[w * 40 + tid]);
+  if (pn > 0 && tid < wm.prior_nb) prior_dx_block(b, w, tid, b.x + (size_t)w * XSTRIDE, dxs);
   __syncthreads();
   if (tid < pn) inv_pmap[pmap[tid]] = (short)tid;
   __syncthreads();

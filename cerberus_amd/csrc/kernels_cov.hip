@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0
     if (on && lk == 0) {
       const int gi = wm.lm_off + l, o = wm.lm_off + b.lm_perm[gi];
       const double Ei = 1.0 / b.lm_E[gi], vr = Ei + q * Ei * Ei;
-      // first observation: the packed wave and lane of device landmark l (t = 0 rows of the wave's [t][11][lanes] image)
+      // first observation: the packed wave and lane of device landmark l (the left point of t = 0 in the wave's image)
       double f[3] = {0.0, 0.0, 0.0};
       for (int wi = wm.wave_off; wi < wm.wave_off + wm.n_waves; ++wi) {
         const WaveMeta wv = b.wave[wi];
@@ -455,8 +455,7 @@ __global__ void __launch_bounds__(LC_T) k_landmark_covariance(BatchDev b, int w0
           const ChunkMeta cm = b.chunk[wv.seg_chunk[g]];
           const int i = l - cm.lm_local;
           if (i >= 0 && i < cm.n) {
-            const double *ob = b.obs + wv.obs_off + wv.seg_lane0[g] + i;
-            for (int c = 0; c < 3; ++c) f[c] = ob[(size_t)c * wv.n_lanes];
+            for (int c = 0; c < 3; ++c) f[c] = obs_at(b.obs + wv.obs_off, wv.n_lanes, wv.seg_lane0[g] + i, 0, OBS_LX + c);
           }
         }
       }

@@ -15,6 +15,7 @@
 
 #include <type_traits>
 #include "batch_call.hpp"
+#include "cost_eval.hpp"
 #include "solve_common.hpp"
 
 using namespace vilo;
@@ -145,9 +146,7 @@ __global__ void __launch_bounds__(MT) k_marginalize(BatchDev bd, const MargWin *
     const int pn = M.prior_n;
     const double *Hp = bd.prior_H + (size_t)win * 96 * 96, *b0 = bd.prior_b0 + (size_t)win * 96;
     const int *pmap = bd.prior_map + (size_t)win * 96;
-    if (tid < wm.prior_nb)
-      prior_dx(x + bd.prior_bstate[win * 40 + tid], bd.prior_x0 + (size_t)win * 280 + bd.prior_bxoff[win * 40 + tid],
-               bd.prior_bsize[win * 40 + tid], dx + bd.prior_bidx[win * 40 + tid]);
+    if (tid < wm.prior_nb) prior_dx_block(bd, win, tid, x, dx);
     __syncthreads();
     for (int e = tid; e < pn * pn; e += MT) add(pmap[e / pn], pmap[e % pn], Hp[e]);
     for (int i = tid; i < pn; i += MT) {
@@ -674,9 +673,7 @@ __global__ void __launch_bounds__(MGT) k_marginalize_lds(BatchDev bd, const Marg
     const int pn = M.prior_n;
     const double *Hp = bd.prior_H + (size_t)win * 96 * 96, *b0 = bd.prior_b0 + (size_t)win * 96;
     const int *pmap = bd.prior_map + (size_t)win * 96;
-    if (tid < wm.prior_nb)
-      prior_dx(x + bd.prior_bstate[win * 40 + tid], bd.prior_x0 + (size_t)win * 280 + bd.prior_bxoff[win * 40 + tid],
-               bd.prior_bsize[win * 40 + tid], dx + bd.prior_bidx[win * 40 + tid]);
+    if (tid < wm.prior_nb) prior_dx_block(bd, win, tid, x, dx);
     __syncthreads();
     for (int e = tid; e < pn * pn; e += MGT) add(pmap[e / pn], pmap[e % pn], Hp[e]);
     for (int i = tid; i < pn; i += MGT) {

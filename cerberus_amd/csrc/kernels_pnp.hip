@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "batch_call.hpp"
+#include "cost_eval.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
 
@@ -185,12 +186,12 @@ __global__ void __launch_bounds__(PNP_THREADS) k_frame_pose_pnp(BatchDev b, PnpA
         const double lam = b.lam[ls.gi];
         if (lam > 0.0) {
           const double *obs = b.obs + wv.obs_off;
-          const v3 pt0 = mk3(obs[lane], obs[(size_t)n + lane], obs[(size_t)2 * n + lane]);
+          const v3 pt0 = mk3(obs_at(obs, n, lane, 0, OBS_LX), obs_at(obs, n, lane, 0, OBS_LY), obs_at(obs, n, lane, 0, OBS_LZ));
           const double *pose_s = xs + 7 * ls.s;
           const v3 X = qR(qnormalized(ldq_pose(pose_s))) * (ric0 * (pt0 * (1.0 / lam)) + tic0) + ld3(pose_s);
           p[0] = X.x; p[1] = X.y; p[2] = X.z;
-          p[3] = obs[((size_t)t * 11) * n + lane];
-          p[4] = obs[((size_t)t * 11 + 1) * n + lane];
+          p[3] = obs_at(obs, n, lane, t, OBS_LX);
+          p[4] = obs_at(obs, n, lane, t, OBS_LY);
           use = true;
         }
       }

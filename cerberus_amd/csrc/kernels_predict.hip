@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "batch_call.hpp"
+#include "cost_eval.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
 
@@ -112,7 +113,7 @@ __global__ void __launch_bounds__(64) k_predict_next_frame(BatchDev b, PredictAr
     const m3 Rn = qR(qnormalized(ldq_pose(np.pose)));
     const v3 Pn = ld3(np.pose);
     const double *obs = b.obs + wv.obs_off;
-    const v3 uv0 = mk3(obs[lane], obs[(size_t)n + lane], obs[(size_t)2 * n + lane]);
+    const v3 uv0 = mk3(obs_at(obs, n, lane, 0, OBS_LX), obs_at(obs, n, lane, 0, OBS_LY), obs_at(obs, n, lane, 0, OBS_LZ));
     const m3 ric0 = qR(qnormalized(ldq_pose(xs + WIN_XS_EX)));
     const v3 tic0 = ld3(xs + WIN_XS_EX);
     const v3 pts_j = ric0 * (uv0 * (1.0 / lam)) + tic0;

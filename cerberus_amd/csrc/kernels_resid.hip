@@ -2,15 +2,16 @@
 // (vilo_batch_residuals, include/vilo_gpu.h; Estimator::outliersRejection, estimator.cpp:1741-1798; FeatureManager::setDepth /
 // removeFailures, feature_manager.cpp:142-171).
 //
-// Three launches, one code path for every batch size (no output depends on the batch a window shares, nor on its position):
-//   k_resid_landmarks  one wave per packed visual wave, lane = landmark: walks the frames as k_visual_cost_walk does, at x / lambda. Per
-//                      block the whitened residual (stored in the caller's observation row), rho and |r|^2; per landmark the reference's
-//                      reprojection sum in its own order of operations (no td, no velocities, no sqrt_info) and the flags. Per-landmark
-//                      values go to the caller's landmark order (lm_off + lm_perm): no floating-point atomics.
-//   k_resid_imu        k_imu_cost's layout (lane = factor for the raw residual, then lane = row of sqrt_info): the whitened vector and
-//                      1/2 |u|^2 per interval, whatever the window's solver state.
-//   k_resid_window     one workgroup per window: the prior's cost from its normal-equation form (k_accept's prior_H / prior_b0 / prior_c0),
-//                      then the landmark sums in caller order (a fixed per-thread stride and tree) and the window record.
+// Three launches, one code path for every batch size (no output depends on the batch a window shares, nor on its position); the cost's
+// arithmetic is cost_eval.hpp's pieces:
+//   k_resid_landmarks  one wave per packed visual wave, lane = landmark, walking the wave's frames at x / lambda. Per block the whitened
+//                      residual (stored in the caller's observation row), rho and |r|^2; per landmark the reference's reprojection sum
+//                      in its own order of operations (no td, no velocities, no sqrt_info) and the flags. Per-landmark values go to
+//                      the caller's landmark order (lm_off + lm_perm): no floating-point atomics.
+//   k_resid_imu        lane = factor for the raw residual, then lane = row of sqrt_info: the whitened vector and 1/2 |u|^2 per
+//                      interval, whatever the window's solver state.
+//   k_resid_window     one workgroup per window: the prior's cost from its normal-equation form (prior_H / prior_b0 / prior_c0), then
+//                      the landmark sums in caller order (a fixed per-thread stride and tree) and the window record.
 // With vilo_batch_set_samples in force the records are first integrated again at x by the marginalisation's pass (k_repropagate mode 0 +
 // the preparation), on copies: the call hands those kernels a BatchDev whose records, prepared records, flags and contact-force filters
 // point into the call's own memory, so the batch's are never written.
@@ -49,37 +50,30 @@ __global__ void __launch_bounds__(64) k_resid_landmarks(BatchDev b, double sq, d
   const unsigned char *flg = b.flags + wv.flag_off;
   double *orow = obs_res ? obs_res + 4 * (size_t)obs_row[gi] : nullptr;
   const double lam = b.lam[gi];
-  // the factors' form (k_visual_cost_walk): td-compensated start-frame point, its world point once per landmark
+  // the factors' form (cost_eval.hpp): td-compensated start-frame point, its world point once per landmark
+  auto row = [&](int t, int r) { return obs_at(obs, n, lane, t, r); };
   const double td = x[XO_TD];
   const double *ex0 = x + XO_EX, *ex1 = x + XO_EX + 7;
   const quat qic = ldq_pose(ex0), qic2 = ldq_pose(ex1);
   const v3 tic = ld3(ex0), tic2 = ld3(ex1);
-  const double inv_lam = 1.0 / lam;
-  const double dti = td - obs[(size_t)10 * n + lane];
-  const v3 pci = mk3((obs[(size_t)0 * n + lane] - obs[(size_t)6 * n + lane] * dti) * inv_lam, (obs[(size_t)1 * n + lane] - obs[(size_t)7 * n + lane] * dti) * inv_lam,
-                     obs[(size_t)2 * n + lane] * inv_lam);
-  const v3 p_i = qrot(qic, pci) + tic;
+  const v3 p_i = start_point(row(0, OBS_LX), row(0, OBS_LY), row(0, OBS_LZ), row(0, OBS_LVX), row(0, OBS_LVY), row(0, OBS_TD), td, 1.0 / lam, qic, tic);
   const double *pose_s = x + XO_POSE + 7 * s;
-  const v3 p_w = qrot(ldq_pose(pose_s), p_i) + ld3(pose_s);
+  const v3 p_w = world_point(pose_s, p_i);
   // Estimator::reprojectionError's form: rotation matrices of the normalised quaternions, depth = 1 / inv_depth, raw points
   const m3 Ri = qR(qnormalized(ldq_pose(pose_s))), ric0 = qR(qnormalized(qic)), ric1 = qR(qnormalized(qic2));
   const v3 Pi = ld3(pose_s);
   const double depth = 1.0 / lam;
-  const v3 uvi = mk3(obs[(size_t)0 * n + lane], obs[(size_t)1 * n + lane], obs[(size_t)2 * n + lane]);
+  const v3 uvi = mk3(row(0, OBS_LX), row(0, OBS_LY), row(0, OBS_LZ));
   const v3 pts_w = Ri * (ric0 * (uvi * depth) + tic) + Pi;
   double cost = 0.0, plain = 0.0, err = 0.0;
   int nb = 0, nh = 0, cnt = 0;
   auto block = [&](const v3 &pcj, double px, double py, double *rout) {
-    const double inv_z = 1.0 / pcj.z;
-    const double r0 = sq * (pcj.x * inv_z - px), r1 = sq * (pcj.y * inv_z - py);
-    const double s2 = r0 * r0 + r1 * r1;
-    double rho[3];
-    huber_rho(huber_a, s2, rho);
-    cost += rho[0];
-    plain += s2;
+    const CamBlock cb = camera_block(pcj, px, py, sq, huber_a);
+    cost += cb.rho0;
+    plain += cb.s2;
     ++nb;
-    if (s2 > huber_a * huber_a) ++nh;
-    if (rout) { rout[0] = r0; rout[1] = r1; }
+    if (cb.s2 > huber_a * huber_a) ++nh;
+    if (rout) { rout[0] = cb.r0; rout[1] = cb.r1; }
   };
   auto reproj = [&](const m3 &Rj, const v3 &Pj, const m3 &ricj, const v3 &ticj, double ux, double uy) {
     const v3 pts_cj = tr(ricj) * (tr(Rj) * (pts_w - Pj) - ticj);
@@ -90,23 +84,22 @@ __global__ void __launch_bounds__(64) k_resid_landmarks(BatchDev b, double sq, d
   for (int t = 0; t < wv.kmax; ++t) {
     const unsigned char fl = flg[(size_t)t * n + lane];
     if (!(fl & 1)) continue;
-    const double *ob = obs + (size_t)t * 11 * n + lane;
     double *rr = orow ? orow + 4 * (size_t)t : nullptr;
-    const double dtj = td - ob[(size_t)10 * n];
+    const double dtj = td - row(t, OBS_TD);
     const double *pose_j = x + XO_POSE + 7 * min(s + t, VILO_MAX_FRAMES - 1);
     const m3 Rj = qR(qnormalized(ldq_pose(pose_j)));
     const v3 Pj = ld3(pose_j);
     v3 p_j = p_i;
     if (t > 0) {
-      p_j = qrot(qinv(ldq_pose(pose_j)), p_w - Pj);
-      block(qrot(qinv(qic), p_j - tic), ob[0] - ob[(size_t)6 * n] * dtj, ob[(size_t)1 * n] - ob[(size_t)7 * n] * dtj, rr);
-      reproj(Rj, Pj, ric0, tic, ob[0], ob[(size_t)1 * n]);
+      p_j = frame_point(pose_j, p_w);
+      block(camera_point(qic, tic, p_j), row(t, OBS_LX) - row(t, OBS_LVX) * dtj, row(t, OBS_LY) - row(t, OBS_LVY) * dtj, rr);
+      reproj(Rj, Pj, ric0, tic, row(t, OBS_LX), row(t, OBS_LY));
     } else if (rr) {
       rr[0] = NAN; rr[1] = NAN;
     }
     if (fl & 2) {
-      block(qrot(qinv(qic2), p_j - tic2), ob[(size_t)3 * n] - ob[(size_t)8 * n] * dtj, ob[(size_t)4 * n] - ob[(size_t)9 * n] * dtj, rr ? rr + 2 : nullptr);
-      reproj(Rj, Pj, ric1, tic2, ob[(size_t)3 * n], ob[(size_t)4 * n]);
+      block(camera_point(qic2, tic2, p_j), row(t, OBS_RX) - row(t, OBS_RVX) * dtj, row(t, OBS_RY) - row(t, OBS_RVY) * dtj, rr ? rr + 2 : nullptr);
+      reproj(Rj, Pj, ric1, tic2, row(t, OBS_RX), row(t, OBS_RY));
     } else if (rr) {
       rr[2] = NAN; rr[3] = NAN;
     }
@@ -120,7 +113,7 @@ __global__ void __launch_bounds__(64) k_resid_landmarks(BatchDev b, double sq, d
   out.flags[o] = (unsigned char)((px > thr ? 1 : 0) | (depth < 0.0 ? 2 : 0) | (nh > 0 ? 4 : 0));
 }
 
-// one wave per 64 factors (k_imu_cost's layout); cost_out [W * 10], res_out [W * 10][31] or null
+// one wave per 64 factors (imu_stage's tile); cost_out [W * 10], res_out [W * 10][31] or null
 __global__ void __launch_bounds__(64) k_resid_imu(BatchDev b, double g_norm, double *cost_out, double *res_out) {
   using namespace vilo;
   __shared__ double rs[32 * 64];   // [entry][factor of the wave]; row 31: 1/2 |u|^2 per factor
@@ -128,27 +121,14 @@ __global__ void __launch_bounds__(64) k_resid_imu(BatchDev b, double g_norm, dou
   const int NF = b.W * 10;
   bool live = false, bad = false;
   {
-    double r[31];
-#pragma unroll
-    for (int i = 0; i < 31; ++i) r[i] = 0.0;
+    ImuResid r = {};
     if (f < NF) {
-      const int win = f / 10, k = f % 10;
+      const int win = f / 10;
       live = !b.imu_skip[f];
       bad = live && b.prep_bad && b.prep_bad[f];
-      if (live) {
-        const PreintPrepared &pp = b.prep[f];
-        const double *x = b.x + (size_t)win * XSTRIDE;
-        if (b.win[win].use_leg) {
-          imu_leg_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_LB + 4 * k, x + XO_POSE + 7 * (k + 1),
-                      x + XO_SB + 9 * (k + 1), x + XO_LB + 4 * (k + 1), r, false, nullptr, 0);
-        } else {
-          imu_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_POSE + 7 * (k + 1), x + XO_SB + 9 * (k + 1), r, false, nullptr, 0);
-        }
-      }
+      if (live) r = imu_factor_raw(b, f, b.x + (size_t)win * XSTRIDE, g_norm, b.win[win].use_leg);
     }
-#pragma unroll
-    for (int i = 0; i < 31; ++i) rs[i * 64 + lane] = r[i];
-    rs[31 * 64 + lane] = 0.0;
+    imu_stage(rs, lane, r);
   }
   lds_barrier();
   const unsigned long long livem = __ballot(live), badm = __ballot(bad);
@@ -157,12 +137,9 @@ __global__ void __launch_bounds__(64) k_resid_imu(BatchDev b, double g_norm, dou
     if (f0 + fl >= NF) break;
     double u = 0.0;
     if ((livem >> fl) & 1ULL) {
-      const double *U = b.prep[f0 + fl].sqrt_info + row * 31;
       double uq[31];
-#pragma unroll
-      for (int q = 0; q < 31; ++q) uq[q] = (q >= row) ? U[q] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 31; ++q) u += uq[q] * rs[q * 64 + fl];
+      imu_info_row(b.prep[f0 + fl].sqrt_info, row, uq);
+      u = imu_row_dot(uq, rs, fl);
     }
     const bool nan_f = (badm >> fl) & 1ULL;
     if (res_out && lane < 31) res_out[(size_t)(f0 + fl) * 31 + lane] = nan_f ? NAN : u;
@@ -173,11 +150,6 @@ __global__ void __launch_bounds__(64) k_resid_imu(BatchDev b, double g_norm, dou
   if (f < NF) cost_out[f] = rs[31 * 64 + lane];
 }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return __shfl(v, 0, 64);
-}
-
 // one workgroup of 128 threads per window
 __global__ void __launch_bounds__(128) k_resid_window(BatchDev b, ResidLm lm, const double *imu_cost, vilo_window_residual *out) {
   using namespace vilo;
@@ -186,20 +158,17 @@ __global__ void __launch_bounds__(128) k_resid_window(BatchDev b, ResidLm lm, co
   __shared__ int ired[8];
   const int win = blockIdx.x, tid = threadIdx.x;
   const WinMeta wm = b.win[win];
-  // prior: 1/2 (dx^T (H dx + 2 b0) + c0) at x, k_accept's form (MarginalizationFactor::Evaluate through H = J0^T J0, b0 = J0^T r0, c0 = r0^T r0)
+  // prior: 1/2 (dx^T (H dx + 2 b0) + c0) at x, from cost_eval.hpp's prior pieces
   double pri = 0.0;
   if (wm.prior_n > 0) {
     const int n = wm.prior_n;
-    const double *x = b.x + (size_t)win * XSTRIDE;
-    if (tid < wm.prior_nb)
-      prior_dx(x + b.prior_bstate[win * 40 + tid], b.prior_x0 + (size_t)win * 280 + b.prior_bxoff[win * 40 + tid], b.prior_bsize[win * 40 + tid],
-               dxs + b.prior_bidx[win * 40 + tid]);
+    if (tid < wm.prior_nb) prior_dx_block(b, win, tid, b.x + (size_t)win * XSTRIDE, dxs);
     __syncthreads();
     const double *Hp = b.prior_H + (size_t)win * 96 * 96, *b0 = b.prior_b0 + (size_t)win * 96;
     if (tid < n) {
       double sacc = 0.0;
       for (int q = 0; q < n; ++q) sacc += Hp[(size_t)q * n + tid] * dxs[q];
-      pri = dxs[tid] * (sacc + 2.0 * b0[tid]);
+      pri = prior_row_term(dxs[tid], sacc, b0[tid]);
     }
   }
   // landmark sums in caller order: thread t takes l = t, t + 128, ...; one fixed tree over the threads

@@ -876,26 +876,25 @@ __global__ void __launch_bounds__(64) k_visual_cost(BatchDev b, double sq, doubl
     const double lam = b.lamc[gi];
     const unsigned char fl = flg[(size_t)t * n + lane];
     if (fl & 1) {
-      double o12[12];
-      o12[0] = obs[(size_t)0 * n + lane]; o12[1] = obs[(size_t)1 * n + lane]; o12[2] = obs[(size_t)2 * n + lane];
-      o12[6] = obs[(size_t)6 * n + lane]; o12[7] = obs[(size_t)7 * n + lane]; o12[10] = obs[(size_t)10 * n + lane];
+      double o12[12];   // proj_factor's operands: point of the start frame, point of frame j, their velocities, the two td
+      o12[0] = obs_at(obs, n, lane, 0, OBS_LX); o12[1] = obs_at(obs, n, lane, 0, OBS_LY); o12[2] = obs_at(obs, n, lane, 0, OBS_LZ);
+      o12[6] = obs_at(obs, n, lane, 0, OBS_LVX); o12[7] = obs_at(obs, n, lane, 0, OBS_LVY); o12[10] = obs_at(obs, n, lane, 0, OBS_TD);
       const double *pose_s = x + XO_POSE + 7 * s, *ex0 = x + XO_EX, *ex1 = x + XO_EX + 7;
       const double td = x[XO_TD];
       const double *pose_j = x + XO_POSE + 7 * min(s + t, VILO_MAX_FRAMES - 1);
-      const double *ob = obs + (size_t)t * 11 * n;
-      o12[11] = ob[(size_t)10 * n + lane];
+      o12[11] = obs_at(obs, n, lane, t, OBS_TD);
       double r[2];
       if (t > 0) {
-        o12[3] = ob[(size_t)0 * n + lane]; o12[4] = ob[(size_t)1 * n + lane]; o12[5] = ob[(size_t)2 * n + lane];
-        o12[8] = ob[(size_t)6 * n + lane]; o12[9] = ob[(size_t)7 * n + lane];
+        o12[3] = obs_at(obs, n, lane, t, OBS_LX); o12[4] = obs_at(obs, n, lane, t, OBS_LY); o12[5] = obs_at(obs, n, lane, t, OBS_LZ);
+        o12[8] = obs_at(obs, n, lane, t, OBS_LVX); o12[9] = obs_at(obs, n, lane, t, OBS_LVY);
         proj_factor<0>(o12, pose_s, pose_j, ex0, ex1, lam, td, sq, r, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         double rho[3];
         huber_rho(huber_a, r[0] * r[0] + r[1] * r[1], rho);
         cost += rho[0];
       }
       if (fl & 2) {
-        o12[3] = ob[(size_t)3 * n + lane]; o12[4] = ob[(size_t)4 * n + lane]; o12[5] = ob[(size_t)5 * n + lane];
-        o12[8] = ob[(size_t)8 * n + lane]; o12[9] = ob[(size_t)9 * n + lane];
+        o12[3] = obs_at(obs, n, lane, t, OBS_RX); o12[4] = obs_at(obs, n, lane, t, OBS_RY); o12[5] = obs_at(obs, n, lane, t, OBS_RZ);
+        o12[8] = obs_at(obs, n, lane, t, OBS_RVX); o12[9] = obs_at(obs, n, lane, t, OBS_RVY);
         if (t > 0) proj_factor<1>(o12, pose_s, pose_j, ex0, ex1, lam, td, sq, r, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         else proj_factor<2>(o12, pose_s, pose_j, ex0, ex1, lam, td, sq, r, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         double rho[3];
@@ -929,36 +928,20 @@ __global__ void __launch_bounds__(64) k_visual_cost_walk(BatchDev b, double sq, 
     const double *ex0 = x + XO_EX, *ex1 = x + XO_EX + 7;
     const quat qic = ldq_pose(ex0), qic2 = ldq_pose(ex1);
     const v3 tic = ld3(ex0), tic2 = ld3(ex1);
-    const double inv_lam = 1.0 / b.lamc[ls.gi];
-    const double dti = td - obs[(size_t)10 * n + lane];
-    const v3 pci = mk3((obs[(size_t)0 * n + lane] - obs[(size_t)6 * n + lane] * dti) * inv_lam, (obs[(size_t)1 * n + lane] - obs[(size_t)7 * n + lane] * dti) * inv_lam,
-                       obs[(size_t)2 * n + lane] * inv_lam);
-    const v3 p_i = qrot(qic, pci) + tic;
-    const double *pose_s = x + XO_POSE + 7 * s;
-    const v3 p_w = qrot(ldq_pose(pose_s), p_i) + ld3(pose_s);
-    auto rho_of = [&](const v3 &pcj, double px, double py) {
-      const double inv_z = 1.0 / pcj.z;
-      const double r0 = sq * (pcj.x * inv_z - px), r1 = sq * (pcj.y * inv_z - py);
-      double rho[3];
-      huber_rho(huber_a, r0 * r0 + r1 * r1, rho);
-      return rho[0];
-    };
+    auto row = [&](int t, int r) { return obs_at(obs, n, lane, t, r); };
+    const v3 p_i = start_point(row(0, OBS_LX), row(0, OBS_LY), row(0, OBS_LZ), row(0, OBS_LVX), row(0, OBS_LVY), row(0, OBS_TD), td, 1.0 / b.lamc[ls.gi], qic, tic);
+    const v3 p_w = world_point(x + XO_POSE + 7 * s, p_i);
     for (int t = 0; t < wv.kmax; ++t) {
       const unsigned char fl = flg[(size_t)t * n + lane];
       if (!(fl & 1)) continue;
-      const double *ob = obs + (size_t)t * 11 * n + lane;
-      const double dtj = td - ob[(size_t)10 * n];
+      const double dtj = td - row(t, OBS_TD);
       v3 p_j = p_i;
       if (t > 0) {
-        const double *pose_j = x + XO_POSE + 7 * min(s + t, VILO_MAX_FRAMES - 1);
-        p_j = qrot(qinv(ldq_pose(pose_j)), p_w - ld3(pose_j));
-        const v3 pcj = qrot(qinv(qic), p_j - tic);
-        cost += rho_of(pcj, ob[0] - ob[(size_t)6 * n] * dtj, ob[(size_t)1 * n] - ob[(size_t)7 * n] * dtj);
+        p_j = frame_point(x + XO_POSE + 7 * min(s + t, VILO_MAX_FRAMES - 1), p_w);
+        cost += camera_block(camera_point(qic, tic, p_j), row(t, OBS_LX) - row(t, OBS_LVX) * dtj, row(t, OBS_LY) - row(t, OBS_LVY) * dtj, sq, huber_a).rho0;
       }
-      if (fl & 2) {
-        const v3 pcj = qrot(qinv(qic2), p_j - tic2);
-        cost += rho_of(pcj, ob[(size_t)3 * n] - ob[(size_t)8 * n] * dtj, ob[(size_t)4 * n] - ob[(size_t)9 * n] * dtj);
-      }
+      if (fl & 2)
+        cost += camera_block(camera_point(qic2, tic2, p_j), row(t, OBS_RX) - row(t, OBS_RVX) * dtj, row(t, OBS_RY) - row(t, OBS_RVY) * dtj, sq, huber_a).rho0;
     }
   }
   const double csum = wave_sum(ls.active ? cost : 0.0);
@@ -1246,39 +1229,22 @@ __global__ void __launch_bounds__(64) k_imu_cost(BatchDev b, double g_norm) {
   const int NF = b.W * 10;
   bool live = false;
   {
-    double r[31];
-#pragma unroll
-    for (int i = 0; i < 31; ++i) r[i] = 0.0;
+    ImuResid r = {};
     if (f < NF) {
-      const int win = f / 10, k = f % 10;
+      const int win = f / 10;
       live = !b.st[win].done && !b.imu_skip[f];
-      if (live) {
-        const PreintPrepared &pp = b.prep[f];
-        const double *x = b.xc + (size_t)win * XSTRIDE;
-        if (b.win[win].use_leg) {
-          imu_leg_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_LB + 4 * k, x + XO_POSE + 7 * (k + 1),
-                      x + XO_SB + 9 * (k + 1), x + XO_LB + 4 * (k + 1), r, false, nullptr, 0);
-        } else {
-          imu_raw(pp.head, g_norm, x + XO_POSE + 7 * k, x + XO_SB + 9 * k, x + XO_POSE + 7 * (k + 1), x + XO_SB + 9 * (k + 1), r, false, nullptr, 0);
-        }
-      }
+      if (live) r = imu_factor_raw(b, f, b.xc + (size_t)win * XSTRIDE, g_norm, b.win[win].use_leg);
     }
-#pragma unroll
-    for (int i = 0; i < 31; ++i) rs[i * 64 + lane] = r[i];
-    rs[31 * 64 + lane] = 0.0;
+    imu_stage(rs, lane, r);
   }
   lds_barrier();
   const unsigned long long livem = __ballot(live);
   const int row = min(lane, 30);
   for (int fl = 0; fl < 64; ++fl) {
     if (!((livem >> fl) & 1ULL)) continue;
-    const double *U = b.prep[f0 + fl].sqrt_info + row * 31;
-    double u[31];
-#pragma unroll
-    for (int q = 0; q < 31; ++q) u[q] = (q >= row) ? U[q] : 0.0;
-    double sacc = 0.0;
-#pragma unroll
-    for (int q = 0; q < 31; ++q) sacc += u[q] * rs[q * 64 + fl];
+    double uq[31];
+    imu_info_row(b.prep[f0 + fl].sqrt_info, row, uq);
+    const double sacc = imu_row_dot(uq, rs, fl);
     const double c = wave_sum(lane < 31 ? sacc * sacc : 0.0);
     if (lane == 0) rs[31 * 64 + fl] = c;
   }

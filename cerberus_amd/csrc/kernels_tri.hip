@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "batch_call.hpp"
+#include "cost_eval.hpp"
 #include "lin_common.hpp"
 #include "vilo_math.hpp"
 
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(64) k_triangulate(BatchDev b, TriArgs a) {
   const bool st = a.stereo && (f0 & 2);
   bool sel = a.select == 1 ? true : (a.select == 2 ? a.mask[o] != 0 : !(lam > 0.0));
   if (!st && !two_views) sel = false;   // a single mono observation: nothing to triangulate with (the reference leaves its depth alone)
-  const v3 uv0 = mk3(obs[lane], obs[(size_t)n + lane], obs[(size_t)2 * n + lane]);
+  const v3 uv0 = mk3(obs_at(obs, n, lane, 0, OBS_LX), obs_at(obs, n, lane, 0, OBS_LY), obs_at(obs, n, lane, 0, OBS_LZ));
   const int j = min(s + 1, VILO_MAX_FRAMES - 1);
   const m3 ric0 = qR(qnormalized(ldq_pose(xs + WIN_XS_EX)));
   const v3 tic0 = ld3(xs + WIN_XS_EX);
@@ -132,8 +133,8 @@ __global__ void __launch_bounds__(64) k_triangulate(BatchDev b, TriArgs a) {
     // second view: the right camera on the start frame, or the left camera on the next frame
     const double *pose1 = xs + 7 * (st ? s : j), *ex1 = xs + WIN_XS_EX + (st ? 7 : 0);
     const TriCam c1 = tri_camera(qR(qnormalized(ldq_pose(pose1))), ld3(pose1), qR(qnormalized(ldq_pose(ex1))), ld3(ex1));
-    const double p1x = st ? obs[(size_t)3 * n + lane] : obs[(size_t)11 * n + lane];
-    const double p1y = st ? obs[(size_t)4 * n + lane] : obs[(size_t)12 * n + lane];
+    const double p1x = st ? obs_at(obs, n, lane, 0, OBS_RX) : obs_at(obs, n, lane, 1, OBS_LX);
+    const double p1y = st ? obs_at(obs, n, lane, 0, OBS_RY) : obs_at(obs, n, lane, 1, OBS_LY);
     double U[16], v[4];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

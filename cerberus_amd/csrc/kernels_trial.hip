@@ -1,21 +1,21 @@
 // The cost of every window of a batch at up to 16 trial steps from its current device state, the state left where it is
-// (vilo_batch_trial_cost, include/vilo_gpu.h; TrustRegionMinimizer's candidate evaluation, the solver's k_visual_cost_walk / k_imu_cost /
-// k_accept on xc, opened to a caller's own steps).
+// (vilo_batch_trial_cost, include/vilo_gpu.h; TrustRegionMinimizer's candidate evaluation, which the solver runs on xc, opened to a
+// caller's own steps). The cost's arithmetic is cost_eval.hpp's pieces, as in the solver's cost kernels and in kernels_resid.hip.
 //
 // Four launches, one code path for every batch size and every K; no atomics, every sum in a fixed order. The call evaluates K + 1 columns
 // per window: the K trial states and, as column K, the state itself (the base cost every cost_change needs), all by the same arithmetic.
 //   k_trial_states     one wave per (window, column): x [+] alpha * delta into the call's scratch through retract_step.hpp, the device
 //                      function k_retract runs; the NUMERIC decision and the negative-depth count per column. Column K, and a NUMERIC
 //                      column, is a plain copy of x and lambda.
-//   k_trial_landmarks  one wave per packed visual wave, lane = landmark, k_resid_landmarks's walk. The columns' frame poses, extrinsics
+//   k_trial_landmarks  one wave per packed visual wave, lane = landmark, walking the wave's frames. The columns' frame poses, extrinsics
 //                      and td (92 doubles each) are staged in LDS with the lanes' inverse depths and cost accumulators. t is the outer
 //                      loop: a wave's observation and flag rows are fetched once per t and used for every column before the next t.
-//   k_trial_imu        k_resid_imu's layout (lane = factor for the raw residual, then lane = row of sqrt_info), the columns in chunks
-//                      of TI_KC: a row of sqrt_info is loaded once per chunk and applied to the chunk's residual vectors.
+//   k_trial_imu        lane = factor for the raw residual, then lane = row of sqrt_info, the columns in chunks of TI_KC: a row
+//                      (imu_info_row) is loaded once per chunk and applied to the chunk's residual vectors (imu_row_dot).
 //   k_trial_window     one workgroup per window: the prior's cost at every column with prior_H read once (H dx_k for all k per row), the
 //                      landmark and interval sums in k_resid_window's stride, tree and order, the records and `best`.
 // The walk keeps nothing per column in registers: per (t, column) it forms the landmark's start-frame point and world point again from the
-// staged column (two quaternion rotations more than k_resid_landmarks's one-state walk per block) and adds into an LDS accumulator.
+// staged column (two quaternion rotations more per block than a one-state walk, which forms them once per landmark) and adds into an LDS accumulator.
 // Holding them would take 6 doubles per column and lane, 192 registers at 16 columns, and a register array indexed by a run-time column
 // lives in scratch; DESIGN 4.30 has the figures.
 #include <hip/hip_runtime.h>
@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(64) k_trial_states(BatchDev b, TrialArgs a) {
   int nneg = 0;
   for (int l = lane; l < wm.L; l += 64)
     if (!(a.mask && a.mask[wm.lm_off + l]) && lo[l] < 0.0) ++nneg;
-  for (int off = 32; off > 0; off >>= 1) nneg += __shfl_xor(nneg, off, 64);
+  nneg = wave_sum_int(nneg);
   if (lane == 0) {
     a.numeric[(size_t)win * KK + k] = numeric ? 1 : 0;
     a.nneg[(size_t)win * KK + k] = numeric ? 0 : nneg;
@@ -103,47 +103,34 @@ __global__ void __launch_bounds__(64) k_trial_landmarks(BatchDev b, TrialArgs a,
   const int n = wv.n_lanes, s = ls.s;
   const double *obs = b.obs + wv.obs_off;
   const unsigned char *flg = b.flags + wv.flag_off;
+  auto row = [&](int t, int r) { return obs_at(obs, n, lane, t, r); };
   // the start frame's row, read once
-  const double u0 = obs[(size_t)0 * n + lane], u1 = obs[(size_t)1 * n + lane], u2 = obs[(size_t)2 * n + lane], v0 = obs[(size_t)6 * n + lane],
-               v1 = obs[(size_t)7 * n + lane], t0 = obs[(size_t)10 * n + lane];
+  const double u0 = row(0, OBS_LX), u1 = row(0, OBS_LY), u2 = row(0, OBS_LZ), v0 = row(0, OBS_LVX), v1 = row(0, OBS_LVY), t0 = row(0, OBS_TD);
   for (int t = 0; t < wv.kmax; ++t) {
     const unsigned char fl = flg[(size_t)t * n + lane];
     if (!(fl & 1)) continue;
-    const double *ob = obs + (size_t)t * 11 * n + lane;
     // this frame's row, read once for every column
-    const double tj = ob[(size_t)10 * n];
+    const double tj = row(t, OBS_TD);
     double lx = 0.0, ly = 0.0, lvx = 0.0, lvy = 0.0, rx = 0.0, ry = 0.0, rvx = 0.0, rvy = 0.0;
-    if (t > 0) { lx = ob[0]; ly = ob[(size_t)1 * n]; lvx = ob[(size_t)6 * n]; lvy = ob[(size_t)7 * n]; }
-    if (fl & 2) { rx = ob[(size_t)3 * n]; ry = ob[(size_t)4 * n]; rvx = ob[(size_t)8 * n]; rvy = ob[(size_t)9 * n]; }
+    if (t > 0) { lx = row(t, OBS_LX); ly = row(t, OBS_LY); lvx = row(t, OBS_LVX); lvy = row(t, OBS_LVY); }
+    if (fl & 2) { rx = row(t, OBS_RX); ry = row(t, OBS_RY); rvx = row(t, OBS_RVX); rvy = row(t, OBS_RVY); }
     const int fj = min(s + t, VILO_MAX_FRAMES - 1);
     for (int k = 0; k < KK; ++k) {
       const double *xk = tl_lds + k * TL_COL;
-      // the factors' form (k_resid_landmarks, k_visual_cost_walk): td-compensated start-frame point, its world point
+      // the factors' form (cost_eval.hpp) on the staged column: the start-frame point and, for t > 0, its world point, once per (t, column)
       const double td = xk[TL_TD];
       const double *ex0 = xk + TL_EX, *ex1 = xk + TL_EX + 7;
       const quat qic = ldq_pose(ex0);
       const v3 tic = ld3(ex0);
-      const double inv_lam = 1.0 / xk[TL_XS + lane];
-      const double dti = td - t0;
-      const v3 pci = mk3((u0 - v0 * dti) * inv_lam, (u1 - v1 * dti) * inv_lam, u2 * inv_lam);
-      const v3 p_i = qrot(qic, pci) + tic;
+      const v3 p_i = start_point(u0, u1, u2, v0, v1, t0, td, 1.0 / xk[TL_XS + lane], qic, tic);
       const double dtj = td - tj;
       double cost = xk[TL_XS + 64 + lane];
-      auto block = [&](const v3 &pcj, double px, double py) {
-        const double inv_z = 1.0 / pcj.z;
-        const double r0 = sq * (pcj.x * inv_z - px), r1 = sq * (pcj.y * inv_z - py);
-        double rho[3];
-        huber_rho(huber_a, r0 * r0 + r1 * r1, rho);
-        cost += rho[0];
-      };
       v3 p_j = p_i;
       if (t > 0) {
-        const double *pose_s = xk + 7 * s, *pose_j = xk + 7 * fj;
-        const v3 p_w = qrot(ldq_pose(pose_s), p_i) + ld3(pose_s);
-        p_j = qrot(qinv(ldq_pose(pose_j)), p_w - ld3(pose_j));
-        block(qrot(qinv(qic), p_j - tic), lx - lvx * dtj, ly - lvy * dtj);
+        p_j = frame_point(xk + 7 * fj, world_point(xk + 7 * s, p_i));
+        cost += camera_block(camera_point(qic, tic, p_j), lx - lvx * dtj, ly - lvy * dtj, sq, huber_a).rho0;
       }
-      if (fl & 2) block(qrot(qinv(ldq_pose(ex1)), p_j - ld3(ex1)), rx - rvx * dtj, ry - rvy * dtj);
+      if (fl & 2) cost += camera_block(camera_point(ldq_pose(ex1), ld3(ex1), p_j), rx - rvx * dtj, ry - rvy * dtj, sq, huber_a).rho0;
       tl_lds[k * TL_COL + TL_XS + 64 + lane] = cost;
     }
   }
@@ -158,7 +145,7 @@ __global__ void __launch_bounds__(64) k_trial_imu(BatchDev b, TrialArgs a, doubl
   const int KK = a.K + 1;
   const int lane = threadIdx.x, f0 = blockIdx.x * 64, f = f0 + lane;
   const int NF = b.W * 10;
-  const int win = f / 10, kf = f % 10;
+  const int win = f / 10;
   const bool live = f < NF && !b.imu_skip[f];
   const bool bad = live && b.prep_bad && b.prep_bad[f];
   const bool leg = live && b.win[win].use_leg;
@@ -167,38 +154,20 @@ __global__ void __launch_bounds__(64) k_trial_imu(BatchDev b, TrialArgs a, doubl
   for (int k0 = 0; k0 < KK; k0 += TI_KC) {
     const int nk = min(TI_KC, KK - k0);
     for (int kc = 0; kc < nk; ++kc) {
-      double r[31];
-#pragma unroll
-      for (int i = 0; i < 31; ++i) r[i] = 0.0;
-      if (live) {
-        const PreintPrepared &pp = b.prep[f];
-        const double *x = a.xt + ((size_t)win * KK + k0 + kc) * XSTRIDE;
-        if (leg) {
-          imu_leg_raw(pp.head, g_norm, x + XO_POSE + 7 * kf, x + XO_SB + 9 * kf, x + XO_LB + 4 * kf, x + XO_POSE + 7 * (kf + 1),
-                      x + XO_SB + 9 * (kf + 1), x + XO_LB + 4 * (kf + 1), r, false, nullptr, 0);
-        } else {
-          imu_raw(pp.head, g_norm, x + XO_POSE + 7 * kf, x + XO_SB + 9 * kf, x + XO_POSE + 7 * (kf + 1), x + XO_SB + 9 * (kf + 1), r, false, nullptr, 0);
-        }
-      }
-      double *rs = ti_lds + kc * 32 * 64;
-#pragma unroll
-      for (int i = 0; i < 31; ++i) rs[i * 64 + lane] = r[i];
-      rs[31 * 64 + lane] = 0.0;
+      ImuResid r = {};
+      if (live) r = imu_factor_raw(b, f, a.xt + ((size_t)win * KK + k0 + kc) * XSTRIDE, g_norm, leg);
+      imu_stage(ti_lds + kc * 32 * 64, lane, r);
     }
     lds_barrier();
     for (int fl = 0; fl < 64; ++fl) {
       if (f0 + fl >= NF) break;
       if (!((livem >> fl) & 1ULL)) continue;   // (its costs stay 0)
-      const double *U = b.prep[f0 + fl].sqrt_info + row * 31;
       double uq[31];
-#pragma unroll
-      for (int q = 0; q < 31; ++q) uq[q] = (q >= row) ? U[q] : 0.0;
+      imu_info_row(b.prep[f0 + fl].sqrt_info, row, uq);
       const bool nan_f = (badm >> fl) & 1ULL;
       for (int kc = 0; kc < nk; ++kc) {
         double *rs = ti_lds + kc * 32 * 64;
-        double u = 0.0;
-#pragma unroll
-        for (int q = 0; q < 31; ++q) u += uq[q] * rs[q * 64 + fl];
+        const double u = imu_row_dot(uq, rs, fl);
         const double c = wave_sum(lane < 31 ? u * u : 0.0);
         if (lane == 0) rs[31 * 64 + fl] = nan_f ? NAN : 0.5 * c;
       }
@@ -220,12 +189,10 @@ __global__ void __launch_bounds__(128) k_trial_window(BatchDev b, TrialArgs a, v
   const int win = blockIdx.x, tid = threadIdx.x, K = a.K, KK = K + 1;
   const WinMeta wm = b.win[win];
   const int n = wm.prior_n;
-  // prior: 1/2 (dx^T (H dx + 2 b0) + c0) at every column, k_resid_window's form; a row of prior_H is read once for all columns
+  // prior: 1/2 (dx^T (H dx + 2 b0) + c0) at every column (cost_eval.hpp's prior pieces); a row of prior_H is read once for all columns
   if (n > 0) {
     if (tid < wm.prior_nb)
-      for (int k = 0; k < KK; ++k)
-        prior_dx(a.xt + ((size_t)win * KK + k) * XSTRIDE + b.prior_bstate[win * 40 + tid], b.prior_x0 + (size_t)win * 280 + b.prior_bxoff[win * 40 + tid],
-                 b.prior_bsize[win * 40 + tid], dxs + k * VILO_MAX_PRIOR_DIM + b.prior_bidx[win * 40 + tid]);
+      for (int k = 0; k < KK; ++k) prior_dx_block(b, win, tid, a.xt + ((size_t)win * KK + k) * XSTRIDE, dxs + k * VILO_MAX_PRIOR_DIM);
     __syncthreads();
     const double *Hp = b.prior_H + (size_t)win * 96 * 96, *b0 = b.prior_b0 + (size_t)win * 96;
     double sacc[TR_MAXC];
@@ -240,10 +207,10 @@ __global__ void __launch_bounds__(128) k_trial_window(BatchDev b, TrialArgs a, v
       }
     __syncthreads();
     if (tid < n) {
-      const double b2 = 2.0 * b0[tid];
+      const double b0r = b0[tid];
 #pragma unroll
       for (int k = 0; k < TR_MAXC; ++k)
-        if (k < KK) dxs[k * VILO_MAX_PRIOR_DIM + tid] = dxs[k * VILO_MAX_PRIOR_DIM + tid] * (sacc[k] + b2);
+        if (k < KK) dxs[k * VILO_MAX_PRIOR_DIM + tid] = prior_row_term(dxs[k * VILO_MAX_PRIOR_DIM + tid], sacc[k], b0r);
     }
     __syncthreads();
   }

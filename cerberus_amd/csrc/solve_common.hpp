@@ -113,6 +113,10 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return __shfl(v, 0, 64);
 }
+__device__ __forceinline__ int wave_sum_int(int v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return __shfl(v, 0, 64);
+}
 __device__ __forceinline__ double wave_max(double v) {
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
   return __shfl(v, 0, 64);
