@@ -231,6 +231,18 @@ class DrCovOpts(C.Structure):
     _fields_ = [("from_frame", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LegDeadReckonOpts(C.Structure):
+    """vilo_leg_dead_reckon_opts (8 bytes)"""
+    _fields_ = [("from_frame", C.c_int32), ("reserved", C.c_int32)]
+
+
+class WindowLegDeadReckonRecord(C.Structure):
+    """vilo_window_leg_dead_reckon_record (8 bytes)"""
+    _fields_ = [("n_steps", C.c_int32), ("status", C.c_int32)]
+
+
+LEG_DR_STATE, LEG_DR_LEGS, LEG_DR_TRAJ = 32, 12, 48   # doubles of a state_out, legs_out and trajectory row of a leg dead reckoning
+
 DR_COV_N = 15     # error-state coordinates of a dead-reckoned covariance: dp, dtheta, dv, dba, dbg
 DR_COV_POSE = 6   # the pose block of a trajectory row: dp, dtheta
 

@@ -12,6 +12,7 @@ The methods mirror the reference's operator interface for the hot path:
   Batch.save_state ..... the current state into the batch's snapshot slot (vilo_batch_save_state)
   Batch.restore_state .. the snapshot back, bit for bit (vilo_batch_restore_state)
   Batch.dead_reckon_covariance  IntegrationBase::midPointIntegration's F, V covariance recurrence beside dead_reckon's state (vilo_batch_dead_reckon_covariance)
+  Batch.leg_dead_reckon  the nominal-state part of IMULegIntegrationBase::midPointIntegration with the fused leg position (vilo_batch_leg_dead_reckon)
   Batch.gauss_newton_step  the step Ceres' linear solver computes, (H + mu D^2) delta = -g, per window (vilo_batch_gauss_newton_step)
 """
 import collections
@@ -47,6 +48,7 @@ def lib():
         L.vilo_last_predict_ms.restype = C.c_double
         L.vilo_last_dead_reckon_ms.restype = C.c_double
         L.vilo_last_dr_cov_ms.restype = C.c_double
+        L.vilo_last_leg_dead_reckon_ms.restype = C.c_double
         L.vilo_last_gauge_fix_ms.restype = C.c_double
         L.vilo_last_failure_detection_ms.restype = C.c_double
         L.vilo_last_repropagate_ms.restype = C.c_double
@@ -348,6 +350,38 @@ def _dead_reckon(ctx, n, samples, offsets, from_frame, write, trajectory, call):
     ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(state), _p(traj), rec))
     a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowDeadReckonRecord._fields_]), count=n).copy()
     return DeadReckoning(state, traj, step_offsets, a["n_steps"], a["status"])
+
+
+LegDeadReckoning = collections.namedtuple("LegDeadReckoning", "state legs trajectory step_offsets n_steps status")
+
+
+def leg_dead_reckon_opts(from_frame=-1):
+    """T.LegDeadReckonOpts of a leg_dead_reckon call; needs no device. from_frame: -1 (each window's last frame) or 0 .. T.MAX_FRAMES - 1."""
+    if int(from_frame) != from_frame or not -1 <= from_frame <= T.MAX_FRAMES - 1:
+        raise ValueError("from_frame must be -1 (the last frame) or 0 .. %d" % (T.MAX_FRAMES - 1))
+    o = T.LegDeadReckonOpts()
+    o.from_frame, o.reserved = int(from_frame), 0
+    return o
+
+
+def _leg_dead_reckon(ctx, n, samples, offsets, from_frame, trajectory, call):
+    o = leg_dead_reckon_opts(from_frame)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    if offsets.shape != (n + 1,):
+        raise ValueError("offsets must have one entry per window of the call and one more (%d), got shape %s" % (n + 1, offsets.shape))
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must start at 0 and must not decrease")
+    samples = _c(samples).reshape(-1, T.SAMPLE_DOUBLES)
+    if len(samples) < offsets[-1]:
+        raise ValueError("offsets reach sample %d, samples holds %d" % (offsets[-1], len(samples)))
+    step_offsets = np.zeros(n + 1, np.int64)
+    step_offsets[1:] = np.cumsum(np.maximum(np.diff(offsets) - 1, 0))
+    state, legs = np.zeros((n, T.LEG_DR_STATE)), np.zeros((n, 4, 3))
+    traj = np.zeros((int(step_offsets[-1]), T.LEG_DR_TRAJ)) if trajectory else None
+    rec = (T.WindowLegDeadReckonRecord * n)()
+    ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(state), _p(legs), _p(traj), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowLegDeadReckonRecord._fields_]), count=n).copy()
+    return LegDeadReckoning(state, legs, traj, step_offsets, a["n_steps"], a["status"])
 
 
 DeadReckonedCovariance = collections.namedtuple("DeadReckonedCovariance", "state cov pose_cov_trajectory step_offsets n_steps status")
@@ -851,6 +885,16 @@ class Batch:
         return _dead_reckon(self.ctx, len(self._descs), samples, offsets, from_frame, write, trajectory,
                             lambda *a: lib().vilo_batch_dead_reckon(self.ctx.h, self.handle, *a))
 
+    def leg_dead_reckon(self, samples, offsets, from_frame=-1, trajectory=False):
+        """vilo_batch_leg_dead_reckon at the batch's device state: LegDeadReckoning(state [W, 32]: sum_dt, delta_q x y z w, delta_v,
+        delta_eps (12), sum_delta_eps, fused world position, the last step's contact flags (4), two zeros; legs [W, 4, 3], the legs' world
+        positions; trajectory [sum n_steps, 48] or None: sum_dt, fused world position and velocity, flags (4), the legs' world velocities
+        (12), weights (12), the feet in the world (12), a zero; step_offsets [W + 1]; n_steps and status (T.DR_*), each [W]): frame
+        from_frame (-1: each window's last) dead-reckoned by leg odometry through the window's samples [offsets[w], offsets[w + 1])
+        (the first sample of a range is the start sample). Nothing of the batch changes. A batch without leg factors raises."""
+        return _leg_dead_reckon(self.ctx, len(self._descs), samples, offsets, from_frame, trajectory,
+                                lambda *a: lib().vilo_batch_leg_dead_reckon(self.ctx.h, self.handle, *a))
+
     def dead_reckon_covariance(self, samples, offsets, cov_in=None, from_frame=-1, pose_trajectory=False):
         """vilo_batch_dead_reckon_covariance at the batch's device state: DeadReckonedCovariance(state [W, 10], bit for bit
         dead_reckon()'s; cov [W, 15, 15] over (dp, dtheta, dv, dba, dbg), bitwise symmetric; pose_cov_trajectory [sum n_steps, 6, 6] or
@@ -1316,6 +1360,15 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _dead_reckon(self, n, samples, offsets, from_frame, write, trajectory,
                             lambda *a: lib().vilo_window_dead_reckon(self.h, n, descs, states, *a))
+
+    def window_leg_dead_reckon(self, windows, samples, offsets, from_frame=-1, trajectory=False):
+        """vilo_window_leg_dead_reckon: Batch.leg_dead_reckon of host windows at their current state arrays."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _leg_dead_reckon(self, n, samples, offsets, from_frame, trajectory,
+                                lambda *a: lib().vilo_window_leg_dead_reckon(self.h, n, descs, states, *a))
 
     def window_dead_reckon_covariance(self, windows, samples, offsets, cov_in=None, from_frame=-1, pose_trajectory=False):
         """vilo_window_dead_reckon_covariance: Batch.dead_reckon_covariance of host windows at their current state arrays."""

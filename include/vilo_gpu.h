@@ -1084,6 +1084,84 @@ int vilo_window_dead_reckon_covariance(vilo_ctx *ctx, int n_windows, const vilo_
  * of the samples and of cov_in and the copies out. */
 double vilo_last_dr_cov_ms(const vilo_ctx *ctx);
 
+/* ---- leg-odometry dead reckoning of a frame through samples (the nominal-state part of IMULegIntegrationBase::midPointIntegration,
+ * imu_leg_integration_base.cpp:152-158 and :181-351, with propagate()'s carry, :121-135; literally and in that order of operations,
+ * without the Jacobian, covariance, g / h and noise_diag work) ----
+ * Where the body is according to the legs, the body velocity each leg reports, which feet the contact model counts as standing, the
+ * weight each leg gets in the fused velocity and where the feet are in the world, at sensor rate. A batch of use_leg windows only.
+ * State: the batch's current state. Per window, with f = opts->from_frame (-1: the window's last frame) and the window's samples
+ * [offsets[w], offsets[w + 1]) in vilo_preintegrate's convention: the first sample of the range plays (acc_0, gyr_0, phi_0, dphi_0, c_0)
+ * and its dt is not read; every later sample is one step.
+ *   start  delta_q = identity, delta_v = 0, delta_eps[j] = 0, sum_delta_eps = 0, sum_dt = 0 (:7-47). The linearisation point is frame f's
+ *          Ba, Bg and leg biases rho of the current state, with rho_fix, p_br, R_br of the context's config. The contact-force filter of
+ *          contact_sensor_type 2 starts as a fresh object's (min, max, variance, window and index all zero), exactly as
+ *          vilo_preintegrate starts it.
+ *   step   with sample s after the previous sample s0, dt = s.dt:
+ *            :152-158  un_acc_0 = delta_q (s0.acc - Ba); un_gyr = 1/2 (s0.gyr + s.gyr) - Bg;
+ *                      result_delta_q = delta_q * (1, un_gyr dt / 2), un-normalised; un_acc_1 = result_delta_q (s.acc - Ba);
+ *                      result_delta_v = delta_v + 1/2 (un_acc_0 + un_acc_1) dt. (delta_p, :157, reaches no output and is not carried.)
+ *            :183-229  foot_contact_flag[j]: contact_sensor_type 0 and 1: s.c[j] >= 0.5. Type 2: force = 1/2 (s0.c[j] + s.c[j]) through the
+ *                      min / max filter with its decays 0.9991 / 0.997, threshold = min + v_n_force_thres_ratio (max - min), the
+ *                      logistic 1 / (1 + exp(-v_n_term1_steep (force - threshold))) TRUNCATED to 0 or 1 (foot_contact_flag is a
+ *                      Vector4i), and the variance over the five-slot window the force has just entered (sum in slot order, / 4).
+ *            :232-257  v = -R_br jac(phi) dphi - [gyr - Bg]x (p_br + R_br fk(phi)) of s0 and of s (A1Kinematics at rho[j], rho_fix[j]);
+ *                      lo_v_j = 1/2 (delta_q v(s0) + result_delta_q v(s)); delta_eps[j] += lo_v_j dt.
+ *            :290-317  uncertainties: types 0 / 1: (n_xy, n_xy, n_z), n = v_n_max (1 - flag) + flag v_n_min_xy (or _z). Type 2:
+ *                      (v_n_max (1 - flag) + v_n_min + v_n_term2_var_rescale variance) + v_n_term3_distance_rescale (lo_v_j - delta_v)^2
+ *                      per component, delta_v the one BEFORE the step.
+ *            :333-351  w_j = (v_n_max + v_n_term2_var_rescale + v_n_term3_distance_rescale) / uncertainty, per component, at least
+ *                      0.001; sum_delta_eps += (sum_j w_j o lo_v_j dt) / (sum_j w_j), component-wise, j = 0, 1, 2, 3 in that order.
+ *                      The weights stay component-wise in frame f's body frame, as in the reference: nothing is rotated before weighting.
+ *            :354-358  (all four flags 0) only overwrites uncertainties that go to noise_diag, after the weights were taken: it
+ *                      changes nothing here.
+ *            :121-135  delta_q = result_delta_q / |result_delta_q|, delta_v = result_delta_v, sum_dt += dt, s becomes s0.
+ *   world  R0 = R(q_f / |q_f|), P0 = frame f's position. Fused leg position P0 + R0 sum_delta_eps; leg j's P0 + R0 delta_eps[j]: what the
+ *          IMU-leg factor's epsilon rows compare with R_i^T (P_j - P_i).
+ * delta_q, delta_v and delta_eps are those of vilo_preintegrate on the same samples at the same linearisation point, and through it of
+ * the reference (pinned at 1e-12). sum_delta_eps, the weights and the flags have no public counterpart in the pinned oracle (the
+ * reference's result_sum_delta_epsilon is not part of vilo_preint): they are restated from the lines above, unpinned.
+ * Outputs:
+ *   state_out[w][32]  after the last step: sum_dt [0], delta_q x y z w [1..5), delta_v [5..8), delta_eps [8..20), sum_delta_eps [20..23),
+ *                     fused world position [23..26), the last step's foot_contact_flag [26..30) (zeros without a step), zeros [30..32).
+ *   legs_out[w][12]   leg j's world position at [3 j .. 3 j + 3).
+ *   trajectory_out    (may be NULL) [sum n_steps][48], one row per step, window by window in batch order as vilo_batch_dead_reckon's:
+ *                     sum_dt [0], fused world position [1..4), fused world velocity of the step R0 (sum_j w_j o lo_v_j / sum_j w_j)
+ *                     [4..7), foot_contact_flag [7..11), R0 lo_v_j [11 + 3 j ..), w_j [23 + 3 j ..), foot j in the world
+ *                     fused position + R0 result_delta_q (p_br + R_br fk(s.phi)) [35 + 3 j ..), zero [47]. A window's last row agrees
+ *                     bit for bit with its state_out (sum_dt, position, flags). The state_out of a call is bit for bit the same with
+ *                     and without a trajectory.
+ *   records[w]        (may be NULL) n_steps = max(0, offsets[w + 1] - offsets[w] - 1), whatever the status, and the status:
+ *                     VILO_DR_OK; VILO_DR_NO_FRAME: the window has no frame f; VILO_DR_NUMERIC: a value that is not finite in the start
+ *                     (P, q, Ba, Bg, rho of frame f), in a sample value the range reads (with at least one step: everything but the first
+ *                     sample's dt), or in state_out / legs_out. For NO_FRAME and NUMERIC the window's rows of all three arrays are zeros;
+ *                     the other windows are not affected.
+ * Side effects: none, and there is no write option: current and uploaded state, records, mask, snapshot and summaries stay bytewise as
+ * they were. The call's device memory is returned when it returns. Every output of a window is bitwise independent of the batch it
+ * shares and of its position in it. opts NULL: vilo_default_leg_dead_reckon_opts. A batch of use_leg == 0 windows: VILO_ERR_UNSUPPORTED.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched, the caller's arrays untouched): as for vilo_batch_dead_reckon (NULL ctx or batch;
+ * with windows present NULL offsets or state_out; offsets[0] != 0 or offsets decreasing; NULL samples with offsets[W] > 0; from_frame
+ * below -1 or above VILO_MAX_FRAMES - 1), and with windows present NULL legs_out; reserved other than 0. */
+typedef struct {
+  int32_t from_frame;       /* -1: each window's last frame; else 0 .. VILO_MAX_FRAMES - 1 */
+  int32_t reserved;         /* 0 */
+} vilo_leg_dead_reckon_opts;
+void vilo_default_leg_dead_reckon_opts(vilo_leg_dead_reckon_opts *o);
+typedef struct {
+  int32_t n_steps;
+  int32_t status;           /* VILO_DR_* */
+} vilo_window_leg_dead_reckon_record;
+
+int vilo_batch_leg_dead_reckon(vilo_ctx *ctx, vilo_batch *batch, const vilo_leg_dead_reckon_opts *opts, const vilo_sample *samples,
+                               const int32_t *offsets, double *state_out, double *legs_out, double *trajectory_out,
+                               vilo_window_leg_dead_reckon_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed. */
+int vilo_window_leg_dead_reckon(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                const vilo_leg_dead_reckon_opts *opts, const vilo_sample *samples, const int32_t *offsets,
+                                double *state_out, double *legs_out, double *trajectory_out, vilo_window_leg_dead_reckon_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_leg_dead_reckon: k_leg_dead_reckon, without the packing and upload of the
+ * samples and the copies out. */
+double vilo_last_leg_dead_reckon_ms(const vilo_ctx *ctx);
+
 /* ---- double2vector's gauge fix on a resident batch (estimator.cpp:903-1003) ---------------------------------------------------------
  * After vilo_batch_solve the batch's device state is the raw solver output (para_*). The reference never reads that state:
  * Estimator::optimization() calls double2vector() right after ceres::Solve, and the marginalisation (:1247-1455), outliersRejection,
