@@ -243,6 +243,16 @@ class WindowLegDeadReckonRecord(C.Structure):
 
 LEG_DR_STATE, LEG_DR_LEGS, LEG_DR_TRAJ = 32, 12, 48   # doubles of a state_out, legs_out and trajectory row of a leg dead reckoning
 
+
+class LegDrCovOpts(C.Structure):
+    """vilo_leg_dr_cov_opts (8 bytes)"""
+    _fields_ = [("from_frame", C.c_int32), ("reserved", C.c_int32)]
+
+
+LEG_DR_COV_N = 31      # error-state coordinates of a leg dead-reckoned covariance: dp dtheta dv deps_1..4 dba dbg drho_1..4
+LEG_DR_COV_IN = 19     # its cov_in: a frame block of Batch.covariance() (COV_FRAME)
+LEG_DR_COV_POSE = 6    # the pose block of a pose_cov_trajectory row: dp, dtheta
+
 DR_COV_N = 15     # error-state coordinates of a dead-reckoned covariance: dp, dtheta, dv, dba, dbg
 DR_COV_POSE = 6   # the pose block of a trajectory row: dp, dtheta
 

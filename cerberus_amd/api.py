@@ -13,6 +13,7 @@ The methods mirror the reference's operator interface for the hot path:
   Batch.restore_state .. the snapshot back, bit for bit (vilo_batch_restore_state)
   Batch.dead_reckon_covariance  IntegrationBase::midPointIntegration's F, V covariance recurrence beside dead_reckon's state (vilo_batch_dead_reckon_covariance)
   Batch.leg_dead_reckon  the nominal-state part of IMULegIntegrationBase::midPointIntegration with the fused leg position (vilo_batch_leg_dead_reckon)
+  Batch.leg_dead_reckon_covariance  its 31 x 31 F, V covariance recurrence beside leg_dead_reckon's state (vilo_batch_leg_dead_reckon_covariance)
   Batch.gauss_newton_step  the step Ceres' linear solver computes, (H + mu D^2) delta = -g, per window (vilo_batch_gauss_newton_step)
 """
 import collections
@@ -49,6 +50,7 @@ def lib():
         L.vilo_last_dead_reckon_ms.restype = C.c_double
         L.vilo_last_dr_cov_ms.restype = C.c_double
         L.vilo_last_leg_dead_reckon_ms.restype = C.c_double
+        L.vilo_last_leg_dr_cov_ms.restype = C.c_double
         L.vilo_last_gauge_fix_ms.restype = C.c_double
         L.vilo_last_failure_detection_ms.restype = C.c_double
         L.vilo_last_repropagate_ms.restype = C.c_double
@@ -436,6 +438,64 @@ def _dead_reckon_covariance(ctx, n, samples, offsets, cov_in, from_frame, pose_t
     ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(cov_in), _p(state), _p(cov), _p(traj), rec))
     a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowDeadReckonRecord._fields_]), count=n).copy()
     return DeadReckonedCovariance(state, cov, traj, step_offsets, a["n_steps"], a["status"])
+
+
+LegDeadReckonedCovariance = collections.namedtuple("LegDeadReckonedCovariance",
+                                                   "state legs cov pose_cov_trajectory leg_cov_trajectory step_offsets n_steps status")
+
+
+def leg_dr_cov_opts(from_frame=-1):
+    """T.LegDrCovOpts of a leg_dead_reckon_covariance call; needs no device. from_frame: -1 (each window's last frame) or 0 .. T.MAX_FRAMES - 1."""
+    if int(from_frame) != from_frame or not -1 <= from_frame <= T.MAX_FRAMES - 1:
+        raise ValueError("from_frame must be -1 (the last frame) or 0 .. %d" % (T.MAX_FRAMES - 1))
+    o = T.LegDrCovOpts()
+    o.from_frame, o.reserved = int(from_frame), 0
+    return o
+
+
+def leg_dr_cov_in(frames, n_frames, from_frame=-1):
+    """cov_in [W, 19, 19] of a leg_dead_reckon_covariance call, cut out of Batch.covariance()'s frames [W, 11, 19, 19]: for every window the
+    whole block (dp, dtheta, dv, dba, dbg, drho) of frame from_frame, -1: the window's last, n_frames[w] - 1. Needs no device. A window
+    that has no such frame gets zeros (the call reports it as NO_FRAME)."""
+    frames = np.asarray(frames, dtype=np.float64)
+    if frames.ndim != 4 or frames.shape[1:] != (T.F, T.COV_FRAME, T.COV_FRAME):
+        raise ValueError("frames must have shape (W, %d, %d, %d), got %s" % (T.F, T.COV_FRAME, T.COV_FRAME, frames.shape))
+    n_frames = np.asarray(n_frames)
+    if n_frames.shape != (frames.shape[0],) or n_frames.dtype.kind not in "iu" or (n_frames < 1).any() or (n_frames > T.MAX_FRAMES).any():
+        raise ValueError("n_frames must hold one frame count in 1 .. %d per window (%d)" % (T.MAX_FRAMES, frames.shape[0]))
+    leg_dr_cov_opts(from_frame)
+    f = n_frames - 1 if from_frame == -1 else np.full(len(n_frames), int(from_frame))
+    out = np.zeros((len(n_frames), T.LEG_DR_COV_IN, T.LEG_DR_COV_IN))
+    have = f < n_frames
+    out[have] = frames[np.nonzero(have)[0], f[have]]
+    return out
+
+
+def _leg_dead_reckon_covariance(ctx, n, samples, offsets, cov_in, from_frame, pose_trajectory, leg_trajectory, call):
+    o = leg_dr_cov_opts(from_frame)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    if offsets.shape != (n + 1,):
+        raise ValueError("offsets must have one entry per window of the call and one more (%d), got shape %s" % (n + 1, offsets.shape))
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must start at 0 and must not decrease")
+    samples = _c(samples).reshape(-1, T.SAMPLE_DOUBLES)
+    if len(samples) < offsets[-1]:
+        raise ValueError("offsets reach sample %d, samples holds %d" % (offsets[-1], len(samples)))
+    if cov_in is not None:
+        cov_in = _c(cov_in)
+        if cov_in.shape != (n, T.LEG_DR_COV_IN, T.LEG_DR_COV_IN):
+            raise ValueError("cov_in must have shape (%d, %d, %d), got %s" % (n, T.LEG_DR_COV_IN, T.LEG_DR_COV_IN, cov_in.shape))
+    step_offsets = np.zeros(n + 1, np.int64)
+    step_offsets[1:] = np.cumsum(np.maximum(np.diff(offsets) - 1, 0))
+    rows = int(step_offsets[-1])
+    state, legs, cov = np.zeros((n, T.LEG_DR_STATE)), np.zeros((n, 4, 3)), np.zeros((n, T.LEG_DR_COV_N, T.LEG_DR_COV_N))
+    pose = np.zeros((rows, T.LEG_DR_COV_POSE, T.LEG_DR_COV_POSE)) if pose_trajectory else None
+    legc = np.zeros((rows, 4, 3, 3)) if leg_trajectory else None
+    rec = (T.WindowLegDeadReckonRecord * n)()
+    ctx._check(call(C.byref(o), C.cast(samples.ctypes.data, C.POINTER(T.Sample)), T.iptr(offsets), _p(cov_in), _p(state), _p(legs), _p(cov), _p(pose),
+                    _p(legc), rec))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.int32) for f, _ in T.WindowLegDeadReckonRecord._fields_]), count=n).copy()
+    return LegDeadReckonedCovariance(state, legs, cov, pose, legc, step_offsets, a["n_steps"], a["status"])
 
 
 GaugeFix = collections.namedtuple("GaugeFix", "yaw_diff_deg singular status pose0_before")
@@ -903,6 +963,18 @@ class Batch:
         (-1: each window's last) carried through the window's samples by Sigma <- F Sigma F^T + V Q V^T. The batch is left as it was."""
         return _dead_reckon_covariance(self.ctx, len(self._descs), samples, offsets, cov_in, from_frame, pose_trajectory,
                                        lambda *a: lib().vilo_batch_dead_reckon_covariance(self.ctx.h, self.handle, *a))
+
+    def leg_dead_reckon_covariance(self, samples, offsets, cov_in=None, from_frame=-1, pose_trajectory=False, leg_trajectory=False):
+        """vilo_batch_leg_dead_reckon_covariance at the batch's device state: LegDeadReckonedCovariance(state [W, 32] and legs [W, 4, 3],
+        bit for bit leg_dead_reckon()'s; cov [W, 31, 31] over (dp, dtheta, dv, deps_1..4, dba, dbg, drho_1..4), dp dv deps in the world
+        frame, bitwise symmetric; pose_cov_trajectory [sum n_steps, 6, 6] or None, the pose block after every step; leg_cov_trajectory
+        [sum n_steps, 4, 3, 3] or None, the covariance of each leg's world position after every step; step_offsets [W + 1]; n_steps and
+        status (T.DR_*), each [W]): the covariance cov_in [W, 19, 19] (None: zero; only its upper triangle is read; leg_dr_cov_in() cuts
+        it out of covariance()'s frames) of frame from_frame (-1: each window's last) carried through the window's samples by
+        Sigma <- F Sigma F^T + V Q V^T of IMULegIntegrationBase::midPointIntegration. The batch is left as it was. A batch without leg
+        factors raises."""
+        return _leg_dead_reckon_covariance(self.ctx, len(self._descs), samples, offsets, cov_in, from_frame, pose_trajectory, leg_trajectory,
+                                           lambda *a: lib().vilo_batch_leg_dead_reckon_covariance(self.ctx.h, self.handle, *a))
 
     def gauge_fix(self, anchor="uploaded", anchor_pose=None, pose0_before=False):
         """vilo_batch_gauge_fix, in place on the batch's device state (normally right after solve()): double2vector's re-anchoring of yaw
@@ -1378,6 +1450,15 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _dead_reckon_covariance(self, n, samples, offsets, cov_in, from_frame, pose_trajectory,
                                        lambda *a: lib().vilo_window_dead_reckon_covariance(self.h, n, descs, states, *a))
+
+    def window_leg_dead_reckon_covariance(self, windows, samples, offsets, cov_in=None, from_frame=-1, pose_trajectory=False, leg_trajectory=False):
+        """vilo_window_leg_dead_reckon_covariance: Batch.leg_dead_reckon_covariance of host windows at their current state arrays."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _leg_dead_reckon_covariance(self, n, samples, offsets, cov_in, from_frame, pose_trajectory, leg_trajectory,
+                                           lambda *a: lib().vilo_window_leg_dead_reckon_covariance(self.h, n, descs, states, *a))
 
     def window_gauge_fix(self, windows, anchor="given", anchor_pose=None, pose0_before=False):
         """vilo_window_gauge_fix: the gauge fix of host windows at their current state arrays, each with its own number of frames (see

@@ -52,6 +52,7 @@ struct vilo_ctx {
   double last_dead_reckon_ms = 0.0;   // GPU time of the last vilo_batch_dead_reckon (k_dead_reckon)
   double last_dr_cov_ms = 0.0;        // GPU time of the last vilo_batch_dead_reckon_covariance (k_dr_covariance)
   double last_leg_dr_ms = 0.0;        // GPU time of the last vilo_batch_leg_dead_reckon (k_leg_dead_reckon)
+  double last_leg_dr_cov_ms = 0.0;    // GPU time of the last vilo_batch_leg_dead_reckon_covariance (k_leg_dr_covariance)
   double last_gauge_fix_ms = 0.0;    // GPU time of the last vilo_batch_gauge_fix (k_gauge_fix_x)
   double last_failure_ms = 0.0;       // GPU time of the last vilo_batch_failure_detection (k_failure_detection)
   double last_mask_ms = 0.0;          // GPU time of the last vilo_batch_mask_landmarks (k_mask_landmarks + k_mask_windows; with OUTLIER_FLAGS also k_resid_landmarks)

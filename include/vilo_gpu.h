@@ -1162,6 +1162,90 @@ int vilo_window_leg_dead_reckon(vilo_ctx *ctx, int n_windows, const vilo_window_
  * samples and the copies out. */
 double vilo_last_leg_dead_reckon_ms(const vilo_ctx *ctx);
 
+/* ---- covariance of a frame's leg-odometry state carried through samples (the error-state recurrence of
+ * IMULegIntegrationBase::midPointIntegration, imu_leg_integration_base.cpp:288-468, written in the world frame beside
+ * vilo_batch_leg_dead_reckon's nominal state) ----
+ * How uncertain the legs' answer is, at sensor rate: a foot in the air carries v_n_max, a standing foot v_n_min_*. A batch of use_leg
+ * windows only. Arguments as vilo_batch_leg_dead_reckon: f = opts->from_frame (-1: the window's last frame) and the samples
+ * [offsets[w], offsets[w + 1]) in vilo_preintegrate's convention (the first sample of the range plays the _0 values, its dt is not read;
+ * every later sample is one step).
+ *   nominal  exactly vilo_batch_leg_dead_reckon's (legdr_host.hpp's legdr_step, called): state_out[w][32] and legs_out[w][12] are bit for
+ *            bit what that call returns for the same arguments.
+ *   error    31 coordinates in the reference's ILStateOrder (parameters.h:135-149): dp (0), dtheta (3), dv (6), deps_1..4 (9 .. 20),
+ *            dba (21), dbg (24), drho_1..4 (27 .. 30). dtheta is the body-frame right perturbation; dp, dv and deps_j are in the WORLD
+ *            frame; deps_j is the error of leg j's world position P0 + R0 delta_eps[j], that is, of legs_out.
+ *   start    cov_in[w][19][19] is the frame block of vilo_batch_covariance (dp dtheta dv dba dbg drho), row-major. Only the upper triangle
+ *            with the diagonal is read; cov_in NULL: zero. Sigma_0 = E cov_in E^T with E (31 x 19): the frame block's rows go to
+ *            P, R, V, BA, BG, RHO, and the dp rows also into each of the four eps_j row groups (a leg's world position starts at the
+ *            frame's position and shares its error).
+ *   step     with sample s after s0, dt = s.dt, R_f = R(q_f / |q_f|), R0 = R_f R(delta_q) before the step, R1 = R_f R(result_delta_q)
+ *            (un-normalised, :154), Ba, Bg, rho the frame's:   Sigma <- F Sigma F^T + V Q V^T
+ *            F (31 x 31) and V (31 x 46) are the blocks of :376-465 with delta_q.toRotationMatrix() -> R0,
+ *            result_delta_q.toRotationMatrix() -> R1 and linearized_ba / bg / rho -> the frame's biases; every other operand is the
+ *            nominal step's own value. With a = dt^2 / 4, h = dt / 2, A0 = [s0.acc - Ba]x, A1 = [s.acc - Ba]x, C = R1 A1,
+ *            K = kappa_7 = I - [un_gyr]x dt, S = R0 + R1, and per leg j and endpoint e (0: s0, 1: s) v_e (:242-243),
+ *            p_e = p_br + R_br fk(phi_e), J_e = jac(phi_e), g_e, h_e (:272-286 without their leading rotation, g without its sign):
+ *              row      dtheta                          dv      deps_j   dba      dbg                                       drho_j
+ *              dp       -a (R0 A0 + C K)                dt I             -a S      a dt C
+ *              dtheta   K                                                         -dt I
+ *              dv       -h (R0 A0 + C K)                I                -h S      h dt C
+ *              deps_j   -h (R0 [v_0]x + R1 [v_1]x K)            I                  h dt R1 [v_1]x - h (R0 [p_0]x + R1 [p_1]x)   -h (R0 g_0 + R1 g_1)
+ *              dba, dbg, drho_j: unit rows; dp and deps_j: unit columns
+ *            V, by noise block (acc_0, gyr_0, acc_1, gyr_1, acc_w, gyr_w, phi_0, phi_1, dphi_0, dphi_1, v_1..4 (3 each), rho_1..4):
+ *              dp       a R0 | -a h C | a R1 | -a h C
+ *              dtheta        |  h I   |      |  h I
+ *              dv       h R0 | -h h C | h R1 | -h h C
+ *              deps_j        | -h h R1 [v_1]x + h R0 [p_0]x |  | -h h R1 [v_1]x + h R1 [p_1]x | phi: -h R0 h_0, -h R1 h_1 |
+ *                            dphi: -h R0 R_br J_0, -h R1 R_br J_1 | v_j: -dt R_f
+ *              dba: acc_w -dt I; dbg: gyr_w -dt I; drho_j: rho_j -dt
+ *            Gravity does not appear: it is constant. The v_j block is -I dt in the reference (:456), with no rotation to substitute; the
+ *            uncertainties it carries are per axis of frame f's body frame (n_xy is not n_z), so in the world frame it is -dt R_f:
+ *            the (deps_j, deps_j) block receives dt^2 R_f diag(uncertainties_j) R_f^T. With -dt I the relation to the record below
+ *            would fail by up to 4e-6 under contact models 0 and 1.
+ *   Q        the 46-entry diagonal of :288-374, per step, from that step's foot_contact_flag and foot_force_var:
+ *            (acc_n, acc_n, acc_n_z)^2 (acc_n_z DOES enter here), gyr_n^2 (3), those six again, acc_w^2 (3), gyr_w^2 (3), phi_n^2 (6),
+ *            dphi_n^2 (6), the twelve uncertainties of the contact model in force (types 0 / 1 :290-299; type 2 :300-317 with delta_v
+ *            before the step) and the four rho_uncertainty = rho_c_n flag + rho_nc_n; when all four flags are 0 (:354-358) every
+ *            uncertainty is 10e10 and every rho_uncertainty rho_nc_n. The uncertainties and rho_uncertainty are NOT squared, as the
+ *            reference does not square them.
+ *   record   with T = blkdiag(R_f, I3, R_f, R_f x 4, I3, I3, I4): F = T F_rec T^T, so
+ *              Sigma_out = T (Phi Sigma_0' Phi^T + Sigma_rec) T^T,   Sigma_0' = T^T Sigma_0 T,
+ *            Phi and Sigma_rec the jacobian and covariance of vilo_preintegrate's (the reference's) record of the same samples at a
+ *            linearisation point equal to the frame's biases.
+ * Outputs: cov_out[w][31][31], full, stored from the upper triangle so that it is bitwise symmetric; pose_cov_trajectory (may be NULL)
+ * [sum n_steps][6][6], the (dp, dtheta) block after every step; leg_cov_trajectory (may be NULL) [sum n_steps][4][3][3], the diagonal
+ * block of each deps_j, that is, the covariance of each leg's world position after every step; both in vilo_batch_leg_dead_reckon's
+ * trajectory order, a window's last rows bit for bit the blocks of cov_out[w]; state_out[w][32], legs_out[w][12]; records[w] (may be
+ * NULL) = {n_steps, status}. A range of 0 or 1 samples makes no step: cov_out[w] is then Sigma_0 bit for bit.
+ * Statuses: VILO_DR_OK / VILO_DR_NO_FRAME / VILO_DR_NUMERIC with vilo_batch_leg_dead_reckon's meaning; NUMERIC also for a value that is
+ * not finite in the triangle of cov_in[w] that is read, or in the resulting covariance. For a failed window every row of it in every
+ * output is zeros; the other windows of the batch are not affected.
+ * Not in it: a covariance of the fused position sum_delta_eps (the reference has none), packed-triangle transfers, a write option,
+ * samples held under vilo_batch_set_samples.
+ * Side effects: none. The call's device memory is returned when it returns. Every output of a window is bitwise independent of the batch
+ * it shares and of its position in it. opts NULL: vilo_default_leg_dr_cov_opts. A batch of use_leg == 0 windows: VILO_ERR_UNSUPPORTED.
+ * Bad arguments (VILO_ERR_BAD_ARG, nothing launched, the caller's arrays untouched): as for vilo_batch_leg_dead_reckon, and with windows
+ * present a NULL cov_out; reserved other than 0. */
+typedef struct {
+  int32_t from_frame;       /* -1: each window's last frame; else 0 .. VILO_MAX_FRAMES - 1 */
+  int32_t reserved;         /* 0 */
+} vilo_leg_dr_cov_opts;
+void vilo_default_leg_dr_cov_opts(vilo_leg_dr_cov_opts *o);
+
+int vilo_batch_leg_dead_reckon_covariance(vilo_ctx *ctx, vilo_batch *batch, const vilo_leg_dr_cov_opts *opts, const vilo_sample *samples,
+                                          const int32_t *offsets, const double *cov_in, double *state_out, double *legs_out,
+                                          double *cov_out, double *pose_cov_trajectory, double *leg_cov_trajectory,
+                                          vilo_window_leg_dead_reckon_record *records);
+/* The same for host windows at the given states: one batch is created and destroyed. */
+int vilo_window_leg_dead_reckon_covariance(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                                           const vilo_leg_dr_cov_opts *opts, const vilo_sample *samples, const int32_t *offsets,
+                                           const double *cov_in, double *state_out, double *legs_out, double *cov_out,
+                                           double *pose_cov_trajectory, double *leg_cov_trajectory,
+                                           vilo_window_leg_dead_reckon_record *records);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_leg_dead_reckon_covariance: k_leg_dr_covariance, without the packing and
+ * upload of the samples and of cov_in and the copies out. */
+double vilo_last_leg_dr_cov_ms(const vilo_ctx *ctx);
+
 /* ---- double2vector's gauge fix on a resident batch (estimator.cpp:903-1003) ---------------------------------------------------------
  * After vilo_batch_solve the batch's device state is the raw solver output (para_*). The reference never reads that state:
  * Estimator::optimization() calls double2vector() right after ceres::Solve, and the marginalisation (:1247-1455), outliersRejection,

@@ -1,0 +1,236 @@
+// tests/test_leg_dr_covariance.py compiles this with the address and undefined-behaviour sanitizers and runs it as a child process: the
+// part of vilo_batch_leg_dead_reckon_covariance that needs no device (cerberus_amd/csrc/legdrcov_host.hpp) on a CPU. Without arguments: the
+// argument checks, the call's blocks, the embedding E and the noise diagonal under the three contact models. With `in out`: the CPU path
+// (leg_dr_cov_window: the block builders and the two products the kernel calls) over the windows of file `in`, results to file `out`; the
+// test compares them with the numpy definition (tests/leg_dr_cov_ref.py). Both files are plain doubles:
+//   in   W, vilo_config (sizeof / 8 doubles, as bytes), then per window: n, has_cov, pose (7), speed_bias (9), leg_bias (4),
+//        cov_in (361, only with has_cov), samples (35 n)
+//   out  per window: status, n_steps, state (32), legs (12), cov (961), pose_cov_trajectory (36 n_steps), leg_cov_trajectory (36 n_steps)
+// Prints what fails; exit status 0: nothing did.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../cerberus_amd/csrc/batch_call.hpp"
+#include "../../cerberus_amd/csrc/legdrcov_host.hpp"
+
+namespace {
+
+int bad = 0;
+
+void expect(bool ok, const char *what) {
+  if (!ok) { printf("failed: %s\n", what); ++bad; }
+}
+
+vilo_leg_dr_cov_opts opts(int from_frame, int reserved = 0) {
+  vilo_leg_dr_cov_opts o;
+  o.from_frame = from_frame;
+  o.reserved = reserved;
+  return o;
+}
+
+void self_checks() {
+  using namespace vilo;
+  {
+    const std::vector<int32_t> off = {0, 0, 1, 3, 6, 18};   // ranges of 0, 1, 2, 3 and 12 samples
+    const int W = 5;
+    std::vector<vilo_sample> s(18);
+    std::vector<double> st(LEGDR_STATE * W), lg(LEGDR_LEGS * W), cv((size_t)LDC_N * LDC_N * W);
+    expect(!leg_dr_cov_check(opts(-1), W, s.data(), off.data(), st.data(), lg.data(), cv.data()), "defaults pass");
+    expect(!leg_dr_cov_check(opts(VILO_MAX_FRAMES - 1), W, s.data(), off.data(), st.data(), lg.data(), cv.data()), "the last frame passes");
+    expect(leg_dr_cov_check(opts(-2), W, s.data(), off.data(), st.data(), lg.data(), cv.data()) != nullptr, "from_frame -2");
+    expect(leg_dr_cov_check(opts(VILO_MAX_FRAMES), W, s.data(), off.data(), st.data(), lg.data(), cv.data()) != nullptr, "from_frame VILO_MAX_FRAMES");
+    expect(leg_dr_cov_check(opts(-1, 1), W, s.data(), off.data(), st.data(), lg.data(), cv.data()) != nullptr, "reserved 1");
+    expect(leg_dr_cov_check(opts(-1), W, s.data(), nullptr, st.data(), lg.data(), cv.data()) != nullptr, "NULL offsets");
+    expect(leg_dr_cov_check(opts(-1), W, s.data(), off.data(), nullptr, lg.data(), cv.data()) != nullptr, "NULL state_out");
+    expect(leg_dr_cov_check(opts(-1), W, s.data(), off.data(), st.data(), nullptr, cv.data()) != nullptr, "NULL legs_out");
+    expect(leg_dr_cov_check(opts(-1), W, s.data(), off.data(), st.data(), lg.data(), nullptr) != nullptr, "NULL cov_out");
+    expect(leg_dr_cov_check(opts(-1), W, nullptr, off.data(), st.data(), lg.data(), cv.data()) != nullptr, "NULL samples with samples to read");
+    std::vector<int32_t> o1 = {1, 1, 2, 3, 6, 18};
+    expect(leg_dr_cov_check(opts(-1), W, s.data(), o1.data(), st.data(), lg.data(), cv.data()) != nullptr, "offsets[0] != 0");
+    std::vector<int32_t> o2 = {0, 2, 1, 3, 6, 18};
+    expect(leg_dr_cov_check(opts(-1), W, s.data(), o2.data(), st.data(), lg.data(), cv.data()) != nullptr, "offsets decrease");
+    const std::vector<int32_t> none = {0, 0, 0};
+    expect(!leg_dr_cov_check(opts(-1), 2, nullptr, none.data(), st.data(), lg.data(), cv.data()), "no samples at all: samples may be NULL");
+    expect(!leg_dr_cov_check(opts(-1), 0, nullptr, nullptr, nullptr, nullptr, nullptr), "no windows: nothing to check but the options");
+    expect(leg_dr_cov_check(opts(-2), 0, nullptr, nullptr, nullptr, nullptr, nullptr) != nullptr, "no windows: the options are checked all the same");
+  }
+  // the call's blocks at W = 1, an odd shape and 32 768: samples | offsets | step offsets | cov_in | states | legs | cov | pose | leg | records
+  for (int c = 0; c < 3; ++c) {
+    const size_t W = c == 0 ? 1 : (c == 1 ? 5 : 32768), n_s = c == 0 ? 0 : (c == 1 ? 18 : 30 * W);
+    const int32_t n_rows = (int32_t)(c == 0 ? 0 : (c == 1 ? 14 : 29 * W));
+    const LegDrCovCounts cnt = leg_dr_cov_counts((int)W, n_rows);
+    expect(cnt.cov_in == 361 * W && cnt.cov == 961 * W && cnt.state == 32 * W && cnt.legs == 12 * W && cnt.pose_traj == 36 * (size_t)n_rows &&
+               cnt.leg_traj == 36 * (size_t)n_rows && cnt.rec == W, "element counts");
+    for (int opt = 0; opt < 8; ++opt) {
+      const bool in = opt & 1, pose = opt & 2, leg = opt & 4;
+      CallLayout dev, host;
+      const size_t o_s = dev.take<double>(LEGDR_ROW * n_s), o_o = dev.take<int32_t>(W + 1), o_t = dev.take<int32_t>(W + 1);
+      const size_t o_i = dev.take<double>(cnt.cov_in, in), o_x = dev.take<double>(cnt.state), o_l = dev.take<double>(cnt.legs), o_c = dev.take<double>(cnt.cov);
+      const size_t o_p = dev.take<double>(cnt.pose_traj, pose), o_g = dev.take<double>(cnt.leg_traj, leg), o_r = dev.take<vilo_window_leg_dead_reckon_record>(cnt.rec);
+      const size_t h_s = host.take<double>(LEGDR_ROW * n_s), h_o = host.take<int32_t>(W + 1), h_t = host.take<int32_t>(W + 1);
+      expect(o_s == 0 && h_s == 0 && o_o == h_o && o_t == h_t && host.bytes() == o_i, "the staging is laid out as the device blocks it goes to");
+      const size_t offs[10] = {o_s, o_o, o_t, o_i, o_x, o_l, o_c, o_p, o_g, o_r};
+      const size_t size[10] = {8 * LEGDR_ROW * n_s, 4 * (W + 1), 4 * (W + 1), in ? 8 * cnt.cov_in : 0, 8 * cnt.state, 8 * cnt.legs, 8 * cnt.cov,
+                               pose ? 8 * cnt.pose_traj : 0, leg ? 8 * cnt.leg_traj : 0, 8 * W};
+      size_t end = 0;
+      for (int i = 0; i < 10; ++i) {
+        expect(offs[i] % 256 == 0 && offs[i] == end, "a block starts where the one before it ends, on a multiple of 256");
+        end = offs[i] + (size[i] + 255) / 256 * 256;
+      }
+      expect(dev.bytes() == end, "the total");
+    }
+  }
+  // E: rows P R V and BA BG RHO keep the frame block's rows, the four eps groups take the dp rows; only the upper triangle is read
+  {
+    std::vector<double> ci(LDC_IN * LDC_IN);
+    for (int a = 0; a < LDC_IN; ++a)
+      for (int b = 0; b < LDC_IN; ++b) ci[LDC_IN * a + b] = a <= b ? 100.0 * a + b : -1.0;   // (a read below the diagonal would show)
+    const int src[LDC_N] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18};
+    bool ok = true;
+    for (int i = 0; i < LDC_N; ++i)
+      for (int j = 0; j < LDC_N; ++j) {
+        const int a = src[i] < src[j] ? src[i] : src[j], b = src[i] < src[j] ? src[j] : src[i];
+        ok = ok && ldc_src(i) == src[i] && ldc_sigma0(ci.data(), i, j) == 100.0 * a + b;
+      }
+    expect(ok, "Sigma_0 = E cov_in E^T from the upper triangle");
+  }
+  // the noise diagonal
+  {
+    vilo_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.acc_n = 2; cfg.acc_n_z = 3; cfg.gyr_n = 5; cfg.acc_w = 7; cfg.gyr_w = 11; cfg.phi_n = 13; cfg.dphi_n = 17; cfg.rho_c_n = 0.25; cfg.rho_nc_n = 0.5;
+    cfg.v_n_max = 900; cfg.v_n_min_xy = 1; cfg.v_n_min_z = 2; cfg.v_n_min = 4; cfg.v_n_term2_var_rescale = 8; cfg.v_n_term3_distance_rescale = 16;
+    LdcNoise q;
+    ldc_noise_const(cfg, q);
+    double qd[LDC_WK];
+    ldc_dense_noise(q, qd);
+    const double want[LDC_WK] = {4, 4, 9, 25, 25, 25, 4, 4, 9, 25, 25, 25, 169, 169, 169, 169, 169, 169, 289, 289, 289, 289, 289, 289};
+    expect(!memcmp(qd, want, sizeof(want)), "acc_n acc_n acc_n_z, gyr_n, again, phi_n (6), dphi_n (6), squared");
+    const double ba[3] = {0, 0, 0};
+    for (int type = 0; type < 3; ++type) {
+      cfg.contact_sensor_type = type;
+      LegDrConst c;
+      legdr_const(cfg, ba, ba, c);
+      double unc[3], ru;
+      const v3 lo = mk3(1, 2, 3), dv = mk3(0.5, 0.5, 0.5);
+      ldc_leg_uncertainty(c, q, 1.0, 0.125, lo, dv, false, unc, ru);
+      if (type == 2) expect(unc[0] == 4 + 1 + 16 * 0.25 && unc[1] == 5 + 16 * 2.25 && unc[2] == 5 + 16 * 6.25 && ru == 0.75, "type 2, standing");
+      else expect(unc[0] == 1 && unc[1] == 1 && unc[2] == 2 && ru == 0.75, "types 0 / 1, standing: v_n_min_xy, v_n_min_z, not squared");
+      ldc_leg_uncertainty(c, q, 0.0, 0.125, lo, dv, false, unc, ru);
+      if (type == 2) expect(unc[0] == 900 + 4 + 1 + 4 && ru == 0.5, "type 2, in the air");
+      else expect(unc[0] == 900 && unc[2] == 900 && ru == 0.5, "types 0 / 1, in the air: v_n_max");
+      ldc_leg_uncertainty(c, q, 0.0, 0.125, lo, dv, true, unc, ru);
+      expect(unc[0] == 10e10 && unc[1] == 10e10 && unc[2] == 10e10 && ru == 0.5, "all feet in the air: 10e10 and rho_nc_n");
+    }
+    double sb[LDC_SB_TOTAL];
+    ldc_block_start(q, sb);
+    const double unc[3] = {3, 5, 7};
+    ldc_leg_noise(m3_eye(), 0.5, unc, 11, 2, sb);
+    const double *ne = sb + LDC_SB_NE + 18;
+    expect(ne[0] == 0.75 && ne[4] == 1.25 && ne[8] == 1.75 && ne[1] == 0 && ne[5] == 0 && sb[LDC_SB_ND + 29] == 2.75 && sb[LDC_SB_NE] == 0,
+           "dt^2 times the uncertainty in the leg's own block, dt^2 rho_uncertainty at its diagonal entry");
+    m3 Rz = m3_zero();   // a quarter turn about z swaps the x and y variances
+    Rz.a[1] = -1; Rz.a[3] = 1; Rz.a[8] = 1;
+    ldc_leg_noise(Rz, 0.5, unc, 11, 0, sb);
+    expect(sb[LDC_SB_NE] == 1.25 && sb[LDC_SB_NE + 4] == 0.75 && sb[LDC_SB_NE + 8] == 1.75, "the uncertainties are per axis of the body frame: R_f diag R_f^T");
+  }
+  // the masks name every entry the builders write, and no other
+  {
+    LdcNoise q;
+    memset(&q, 0, sizeof(q));
+    double sb[LDC_SB_TOTAL];
+    ldc_block_start(q, sb);
+    m3 M;
+    for (int i = 0; i < 9; ++i) M.a[i] = 1.0 + i;
+    double t[LDC_T_N];
+    for (int i = 0; i < LDC_T_N; ++i) t[i] = 1.0 + i;
+    ldc_imu_rows(M, M, M, mk3(1, 2, 3), mk3(3, 2, 1), 0.5, q, sb);
+    for (int j = 0; j < 4; ++j) ldc_leg_rows(M, M, M, 0.5, t, t, j, sb);
+    bool ok = true;
+    for (int i = 0; i < LDC_ROWS; ++i) {
+      for (int k = 0; k < LDC_FK; ++k) ok = ok && (ldc_f_used(i, k) || sb[LDC_SB_DF + LDC_FK * i + k] == 0.0);
+      for (int k = 0; k < LDC_WK; ++k) ok = ok && (ldc_w_used(i, k) || sb[LDC_SB_W + LDC_WK * i + k] == 0.0);
+    }
+    expect(ok, "no entry outside ldc_f_used / ldc_w_used is written");
+  }
+}
+
+int run_file(const char *in_path, const char *out_path) {
+  using namespace vilo;
+  FILE *fi = fopen(in_path, "rb");
+  if (!fi) { printf("failed: cannot read %s\n", in_path); return 1; }
+  std::vector<double> in;
+  double buf[4096];
+  size_t got;
+  while ((got = fread(buf, sizeof(double), 4096, fi)) > 0) in.insert(in.end(), buf, buf + got);
+  fclose(fi);
+  constexpr size_t CFG_N = sizeof(vilo_config) / sizeof(double);
+  static_assert(sizeof(vilo_config) % sizeof(double) == 0, "vilo_config is a whole number of doubles");
+  if (in.size() < 1 + CFG_N) { printf("failed: short input\n"); return 1; }
+  const int W = (int)in[0];
+  vilo_config cfg;
+  memcpy(&cfg, in.data() + 1, sizeof(cfg));
+  size_t at = 1 + CFG_N;
+  std::vector<double> out;
+  for (int w = 0; w < W; ++w) {
+    if (at + 22 > in.size()) { printf("failed: short input at window %d\n", w); return 1; }
+    const int n = (int)in[at], has_cov = (int)in[at + 1];
+    const double *pose = in.data() + at + 2, *sb = pose + 7, *lb = sb + 9;
+    at += 22;
+    if (n < 0 || at + (has_cov ? 361 : 0) + (size_t)35 * n > in.size()) { printf("failed: short input at window %d\n", w); return 1; }
+    std::vector<double> cov_in;
+    if (has_cov) { cov_in.assign(in.begin() + at, in.begin() + at + 361); at += 361; }
+    // the samples as the caller's vilo_sample array (a heap block of their own: a stray read is caught), packed as the call packs them
+    std::vector<vilo_sample> smp(n);
+    if (n) memcpy((void *)smp.data(), in.data() + at, sizeof(vilo_sample) * n);
+    at += (size_t)35 * n;
+    std::vector<double> rows((size_t)LEGDR_ROW * n);
+    leg_dead_reckon_pack(smp.data(), n, rows.data());
+    const int n_steps = n > 1 ? n - 1 : 0;
+    std::vector<double> state(LEGDR_STATE, -1.0), legs(LEGDR_LEGS, -1.0), cov(LDC_N * LDC_N, -1.0), pt((size_t)36 * n_steps, -1.0), lt((size_t)36 * n_steps, -1.0);
+    const int status = leg_dr_cov_window(cfg, pose, sb, lb, rows.data(), n, has_cov ? cov_in.data() : nullptr, state.data(), legs.data(), cov.data(), pt.data(), lt.data());
+    // the nominal state is leg_dead_reckon_window's, bit for bit; and without the trajectories the same covariance
+    std::vector<double> state2(LEGDR_STATE, -1.0), legs2(LEGDR_LEGS, -1.0), cov2(LDC_N * LDC_N, -1.0);
+    const int status2 = leg_dead_reckon_window(cfg, pose, sb, lb, rows.data(), n, state2.data(), legs2.data(), nullptr, nullptr);
+    if (status == VILO_DR_OK)
+      expect(status2 == VILO_DR_OK && !memcmp(state.data(), state2.data(), 8 * LEGDR_STATE) && !memcmp(legs.data(), legs2.data(), 8 * LEGDR_LEGS),
+             "state_out and legs_out are leg_dead_reckon_window's");
+    const int status3 = leg_dr_cov_window(cfg, pose, sb, lb, rows.data(), n, has_cov ? cov_in.data() : nullptr, state2.data(), legs2.data(), cov2.data(), nullptr, nullptr);
+    expect(status3 == status && !memcmp(cov.data(), cov2.data(), 8 * LDC_N * LDC_N), "with and without the trajectories: the same cov_out");
+    if (status == VILO_DR_OK && n_steps) {
+      const double *lp = pt.data() + (size_t)36 * (n_steps - 1), *ll = lt.data() + (size_t)36 * (n_steps - 1);
+      bool ok = true;
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) ok = ok && !memcmp(lp + 6 * i + j, cov.data() + LDC_N * i + j, 8);
+      for (int l = 0; l < 4; ++l)
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) ok = ok && !memcmp(ll + 9 * l + 3 * i + j, cov.data() + LDC_N * (9 + 3 * l + i) + 9 + 3 * l + j, 8);
+      expect(ok, "a window's last trajectory rows are the blocks of its cov_out");
+    }
+    out.push_back(status); out.push_back(n_steps);
+    out.insert(out.end(), state.begin(), state.end());
+    out.insert(out.end(), legs.begin(), legs.end());
+    out.insert(out.end(), cov.begin(), cov.end());
+    out.insert(out.end(), pt.begin(), pt.end());
+    out.insert(out.end(), lt.begin(), lt.end());
+  }
+  FILE *fo = fopen(out_path, "wb");
+  if (!fo || fwrite(out.data(), sizeof(double), out.size(), fo) != out.size()) { printf("failed: cannot write %s\n", out_path); return 1; }
+  fclose(fo);
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  if (argc == 3) {
+    if (run_file(argv[1], argv[2])) return 1;
+  } else {
+    self_checks();
+  }
+  if (bad) return 1;
+  printf("ok\n");
+  return 0;
+}
