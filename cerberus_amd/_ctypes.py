@@ -127,6 +127,18 @@ class WindowStepRecord(C.Structure):
                 ("n_free", C.c_int32), ("status", C.c_int32)]
 
 
+class DoglegOpts(C.Structure):
+    """vilo_dogleg_opts (32 bytes: vilo_step_opts' fields)"""
+    _fields_ = list(StepOpts._fields_)
+
+
+class WindowDoglegRecord(C.Structure):
+    """vilo_window_dogleg_record (80 bytes)"""
+    _fields_ = [("alpha", C.c_double), ("gradient_norm", C.c_double), ("gauss_newton_norm", C.c_double), ("step_norm", C.c_double),
+                ("beta", C.c_double), ("model_cost_change", C.c_double), ("grad_dot_step", C.c_double), ("norm", C.c_double),
+                ("branch", C.c_int32), ("n_free", C.c_int32), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 HV_MAX_VECTORS = 16  # VILO_HV_MAX_VECTORS
 
 

@@ -59,6 +59,7 @@ def lib():
         L.vilo_last_set_state_ms.restype = C.c_double
         L.vilo_last_gn_step_ms.restype = C.c_double
         L.vilo_last_hess_vec_ms.restype = C.c_double
+        L.vilo_last_dogleg_step_ms.restype = C.c_double
         L.vilo_last_trial_cost_ms.restype = C.c_double
         L.vilo_solve_wave_lds_bytes.restype = C.c_size_t
         _lib = L
@@ -702,6 +703,42 @@ def _gn_step(ctx, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_di
     return GaussNewtonStep(ss, ls, offsets, a["model_cost_change"], a["scaled_norm"], a["norm"], a["grad_dot_step"], a["n_free"], a["status"])
 
 
+DoglegStep = collections.namedtuple("DoglegStep", "state_step lm_step cauchy_state cauchy_lm offsets alpha gradient_norm gauss_newton_norm "
+                                                  "step_norm beta model_cost_change grad_dot_step norm branch n_free status")
+
+
+def dogleg_step_args(n_windows, radius, mu=None, gauge="none", min_lm_diagonal=1e-6, max_lm_diagonal=1e32, min_pivot=1e-14):
+    """(T.DoglegOpts, radius [n_windows], mu [n_windows] or None) of a dogleg_step call, checked; needs no device. radius: a scalar or one
+    value per window, finite and > 0; mu and the rest as gn_step_opts."""
+    so, mu = gn_step_opts(n_windows, mu, gauge, min_lm_diagonal, max_lm_diagonal, min_pivot)
+    radius = np.asarray(radius, dtype=np.float64)
+    if radius.ndim == 0:
+        radius = np.full(n_windows, float(radius))
+    radius = _c(radius)
+    if radius.shape != (n_windows,):
+        raise ValueError("radius must be a scalar or have one entry per window of the call (%d), got shape %s" % (n_windows, radius.shape))
+    if not np.isfinite(radius).all() or (radius <= 0.0).any():
+        raise ValueError("radius must be finite and > 0")
+    o = T.DoglegOpts()
+    o.gauge, o.pad0, o.min_lm_diagonal, o.max_lm_diagonal, o.min_pivot = so.gauge, 0, so.min_lm_diagonal, so.max_lm_diagonal, so.min_pivot
+    return o, radius, mu
+
+
+def _dogleg_step(ctx, descs, radius, mu, gauge, cauchy, min_lm_diagonal, max_lm_diagonal, min_pivot, call):
+    n = len(descs)
+    o, radius, mu = dogleg_step_args(n, radius, mu, gauge, min_lm_diagonal, max_lm_diagonal, min_pivot)
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([d.n_landmarks for d in descs])
+    rec = (T.WindowDoglegRecord * n)()
+    ss, ls = np.zeros((n, T.GRAD_STATE)), np.zeros(int(offsets[-1]))
+    cs, cl = (np.zeros((n, T.GRAD_STATE)), np.zeros(int(offsets[-1]))) if cauchy else (None, None)
+    ctx._check(call(C.byref(o), _p(radius), _p(mu), rec, _p(ss), _p(ls), _p(cs), _p(cl)))
+    a = np.frombuffer(rec, dtype=np.dtype([(f, np.float64 if t is C.c_double else np.int32) for f, t in T.WindowDoglegRecord._fields_]),
+                      count=n).copy()
+    return DoglegStep(ss, ls, cs, cl, offsets, a["alpha"], a["gradient_norm"], a["gauss_newton_norm"], a["step_norm"], a["beta"],
+                      a["model_cost_change"], a["grad_dot_step"], a["norm"], a["branch"], a["n_free"], a["status"])
+
+
 HessianVector = collections.namedtuple("HessianVector", "state_out lm_out offsets n_vec vHv g_dot_v model_cost_change status")
 
 
@@ -1013,6 +1050,17 @@ class Batch:
         it was."""
         return _gn_step(self.ctx, self._descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
                         lambda *a: lib().vilo_batch_gauss_newton_step(self.ctx.h, self.handle, *a))
+
+    def dogleg_step(self, radius, mu=None, gauge="none", cauchy=False, min_lm_diagonal=1e-6, max_lm_diagonal=1e32, min_pivot=1e-14):
+        """vilo_batch_dogleg_step at the batch's device state: Ceres' traditional dogleg step for the trust-region radius `radius` (a
+        scalar or [W], in the D-scaled space) and the damping mu of its Gauss-Newton point (gauss_newton_step's mu), from one
+        linearisation; in gradient()'s layouts, so that trial_cost(r.state_step, r.lm_step) and retract(r.state_step, r.lm_step) take it.
+        DoglegStep(state_step [W, 222], lm_step [sum L], cauchy_state, cauchy_lm (the Cauchy point -alpha s o (g^ / D); None unless
+        cauchy=True), offsets, and per window alpha, gradient_norm, gauss_newton_norm, step_norm, beta, model_cost_change, grad_dot_step,
+        norm, branch (0 Gauss-Newton, 1 Cauchy-limited, 2 interpolated), n_free, status). A window of status 1 or 2 reads NaN. The
+        batch is left as it was."""
+        return _dogleg_step(self.ctx, self._descs, radius, mu, gauge, cauchy, min_lm_diagonal, max_lm_diagonal, min_pivot,
+                            lambda *a: lib().vilo_batch_dogleg_step(self.ctx.h, self.handle, *a))
 
     def hessian_vector(self, state_vec=None, lm_vec=None, state=True, landmarks=True):
         """vilo_batch_hessian_vector at the batch's device state: y = H v for K vectors per window, H the Gauss-Newton Hessian of
@@ -1510,6 +1558,16 @@ class Context:
             descs[i], states[i] = w.desc(T)
         return _gn_step(self, descs, mu, gauge, state, landmarks, min_lm_diagonal, max_lm_diagonal, min_pivot,
                         lambda *a: lib().vilo_window_gauss_newton_step(self.h, n, descs, states, *a))
+
+    def window_dogleg_step(self, windows, radius, mu=None, gauge="none", cauchy=False, min_lm_diagonal=1e-6, max_lm_diagonal=1e32,
+                           min_pivot=1e-14):
+        """vilo_window_dogleg_step: the dogleg step of host windows at their current state arrays (see Batch.dogleg_step)."""
+        n = len(windows)
+        descs, states = (T.WindowDesc * n)(), (T.WindowState * n)()
+        for i, w in enumerate(windows):
+            descs[i], states[i] = w.desc(T)
+        return _dogleg_step(self, descs, radius, mu, gauge, cauchy, min_lm_diagonal, max_lm_diagonal, min_pivot,
+                            lambda *a: lib().vilo_window_dogleg_step(self.h, n, descs, states, *a))
 
     def window_trial_cost(self, windows, state_step=None, lm_step=None, alpha=None, base=True, best=True):
         """vilo_window_trial_cost: the trial costs of host windows at their current state arrays (see Batch.trial_cost)."""

@@ -1,5 +1,5 @@
 // The one reader of what vilo_marg_linearize (mode 0) leaves behind — visual Gram slots, IMU Grams, the prior, lm_w / lm_E / lm_gbuf — for
-// the query kernels that run one workgroup of GN_T threads per window: k_covariance, k_gradient, k_gn_step, k_hess_vec. Every piece is
+// the query kernels that run one workgroup of GN_T threads per window: k_covariance, k_gradient, k_gn_step, k_hess_vec, k_dogleg. Every piece is
 // defined here once; a change of the Gram slot layout, of the prior_map convention or of the gauge is made here and nowhere else.
 //   caller_cd              caller layout (222 entries) -> camera dimension                   gradient, step, Hessian-vector
 //   prior_view_init        prior dx and the inverse of prior_map                             gradient, step, Hessian-vector
@@ -9,6 +9,8 @@
 //   gauge_basis, gauge_rotate    FRAME0 gauge: Q = [e1 e2 u] and H' = Q^T H Q                covariance, step
 //   scale_system           Jacobi scaling of P, Bd, Ao, BP                                   covariance, step
 //   chol13                 in-place Cholesky of a 13 x 13 block                              covariance, step
+//   step_dd                D^2 / s^2 of a coordinate from its Gauss-Newton diagonal          step, dogleg
+//   hv_imu_cd, hv_tile     an IMU Gram's camera dimensions; one 16 x 16 matrix-core tile     Hessian-vector, dogleg
 // The camera-side dimensions split as the solver splits them (solver_types.hpp):
 //   P  (79 + 1 padding, row stride GN_NP)   poses 6k..6k+5, ex0 66..71, ex1 72..77, td 78
 //   Bd / Ao ([11][13][13] each)             diagonal blocks of the speed / bias / leg-bias chain and A_{k,k-1} (row: frame k, column: frame k - 1)
@@ -267,4 +269,29 @@ __device__ __forceinline__ void chol13(double *ss, double thr, int *bad) {
     }
     __syncthreads();
   }
+}
+
+// D^2 / s^2 of a coordinate with Gauss-Newton diagonal h: s = 1 / (1 + sqrt(h)), D^2 = clamp(s^2 h, lo, hi)
+__device__ __forceinline__ double step_dd(double h, double lo, double hi) {
+  const double s = 1.0 / (1.0 + sqrt(h));
+  return fmin(fmax(s * s * h, lo), hi) / (s * s);
+}
+
+// camera dimension of column c < 38 of interval k's IMU Gram [pose_k 6 | B_k 13 | pose_k+1 6 | B_k+1 13]
+__device__ __forceinline__ int hv_imu_cd(int k, int c) {
+  if (c < 6) return 6 * k + c;
+  if (c < 19) return CD_B0 + 13 * k + (c - 6);
+  if (c < 25) return 6 * (k + 1) + (c - 19);
+  return CD_B0 + 13 * (k + 1) + (c - 25);
+}
+
+// one 16 x 16 tile of A X over nk k-steps of 4: A(i, k) for i = row0 + lr, X(k, column lr)
+template <class FA, class FX>
+__device__ __forceinline__ mfma_d4 hv_tile(int row0, int nk, int lr, int lk, FA A, FX X) {
+  mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (int ks = 0; ks < nk; ++ks) {
+    const int kk = 4 * ks + lk;
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A(row0 + lr, kk), X(kk, lr), acc, 0, 0, 0);
+  }
+  return acc;
 }

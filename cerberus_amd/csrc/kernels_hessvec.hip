@@ -49,25 +49,6 @@ static_assert(VILO_HV_MAX_VECTORS == 16, "k_hess_vec: one 16-column tile of v_mf
 static_assert(HL_VL + HV_LMC * HV_K <= HL_V && 2 * HV_K * HV_WS <= GN_NP * GN_NP, "k_hess_vec: what reuses P's place");
 static_assert(sizeof(double) * HL_N <= 160 * 1024, "k_hess_vec: the CU's LDS");
 
-// camera dimension of column c < 38 of interval k's IMU Gram [pose_k 6 | B_k 13 | pose_k+1 6 | B_k+1 13]
-__device__ __forceinline__ int hv_imu_cd(int k, int c) {
-  if (c < 6) return 6 * k + c;
-  if (c < 19) return CD_B0 + 13 * k + (c - 6);
-  if (c < 25) return 6 * (k + 1) + (c - 19);
-  return CD_B0 + 13 * (k + 1) + (c - 25);
-}
-
-// one 16 x 16 tile of A X over nk k-steps of 4: A(i, k) for i = row0 + lr, X(k, column lr)
-template <class FA, class FX>
-__device__ __forceinline__ mfma_d4 hv_tile(int row0, int nk, int lr, int lk, FA A, FX X) {
-  mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int ks = 0; ks < nk; ++ks) {
-    const int kk = 4 * ks + lk;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A(row0 + lr, kk), X(kk, lr), acc, 0, 0, 0);
-  }
-  return acc;
-}
-
 __global__ void __launch_bounds__(GN_T) k_hess_vec(BatchDev b, int K, const double *sv_in, const double *lv_in, vilo_hess_vec_record *rec, double *ss_out,
                                                   double *ls_out) {
   using namespace vilo;

@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "batch_call.hpp"
+#include "gn_step_launch.hpp"
 #include "gn_system.hpp"
 
 static_assert(sizeof(vilo_step_opts) == 32, "vilo_step_opts: 32 bytes (cerberus_amd/_ctypes.py mirrors it)");
@@ -65,12 +66,6 @@ static_assert(sizeof(double) * StepForm<false>::N + 64 <= 80 * 1024, "k_gn_step,
 static_assert(sizeof(double) * StepForm<true>::N + 64 <= 160 * 1024, "k_gn_step, resident: the CU's LDS");
 static_assert(16 * GN_NP <= StepForm<true>::LMC * GN_NP && 4 * GN_T <= StepForm<true>::LMC * GN_NP && VILO_MAX_PRIOR_DIM + CD_N / 4 <= 16 * GN_NP,
               "k_gn_step: the shared region");
-
-// D^2 / s^2 of a coordinate with Gauss-Newton diagonal h: s = 1 / (1 + sqrt(h)), D^2 = clamp(s^2 h, lo, hi)
-__device__ __forceinline__ double step_dd(double h, double lo, double hi) {
-  const double s = 1.0 / (1.0 + sqrt(h));
-  return fmin(fmax(s * s * h, lo), hi) / (s * s);
-}
 
 // P -= A^T A for A [4 nk][80] row-major in LDS: the 25 16 x 16 tiles (X = t / 5, Y = t % 5) over the four waves, tile t to wave t % 4.
 // Operands of v_mfma_f64_16x16x4f64: lane (lr, lk) gives A^T[16 X + lr][4 ks + lk] and A[4 ks + lk][16 Y + lr]; accumulator r is row
@@ -461,24 +456,18 @@ extern "C" int vilo_set_gn_step_form(vilo_ctx *ctx, int form) {
 
 extern "C" double vilo_last_gn_step_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_gn_step_ms : -1.0; }
 
-extern "C" int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *bt, const vilo_step_opts *opts, const double *mu, vilo_window_step_record *windows,
-                                            double *state_step, double *lm_step) {
-  if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
-  if (bt->mask.refuse(ctx, "vilo_batch_gauss_newton_step") != VILO_OK) return VILO_ERR_UNSUPPORTED;
-  vilo_step_opts o;
-  if (opts) o = *opts; else vilo_default_step_opts(&o);
-  if (!((o.gauge == VILO_COV_GAUGE_FRAME0 || o.gauge == VILO_COV_GAUGE_NONE) && o.pad0 == 0 && o.min_lm_diagonal >= 0.0 &&
-        o.max_lm_diagonal >= o.min_lm_diagonal && isfinite(o.max_lm_diagonal) && o.min_pivot >= 0.0 && isfinite(o.min_pivot))) {
-    ctx->err = "vilo_batch_gauss_newton_step: bad options (gauge, pad0 == 0, 0 <= min_lm_diagonal <= max_lm_diagonal < inf, min_pivot >= 0)";
-    return VILO_ERR_BAD_ARG;
-  }
-  BatchDev &bd = bt->d;
-  const int W = bd.W, n_lm = bd.n_lm, chunk = std::min(W, ST_CHUNK);
-  BatchCall call(ctx, bt, &vilo_ctx::last_gn_step_ms);
-  // the call's device memory: saved solver state | window records | mu | state step | landmark step | per-window scratch of one chunk
-  const size_t o_st = call.lay.take<SolverState>(W), o_rec = call.lay.take<vilo_window_step_record>(W), o_mu = call.lay.take<double>(W, mu != nullptr);
-  const size_t o_ss = call.lay.take<double>(GN_NS * (size_t)W), o_ls = call.lay.take<double>(n_lm), o_scr = call.lay.take<double>((size_t)chunk * SS_N);
-  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+bool vilo_step_opts_ok(const vilo_step_opts &o) {
+  return (o.gauge == VILO_COV_GAUGE_FRAME0 || o.gauge == VILO_COV_GAUGE_NONE) && o.pad0 == 0 && o.min_lm_diagonal >= 0.0 &&
+         o.max_lm_diagonal >= o.min_lm_diagonal && isfinite(o.max_lm_diagonal) && o.min_pivot >= 0.0 && isfinite(o.min_pivot);
+}
+
+// window records | mu | state step | landmark step | per-window scratch of one chunk
+GnStepBlocks::GnStepBlocks(vilo::CallLayout &lay, const BatchDev &bd, bool has_mu_)
+    : has_mu(has_mu_), chunk(std::min(bd.W, ST_CHUNK)), o_rec(lay.take<vilo_window_step_record>(bd.W)), o_mu(lay.take<double>(bd.W, has_mu_)),
+      o_ss(lay.take<double>(GN_NS * (size_t)bd.W)), o_ls(lay.take<double>(bd.n_lm)), o_scr(lay.take<double>((size_t)chunk * SS_N)) {}
+
+int vilo_gn_step_launch(vilo_ctx *ctx, BatchCall &call, const BatchDev &bd, const GnStepBlocks &gb, const vilo_step_opts &o) {
+  const int W = bd.W;
   const bool resident = ctx->gn_step_form == 1;
   const size_t lds_bytes = sizeof(double) * (resident ? StepForm<true>::N : StepForm<false>::N);
   if (!ctx->step_attr_set) {
@@ -486,24 +475,46 @@ extern "C" int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *bt, const
     VILO_HIP(hipFuncSetAttribute((const void *)k_gn_step<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * StepForm<true>::N)));
     ctx->step_attr_set = true;
   }
-  if (mu) VILO_HIP(hipMemcpy(call.ptr<double>(o_mu), mu, sizeof(double) * (size_t)W, hipMemcpyHostToDevice));
+  for (int w0 = 0; w0 < W; w0 += gb.chunk) {
+    const int n = std::min(gb.chunk, W - w0);
+    hipLaunchKernelGGL(resident ? k_gn_step<true> : k_gn_step<false>, dim3(n), dim3(GN_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_lm_diagonal, o.max_lm_diagonal, o.min_pivot,
+                       gb.has_mu ? call.ptr<double>(gb.o_mu) : (const double *)nullptr, call.ptr<double>(gb.o_scr), call.ptr<vilo_window_step_record>(gb.o_rec),
+                       call.ptr<double>(gb.o_ss), call.ptr<double>(gb.o_ls));
+  }
+  VILO_HIP(hipGetLastError());
+  return VILO_OK;
+}
+
+extern "C" int vilo_batch_gauss_newton_step(vilo_ctx *ctx, vilo_batch *bt, const vilo_step_opts *opts, const double *mu, vilo_window_step_record *windows,
+                                            double *state_step, double *lm_step) {
+  if (!ctx || !bt || !windows) return VILO_ERR_BAD_ARG;
+  if (bt->mask.refuse(ctx, "vilo_batch_gauss_newton_step") != VILO_OK) return VILO_ERR_UNSUPPORTED;
+  vilo_step_opts o;
+  if (opts) o = *opts; else vilo_default_step_opts(&o);
+  if (!vilo_step_opts_ok(o)) {
+    ctx->err = "vilo_batch_gauss_newton_step: bad options (gauge, pad0 == 0, 0 <= min_lm_diagonal <= max_lm_diagonal < inf, min_pivot >= 0)";
+    return VILO_ERR_BAD_ARG;
+  }
+  BatchDev &bd = bt->d;
+  const int W = bd.W, n_lm = bd.n_lm;
+  BatchCall call(ctx, bt, &vilo_ctx::last_gn_step_ms);
+  // the call's device memory: saved solver state | k_gn_step's blocks
+  const size_t o_st = call.lay.take<SolverState>(W);
+  const GnStepBlocks gb(call.lay, bd, mu != nullptr);
+  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  if (mu) VILO_HIP(hipMemcpy(call.ptr<double>(gb.o_mu), mu, sizeof(double) * (size_t)W, hipMemcpyHostToDevice));
   VILO_HIP(call.start());
   SolverStateGuard keep(call, bd, o_st);
   VILO_HIP(keep.saved);
-  const int rc = vilo_marg_linearize(ctx, bd);
+  int rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
-  for (int w0 = 0; w0 < W; w0 += chunk) {
-    const int n = std::min(chunk, W - w0);
-    hipLaunchKernelGGL(resident ? k_gn_step<true> : k_gn_step<false>, dim3(n), dim3(GN_T), lds_bytes, ctx->stream, bd, w0, o.gauge, o.min_lm_diagonal, o.max_lm_diagonal, o.min_pivot,
-                       mu ? call.ptr<double>(o_mu) : (const double *)nullptr, call.ptr<double>(o_scr), call.ptr<vilo_window_step_record>(o_rec),
-                       call.ptr<double>(o_ss), call.ptr<double>(o_ls));
-  }
-  VILO_HIP(hipGetLastError());
+  rc = vilo_gn_step_launch(ctx, call, bd, gb, o);
+  if (rc != VILO_OK) return rc;
   VILO_HIP(keep.restore());
   VILO_HIP(call.finish());
-  VILO_HIP(call.down(windows, call.ptr<char>(o_rec), sizeof(vilo_window_step_record) * (size_t)W));
-  VILO_HIP(call.down(state_step, call.ptr<char>(o_ss), sizeof(double) * GN_NS * (size_t)W));
-  VILO_HIP(call.down(lm_step, call.ptr<char>(o_ls), sizeof(double) * (size_t)n_lm));
+  VILO_HIP(call.down(windows, call.ptr<char>(gb.o_rec), sizeof(vilo_window_step_record) * (size_t)W));
+  VILO_HIP(call.down(state_step, call.ptr<char>(gb.o_ss), sizeof(double) * GN_NS * (size_t)W));
+  VILO_HIP(call.down(lm_step, call.ptr<char>(gb.o_ls), sizeof(double) * (size_t)n_lm));
   return VILO_OK;
 }
 

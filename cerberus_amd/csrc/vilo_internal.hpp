@@ -25,7 +25,7 @@
 enum {
   VILO_K_VISUAL_LINEARIZE, VILO_K_IMU_LINEARIZE, VILO_K_ASSEMBLE_BIAS, VILO_K_VISUAL_COST, VILO_K_IMU_COST, VILO_K_ACCEPT, VILO_K_INIT_STATE,
   VILO_K_IMU_RAW, VILO_K_ASSEMBLE, VILO_K_SOLVE_WAVE, VILO_K_REPROPAGATE, VILO_K_PREPARE_PREINT, VILO_K_CHAIN, VILO_K_SOLVE_MID, VILO_K_BACKSUB,
-  VILO_K_CHAIN_FACT,
+  VILO_K_CHAIN_FACT, VILO_K_DOGLEG,
   VILO_NKERNEL
 };
 struct vilo_ctx {
@@ -62,6 +62,7 @@ struct vilo_ctx {
   double last_gn_step_ms = 0.0;       // GPU time of the last vilo_batch_gauss_newton_step (linearisation + k_gn_step)
   double last_hess_vec_ms = 0.0;     // GPU time of the last vilo_batch_hessian_vector (linearisation + k_hess_vec)
   double last_trial_ms = 0.0;        // GPU time of the last vilo_batch_trial_cost (k_trial_states, k_trial_landmarks, k_trial_imu, k_trial_window)
+  double last_dogleg_step_ms = 0.0;  // GPU time of the last vilo_batch_dogleg_step (linearisation + k_gn_step + k_dogleg)
   int gn_step_form = 0;               // vilo_set_gn_step_form: 0 the coupling streamed through global scratch (two workgroups per CU), 1 resident in LDS (one)
   int marg_general_count = 0;   // windows of the last vilo_marginalize that took the global-memory eigen path
   std::string err;
@@ -77,7 +78,7 @@ struct vilo_ctx {
   double initial_mu = 1e-8;         // DoglegStrategy's mu at the start of a solve (Ceres: min_mu; vilo_debug_set_initial_mu: per-step comparisons with the oracle)
   int prior_form = 0;               // vilo_set_prior_form: 0 J0 = sqrt(S) V^T as the reference writes it, 1 any X^T with X X^T = A' (pivoted Cholesky factor) where no eigenvalue would be dropped
   int sqrt_info_mode = 0;           // 0: Cholesky of the index-reversed covariance + triangular inverse; 1: the reference's inverse() + LLT, literally
-  bool wave_attr_set = false, mid_attr_set = false, mw8_attr_set = false, asm_s_attr_set = false, marg_attr_set = false, prior_attr_set = false, cov_attr_set = false, step_attr_set = false, hv_attr_set = false, trial_attr_set = false;   // dynamic-LDS opt-ins done on this context's device
+  bool wave_attr_set = false, mid_attr_set = false, mw8_attr_set = false, asm_s_attr_set = false, marg_attr_set = false, prior_attr_set = false, cov_attr_set = false, step_attr_set = false, hv_attr_set = false, trial_attr_set = false, dogleg_attr_set = false;   // dynamic-LDS opt-ins done on this context's device
   // solver form of the batches this context solves (vilo_set_solver_form; -1: chosen from the batch size) and whether batches created on it
   // may use the compact 16-column visual rows (vilo_set_compact_rows). VILO_SOLVER / VILO_NO_COMPACT give the defaults at vilo_create.
   int solver_form = -1;

@@ -638,6 +638,67 @@ double vilo_last_gn_step_ms(const vilo_ctx *ctx);
  * of the landmark passes). Kept for measurement (tools/time_gn_step.py). VILO_ERR_BAD_ARG for any other value. */
 int vilo_set_gn_step_form(vilo_ctx *ctx, int form);
 
+/* ---- dogleg trust-region step at the current state (Ceres 1.14's DoglegStrategy, TRADITIONAL_DOGLEG: the step vilo_batch_solve takes
+ * inside its kernels, opened to a caller who runs the trust-region loop with an acceptance rule of their own: one iteration is
+ * vilo_batch_dogleg_step -> vilo_batch_trial_cost -> vilo_batch_retract on one resident batch, with one linearisation) ----
+ * Definition. g, H, h = diag H, s_i = 1 / (1 + sqrt(h_i)) and D^2_i = clamp(s_i^2 h_i, min_lm_diagonal, max_lm_diagonal) are
+ * vilo_batch_gauss_newton_step's. Put S = diag(s). For window w with trust-region radius Delta = radius[w] and mu = mu[w]:
+ *   scaled gradient       g^ = (S g) / D
+ *   Cauchy point          u = g^ / D,  alpha = g^T g^ / (u^T S H S u)
+ *   Gauss-Newton point    p^_gn = D o y with (S H S + mu D^2) y = -S g: bitwise what vilo_batch_gauss_newton_step solves at the same mu,
+ *                         gauge and kernel form (vilo_set_gn_step_form); the inverse depths are eliminated and their part is returned
+ *   branch 0, |p^_gn| <= Delta:            p^ = p^_gn
+ *   branch 1, alpha |g^| >= Delta:         p^ = -(Delta / |g^|) g^
+ *   branch 2, otherwise:                   p^ = -alpha (1 - beta) g^ + beta p^_gn, the point of the segment from the Cauchy point a =
+ *       -alpha g^ to b = p^_gn at distance Delta, by Ceres' two-case formula: with c = a.(b - a) and d = sqrt(c^2 + |b - a|^2 (Delta^2 - |a|^2)),
+ *       beta = (d - c) / |b - a|^2 if c <= 0, else (Delta^2 - |a|^2) / (d + c)
+ *   step                  delta = s o (p^ / D)
+ * Gauge (opts->gauge). NONE: as above. FRAME0: the problem restricted to vilo_batch_gauss_newton_step's subspace delta = N z (frame 0's
+ * dp = 0 and (R_0^T e_z) . dtheta_0 = 0). With M = diag(D^2 / s^2), the metric in which |p^| is measured (|p^|^2 = delta^T M delta), the
+ * Cauchy direction is M's steepest descent inside the subspace, S u = N (N^T M N)^-1 N^T g (which is g / M on every coordinate but frame
+ * 0's pose), |g^|^2 = g^T S u, and the rest reads the same; the four held directions of the step are zero.
+ * Outputs. state_step [W][222], lm_step [sum L]: delta in state_grad's / lm_grad's layouts, so that it goes straight into
+ * vilo_batch_retract and vilo_batch_trial_cost; entries of constant blocks, absent frames and gauge-held directions are zero. On branch 0
+ * they are bitwise vilo_batch_gauss_newton_step's. cauchy_state / cauchy_lm (optional, each may be NULL): -alpha s o (g^ / D), the Cauchy
+ * point in the same layouts. The record: see the struct; model_cost_change = -(g^T delta + delta^T H delta / 2) with the undamped H (by
+ * bilinearity from H [S u | delta_gn], no third product), the quantity TrustRegionMinimizer divides the cost decrease by and whose sign
+ * decides whether the step is valid.
+ * radius [W] is required; mu [W], or NULL for 0. Status 0 OK; 1 as vilo_batch_gauss_newton_step (an input or a sum that is not finite, a
+ * pivot at or below min_pivot, a mu that is negative or not finite), or a radius that is <= 0 or not finite: every output of the window is
+ * NaN (branch -1), the other windows are untouched; 2 window invalid (a record without sqrt_info): NaN.
+ * Side effects, samples in force, masked batches (VILO_ERR_UNSUPPORTED), per-call device memory: vilo_batch_gauss_newton_step's. Every
+ * output of a window is bitwise independent of the batch it shares and of its position in it. Bad arguments (VILO_ERR_BAD_ARG): NULL ctx,
+ * batch, windows or radius, and vilo_step_opts' conditions on the options, n_windows < 1. */
+typedef struct {
+  int32_t gauge;                           /* VILO_COV_GAUGE_* */
+  int32_t pad0;                            /* 0 */
+  double min_lm_diagonal, max_lm_diagonal; /* the clamp of D^2 (Ceres: 1e-6, 1e32) */
+  double min_pivot;                        /* smallest accepted Cholesky pivot of the equilibrated Gauss-Newton system */
+} vilo_dogleg_opts;   /* 32 bytes: vilo_step_opts' fields and defaults */
+/* VILO_COV_GAUGE_NONE (what the solver solves), 1e-6, 1e32, 1e-14 */
+void vilo_default_dogleg_opts(vilo_dogleg_opts *o);
+typedef struct {
+  double alpha;               /* Cauchy step length in the D-scaled space */
+  double gradient_norm;       /* |g^| */
+  double gauss_newton_norm;   /* |D o y|: vilo_batch_gauss_newton_step's scaled_norm, bitwise */
+  double step_norm;           /* |p^|: what DoglegStrategy::StepAccepted multiplies by 3 (the radius itself on branch 1) */
+  double beta;                /* interpolation weight; 1 on the Gauss-Newton branch, 0 on the Cauchy branch */
+  double model_cost_change;   /* -(g^T delta + delta^T H delta / 2), undamped H */
+  double grad_dot_step, norm; /* g^T delta, |delta| */
+  int32_t branch;             /* 0 Gauss-Newton inside the radius, 1 Cauchy-limited, 2 interpolated; -1 with a status other than 0 */
+  int32_t n_free, status, pad;/* n_free: vilo_batch_gauss_newton_step's */
+} vilo_window_dogleg_record;   /* 80 bytes */
+/* windows [W] and radius [W] are required; state_step, lm_step, cauchy_state and cauchy_lm may each be NULL to leave it out. opts NULL:
+ * vilo_default_dogleg_opts. */
+int vilo_batch_dogleg_step(vilo_ctx *ctx, vilo_batch *batch, const vilo_dogleg_opts *opts, const double *radius, const double *mu,
+                           vilo_window_dogleg_record *windows, double *state_step, double *lm_step, double *cauchy_state, double *cauchy_lm);
+/* The same for host windows at the given states: one batch is created, queried once and destroyed. */
+int vilo_window_dogleg_step(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, const vilo_window_state *state,
+                            const vilo_dogleg_opts *opts, const double *radius, const double *mu, vilo_window_dogleg_record *windows,
+                            double *state_step, double *lm_step, double *cauchy_state, double *cauchy_lm);
+/* GPU time (HIP events on ctx's stream) of the last vilo_batch_dogleg_step: linearisation + k_gn_step + k_dogleg, without the copies. */
+double vilo_last_dogleg_step_ms(const vilo_ctx *ctx);
+
 /* ---- Gauss-Newton Hessian-vector products at the current state (what a Cauchy point, a predicted decrease of a caller's own step, the
  * curvature along a search direction, conjugate gradients or a few Lanczos steps need) ----
  * Definition. State and problem as for the cost gradient above: g and H = sum_blocks rho'(s) J^T J are exactly vilo_batch_gradient's,
