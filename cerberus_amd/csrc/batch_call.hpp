@@ -3,6 +3,7 @@
 // (one allocation out of the batch's arena, given back when `call` dies); uploads that are not to be timed; call.start(); the copies and
 // launches on ctx->stream, at call.ptr<T>(offset); call.finish() (launch errors, the stream drained, last_X_ms written);
 // call.down(host, dev, bytes) for every output the caller may have asked for.
+// The calls that walk a range of samples per window take their first three blocks and their upload through sample_stream.hpp's SampleUpload.
 #pragma once
 #include <stddef.h>
 

@@ -1,43 +1,23 @@
-// The host half of vilo_batch_dead_reckon (include/vilo_gpu.h, kernels_deadreckon.hip) that needs no device: the argument checks, the
-// windows' step offsets and the packing of the samples to the seven doubles the recurrence reads. HIP-free
-// (tests/host_check/dead_reckon_check.cpp runs it under the address and undefined-behaviour sanitizers).
+// The host half of vilo_batch_dead_reckon (include/vilo_gpu.h, kernels_deadreckon.hip) that needs no device: the argument checks and the
+// packing of the samples to the seven doubles the recurrence reads. The range tests and the step offsets are sample_stream.hpp's.
+// HIP-free (tests/host_check/dead_reckon_check.cpp runs it under the address and undefined-behaviour sanitizers).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/vilo_gpu.h"
+#include "sample_stream.hpp"
 
 namespace vilo {
 
 #define DR_ROW 7      // doubles of a packed sample: dt, acc (3), gyr (3): 56 bytes of vilo_sample's 280
 #define DR_STATE 10   // doubles of a state row: P (3), quaternion x y z w, V (3)
 
-// What is wrong with the arguments of a call on W windows (null: nothing). Reads offsets[0 .. W], nothing else.
+// What is wrong with the arguments of a call on W windows (null: nothing), without the call's name. Reads offsets[0 .. W], nothing else.
 inline const char *dead_reckon_check(const vilo_dead_reckon_opts &o, int W, const vilo_sample *samples, const int32_t *offsets, const double *state_out) {
-  if (o.from_frame < -1 || o.from_frame > VILO_MAX_FRAMES - 1) return "vilo_batch_dead_reckon: from_frame must be -1 or 0 .. VILO_MAX_FRAMES - 1";
-  if (o.write != 0 && o.write != 1) return "vilo_batch_dead_reckon: write must be 0 or 1";
-  if (o.write && o.from_frame == -1) return "vilo_batch_dead_reckon: write needs an explicit from_frame (the frame after a window's last does not exist)";
-  if (W <= 0) return nullptr;
-  if (!offsets) return "vilo_batch_dead_reckon: offsets is NULL";
-  if (!state_out) return "vilo_batch_dead_reckon: state_out is NULL";
-  if (offsets[0] != 0) return "vilo_batch_dead_reckon: offsets[0] must be 0";
-  for (int w = 0; w < W; ++w)
-    if (offsets[w + 1] < offsets[w]) return "vilo_batch_dead_reckon: offsets must not decrease";
-  if (offsets[W] > 0 && !samples) return "vilo_batch_dead_reckon: samples is NULL";
-  return nullptr;
-}
-
-// step_offsets[0 .. W]: window w's trajectory rows are step_offsets[w] .. step_offsets[w + 1]; a range of n samples is max(0, n - 1)
-// steps. Returns their sum (at most offsets[W]: it fits the offsets' type).
-inline int32_t dead_reckon_step_offsets(int W, const int32_t *offsets, int32_t *step_offsets) {
-  int32_t at = 0;
-  step_offsets[0] = 0;
-  for (int w = 0; w < W; ++w) {
-    const int32_t n = offsets[w + 1] - offsets[w];
-    at += n > 1 ? n - 1 : 0;
-    step_offsets[w + 1] = at;
-  }
-  return at;
+  const char *option = o.write != 0 && o.write != 1 ? "write must be 0 or 1"
+                       : o.write && o.from_frame == -1 ? "write needs an explicit from_frame (the frame after a window's last does not exist)"
+                                                       : nullptr;
+  return sample_range_check(o.from_frame, option, W, samples, offsets, state_out ? nullptr : "state_out is NULL");
 }
 
 // out[n][DR_ROW] = dt, acc, gyr of samples[0 .. n)

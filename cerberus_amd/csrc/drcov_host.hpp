@@ -14,20 +14,11 @@ namespace vilo {
 #define DRC_POSE 6    // the pose block of a trajectory row: dp, dtheta
 #define DRC_NOISE 6   // 3 x 3 blocks of the 18 x 18 noise diagonal: acc_0, gyr_0, acc_1, gyr_1, acc_w, gyr_w
 
-// What is wrong with the arguments of a call on W windows (null: nothing). Reads offsets[0 .. W], nothing else.
+// What is wrong with the arguments of a call on W windows (null: nothing), without the call's name. Reads offsets[0 .. W], nothing else.
 inline const char *dr_cov_check(const vilo_dr_cov_opts &o, int W, const vilo_sample *samples, const int32_t *offsets, const double *state_out,
                                 const double *cov_out) {
-  if (o.from_frame < -1 || o.from_frame > VILO_MAX_FRAMES - 1) return "vilo_batch_dead_reckon_covariance: from_frame must be -1 or 0 .. VILO_MAX_FRAMES - 1";
-  if (o.reserved != 0) return "vilo_batch_dead_reckon_covariance: reserved must be 0";
-  if (W <= 0) return nullptr;
-  if (!offsets) return "vilo_batch_dead_reckon_covariance: offsets is NULL";
-  if (!state_out) return "vilo_batch_dead_reckon_covariance: state_out is NULL";
-  if (!cov_out) return "vilo_batch_dead_reckon_covariance: cov_out is NULL";
-  if (offsets[0] != 0) return "vilo_batch_dead_reckon_covariance: offsets[0] must be 0";
-  for (int w = 0; w < W; ++w)
-    if (offsets[w + 1] < offsets[w]) return "vilo_batch_dead_reckon_covariance: offsets must not decrease";
-  if (offsets[W] > 0 && !samples) return "vilo_batch_dead_reckon_covariance: samples is NULL";
-  return nullptr;
+  return sample_range_check(o.from_frame, o.reserved != 0 ? "reserved must be 0" : nullptr, W, samples, offsets,
+                            !state_out ? "state_out is NULL" : (!cov_out ? "cov_out is NULL" : nullptr));
 }
 
 // Element counts of the call's arrays on W windows with n_rows steps in all (dead_reckon_step_offsets' sum).

@@ -74,6 +74,7 @@ __global__ void __launch_bounds__(DR_THREADS) k_dead_reckon(BatchDev b, DeadReck
   double *traj = a.traj ? a.traj + (size_t)DR_STATE * a.step_offsets[win] : nullptr;
   double *x = b.x + (size_t)win * XSTRIDE;
 
+  // (the range, the status and the record are written out here, not taken from SampleRange: DESIGN 4.36)
   int status = VILO_DR_OK;
   DrRow out;
   out.a = out.b = out.c = out.d = out.e = make_double2(0.0, 0.0);
@@ -148,48 +149,35 @@ extern "C" void vilo_default_dead_reckon_opts(vilo_dead_reckon_opts *o) {
   o->write = 0;
 }
 
+static const char DEAD_RECKON_CALL[] = "vilo_batch_dead_reckon";
+
 extern "C" int vilo_batch_dead_reckon(vilo_ctx *ctx, vilo_batch *bt, const vilo_dead_reckon_opts *opts, const vilo_sample *samples,
                                       const int32_t *offsets, double *state_out, double *trajectory_out, vilo_window_dead_reckon_record *records) {
   if (!ctx || !bt) return VILO_ERR_BAD_ARG;
-  vilo_dead_reckon_opts o;
-  if (opts) o = *opts; else vilo_default_dead_reckon_opts(&o);
+  const vilo_dead_reckon_opts o = sample_call_opts(opts, vilo_default_dead_reckon_opts);
   const BatchDev &bd = bt->d;
   const int W = bd.W;
-  if (const char *what = vilo::dead_reckon_check(o, W, samples, offsets, state_out)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
+  if (const char *what = vilo::dead_reckon_check(o, W, samples, offsets, state_out)) return sample_call_fail(ctx, DEAD_RECKON_CALL, what, VILO_ERR_BAD_ARG);
   BatchCall call(ctx, bt, &vilo_ctx::last_dead_reckon_ms);
   if (W == 0) return VILO_OK;
-  // packed, before the timed region, into the context's reusable staging: rows | offsets | step offsets
-  const size_t n_s = (size_t)offsets[W];
-  vilo::CallLayout stage;
-  const size_t h_rows = stage.take<double>(DR_ROW * n_s), h_off = stage.take<int32_t>((size_t)W + 1), h_step = stage.take<int32_t>((size_t)W + 1);
-  char *host = (char *)vilo_host_stage(ctx, 8, stage.bytes());
-  if (!host) {
-    ctx->err = "vilo_batch_dead_reckon: no host memory for the packed samples";
-    return VILO_ERR_HIP;
-  }
-  vilo::dead_reckon_pack(samples, n_s, (double *)(host + h_rows));
-  memcpy(host + h_off, offsets, sizeof(int32_t) * ((size_t)W + 1));
-  const size_t n_rows = (size_t)vilo::dead_reckon_step_offsets(W, offsets, (int32_t *)(host + h_step));
+  SampleUpload up(ctx, call, DEAD_RECKON_CALL, W, samples, offsets, DR_ROW, vilo::dead_reckon_pack);
+  if (!up.staged()) return VILO_ERR_HIP;
+  const size_t n_rows = (size_t)up.n_rows;
   const bool want_traj = trajectory_out != nullptr;
-  // the call's device memory: packed samples | offsets | step offsets | states | trajectory | records
-  const size_t o_s = call.lay.take<double>(DR_ROW * n_s), o_o = call.lay.take<int32_t>((size_t)W + 1), o_t = call.lay.take<int32_t>((size_t)W + 1);
+  // the call's device memory after the samples': states | trajectory | records
   const size_t o_x = call.lay.take<double>(DR_STATE * (size_t)W), o_j = call.lay.take<double>(DR_STATE * n_rows, want_traj);
   const size_t o_c = call.lay.take<vilo_window_dead_reckon_record>(W);
   if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  VILO_HIP(up.send(call));
   DeadReckonArgs a;
   a.from_frame = o.from_frame; a.write = o.write;
   a.g_norm = ctx->cfg.g_norm;
-  a.rows = call.ptr<double>(o_s);
-  a.offsets = call.ptr<int>(o_o);
-  a.step_offsets = call.ptr<int>(o_t);
+  a.rows = up.rows;
+  a.offsets = up.offsets;
+  a.step_offsets = up.step_offsets;
   a.state = call.ptr<double>(o_x);
   a.traj = want_traj && n_rows > 0 ? call.ptr<double>(o_j) : nullptr;
   a.rec = call.ptr<vilo_window_dead_reckon_record>(o_c);
-  // (not timed; the three host blocks and the three device blocks are laid out alike, so they go up in one copy)
-  VILO_HIP(hipMemcpyAsync(call.ptr<char>(o_s), host, h_step + sizeof(int32_t) * ((size_t)W + 1), hipMemcpyHostToDevice, ctx->stream));
   VILO_HIP(call.start());
   hipLaunchKernelGGL(k_dead_reckon, dim3((W + DR_THREADS - 1) / DR_THREADS), dim3(DR_THREADS), 0, ctx->stream, bd, a);
   VILO_HIP(call.finish());
@@ -203,12 +191,8 @@ extern "C" int vilo_window_dead_reckon(vilo_ctx *ctx, int n_windows, const vilo_
                                        const vilo_dead_reckon_opts *opts, const vilo_sample *samples, const int32_t *offsets, double *state_out,
                                        double *trajectory_out, vilo_window_dead_reckon_record *records) {
   if (!ctx || n_windows < 1 || !in || !state) return VILO_ERR_BAD_ARG;
-  vilo_dead_reckon_opts o;
-  if (opts) o = *opts; else vilo_default_dead_reckon_opts(&o);
-  if (const char *what = vilo::dead_reckon_check(o, n_windows, samples, offsets, state_out)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
+  const vilo_dead_reckon_opts o = sample_call_opts(opts, vilo_default_dead_reckon_opts);
+  if (const char *what = vilo::dead_reckon_check(o, n_windows, samples, offsets, state_out)) return sample_call_fail(ctx, DEAD_RECKON_CALL, what, VILO_ERR_BAD_ARG);
   return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) {
     const int r = vilo_batch_dead_reckon(ctx, bt, &o, samples, offsets, state_out, trajectory_out, records);
     if (r != VILO_OK || !o.write) return r;

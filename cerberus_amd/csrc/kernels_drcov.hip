@@ -16,7 +16,7 @@
 //                      + V Q V^T e_j        lane-local: the lane selects row j of V (R0, R1, C rows scaled) and applies V to Q times it
 //                    The only exchange is inside the window's 16 lanes of one wave (no __syncthreads, no atomics), so windows of
 //                    different range lengths that share a wave do not meet: their loops diverge and each touches its own LDS tile.
-//                    Whether a window is finite is agreed over its 16 lanes by one ballot after the loop.
+//                    Whether a window is finite is agreed over its 16 lanes by one ballot after the loop (sigma_column.hpp).
 // The alternative, a wave per window with the padded 16 x 16 products on the matrix cores (four v_mfma_f64_16x16x4 per factor), spends
 // 2 x 4096 multiply-adds per step on products of which F's sparsity leaves about 1300 (16 lanes x (2 x 36 + 9)), moves both operands
 // through LDS or lane permutes every step, and gives a wave's 64 nominal chains to one window; DESIGN §4.29 has the figures.
@@ -29,6 +29,7 @@
 
 #include "batch_call.hpp"
 #include "drcov_host.hpp"
+#include "sigma_column.hpp"
 #include "vilo_math.hpp"
 
 static_assert(sizeof(vilo_dr_cov_opts) == 8, "vilo_dr_cov_opts: 8 bytes (include/vilo_gpu.h)");
@@ -85,10 +86,8 @@ __device__ __forceinline__ m3 drc_mul_skew(const m3 &R, const v3 &v) {
   return o;
 }
 // row jj of M (jj differs between lanes: selects, not an indexed register array)
-__device__ __forceinline__ double drc_pick(int jj, double x0, double x1, double x2) { return jj == 0 ? x0 : (jj == 1 ? x1 : x2); }
 __device__ __forceinline__ v3 drc_row(const m3 &M, int jj) {
-  // (values, not the elements themselves: a conditional between two elements is a choice of address, and that puts M in scratch memory)
-  return vilo::mk3(drc_pick(jj, M.a[0], M.a[3], M.a[6]), drc_pick(jj, M.a[1], M.a[4], M.a[7]), drc_pick(jj, M.a[2], M.a[5], M.a[8]));
+  return vilo::mk3(sigcol_pick(jj, M.a[0], M.a[3], M.a[6]), sigcol_pick(jj, M.a[1], M.a[4], M.a[7]), sigcol_pick(jj, M.a[2], M.a[5], M.a[8]));
 }
 
 // The step's matrices: F and V are made of these and of dt (include/vilo_gpu.h writes the blocks out)
@@ -136,18 +135,6 @@ __device__ __forceinline__ void drc_add_noise(const DrcStep &s, const double *q,
   }
 }
 
-// Entry (i, j) and its mirror, i <= j < n, of an n x n row-major matrix from the lane's column j: one triangle feeds both halves
-template <int N>
-__device__ __forceinline__ void drc_store_sym(double *dst, const double *c, int j) {
-  if (j >= N) return;
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-    if (i <= j) {
-      dst[N * i + j] = c[i];
-      dst[N * j + i] = c[i];
-    }
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(DRC_THREADS) k_dr_covariance(BatchDev b, DrCovArgs a) {
@@ -158,18 +145,14 @@ __global__ void __launch_bounds__(DRC_THREADS) k_dr_covariance(BatchDev b, DrCov
   if (win >= b.W) return;   // (whole windows: the wave's other windows go on; nothing below waits for a workgroup)
   double *T = tile + grp * DRC_LANES * DRC_LD;
   const int blk = j / 3, jj = j - 3 * blk;
-  const int n_frames = b.win[win].n_frames;
-  const int f = a.from_frame < 0 ? n_frames - 1 : a.from_frame;
-  const int s_begin = a.offsets[win], n = a.offsets[win + 1] - s_begin;
-  const int n_steps = n > 1 ? n - 1 : 0;
-  double *traj = a.traj ? a.traj + (size_t)(DRC_POSE * DRC_POSE) * a.step_offsets[win] : nullptr;
+  const SampleRange rg(b, win, a.from_frame, a.offsets);
+  double *traj = rg.trajectory(a.traj, DRC_POSE * DRC_POSE, a.step_offsets, win);
   const double *x = b.x + (size_t)win * XSTRIDE;
 
   // row j of the tile: what lane 15 reads back every step is these zeros (row 15 is never written)
 #pragma unroll
   for (int k = 0; k < DRC_LD; ++k) T[DRC_LD * j + k] = 0.0;
 
-  const bool no_frame = f < 0 || f >= n_frames;   // (f <= VILO_MAX_FRAMES - 1 by the argument check)
   bool finite = true;
   double c[DRC_N];   // column j of Sigma
 #pragma unroll
@@ -177,7 +160,7 @@ __global__ void __launch_bounds__(DRC_THREADS) k_dr_covariance(BatchDev b, DrCov
   double so[DR_STATE];
 #pragma unroll
   for (int i = 0; i < DR_STATE; ++i) so[i] = 0.0;
-  if (!no_frame) {
+  if (!rg.no_frame) {
     if (a.cov_in && j < DRC_N) {
       // the upper triangle alone: entry (i, j) for i <= j, (j, i) for the mirrored rest
       const double *ci = a.cov_in + (size_t)(DRC_N * DRC_N) * win;
@@ -187,26 +170,26 @@ __global__ void __launch_bounds__(DRC_THREADS) k_dr_covariance(BatchDev b, DrCov
         finite = finite && isfinite(c[i]);
       }
     }
-    // the nominal chain: k_dead_reckon's, operation by operation (kernels_deadreckon.hip)
-    const double *pose = x + XO_POSE + 7 * f, *sb = x + XO_SB + 9 * f;
+    // the nominal chain: k_dead_reckon's, operation by operation (kernels_deadreckon.hip); why the two are not one function: DESIGN 4.36
+    const double *pose = x + XO_POSE + 7 * rg.f, *sb = x + XO_SB + 9 * rg.f;
     v3 P = ld3(pose), V = ld3(sb);
     const v3 ba = ld3(sb + 3), bg = ld3(sb + 6);
     const quat q0 = ldq_pose(pose);
     finite = finite && drc_finite3(P) && drc_finite3(V) && drc_finite3(ba) && drc_finite3(bg) && isfinite(q0.w) && isfinite(q0.x) && isfinite(q0.y) && isfinite(q0.z);
     m3 R = qR(qnormalized(q0));
     const v3 g = mk3(0.0, 0.0, a.g_norm);
-    if (n_steps > 0) {
-      const double *row = a.rows + (size_t)DR_ROW * s_begin;
+    if (rg.n_steps > 0) {
+      const double *row = a.rows + (size_t)DR_ROW * rg.s_begin;
       v3 acc_0 = ld3(row + 1), gyr_0 = ld3(row + 4);
       finite = finite && drc_finite3(acc_0) && drc_finite3(gyr_0);
       double nxt[DR_ROW];
 #pragma unroll
       for (int k = 0; k < DR_ROW; ++k) nxt[k] = row[DR_ROW + k];
-      for (int i = 1; i < n; ++i) {
+      for (int i = 1; i < rg.n; ++i) {
         double cur[DR_ROW];
 #pragma unroll
         for (int k = 0; k < DR_ROW; ++k) cur[k] = nxt[k];
-        if (i + 1 < n) {
+        if (i + 1 < rg.n) {
           const double *nr = row + (size_t)DR_ROW * (i + 1);
 #pragma unroll
           for (int k = 0; k < DR_ROW; ++k) nxt[k] = nr[k];
@@ -238,16 +221,13 @@ __global__ void __launch_bounds__(DRC_THREADS) k_dr_covariance(BatchDev b, DrCov
         drc_f_times(s, c);                       // column j of M = F Sigma
 #pragma unroll
         for (int r = 0; r < DRC_N; ++r) T[DRC_LD * r + j] = c[r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        sigcol_fence();
 #pragma unroll
         for (int k = 0; k < DRC_N; ++k) c[k] = T[DRC_LD * j + k];   // row j of M: column j of Sigma F^T
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        sigcol_fence();
         drc_f_times(s, c);                       // column j of F Sigma F^T
         drc_add_noise(s, a.q, blk, jj, c);
-        if (traj) drc_store_sym<DRC_POSE>(traj + (size_t)(DRC_POSE * DRC_POSE) * (i - 1), c, j);
+        if (traj) sigcol_store_sym<DRC_POSE>(traj + (size_t)(DRC_POSE * DRC_POSE) * (i - 1), c, j);
       }
     }
     const quat qo = quat_from_R_dev(R);
@@ -257,27 +237,22 @@ __global__ void __launch_bounds__(DRC_THREADS) k_dr_covariance(BatchDev b, DrCov
 #pragma unroll
     for (int i = 0; i < DRC_N; ++i) finite = finite && isfinite(c[i]);
   }
-  // one verdict per window: its sixteen lanes' (the lanes of a window are all here: they entered and left the loop together)
-  const unsigned long long bad = __ballot(!finite);
-  const bool window_finite = ((bad >> (DRC_LANES * grp)) & 0xffffull) == 0;
-  const int status = no_frame ? VILO_DR_NO_FRAME : (window_finite ? VILO_DR_OK : VILO_DR_NUMERIC);
+  // one verdict per window: its sixteen lanes'
+  const int status = rg.status(sigcol_all_finite<DRC_LANES>(finite, grp));
   if (status != VILO_DR_OK) {
 #pragma unroll
     for (int i = 0; i < DRC_N; ++i) c[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < DR_STATE; ++i) so[i] = 0.0;
     if (traj)
-      for (int i = 0; i < n_steps; ++i) drc_store_sym<DRC_POSE>(traj + (size_t)(DRC_POSE * DRC_POSE) * i, c, j);
+      for (int i = 0; i < rg.n_steps; ++i) sigcol_store_sym<DRC_POSE>(traj + (size_t)(DRC_POSE * DRC_POSE) * i, c, j);
   }
-  drc_store_sym<DRC_N>(a.cov + (size_t)(DRC_N * DRC_N) * win, c, j);
+  sigcol_store_sym<DRC_N>(a.cov + (size_t)(DRC_N * DRC_N) * win, c, j);
   if (j == 0) {
     double2 *sp = (double2 *)(a.state + (size_t)DR_STATE * win);   // (80-byte rows of a 256-byte aligned block: 16-byte aligned)
 #pragma unroll
     for (int i = 0; i < DR_STATE / 2; ++i) sp[i] = make_double2(so[2 * i], so[2 * i + 1]);
-    vilo_window_dead_reckon_record r;
-    r.n_steps = n_steps;
-    r.status = status;
-    a.rec[win] = r;
+    rg.record(a.rec, win, status);
   }
 }
 
@@ -287,53 +262,40 @@ extern "C" void vilo_default_dr_cov_opts(vilo_dr_cov_opts *o) {
   o->reserved = 0;
 }
 
+static const char DR_COV_CALL[] = "vilo_batch_dead_reckon_covariance";
+
 extern "C" int vilo_batch_dead_reckon_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_dr_cov_opts *opts, const vilo_sample *samples,
                                                  const int32_t *offsets, const double *cov_in, double *state_out, double *cov_out,
                                                  double *pose_cov_trajectory, vilo_window_dead_reckon_record *records) {
   if (!ctx || !bt) return VILO_ERR_BAD_ARG;
-  vilo_dr_cov_opts o;
-  if (opts) o = *opts; else vilo_default_dr_cov_opts(&o);
+  const vilo_dr_cov_opts o = sample_call_opts(opts, vilo_default_dr_cov_opts);
   const BatchDev &bd = bt->d;
   const int W = bd.W;
-  if (const char *what = vilo::dr_cov_check(o, W, samples, offsets, state_out, cov_out)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
+  if (const char *what = vilo::dr_cov_check(o, W, samples, offsets, state_out, cov_out)) return sample_call_fail(ctx, DR_COV_CALL, what, VILO_ERR_BAD_ARG);
   BatchCall call(ctx, bt, &vilo_ctx::last_dr_cov_ms);
   if (W == 0) return VILO_OK;
-  // packed, before the timed region, into the context's reusable staging: rows | offsets | step offsets (vilo_batch_dead_reckon's)
-  const size_t n_s = (size_t)offsets[W];
-  vilo::CallLayout stage;
-  const size_t h_rows = stage.take<double>(DR_ROW * n_s), h_off = stage.take<int32_t>((size_t)W + 1), h_step = stage.take<int32_t>((size_t)W + 1);
-  char *host = (char *)vilo_host_stage(ctx, 8, stage.bytes());
-  if (!host) {
-    ctx->err = "vilo_batch_dead_reckon_covariance: no host memory for the packed samples";
-    return VILO_ERR_HIP;
-  }
-  vilo::dead_reckon_pack(samples, n_s, (double *)(host + h_rows));
-  memcpy(host + h_off, offsets, sizeof(int32_t) * ((size_t)W + 1));
-  const int32_t n_rows = vilo::dead_reckon_step_offsets(W, offsets, (int32_t *)(host + h_step));
+  SampleUpload up(ctx, call, DR_COV_CALL, W, samples, offsets, DR_ROW, vilo::dead_reckon_pack);
+  if (!up.staged()) return VILO_ERR_HIP;
+  const int32_t n_rows = up.n_rows;
   const vilo::DrCovCounts cnt = vilo::dr_cov_counts(W, n_rows);
   const bool want_traj = pose_cov_trajectory != nullptr;
-  // the call's device memory: packed samples | offsets | step offsets | cov_in | states | covariances | trajectory | records
-  const size_t o_s = call.lay.take<double>(DR_ROW * n_s), o_o = call.lay.take<int32_t>((size_t)W + 1), o_t = call.lay.take<int32_t>((size_t)W + 1);
+  // the call's device memory after the samples': cov_in | states | covariances | trajectory | records
   const size_t o_i = call.lay.take<double>(cnt.cov, cov_in != nullptr), o_x = call.lay.take<double>(cnt.state), o_c = call.lay.take<double>(cnt.cov);
   const size_t o_j = call.lay.take<double>(cnt.traj, want_traj), o_r = call.lay.take<vilo_window_dead_reckon_record>(cnt.rec);
   if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  VILO_HIP(up.send(call));
   DrCovArgs a;
   a.from_frame = o.from_frame; a.pad = 0;
   a.g_norm = ctx->cfg.g_norm;
   vilo::dr_cov_noise(ctx->cfg, a.q);
-  a.rows = call.ptr<double>(o_s);
-  a.offsets = call.ptr<int>(o_o);
-  a.step_offsets = call.ptr<int>(o_t);
+  a.rows = up.rows;
+  a.offsets = up.offsets;
+  a.step_offsets = up.step_offsets;
   a.cov_in = cov_in ? call.ptr<double>(o_i) : nullptr;
   a.state = call.ptr<double>(o_x);
   a.cov = call.ptr<double>(o_c);
   a.traj = want_traj && n_rows > 0 ? call.ptr<double>(o_j) : nullptr;
   a.rec = call.ptr<vilo_window_dead_reckon_record>(o_r);
-  // (not timed; the three host blocks and the three device blocks are laid out alike, so they go up in one copy)
-  VILO_HIP(hipMemcpyAsync(call.ptr<char>(o_s), host, h_step + sizeof(int32_t) * ((size_t)W + 1), hipMemcpyHostToDevice, ctx->stream));
   if (cov_in) VILO_HIP(hipMemcpyAsync(call.ptr<double>(o_i), cov_in, sizeof(double) * cnt.cov, hipMemcpyHostToDevice, ctx->stream));
   VILO_HIP(call.start());
   hipLaunchKernelGGL(k_dr_covariance, dim3((W + DRC_WPB - 1) / DRC_WPB), dim3(DRC_THREADS), 0, ctx->stream, bd, a);
@@ -350,12 +312,8 @@ extern "C" int vilo_window_dead_reckon_covariance(vilo_ctx *ctx, int n_windows, 
                                                   const double *cov_in, double *state_out, double *cov_out, double *pose_cov_trajectory,
                                                   vilo_window_dead_reckon_record *records) {
   if (!ctx || n_windows < 1 || !in || !state) return VILO_ERR_BAD_ARG;
-  vilo_dr_cov_opts o;
-  if (opts) o = *opts; else vilo_default_dr_cov_opts(&o);
-  if (const char *what = vilo::dr_cov_check(o, n_windows, samples, offsets, state_out, cov_out)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
+  const vilo_dr_cov_opts o = sample_call_opts(opts, vilo_default_dr_cov_opts);
+  if (const char *what = vilo::dr_cov_check(o, n_windows, samples, offsets, state_out, cov_out)) return sample_call_fail(ctx, DR_COV_CALL, what, VILO_ERR_BAD_ARG);
   return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) {
     return vilo_batch_dead_reckon_covariance(ctx, bt, &o, samples, offsets, cov_in, state_out, cov_out, pose_cov_trajectory, records);
   });

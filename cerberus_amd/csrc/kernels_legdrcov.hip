@@ -25,7 +25,7 @@
 //                                            of V add to the diagonal entry alone
 //                        The only exchange is inside the window's 32 lanes of one wave (no __syncthreads, no atomics), so the two
 //                        windows of a wave, whose ranges may differ in length, do not meet: their loops diverge and each touches its
-//                        own LDS. Whether a window is finite is agreed over its 32 lanes by one ballot after the loop.
+//                        own LDS. Whether a window is finite is agreed over its 32 lanes by one ballot after the loop (sigma_column.hpp).
 // The padded 32 x 32 x 32 products on the FP64 matrix cores were not built: F - I has 165 entries of 961 that are ever non-zero.
 //
 // Floating-point contraction is off for the whole file, the inlined helpers of vilo_math.hpp, legdr_host.hpp and legdrcov_host.hpp
@@ -36,7 +36,9 @@
 #include <math.h>
 
 #include "batch_call.hpp"
+#include "legdr_quad.hpp"
 #include "legdrcov_host.hpp"
+#include "sigma_column.hpp"
 #include "vilo_math.hpp"
 
 static_assert(sizeof(vilo_leg_dr_cov_opts) == 8, "vilo_leg_dr_cov_opts: 8 bytes (include/vilo_gpu.h)");
@@ -68,51 +70,13 @@ namespace {
 using vilo::LDC_O_BA;
 using vilo::LDC_O_EPS;
 
-template <int K> __device__ __forceinline__ int ldck_bcast_i(int v) { return __builtin_amdgcn_update_dpp(0, v, K * 0x55, 0xf, 0xf, false); }
-template <int K> __device__ __forceinline__ double ldck_bcast(double v) {
-  return __hiloint2double(ldck_bcast_i<K>(__double2hiint(v)), ldck_bcast_i<K>(__double2loint(v)));
-}
-// legdr_step's policy of a lane: one leg, the quad's values by DPP (kernels_legdr.hip's)
-struct LegDrQuadLane {
-  static constexpr int N = 1;
-  int j;
-  __device__ __forceinline__ int leg(int) const { return j; }
-  __device__ __forceinline__ bool first() const { return j == 0; }
-  __device__ __forceinline__ void gather(const double (&mine)[1], double (&all)[4]) const {
-    all[0] = ldck_bcast<0>(mine[0]); all[1] = ldck_bcast<1>(mine[0]); all[2] = ldck_bcast<2>(mine[0]); all[3] = ldck_bcast<3>(mine[0]);
-  }
-  __device__ __forceinline__ bool all_of(bool v) const {
-    const int a = v ? 1 : 0;
-    return (ldck_bcast_i<0>(a) & ldck_bcast_i<1>(a) & ldck_bcast_i<2>(a) & ldck_bcast_i<3>(a)) != 0;
-  }
-};
-
-__device__ __forceinline__ void ldck_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Entry (i, j) and its mirror, i <= j < N, of an N x N row-major matrix from the lane's column j: one triangle feeds both halves
-template <int N>
-__device__ __forceinline__ void ldck_store_sym(double *dst, const double *c, int j) {
-  if (j >= N) return;
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-    if (i <= j) {
-      dst[N * i + j] = c[i];
-      dst[N * j + i] = c[i];
-    }
-}
-// (values, not the elements themselves: a conditional between two elements is a choice of address, and that puts c in scratch memory)
-__device__ __forceinline__ double ldck_pick4(int l, double x0, double x1, double x2, double x3) { return l == 0 ? x0 : (l == 1 ? x1 : (l == 2 ? x2 : x3)); }
 // The 3 x 3 diagonal block of deps_l from the lanes 9 .. 20 (column 9 + 3 l + jj): values selected, not addresses (c is in registers)
 __device__ __forceinline__ void ldck_store_legs(double *dst /* [4][3][3] */, const double *c, int j) {
   if (j < LDC_O_EPS || j >= LDC_O_BA) return;
   const int l = (j - LDC_O_EPS) / 3, jj = (j - LDC_O_EPS) - 3 * l;
 #pragma unroll
   for (int ii = 0; ii < 3; ++ii) {
-    const double v = ldck_pick4(l, c[LDC_O_EPS + ii], c[LDC_O_EPS + 3 + ii], c[LDC_O_EPS + 6 + ii], c[LDC_O_EPS + 9 + ii]);
+    const double v = sigcol_pick(l, c[LDC_O_EPS + ii], c[LDC_O_EPS + 3 + ii], c[LDC_O_EPS + 6 + ii], c[LDC_O_EPS + 9 + ii]);
     if (ii <= jj) {
       dst[9 * l + 3 * ii + jj] = v;
       dst[9 * l + 3 * jj + ii] = v;
@@ -147,9 +111,9 @@ __global__ void __launch_bounds__(LDCK_THREADS) k_leg_dr_covariance(BatchDev b, 
   LdcNoise q;
   ldc_noise_const(cfg, q);
   for (int k = j; k < LDCK_TILE + LDC_SB_TOTAL; k += LDCK_LANES) T[k] = 0.0;
-  ldck_fence();
+  sigcol_fence();
   if (j == 0) ldc_dense_noise(q, sb + LDC_SB_QD);
-  ldck_fence();
+  sigcol_fence();
 
   const bool no_frame = f < 0 || f >= n_frames;   // (f <= VILO_MAX_FRAMES - 1 by the argument check)
   bool finite = true;
@@ -169,7 +133,8 @@ __global__ void __launch_bounds__(LDCK_THREADS) k_leg_dr_covariance(BatchDev b, 
     // a lane do not hold both
 #pragma unroll
     for (int r = 0; r < LDC_N; ++r) T[LDCK_LD * r + j] = c[r];
-    // the nominal chain: k_leg_dead_reckon's, call by call (kernels_legdr.hip)
+    // the nominal chain: k_leg_dead_reckon's, call by call (kernels_legdr.hip), and the window's range, written out here: through
+    // legdr_window_start / legdr_next_row and SampleRange this kernel, at 256 VGPRs, ran 3 % slower
     const double *pose = xs + XO_POSE + 7 * f, *sbs = xs + XO_SB + 9 * f, *lb = xs + XO_LB + 4 * f;
     finite = finite && legdr_finite(lb[x.j]);
 #pragma unroll
@@ -229,22 +194,22 @@ __global__ void __launch_bounds__(LDCK_THREADS) k_leg_dr_covariance(BatchDev b, 
           ldc_leg_rows(R0, R1, K, dt, t0, t1, x.j, sb);
           if (j == 0) ldc_imu_rows(R0, R1, K, acc0 - lc.ba, s.acc0 - lc.ba, dt, q, sb);
         }
-        ldck_fence();
+        sigcol_fence();
 #pragma unroll
         for (int r = 0; r < LDC_N; ++r) c[r] = T[LDCK_LD * r + j];
         ldc_f_times(sb, c);                      // column j of M = F Sigma
 #pragma unroll
         for (int r = 0; r < LDC_N; ++r) T[LDCK_LD * r + j] = c[r];
-        ldck_fence();
+        sigcol_fence();
 #pragma unroll
         for (int k = 0; k < LDC_N; ++k) c[k] = T[LDCK_LD * j + k];   // row j of M: column j of Sigma F^T
-        ldck_fence();
+        sigcol_fence();
         ldc_f_times(sb, c);                      // column j of F Sigma F^T
         ldc_add_noise(sb, j, c);
 #pragma unroll
         for (int r = 0; r < LDC_N; ++r) T[LDCK_LD * r + j] = c[r];
-        ldck_fence();                            // (the next step's blocks are stored after this step's were read)
-        if (pose_traj) ldck_store_sym<LDC_POSE>(pose_traj + (size_t)(LDC_POSE * LDC_POSE) * (i - 1), c, j);
+        sigcol_fence();                            // (the next step's blocks are stored after this step's were read)
+        if (pose_traj) sigcol_store_sym<LDC_POSE>(pose_traj + (size_t)(LDC_POSE * LDC_POSE) * (i - 1), c, j);
         if (leg_traj) ldck_store_legs(leg_traj + (size_t)LDC_LEGCOV * (i - 1), c, j);
       }
     } else {
@@ -260,9 +225,8 @@ __global__ void __launch_bounds__(LDCK_THREADS) k_leg_dr_covariance(BatchDev b, 
       finite = finite && legdr_finite(c[r]);
     }
   }
-  // one verdict per window: its 32 lanes' (the lanes of a window are all here: they entered and left the loop together)
-  const unsigned long long bad = __ballot(!finite);
-  const bool window_finite = ((bad >> (LDCK_LANES * grp)) & 0xffffffffull) == 0;
+  // one verdict per window: its 32 lanes'
+  const bool window_finite = sigcol_all_finite<LDCK_LANES>(finite, grp);
   const int status = no_frame ? VILO_DR_NO_FRAME : (window_finite ? VILO_DR_OK : VILO_DR_NUMERIC);
   if (status != VILO_DR_OK) {
 #pragma unroll
@@ -276,7 +240,7 @@ __global__ void __launch_bounds__(LDCK_THREADS) k_leg_dr_covariance(BatchDev b, 
     if (leg_traj)
       for (size_t i = j; i < (size_t)LDC_LEGCOV * n_steps; i += LDCK_LANES) leg_traj[i] = 0.0;
   }
-  ldck_store_sym<LDC_N>(a.cov + (size_t)(LDC_N * LDC_N) * win, c, j);
+  sigcol_store_sym<LDC_N>(a.cov + (size_t)(LDC_N * LDC_N) * win, c, j);
   if (j == 0) {
     vilo_window_leg_dead_reckon_record r;
     r.n_steps = n_steps;
@@ -291,50 +255,36 @@ extern "C" void vilo_default_leg_dr_cov_opts(vilo_leg_dr_cov_opts *o) {
   o->reserved = 0;
 }
 
+static const char LEG_DR_COV_CALL[] = "vilo_batch_leg_dead_reckon_covariance";
+
 extern "C" int vilo_batch_leg_dead_reckon_covariance(vilo_ctx *ctx, vilo_batch *bt, const vilo_leg_dr_cov_opts *opts, const vilo_sample *samples,
                                                      const int32_t *offsets, const double *cov_in, double *state_out, double *legs_out,
                                                      double *cov_out, double *pose_cov_trajectory, double *leg_cov_trajectory,
                                                      vilo_window_leg_dead_reckon_record *records) {
   if (!ctx || !bt) return VILO_ERR_BAD_ARG;
-  vilo_leg_dr_cov_opts o;
-  if (opts) o = *opts; else vilo_default_leg_dr_cov_opts(&o);
+  const vilo_leg_dr_cov_opts o = sample_call_opts(opts, vilo_default_leg_dr_cov_opts);
   const BatchDev &bd = bt->d;
   const int W = bd.W;
-  if (const char *what = vilo::leg_dr_cov_check(o, W, samples, offsets, state_out, legs_out, cov_out)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
+  if (const char *what = vilo::leg_dr_cov_check(o, W, samples, offsets, state_out, legs_out, cov_out)) return sample_call_fail(ctx, LEG_DR_COV_CALL, what, VILO_ERR_BAD_ARG);
   BatchCall call(ctx, bt, &vilo_ctx::last_leg_dr_cov_ms);
   if (W == 0) return VILO_OK;
-  if (!bt->rec.leg) {
-    ctx->err = "vilo_batch_leg_dead_reckon_covariance: the batch's windows have no leg factors (use_leg == 0)";
-    return VILO_ERR_UNSUPPORTED;
-  }
-  // packed, before the timed region, into the context's reusable staging: rows | offsets | step offsets (vilo_batch_leg_dead_reckon's)
-  const size_t n_s = (size_t)offsets[W];
-  vilo::CallLayout stage;
-  const size_t h_rows = stage.take<double>(LEGDR_ROW * n_s), h_off = stage.take<int32_t>((size_t)W + 1), h_step = stage.take<int32_t>((size_t)W + 1);
-  char *host = (char *)vilo_host_stage(ctx, 8, stage.bytes());
-  if (!host) {
-    ctx->err = "vilo_batch_leg_dead_reckon_covariance: no host memory for the packed samples";
-    return VILO_ERR_HIP;
-  }
-  vilo::leg_dead_reckon_pack(samples, n_s, (double *)(host + h_rows));
-  memcpy(host + h_off, offsets, sizeof(int32_t) * ((size_t)W + 1));
-  const int32_t n_rows = vilo::dead_reckon_step_offsets(W, offsets, (int32_t *)(host + h_step));
+  if (!bt->rec.leg) return sample_call_fail(ctx, LEG_DR_COV_CALL, "the batch's windows have no leg factors (use_leg == 0)", VILO_ERR_UNSUPPORTED);
+  SampleUpload up(ctx, call, LEG_DR_COV_CALL, W, samples, offsets, LEGDR_ROW, vilo::leg_dead_reckon_pack);
+  if (!up.staged()) return VILO_ERR_HIP;
+  const int32_t n_rows = up.n_rows;
   const vilo::LegDrCovCounts cnt = vilo::leg_dr_cov_counts(W, n_rows);
   const bool want_pose = pose_cov_trajectory != nullptr, want_leg = leg_cov_trajectory != nullptr;
-  // the call's device memory: packed samples | offsets | step offsets | cov_in | states | legs | covariances | trajectories | records
-  const size_t o_s = call.lay.take<double>(LEGDR_ROW * n_s), o_o = call.lay.take<int32_t>((size_t)W + 1), o_t = call.lay.take<int32_t>((size_t)W + 1);
+  // the call's device memory after the samples': cov_in | states | legs | covariances | trajectories | records
   const size_t o_i = call.lay.take<double>(cnt.cov_in, cov_in != nullptr), o_x = call.lay.take<double>(cnt.state), o_l = call.lay.take<double>(cnt.legs);
   const size_t o_c = call.lay.take<double>(cnt.cov), o_p = call.lay.take<double>(cnt.pose_traj, want_pose), o_g = call.lay.take<double>(cnt.leg_traj, want_leg);
   const size_t o_r = call.lay.take<vilo_window_leg_dead_reckon_record>(cnt.rec);
   if (call.begin() != VILO_OK) return VILO_ERR_HIP;
+  VILO_HIP(up.send(call));
   LegDrCovArgs a;
   a.from_frame = o.from_frame; a.pad = 0;
-  a.rows = call.ptr<double>(o_s);
-  a.offsets = call.ptr<int>(o_o);
-  a.step_offsets = call.ptr<int>(o_t);
+  a.rows = up.rows;
+  a.offsets = up.offsets;
+  a.step_offsets = up.step_offsets;
   a.cov_in = cov_in ? call.ptr<double>(o_i) : nullptr;
   a.state = call.ptr<double>(o_x);
   a.legs = call.ptr<double>(o_l);
@@ -342,8 +292,6 @@ extern "C" int vilo_batch_leg_dead_reckon_covariance(vilo_ctx *ctx, vilo_batch *
   a.pose_traj = want_pose && n_rows > 0 ? call.ptr<double>(o_p) : nullptr;
   a.leg_traj = want_leg && n_rows > 0 ? call.ptr<double>(o_g) : nullptr;
   a.rec = call.ptr<vilo_window_leg_dead_reckon_record>(o_r);
-  // (not timed; the three host blocks and the three device blocks are laid out alike, so they go up in one copy)
-  VILO_HIP(hipMemcpyAsync(call.ptr<char>(o_s), host, h_step + sizeof(int32_t) * ((size_t)W + 1), hipMemcpyHostToDevice, ctx->stream));
   if (cov_in) VILO_HIP(hipMemcpyAsync(call.ptr<double>(o_i), cov_in, sizeof(double) * cnt.cov_in, hipMemcpyHostToDevice, ctx->stream));
   VILO_HIP(call.start());
   hipLaunchKernelGGL(k_leg_dr_covariance, dim3((W + LDCK_WPB - 1) / LDCK_WPB), dim3(LDCK_THREADS), 0, ctx->stream, bd,
@@ -364,12 +312,8 @@ extern "C" int vilo_window_leg_dead_reckon_covariance(vilo_ctx *ctx, int n_windo
                                                       double *pose_cov_trajectory, double *leg_cov_trajectory,
                                                       vilo_window_leg_dead_reckon_record *records) {
   if (!ctx || n_windows < 1 || !in || !state) return VILO_ERR_BAD_ARG;
-  vilo_leg_dr_cov_opts o;
-  if (opts) o = *opts; else vilo_default_leg_dr_cov_opts(&o);
-  if (const char *what = vilo::leg_dr_cov_check(o, n_windows, samples, offsets, state_out, legs_out, cov_out)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
+  const vilo_leg_dr_cov_opts o = sample_call_opts(opts, vilo_default_leg_dr_cov_opts);
+  if (const char *what = vilo::leg_dr_cov_check(o, n_windows, samples, offsets, state_out, legs_out, cov_out)) return sample_call_fail(ctx, LEG_DR_COV_CALL, what, VILO_ERR_BAD_ARG);
   return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) {
     return vilo_batch_leg_dead_reckon_covariance(ctx, bt, &o, samples, offsets, cov_in, state_out, legs_out, cov_out, pose_cov_trajectory,
                                                  leg_cov_trajectory, records);

@@ -42,20 +42,11 @@ VD constexpr int ff_idx_at(int j) { return 32 + j; }
 enum { LS_SUM_DT = 0, LS_DQ = 1, LS_DV = 5, LS_EPS = 8, LS_SUM_EPS = 20, LS_POS = 23, LS_FLAG = 26, LS_PAD = 30 };
 enum { LT_SUM_DT = 0, LT_POS = 1, LT_VEL = 4, LT_FLAG = 7, LT_LOV = 11, LT_W = 23, LT_FOOT = 35, LT_PAD = 47 };
 
-// What is wrong with the arguments of a call on W windows (null: nothing). Reads offsets[0 .. W], nothing else.
+// What is wrong with the arguments of a call on W windows (null: nothing), without the call's name. Reads offsets[0 .. W], nothing else.
 inline const char *leg_dead_reckon_check(const vilo_leg_dead_reckon_opts &o, int W, const vilo_sample *samples, const int32_t *offsets,
                                          const double *state_out, const double *legs_out) {
-  if (o.from_frame < -1 || o.from_frame > VILO_MAX_FRAMES - 1) return "vilo_batch_leg_dead_reckon: from_frame must be -1 or 0 .. VILO_MAX_FRAMES - 1";
-  if (o.reserved != 0) return "vilo_batch_leg_dead_reckon: reserved must be 0";
-  if (W <= 0) return nullptr;
-  if (!offsets) return "vilo_batch_leg_dead_reckon: offsets is NULL";
-  if (!state_out) return "vilo_batch_leg_dead_reckon: state_out is NULL";
-  if (!legs_out) return "vilo_batch_leg_dead_reckon: legs_out is NULL";
-  if (offsets[0] != 0) return "vilo_batch_leg_dead_reckon: offsets[0] must be 0";
-  for (int w = 0; w < W; ++w)
-    if (offsets[w + 1] < offsets[w]) return "vilo_batch_leg_dead_reckon: offsets must not decrease";
-  if (offsets[W] > 0 && !samples) return "vilo_batch_leg_dead_reckon: samples is NULL";
-  return nullptr;
+  return sample_range_check(o.from_frame, o.reserved != 0 ? "reserved must be 0" : nullptr, W, samples, offsets,
+                            !state_out ? "state_out is NULL" : (!legs_out ? "legs_out is NULL" : nullptr));
 }
 
 // out[n][LEGDR_ROW]: what a quad of lanes loads in one step lies together: dt acc gyr, then leg j's phi dphi c at 7 + 7 j
@@ -297,6 +288,63 @@ VD bool legdr_rows_finite(const double *state, const double *legs, const X &x) {
   return ok;
 }
 
+// A caller's walk through a range: what is constant over it, the integration object, the last step's by-products and the row in hand
+template <int N> struct LegDrWalk {
+  LegDrConst c;
+  LegDrWorld wf;
+  LegDrState<N> s;
+  LegDrStep<N> o;
+  double sh[LEGDR_ROW_SHARED], lg[N][LEGDR_ROW_LEG];   // dt acc gyr; phi dphi c of every owned leg
+};
+// r[LEGDR_ROW] as its caller reads it. from 1: the first sample of a range, whose dt is not read
+template <class X>
+VD void legdr_load_row(const double *r, int from, const X &x, double *sh, double (*lg)[LEGDR_ROW_LEG]) {
+  if (from) sh[0] = 0.0;
+  for (int k = from; k < LEGDR_ROW_SHARED; ++k) sh[k] = r[k];
+  for (int l = 0; l < X::N; ++l)
+    for (int k = 0; k < LEGDR_ROW_LEG; ++k) lg[l][k] = r[LEGDR_ROW_SHARED + LEGDR_ROW_LEG * x.leg(l) + k];
+}
+template <class X>
+VD bool legdr_row_finite(int from, const X &, const double *sh, const double (*lg)[LEGDR_ROW_LEG]) {
+  bool ok = true;
+  for (int k = from; k < LEGDR_ROW_SHARED; ++k) ok = ok && legdr_finite(sh[k]);
+  for (int l = 0; l < X::N; ++l)
+    for (int k = 0; k < LEGDR_ROW_LEG; ++k) ok = ok && legdr_finite(lg[l][k]);
+  return ok;
+}
+// the row of the next step into w; returns whether it is finite
+template <class X>
+VD bool legdr_next_row(const double *r, const X &x, LegDrWalk<X::N> &w) {
+  legdr_load_row(r, 0, x, w.sh, w.lg);
+  return legdr_row_finite(0, x, w.sh, w.lg);
+}
+// The start of a walk at a frame (pose: its 7, sb: its 9 (V, Ba, Bg), lb: its 4) with row0, the first sample of the range (null: a range
+// without steps). Returns whether what the caller read, of the frame for its legs and of the row, is finite.
+template <class X>
+VD bool legdr_window_start(const vilo_config &cfg, const double *pose, const double *sb, const double *lb, const double *row0, const X &x, LegDrWalk<X::N> &w) {
+  bool finite = true;
+  for (int l = 0; l < X::N; ++l) finite = finite && legdr_finite(lb[x.leg(l)]);
+  for (int k = 0; k < 7; ++k) finite = finite && legdr_finite(pose[k]);
+  for (int k = 3; k < 9; ++k) finite = finite && legdr_finite(sb[k]);
+  legdr_const(cfg, sb + 3, sb + 6, w.c);
+  w.wf.R0 = qR(qnormalized(ldq_pose(pose)));
+  w.wf.P0 = ld3(pose);
+  for (int l = 0; l < X::N; ++l) w.o.flag[l] = 0.0;
+  if (row0) {
+    legdr_load_row(row0, 1, x, w.sh, w.lg);
+    finite = finite && legdr_row_finite(1, x, w.sh, w.lg);
+    legdr_start(w.c, cfg, lb, w.sh, w.lg, x, w.s);
+  } else {
+    legdr_start(w.c, cfg, lb, (const double *)nullptr, (const double (*)[LEGDR_ROW_LEG])nullptr, x, w.s);
+  }
+  return finite;
+}
+// Zeros in the caller's share of p[n]: the owner of N of the four legs takes every (4 / N)-th entry from its first leg's on
+template <class X>
+VD void legdr_zero_share(const X &x, double *p, size_t n) {
+  for (size_t i = x.leg(0); i < n; i += 4 / X::N) p[i] = 0.0;
+}
+
 // the filter of the four legs in the O_FF layout
 inline void legdr_ff_export(const LegDrState<4> &s, double *ff /* LEGDR_FF_N */) {
   for (int j = 0; j < 4; ++j) {
@@ -307,43 +355,27 @@ inline void legdr_ff_export(const LegDrState<4> &s, double *ff /* LEGDR_FF_N */)
 
 // The CPU path: one window whose frame f exists, through rows[n][LEGDR_ROW]. pose: frame f's 7, sb: its 9 (V, Ba, Bg), lb: its 4.
 // traj: null or [max(0, n - 1)][LEGDR_TRAJ]; ff_out: null or [LEGDR_FF_N]. Returns VILO_DR_OK or VILO_DR_NUMERIC (then the rows are zeros).
+// Like the kernel, this path (and leg_dr_cov_window) walks on through a non-finite row and zeroes its outputs at the end: legdr_step and
+// the ldc_* functions must stay free of double-to-integer conversions and of indices computed from sample values, which a NaN would
+// make undefined.
 inline int leg_dead_reckon_window(const vilo_config &cfg, const double *pose, const double *sb, const double *lb, const double *rows, int n,
                                   double *state, double *legs, double *traj, double *ff_out) {
   const int n_steps = n > 1 ? n - 1 : 0;
   const LegDrAllLegs x;
-  bool finite = true;
-  for (int i = 0; i < 7; ++i) finite = finite && legdr_finite(pose[i]);
-  for (int i = 3; i < 9; ++i) finite = finite && legdr_finite(sb[i]);
-  for (int i = 0; i < 4; ++i) finite = finite && legdr_finite(lb[i]);
-  if (n_steps)
-    for (int i = 1; i < LEGDR_ROW * n; ++i) finite = finite && legdr_finite(rows[i]);   // (the first sample's dt is not read)
-  if (finite) {
-    LegDrConst c;
-    legdr_const(cfg, sb + 3, sb + 6, c);
-    LegDrWorld wf;
-    wf.R0 = qR(qnormalized(ldq_pose(pose)));
-    wf.P0 = ld3(pose);
-    LegDrState<4> s;
-    LegDrStep<4> o;
-    for (int l = 0; l < 4; ++l) o.flag[l] = 0.0;
-    legdr_start(c, cfg, lb, n_steps ? rows : nullptr, n_steps ? (const double (*)[LEGDR_ROW_LEG])(rows + LEGDR_ROW_SHARED) : nullptr, x, s);
-    for (int i = 1; i < n; ++i) {
-      const double *r = rows + (size_t)LEGDR_ROW * i;
-      legdr_step(c, s, r, (const double (*)[LEGDR_ROW_LEG])(r + LEGDR_ROW_SHARED), x, o);
-      if (traj) {
-        double *row = traj + (size_t)LEGDR_TRAJ * (i - 1);
-        legdr_traj_row(wf, s, o, x, row);
-      }
-    }
-    legdr_state_row(wf, s, o.flag, x, state, legs);
-    finite = legdr_rows_finite(state, legs, x);
-    if (ff_out) legdr_ff_export(s, ff_out);
+  LegDrWalk<4> w;
+  bool finite = legdr_window_start(cfg, pose, sb, lb, n_steps ? rows : nullptr, x, w);
+  for (int i = 1; i < n; ++i) {
+    finite = legdr_next_row(rows + (size_t)LEGDR_ROW * i, x, w) && finite;
+    legdr_step(w.c, w.s, w.sh, w.lg, x, w.o);
+    if (traj) legdr_traj_row(w.wf, w.s, w.o, x, traj + (size_t)LEGDR_TRAJ * (i - 1));
   }
+  legdr_state_row(w.wf, w.s, w.o.flag, x, state, legs);
+  finite = finite && legdr_rows_finite(state, legs, x);
+  if (ff_out) legdr_ff_export(w.s, ff_out);
   if (!finite) {
-    for (int i = 0; i < LEGDR_STATE; ++i) state[i] = 0.0;
-    for (int i = 0; i < LEGDR_LEGS; ++i) legs[i] = 0.0;
-    if (traj)
-      for (size_t i = 0; i < (size_t)LEGDR_TRAJ * n_steps; ++i) traj[i] = 0.0;
+    legdr_zero_share(x, state, LEGDR_STATE);
+    legdr_zero_share(x, legs, LEGDR_LEGS);
+    if (traj) legdr_zero_share(x, traj, (size_t)LEGDR_TRAJ * n_steps);
     if (ff_out)
       for (int i = 0; i < LEGDR_FF_N; ++i) ff_out[i] = 0.0;
     return VILO_DR_NUMERIC;

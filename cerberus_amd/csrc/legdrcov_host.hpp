@@ -63,21 +63,11 @@ enum {
 VD constexpr int ldc_fcol(int k) { return k < 6 ? 3 + k : 15 + k; }   // compact column of dF -> column of F
 VD constexpr int ldc_terms_at(int slot, int leg) { return LDC_SB_TERMS + LDC_T_N * (4 * slot + leg); }
 
-// What is wrong with the arguments of a call on W windows (null: nothing). Reads offsets[0 .. W], nothing else.
+// What is wrong with the arguments of a call on W windows (null: nothing), without the call's name. Reads offsets[0 .. W], nothing else.
 inline const char *leg_dr_cov_check(const vilo_leg_dr_cov_opts &o, int W, const vilo_sample *samples, const int32_t *offsets, const double *state_out,
                                     const double *legs_out, const double *cov_out) {
-  if (o.from_frame < -1 || o.from_frame > VILO_MAX_FRAMES - 1) return "vilo_batch_leg_dead_reckon_covariance: from_frame must be -1 or 0 .. VILO_MAX_FRAMES - 1";
-  if (o.reserved != 0) return "vilo_batch_leg_dead_reckon_covariance: reserved must be 0";
-  if (W <= 0) return nullptr;
-  if (!offsets) return "vilo_batch_leg_dead_reckon_covariance: offsets is NULL";
-  if (!state_out) return "vilo_batch_leg_dead_reckon_covariance: state_out is NULL";
-  if (!legs_out) return "vilo_batch_leg_dead_reckon_covariance: legs_out is NULL";
-  if (!cov_out) return "vilo_batch_leg_dead_reckon_covariance: cov_out is NULL";
-  if (offsets[0] != 0) return "vilo_batch_leg_dead_reckon_covariance: offsets[0] must be 0";
-  for (int w = 0; w < W; ++w)
-    if (offsets[w + 1] < offsets[w]) return "vilo_batch_leg_dead_reckon_covariance: offsets must not decrease";
-  if (offsets[W] > 0 && !samples) return "vilo_batch_leg_dead_reckon_covariance: samples is NULL";
-  return nullptr;
+  return sample_range_check(o.from_frame, o.reserved != 0 ? "reserved must be 0" : nullptr, W, samples, offsets,
+                            !state_out ? "state_out is NULL" : (!legs_out ? "legs_out is NULL" : (!cov_out ? "cov_out is NULL" : nullptr)));
 }
 
 // Element counts of the call's arrays on W windows with n_rows steps in all (dead_reckon_step_offsets' sum).
@@ -301,86 +291,72 @@ inline int leg_dr_cov_window(const vilo_config &cfg, const double *pose, const d
                              double *state, double *legs, double *cov, double *pose_traj, double *leg_traj) {
   const int n_steps = n > 1 ? n - 1 : 0;
   const LegDrAllLegs x;
-  bool finite = true;
-  for (int i = 0; i < 7; ++i) finite = finite && legdr_finite(pose[i]);
-  for (int i = 3; i < 9; ++i) finite = finite && legdr_finite(sb9[i]);
-  for (int i = 0; i < 4; ++i) finite = finite && legdr_finite(lb[i]);
-  if (n_steps)
-    for (int i = 1; i < LEGDR_ROW * n; ++i) finite = finite && legdr_finite(rows[i]);
+  LegDrWalk<4> w;
+  bool finite = legdr_window_start(cfg, pose, sb9, lb, n_steps ? rows : nullptr, x, w);
+  const LegDrConst &c = w.c;
+  LegDrState<4> &s = w.s;
+  LegDrStep<4> &o = w.o;
   double S[LDC_N][LDC_N];   // S[j]: column j of Sigma
   for (int j = 0; j < LDC_N; ++j)
     for (int i = 0; i < LDC_N; ++i) {
       S[j][i] = cov_in ? ldc_sigma0(cov_in, i, j) : 0.0;
       finite = finite && legdr_finite(S[j][i]);
     }
-  if (finite) {
-    LegDrConst c;
-    legdr_const(cfg, sb9 + 3, sb9 + 6, c);
-    LdcNoise q;
-    ldc_noise_const(cfg, q);
-    LegDrWorld wf;
-    wf.R0 = qR(qnormalized(ldq_pose(pose)));
-    wf.P0 = ld3(pose);
-    LegDrState<4> s;
-    LegDrStep<4> o;
-    for (int l = 0; l < 4; ++l) o.flag[l] = 0.0;
-    const double (*leg0)[LEGDR_ROW_LEG] = n_steps ? (const double (*)[LEGDR_ROW_LEG])(rows + LEGDR_ROW_SHARED) : nullptr;
-    legdr_start(c, cfg, lb, n_steps ? rows : nullptr, leg0, x, s);
-    double sb[LDC_SB_TOTAL];
-    ldc_block_start(q, sb);
-    if (n_steps)
-      for (int l = 0; l < 4; ++l) ldc_sample_terms(c, s.gyr0, leg0[l], s.rho[l], s.rf[l], s.v0[l], sb + ldc_terms_at(0, l));
-    for (int i = 1; i < n; ++i) {
-      const double *r = rows + (size_t)LEGDR_ROW * i;
-      const double (*leg1)[LEGDR_ROW_LEG] = (const double (*)[LEGDR_ROW_LEG])(r + LEGDR_ROW_SHARED);
-      const quat dq0 = s.dq;
-      const v3 dv0 = s.dv, acc0 = s.acc0, gyr0 = s.gyr0;
-      legdr_step(c, s, r, leg1, x, o);
-      const double dt = r[0];
-      const m3 R0 = wf.R0 * qR(dq0), R1 = wf.R0 * qR(o.rq);
-      const m3 K = ldc_kappa7(0.5 * (gyr0 + s.gyr0) - c.bg, dt);
-      const bool all_air = o.flag[0] + o.flag[1] + o.flag[2] + o.flag[3] < 1e-6;
-      const int e0 = (i - 1) & 1, e1 = i & 1;
-      for (int l = 0; l < 4; ++l) {
-        ldc_sample_terms(c, s.gyr0, leg1[l], s.rho[l], s.rf[l], s.v0[l], sb + ldc_terms_at(e1, l));
-        double unc[3], rho_unc;
-        ldc_leg_uncertainty(c, q, o.flag[l], s.ff_var[l], o.lo_v[l], dv0, all_air, unc, rho_unc);
-        ldc_leg_noise(wf.R0, dt, unc, rho_unc, l, sb);
-        ldc_leg_rows(R0, R1, K, dt, sb + ldc_terms_at(e0, l), sb + ldc_terms_at(e1, l), l, sb);
-      }
-      ldc_imu_rows(R0, R1, K, acc0 - c.ba, s.acc0 - c.ba, dt, q, sb);
-      for (int j = 0; j < LDC_N; ++j) ldc_f_times(sb, S[j]);
-      for (int j = 0; j < LDC_N; ++j)
-        for (int k = 0; k < j; ++k) { const double t = S[j][k]; S[j][k] = S[k][j]; S[k][j] = t; }
-      for (int j = 0; j < LDC_N; ++j) {
-        ldc_f_times(sb, S[j]);
-        ldc_add_noise(sb, j, S[j]);
-      }
-      if (pose_traj)
-        for (int j = 0; j < LDC_POSE; ++j)
-          for (int k = 0; k <= j; ++k) {
-            double *d = pose_traj + (size_t)(LDC_POSE * LDC_POSE) * (i - 1);
-            d[LDC_POSE * k + j] = d[LDC_POSE * j + k] = S[j][k];
-          }
-      if (leg_traj)
-        for (int l = 0; l < 4; ++l)
-          for (int j = 0; j < 3; ++j)
-            for (int k = 0; k <= j; ++k) {
-              double *d = leg_traj + (size_t)LDC_LEGCOV * (i - 1) + 9 * l;
-              d[3 * k + j] = d[3 * j + k] = S[LDC_O_EPS + 3 * l + j][LDC_O_EPS + 3 * l + k];
-            }
+  LdcNoise q;
+  ldc_noise_const(cfg, q);
+  double sb[LDC_SB_TOTAL];
+  ldc_block_start(q, sb);
+  if (n_steps)
+    for (int l = 0; l < 4; ++l) ldc_sample_terms(c, s.gyr0, w.lg[l], s.rho[l], s.rf[l], s.v0[l], sb + ldc_terms_at(0, l));
+  for (int i = 1; i < n; ++i) {
+    finite = legdr_next_row(rows + (size_t)LEGDR_ROW * i, x, w) && finite;
+    const quat dq0 = s.dq;
+    const v3 dv0 = s.dv, acc0 = s.acc0, gyr0 = s.gyr0;
+    legdr_step(c, s, w.sh, w.lg, x, o);
+    const double dt = w.sh[0];
+    const m3 R0 = w.wf.R0 * qR(dq0), R1 = w.wf.R0 * qR(o.rq);
+    const m3 K = ldc_kappa7(0.5 * (gyr0 + s.gyr0) - c.bg, dt);
+    const bool all_air = o.flag[0] + o.flag[1] + o.flag[2] + o.flag[3] < 1e-6;
+    const int e0 = (i - 1) & 1, e1 = i & 1;
+    for (int l = 0; l < 4; ++l) {
+      ldc_sample_terms(c, s.gyr0, w.lg[l], s.rho[l], s.rf[l], s.v0[l], sb + ldc_terms_at(e1, l));
+      double unc[3], rho_unc;
+      ldc_leg_uncertainty(c, q, o.flag[l], s.ff_var[l], o.lo_v[l], dv0, all_air, unc, rho_unc);
+      ldc_leg_noise(w.wf.R0, dt, unc, rho_unc, l, sb);
+      ldc_leg_rows(R0, R1, K, dt, sb + ldc_terms_at(e0, l), sb + ldc_terms_at(e1, l), l, sb);
     }
-    legdr_state_row(wf, s, o.flag, x, state, legs);
-    finite = legdr_rows_finite(state, legs, x);
+    ldc_imu_rows(R0, R1, K, acc0 - c.ba, s.acc0 - c.ba, dt, q, sb);
+    for (int j = 0; j < LDC_N; ++j) ldc_f_times(sb, S[j]);
     for (int j = 0; j < LDC_N; ++j)
-      for (int k = 0; k <= j; ++k) {
-        finite = finite && legdr_finite(S[j][k]);
-        cov[LDC_N * k + j] = cov[LDC_N * j + k] = S[j][k];
-      }
+      for (int k = 0; k < j; ++k) { const double t = S[j][k]; S[j][k] = S[k][j]; S[k][j] = t; }
+    for (int j = 0; j < LDC_N; ++j) {
+      ldc_f_times(sb, S[j]);
+      ldc_add_noise(sb, j, S[j]);
+    }
+    if (pose_traj)
+      for (int j = 0; j < LDC_POSE; ++j)
+        for (int k = 0; k <= j; ++k) {
+          double *d = pose_traj + (size_t)(LDC_POSE * LDC_POSE) * (i - 1);
+          d[LDC_POSE * k + j] = d[LDC_POSE * j + k] = S[j][k];
+        }
+    if (leg_traj)
+      for (int l = 0; l < 4; ++l)
+        for (int j = 0; j < 3; ++j)
+          for (int k = 0; k <= j; ++k) {
+            double *d = leg_traj + (size_t)LDC_LEGCOV * (i - 1) + 9 * l;
+            d[3 * k + j] = d[3 * j + k] = S[LDC_O_EPS + 3 * l + j][LDC_O_EPS + 3 * l + k];
+          }
   }
+  legdr_state_row(w.wf, s, o.flag, x, state, legs);
+  finite = finite && legdr_rows_finite(state, legs, x);
+  for (int j = 0; j < LDC_N; ++j)
+    for (int k = 0; k <= j; ++k) {
+      finite = finite && legdr_finite(S[j][k]);
+      cov[LDC_N * k + j] = cov[LDC_N * j + k] = S[j][k];
+    }
   if (!finite) {
-    for (int i = 0; i < LEGDR_STATE; ++i) state[i] = 0.0;
-    for (int i = 0; i < LEGDR_LEGS; ++i) legs[i] = 0.0;
+    legdr_zero_share(x, state, LEGDR_STATE);
+    legdr_zero_share(x, legs, LEGDR_LEGS);
     for (int i = 0; i < LDC_N * LDC_N; ++i) cov[i] = 0.0;
     if (pose_traj)
       for (size_t i = 0; i < (size_t)(LDC_POSE * LDC_POSE) * n_steps; ++i) pose_traj[i] = 0.0;

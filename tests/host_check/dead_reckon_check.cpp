@@ -11,6 +11,7 @@
 
 #include "../../cerberus_amd/csrc/batch_call.hpp"
 #include "../../cerberus_amd/csrc/deadreckon_host.hpp"
+#include "../../cerberus_amd/csrc/sample_stream.hpp"
 
 namespace {
 

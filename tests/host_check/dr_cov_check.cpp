@@ -12,6 +12,7 @@
 
 #include "../../cerberus_amd/csrc/batch_call.hpp"
 #include "../../cerberus_amd/csrc/drcov_host.hpp"
+#include "../../cerberus_amd/csrc/sample_stream.hpp"
 
 namespace {
 

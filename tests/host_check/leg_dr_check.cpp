@@ -13,6 +13,7 @@
 
 #include "../../cerberus_amd/csrc/batch_call.hpp"
 #include "../../cerberus_amd/csrc/legdr_host.hpp"
+#include "../../cerberus_amd/csrc/sample_stream.hpp"
 
 namespace {
 

@@ -14,6 +14,7 @@
 
 #include "../../cerberus_amd/csrc/batch_call.hpp"
 #include "../../cerberus_amd/csrc/legdrcov_host.hpp"
+#include "../../cerberus_amd/csrc/sample_stream.hpp"
 
 namespace {
 
