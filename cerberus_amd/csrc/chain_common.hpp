@@ -24,6 +24,60 @@
 
 __device__ __forceinline__ int chain_x_lo(int k, int kb) { return (k <= kb) ? 0 : max(0, (6 * (k - 1)) >> 4); }   // T(k) is zero left of pose k - 1 (dense from the prior's frame down)
 
+// C -= T_B(k)^T T_B(k) for frames F-1 .. 0 on the pose system's 15 accumulator tiles (solve_wave_body's middle stage, kernels_wave.hip),
+// the operands as k_chain left them in Tg ([frame k][tile X][register kk][lane], L2-resident): per frame the tiles (I, J) with
+// J >= x_lo(k) in tile order, four kk steps each — k_solve_wave's sequence on the same values, so the tiles agree bitwise.
+// The operands of a frame are in flight one frame ahead through unconditional loads with clamped addresses — no load sits under a branch,
+// which would cost the compiler its count of loads in flight: the frame index is clamped at 0, a tile left of x_lo (never written) reads
+// tile x_lo again, and the padding rows 13 .. 15 (register 3 of lanes beyond the first 16: never written) read row 12's lane group.
+// One branch-free form of the MFMAs per x_lo (conditions between the MFMAs of a frame stall the stream). The sign of the A operand is
+// flipped by the instruction (neg:[1,0,0], exact) instead of by 20 sign flips per frame in front of the MFMAs.
+__device__ __forceinline__ void chain_rank_updates(mfma_d4 (&acc)[15], const double *Tg, int F, int kb, int lane) {
+  const int lk = lane >> 4;
+  const int lane3 = lk == 0 ? lane : (lane & 15);
+  double tb[2][5][4];
+  auto ldT = [&](int k, auto selc) {
+    constexpr int sel = decltype(selc)::value;
+    const int x_lo = chain_x_lo(k, kb);
+#pragma unroll
+    for (int X = 0; X < 5; ++X) {
+      const double *src = Tg + 1280 * k + max(X, x_lo) * 256;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const double t = src[kk * 64 + (kk < 3 ? lane : lane3)];
+        tb[sel][X][kk] = (kk < 3 || lk == 0) ? t : 0.0;   // (rows 13 .. 15: padding)
+      }
+    }
+  };
+  auto upd_x = [&](auto selc, auto xc) {
+    constexpr int sel = decltype(selc)::value, XLO = decltype(xc)::value;
+#pragma unroll
+    for (int t = 0; t < 15; ++t) {
+      if (c_tJ[t] >= XLO) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(tb[sel][c_tI[t]][kk], tb[sel][c_tJ[t]][kk], acc[t], 0, 0, 1);   // neg:[1,0,0]: -A, the sign flipped in the instruction
+      }
+    }
+  };
+  auto upd = [&](int k, auto selc) {
+    switch (chain_x_lo(k, kb)) {
+      case 0: upd_x(selc, std::integral_constant<int, 0>{}); break;
+      case 1: upd_x(selc, std::integral_constant<int, 1>{}); break;
+      case 2: upd_x(selc, std::integral_constant<int, 2>{}); break;
+      default: upd_x(selc, std::integral_constant<int, 3>{}); break;
+    }
+  };
+  std::integral_constant<int, 0> s0;
+  std::integral_constant<int, 1> s1;
+  ldT(max(F - 1, 0), s0);
+  for (int k = F - 1; k >= 0; k -= 2) {
+    ldT(max(k - 1, 0), s1);
+    upd(k, s0);
+    ldT(max(k - 2, 0), s0);
+    if (k >= 1) upd(k - 1, s1);
+  }
+}
+
 // DB / GB: dhat^2 and gradient of the 143 speed / leg-bias dimensions (LDS). Returns 1 when a pivot was not positive.
 __device__ __forceinline__ int chain_to_global(const double *bimg, const double *gin, double *scr, const double *DB, const double *GB,
                                                double *Mg, double *TAg, double *Tout, double *vout, int F, int kb, double mu, int lane) {

@@ -527,54 +527,9 @@ __device__ __forceinline__ void solve_wave_body(BatchDev &b, const SolveParams &
       if constexpr (MID) {
         // the chain's part comes from k_chain (chain_common.hpp) through global memory: T_B(k) in operand order, the reduced right-hand side
         const double *Tg = b.Tk + (size_t)win * TK_N;
-        // C -= T_B(k)^T T_B(k) for frames F-1 .. 0, operands as the chain left them (L2-resident; the next frame's in flight)
         for (int cd = lane; cd < 80; cd += 64) v[cd] = Tg[TK_V + cd];
-        double tb[2][5][4];
-        // (one branch-free form per x_lo: conditions between the MFMAs of a frame stall the stream)
-        auto ldT_x = [&](int k, auto selc, auto xc) {
-          constexpr int sel = decltype(selc)::value, XLO = decltype(xc)::value;
-#pragma unroll
-          for (int X = XLO; X < 5; ++X)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) tb[sel][X][kk] = (kk < 3 || lk == 0) ? Tg[1280 * k + (X * 4 + kk) * 64 + lane] : 0.0;   // (rows 13 .. 15: padding)
-        };
-        auto upd_x = [&](auto selc, auto xc) {
-          constexpr int sel = decltype(selc)::value, XLO = decltype(xc)::value;
-#pragma unroll
-          for (int t = 0; t < 15; ++t) {
-            if (c_tJ[t] >= XLO) {
-#pragma unroll
-              for (int kk = 0; kk < 4; ++kk) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-tb[sel][c_tI[t]][kk], tb[sel][c_tJ[t]][kk], acc[t], 0, 0, 0);
-            }
-          }
-        };
-        auto ldT = [&](int k, auto selc) {
-          switch (chain_x_lo(k, kb)) {
-            case 0: ldT_x(k, selc, std::integral_constant<int, 0>{}); break;
-            case 1: ldT_x(k, selc, std::integral_constant<int, 1>{}); break;
-            case 2: ldT_x(k, selc, std::integral_constant<int, 2>{}); break;
-            default: ldT_x(k, selc, std::integral_constant<int, 3>{}); break;
-          }
-        };
-        auto upd = [&](int k, auto selc) {
-          switch (chain_x_lo(k, kb)) {
-            case 0: upd_x(selc, std::integral_constant<int, 0>{}); break;
-            case 1: upd_x(selc, std::integral_constant<int, 1>{}); break;
-            case 2: upd_x(selc, std::integral_constant<int, 2>{}); break;
-            default: upd_x(selc, std::integral_constant<int, 3>{}); break;
-          }
-        };
-        std::integral_constant<int, 0> s0;
-        std::integral_constant<int, 1> s1;
-        ldT(F - 1, s0);
-        for (int k = F - 1; k >= 0; k -= 2) {
-          if (k >= 1) ldT(k - 1, s1);
-          upd(k, s0);
-          if (k >= 1) {
-            if (k >= 2) ldT(k - 2, s0);
-            upd(k - 1, s1);
-          }
-        }
+        // C -= T_B(k)^T T_B(k) for frames F-1 .. 0, operands as the chain left them (chain_common.hpp)
+        chain_rank_updates(acc, Tg, F, kb, lane);
       } else {
       // ---- block-tridiagonal Cholesky chain of the speed / leg-bias part (13 x 13 blocks, frames F-1 .. 0):
       //        S_k = A_kk + mu D_k - T_A(k+1)^T T_A(k+1),  L_k = chol(S_k),  M_k = L_k^-1,  T_A(k) = M_k A_{k,k-1},
