@@ -1,6 +1,8 @@
 // Marginalisation half of Estimator::optimization() (estimator.cpp:1247-1455) and MarginalizationInfo
-// (marginalization_factor.cpp:98-333) on gfx950, plus double2vector's gauge fix (estimator.cpp:903-957): vilo_gauge_fix on host arrays, inside
-// vilo_optimize_windows, and as vilo_batch_gauge_fix in place on a resident batch.
+// (marginalization_factor.cpp:98-333) on gfx950: vilo_marginalize on host windows, vilo_batch_marginalize on a resident batch, and
+// vilo_marginalize_batch inside vilo_optimize_windows (vilo_optimize.hip), where a window's new prior may go to a slot of a prior pool.
+// The call is three steps: marg_plan (the block bookkeeping of marg_plan.hpp, no GPU), marg_run (upload, linearise, the kernels, the
+// flags), marg_store (the priors into pool slots or host memory).
 //
 // The factors touching the dropped blocks are linearised by the same kernels the solver uses
 // (k_visual_linearize / k_imu_linearize: residuals, Jacobians, Huber corrector), then one workgroup per window
@@ -11,11 +13,11 @@
 //   * eigen-decomposes A' and emits J0 = sqrt(S) V^T, r0 = sqrt(S^-1) V^T b' (:297-305).
 // Address-keyed bookkeeping (addr_shift, estimator.cpp:1358-1370) is replaced by integer block ids.
 #include <algorithm>
-#include <chrono>
-
 #include <type_traits>
+
 #include "batch_call.hpp"
 #include "cost_eval.hpp"
+#include "marg_plan.hpp"
 #include "solve_common.hpp"
 
 using namespace vilo;
@@ -108,17 +110,6 @@ __device__ void jacobi_eigh_dev(double *A, double *V, int n, double *cs /*LDS 2*
   }
   __syncthreads();
 }
-
-struct MargWin {
-  int m, n;             // dropped / kept local dims
-  int n_drop_lm;        // landmarks among the dropped dims (they follow the 19 frame-0 dims; mode 0)
-  int mode;
-  int has_imu, prior_n;
-  int general;          // 1: this window goes through the global-memory eigen path (set by the host from k_marginalize_lds' verdict)
-  int pad1;
-  long long scratch_off;  // doubles into the scratch arena
-  int cdmap[CD_N];      // camera dim -> index in [dropped | kept] ordering, -1 if absent
-};
 
 // scratch layout per window (doubles): A (T*T) | b (T) | Amm (m*m) | Vm (m*m) | Ainv (m*m) | tmp (n*m) | Ar (n*n) | V2 (n*n) | br (n)
 __global__ void __launch_bounds__(MT) k_marginalize(BatchDev bd, const MargWin *mw, const int *drop_lm /*[W][maxL0] device-order local idx*/,
@@ -277,7 +268,6 @@ __global__ void __launch_bounds__(MT) k_marginalize(BatchDev bd, const MargWin *
   }
 }
 
-// double2vector gauge fix + re-pack (estimator.cpp:903-957, 848-873)
 // ---------------------------------------------------------------------------------------------------------------------
 // LDS-resident marginalisation (the path every well-conditioned window takes).
 //
@@ -908,346 +898,101 @@ __global__ void __launch_bounds__(256) k_prior_scatter(int W, const MargWin *mw,
   for (int e = threadIdx.x; e < n; e += 256) dr[e] = sr[e];
 }
 
-__device__ v3 R2ypr_deg(const m3 &R) {
-  const v3 nn = mk3(R.a[0], R.a[3], R.a[6]), o = mk3(R.a[1], R.a[4], R.a[7]), a = mk3(R.a[2], R.a[5], R.a[8]);
-  const double y = atan2(nn.y, nn.x);
-  const double p = atan2(-nn.z, nn.x * cos(y) + nn.y * sin(y));
-  const double r = atan2(a.x * sin(y) - a.y * cos(y), -o.x * sin(y) + o.y * cos(y));
-  return mk3(y / M_PI * 180.0, p / M_PI * 180.0, r / M_PI * 180.0);   // `ypr / M_PI * 180.0` as utility.h:98 writes it (an ulp from `* (180 / pi)`)
-}
-// what a window's fix reports (vilo_window_gauge_record)
-struct GaugeInfo { double yaw_diff_deg; int singular, numeric; };
-
-// One workgroup per window, thread t < F frame t, threads F and F + 1 the two extrinsics. check: a value read that is not finite leaves
-// the window unwritten (numeric = 1); write_ex: the extrinsic quaternions are rewritten normalised; p0_out: [7] the solved frame-0 pose.
-// vilo_gauge_fix and vilo_optimize_windows run it with check = false and write_ex = true, as they always have.
-__device__ GaugeInfo k_gauge_fix_body(int F, const double *bp /*[7]*/, double *pw /*[F][7]*/, double *sw /*[F][9]*/, double *exw /*[2][7]*/, bool check,
-                                      bool write_ex, double *p0_out) {
-  const int t = threadIdx.x;
-  const m3 Rs0 = qR(ldq_pose(bp));
-  const m3 R00 = qR(ldq_pose(pw));
-  const v3 o0 = R2ypr_deg(Rs0), o00 = R2ypr_deg(R00);
-  const double yd = (o0.x - o00.x) / 180.0 * M_PI;
-  m3 rot = m3_eye();
-  rot.a[0] = cos(yd); rot.a[1] = -sin(yd); rot.a[3] = sin(yd); rot.a[4] = cos(yd);
-  const bool singular = fabs(fabs(o0.y) - 90) < 1.0 || fabs(fabs(o00.y) - 90) < 1.0;
-  if (singular) rot = Rs0 * tr(R00);
-  const v3 P0 = ld3(pw), origin = ld3(bp);
-  bool bad = false;
-  if (check)
-    for (int k = 0; k < 7; ++k) bad = bad || !isfinite(bp[k]) || !isfinite(pw[k]);
-  if (p0_out && t == 0)
-    for (int k = 0; k < 7; ++k) p0_out[k] = pw[k];
-  v3 Pi = P0, Vi = P0;
-  quat q = mkq(1.0, 0.0, 0.0, 0.0);
-  if (t < F) {
-    const double *pp = pw + 7 * t, *ss = sw + 9 * t;
-    if (check) {
-      for (int k = 0; k < 7; ++k) bad = bad || !isfinite(pp[k]);
-      for (int k = 0; k < 3; ++k) bad = bad || !isfinite(ss[k]);
-    }
-    const m3 Ri = rot * qR(qnormalized(ldq_pose(pp)));
-    Pi = rot * (ld3(pp) - P0) + origin;
-    Vi = rot * ld3(ss);
-    q = quat_from_R_dev(Ri);
-  } else if (t < F + 2 && write_ex) {
-    const double *pp = exw + 7 * (t - F);
-    if (check)
-      for (int k = 3; k < 7; ++k) bad = bad || !isfinite(pp[k]);
-    q = quat_from_R_dev(qR(qnormalized(ldq_pose(pp))));
-  }
-  // every read of the window is done before its first write
-  const int numeric = __syncthreads_or(check && bad);
-  GaugeInfo info;
-  info.yaw_diff_deg = numeric ? 0.0 : o0.x - o00.x;
-  info.singular = !numeric && singular;
-  info.numeric = numeric != 0;
-  if (numeric) return info;
-  if (t < F) {
-    double *pp = pw + 7 * t, *ss = sw + 9 * t;
-    st3(pp, Pi);
-    pp[3] = q.x; pp[4] = q.y; pp[5] = q.z; pp[6] = q.w;
-    st3(ss, Vi);
-  } else if (t < F + 2 && write_ex) {
-    double *pp = exw + 7 * (t - F);
-    pp[3] = q.x; pp[4] = q.y; pp[5] = q.z; pp[6] = q.w;
-  }
-  return info;
-}
-
-__global__ void k_gauge_fix(int W, int F, const double *before_pose0 /*[W][7]*/, double *pose /*[W][F][7]*/, double *sb /*[W][F][9]*/,
-                            double *ex /*[W][2][7]*/) {
-  const int w = blockIdx.x;
-  if (w >= W) return;
-  k_gauge_fix_body(F, before_pose0 + 7 * w, pose + (size_t)w * F * 7, sb + (size_t)w * F * 9, ex + (size_t)w * 14, false, true, nullptr);
-}
-
-// the same on the state block of a device-resident batch (pose [F][7] at XO_POSE, speed/bias [F][9] at XO_SB, extrinsics at XO_EX).
-// anchor null: Rs[0] / Ps[0] of before the solve come from the batch's uploaded initial states. vilo_optimize_windows launches it with
-// query = 0: no check, every extrinsic quaternion rewritten, nothing reported; vilo_batch_gauge_fix with query = 1: checked, a constant
-// extrinsic block left as uploaded, records and the replaced frame-0 poses where asked for.
-struct GaugeArgs {
-  const double *anchor;                 // [W][7], or null
-  vilo_window_gauge_record *rec;        // [W], or null
-  double *pose0_before;                 // [W][7], or null
-  int query;
+// What marg_run leaves for marg_store: the call's device blocks (BatchCall memory), the staging they went up from, the flags as last read
+struct MargMem {
+  char *hblob = nullptr;       // page-locked staging of the block that goes up: window tables | dropped landmarks | flags | pool slots
+  MargWin *h_mw = nullptr, *d_mw = nullptr;
+  int *h_slots = nullptr, *d_slots = nullptr;   // [2][W] prior-pool slots: destination, source
+  int *d_flags = nullptr;      // [3][W] status | need_general | the IMU factor of interval 0 stands on a covariance without sqrt_info
+  double *d_J0 = nullptr, *d_r0 = nullptr;
+  size_t nJ0 = 0, nr0 = 0;
+  std::vector<int> flags;      // d_flags on the host
 };
-__global__ void __launch_bounds__(64) k_gauge_fix_x(BatchDev b, GaugeArgs a) {
-  const int w = blockIdx.x;
-  double *x = b.x + (size_t)w * XSTRIDE;
-  const bool write_ex = !(a.query && (b.win[w].const_mask & CONST_EX));
-  const GaugeInfo info = k_gauge_fix_body(b.win[w].n_frames, a.anchor ? a.anchor + 7 * (size_t)w : b.x0 + (size_t)w * XSTRIDE + XO_POSE, x + XO_POSE, x + XO_SB,
-                                          x + XO_EX, a.query != 0, write_ex, a.pose0_before ? a.pose0_before + 7 * (size_t)w : nullptr);
-  if (a.rec && threadIdx.x == 0) {
-    vilo_window_gauge_record r;
-    r.yaw_diff_deg = info.yaw_diff_deg;
-    r.singular = info.singular;
-    r.status = info.numeric ? VILO_GAUGE_NUMERIC : VILO_GAUGE_OK;
-    a.rec[w] = r;
-  }
-}
 
-}  // namespace
-
-int vilo_gauge_fix_batch(vilo_ctx *ctx, BatchDev &bd) {
-  GaugeArgs a;
-  a.anchor = nullptr; a.rec = nullptr; a.pose0_before = nullptr; a.query = 0;
-  hipLaunchKernelGGL(k_gauge_fix_x, dim3(bd.W), dim3(64), 0, ctx->stream, bd, a);
-  VILO_HIP(hipGetLastError());
-  return VILO_OK;
-}
-
-static_assert(sizeof(vilo_gauge_opts) == 8, "vilo_gauge_opts: 8 bytes (include/vilo_gpu.h)");
-static_assert(sizeof(vilo_window_gauge_record) == 16, "vilo_window_gauge_record: 16 bytes (include/vilo_gpu.h)");
-
-extern "C" void vilo_default_gauge_opts(vilo_gauge_opts *o) {
-  if (!o) return;
-  o->anchor = VILO_GAUGE_ANCHOR_UPLOADED;
-  o->reserved = 0;
-}
-
-// what is wrong with a gauge-fix call's arguments, or null
-static const char *gauge_check(const vilo_gauge_opts &o, const double *anchor_pose) {
-  if (o.anchor != VILO_GAUGE_ANCHOR_UPLOADED && o.anchor != VILO_GAUGE_ANCHOR_GIVEN) return "vilo_batch_gauge_fix: anchor must be VILO_GAUGE_ANCHOR_UPLOADED or VILO_GAUGE_ANCHOR_GIVEN";
-  if (o.anchor == VILO_GAUGE_ANCHOR_GIVEN && !anchor_pose) return "vilo_batch_gauge_fix: VILO_GAUGE_ANCHOR_GIVEN needs anchor_pose";
-  if (o.anchor != VILO_GAUGE_ANCHOR_GIVEN && anchor_pose) return "vilo_batch_gauge_fix: anchor_pose needs VILO_GAUGE_ANCHOR_GIVEN";
-  return nullptr;
-}
-
-// double2vector's gauge fix (estimator.cpp:903-1003) in place on a resident batch's device state
-extern "C" int vilo_batch_gauge_fix(vilo_ctx *ctx, vilo_batch *bt, const vilo_gauge_opts *opts, const double *anchor_pose, vilo_window_gauge_record *records,
-                                    double *pose0_before) {
-  if (!ctx || !bt) return VILO_ERR_BAD_ARG;
-  vilo_gauge_opts o;
-  if (opts) o = *opts; else vilo_default_gauge_opts(&o);
-  if (const char *what = gauge_check(o, anchor_pose)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
-  const BatchDev &bd = bt->d;
-  const int W = bd.W;
-  BatchCall call(ctx, bt, &vilo_ctx::last_gauge_fix_ms);
-  if (W == 0) return VILO_OK;
-  const bool given = o.anchor == VILO_GAUGE_ANCHOR_GIVEN;
-  // the call's device memory: anchor poses | records | replaced frame-0 poses
-  const size_t o_a = call.lay.take<double>(7 * (size_t)W, given), o_r = call.lay.take<vilo_window_gauge_record>(W),
-               o_p = call.lay.take<double>(7 * (size_t)W, pose0_before != nullptr);
-  if (call.begin() != VILO_OK) return VILO_ERR_HIP;
-  GaugeArgs a;
-  a.anchor = given ? call.ptr<double>(o_a) : nullptr;
-  a.rec = call.ptr<vilo_window_gauge_record>(o_r);
-  a.pose0_before = pose0_before ? call.ptr<double>(o_p) : nullptr;
-  a.query = 1;
-  // (not timed)
-  if (given) VILO_HIP(hipMemcpyAsync(call.ptr<double>(o_a), anchor_pose, sizeof(double) * 7 * (size_t)W, hipMemcpyHostToDevice, ctx->stream));
-  VILO_HIP(call.start());
-  hipLaunchKernelGGL(k_gauge_fix_x, dim3(W), dim3(64), 0, ctx->stream, bd, a);
-  VILO_HIP(call.finish());
-  VILO_HIP(call.down(records, a.rec, sizeof(vilo_window_gauge_record) * (size_t)W));
-  VILO_HIP(call.down(pose0_before, a.pose0_before, sizeof(double) * 7 * (size_t)W));
-  return VILO_OK;
-}
-
-extern "C" int vilo_window_gauge_fix(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *state, const vilo_gauge_opts *opts,
-                                     const double *anchor_pose, vilo_window_gauge_record *records, double *pose0_before) {
-  if (!ctx || n_windows < 1 || !in || !state) return VILO_ERR_BAD_ARG;
-  vilo_gauge_opts o;
-  if (opts) o = *opts; else vilo_default_gauge_opts(&o);
-  if (const char *what = gauge_check(o, anchor_pose)) {
-    ctx->err = what;
-    return VILO_ERR_BAD_ARG;
-  }
-  return vilo_with_batch(ctx, n_windows, in, state, [&](vilo_batch *bt) {
-    const int r = vilo_batch_gauge_fix(ctx, bt, &o, anchor_pose, records, pose0_before);
-    if (r != VILO_OK) return r;
-    return vilo_batch_download(ctx, bt, state, nullptr);   // (the other state arrays come back as they went up)
-  });
-}
-
-extern "C" double vilo_last_gauge_fix_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_gauge_fix_ms : -1.0; }
-
-extern "C" double vilo_last_marginalize_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_marg_ms : 0.0; }
-extern "C" int vilo_debug_marg_general_count(const vilo_ctx *ctx) { return ctx ? ctx->marg_general_count : 0; }
-
-extern "C" int vilo_gauge_fix(vilo_ctx *ctx, int W, const vilo_window_state *before, vilo_window_state *after, int F) {
-  if (!ctx || W <= 0 || !before || !after || F < 1 || F > VILO_MAX_FRAMES) return VILO_ERR_BAD_ARG;
-  VILO_HIP(hipSetDevice(ctx->device));
-  std::vector<double> bp((size_t)W * 7), pose((size_t)W * F * 7), sb((size_t)W * F * 9), ex((size_t)W * 14);
+// Step 1, no GPU: what each window's marginalisation drops and keeps (marg_plan.hpp), from the batch's landmark order and mask mirror and
+// the windows' references
+int marg_plan(vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const int *modes, MargPlan &plan) {
+  std::vector<MargWindow> win(W);
   for (int w = 0; w < W; ++w) {
-    memcpy(&bp[(size_t)w * 7], before[w].pose, 7 * sizeof(double));
-    memcpy(&pose[(size_t)w * F * 7], after[w].pose, sizeof(double) * F * 7);
-    memcpy(&sb[(size_t)w * F * 9], after[w].speed_bias, sizeof(double) * F * 9);
-    memcpy(&ex[(size_t)w * 14], after[w].ex_pose, sizeof(double) * 14);
-  }
-  DevBuf d_bp, d_pose, d_sb, d_ex;
-  VILO_HIP(d_bp.alloc(bp.size() * 8)); VILO_HIP(d_pose.alloc(pose.size() * 8)); VILO_HIP(d_sb.alloc(sb.size() * 8)); VILO_HIP(d_ex.alloc(ex.size() * 8));
-  VILO_HIP(hipMemcpyAsync(d_bp.p, bp.data(), bp.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(d_pose.p, pose.data(), pose.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(d_sb.p, sb.data(), sb.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(d_ex.p, ex.data(), ex.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_gauge_fix, dim3(W), dim3(64), 0, ctx->stream, W, F, d_bp.as<double>(), d_pose.as<double>(), d_sb.as<double>(), d_ex.as<double>());
-  VILO_HIP(hipGetLastError());
-  VILO_HIP(hipMemcpyAsync(pose.data(), d_pose.p, pose.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(sb.data(), d_sb.p, sb.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  VILO_HIP(hipMemcpyAsync(ex.data(), d_ex.p, ex.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  VILO_HIP(hipStreamSynchronize(ctx->stream));
-  for (int w = 0; w < W; ++w) {
-    memcpy(after[w].pose, &pose[(size_t)w * F * 7], sizeof(double) * F * 7);
-    memcpy(after[w].speed_bias, &sb[(size_t)w * F * 9], sizeof(double) * F * 9);
-    memcpy(after[w].ex_pose, &ex[(size_t)w * 14], sizeof(double) * 14);
-  }
-  return VILO_OK;
-}
-
-// Marginalisation of every window of an existing batch at its current device state (b.x, b.lam). `state` holds the same
-// values on the host (they become keep_block_data of the new prior); modes[w]: 0 MARGIN_OLD, 1 MARGIN_SECOND_NEW, < 0 skip
-// (out[w] untouched). The batch is left alive.
-static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *state,
-                             const int *modes, vilo_prior *out) {
-  int rc = VILO_OK;
-  if (bt->mask.stale(ctx, "vilo_batch_marginalize") != VILO_OK) return VILO_ERR_HIP;
-  BatchDev &bd = bt->d;
-  std::vector<MargWin> mws(W);
-  std::vector<std::vector<int>> kept_ids(W), kept_cd(W), kept_gs(W), kept_soff(W);
-  int max_l0 = 1;
-  std::vector<std::vector<int>> drops(W);
-  std::vector<char> keep_prior(W, 0), skip(W, 0);
-  for (int w = 0; w < W; ++w) {
-    const vilo_window_desc &d = in[w];
-    MargWin &M = mws[w];
-    memset(&M, 0, sizeof(M));
-    for (int i = 0; i < CD_N; ++i) M.cdmap[i] = -1;
-    const int mode = modes[w];
-    if (mode < 0) { M.m = 0; M.n = 0; M.mode = 0; skip[w] = 1; continue; }
-    M.mode = mode;
-    const int F = d.n_frames, WS = F - 1;
     const vilo_resident_refs *rf = refs ? refs + w : nullptr;
-    const vilo_prior *prw = vilo_win_prior(d, rf);
-    const bool has_prior = prw && prw->valid && prw->n > 0;
-    M.prior_n = has_prior ? prw->n : 0;
-    // which camera blocks take part (id = kind*16 + index), in the oracle's canonical order
-    std::vector<int> present;   // block ids
-    auto mark = [&](int id) { if (std::find(present.begin(), present.end(), id) == present.end()) present.push_back(id); };
-    if (has_prior)
-      for (int k = 0; k < prw->n_blocks; ++k) mark(prw->block_id[k]);
-    std::vector<int> dropped_ids;
-    if (mode == 0) {
-      const int nkind = d.use_leg ? 3 : 2;   // pose, speed/bias (, leg bias)
-      M.has_imu = vilo_win_sum_dt(d, rf, 0) < 10.0 ? 1 : 0;
-      if (M.has_imu)
-        for (int kind = 0; kind < nkind; ++kind) { mark(kind * 16 + 0); mark(kind * 16 + 1); }
-      const int L = bt->lm.L[w], *perm = bt->lm.perm.data() + bt->lm.lm_off[w];
-      // a masked landmark (vilo_batch_mask_landmarks) is the deleted one: in no residual block, so it marks no block and is not among
-      // the eliminated landmarks (its E_l is 0: the inverse k_marginalize_lds takes of it would send the window to the eigen path)
-      const unsigned char *msk = bt->mask.host(bt->lm.lm_off[w]);
-      for (int i = 0; i < L; ++i) {
-        const int l = perm[i];
-        if (d.lm_start_frame[l] != 0 || (msk && msk[i])) continue;
-        const int K = d.lm_obs_offset[l + 1] - d.lm_obs_offset[l];
-        mark(VILO_BLK_POSE * 16 + 0);
-        for (int t = 1; t < K; ++t) mark(VILO_BLK_POSE * 16 + t);
-        mark(VILO_BLK_EX * 16 + 0); mark(VILO_BLK_EX * 16 + 1); mark(VILO_BLK_TD * 16);
-      }
-      // dropped landmark list in ORIGINAL feature order (oracle: ascending parameter index)
-      std::vector<std::pair<int, int>> dl;
-      for (int i = 0; i < L; ++i)
-        if (d.lm_start_frame[perm[i]] == 0 && !(msk && msk[i])) dl.push_back({perm[i], i});
-      std::sort(dl.begin(), dl.end());
-      for (auto &pr : dl) drops[w].push_back(pr.second);
-      M.n_drop_lm = (int)drops[w].size();
-      max_l0 = std::max(max_l0, M.n_drop_lm);
-      for (int kind = 0; kind < 3; ++kind)
-        if (std::find(present.begin(), present.end(), kind * 16) != present.end()) dropped_ids.push_back(kind * 16);
-    } else {
-      if (!has_prior || std::find(present.begin(), present.end(), VILO_BLK_POSE * 16 + (WS - 1)) == present.end()) {
-        // estimator.cpp:1379-1380: nothing is marginalised and last_marginalization_info stays as it is
-        keep_prior[w] = has_prior ? 1 : 0;
-        M.m = 0; M.n = 0;
-        continue;
-      }
-      dropped_ids.push_back(VILO_BLK_POSE * 16 + (WS - 1));
-    }
-    auto blk = [&](int id, int &cd, int &ls, int &gs, int &soff) {
-      const int kind = id / 16, index = id % 16;
-      if (kind == VILO_BLK_POSE) { cd = 6 * index; ls = 6; gs = 7; soff = XO_POSE + 7 * index; }
-      else if (kind == VILO_BLK_SB) { cd = CD_B0 + 13 * index; ls = 9; gs = 9; soff = XO_SB + 9 * index; }
-      else if (kind == VILO_BLK_LB) { cd = CD_B0 + 13 * index + 9; ls = 4; gs = 4; soff = XO_LB + 4 * index; }
-      else if (kind == VILO_BLK_EX) { cd = CD_EX0 + 6 * index; ls = 6; gs = 7; soff = XO_EX + 7 * index; }
-      else { cd = CD_TD; ls = 1; gs = 1; soff = XO_TD; }
-    };
-    int pos = 0;
-    std::sort(dropped_ids.begin(), dropped_ids.end());
-    for (int id : dropped_ids) {
-      int cd, ls, gs, soff; blk(id, cd, ls, gs, soff);
-      for (int c = 0; c < ls; ++c) M.cdmap[cd + c] = pos + c;
-      pos += ls;
-    }
-    // (without an IMU factor on interval (0, 1) — sum_dt > 10 s — and without a prior on them, speed-bias / leg-bias of frame 0 are in no
-    // residual block and are not marginalised: the dense dropped part is the pose alone, as in MarginalizationInfo::addResidualBlockInfo)
-    pos += M.n_drop_lm;
-    M.m = pos;
-    std::vector<int> kept;
-    for (int id : present)
-      if (std::find(dropped_ids.begin(), dropped_ids.end(), id) == dropped_ids.end()) kept.push_back(id);
-    std::sort(kept.begin(), kept.end());
-    for (int id : kept) {
-      int cd, ls, gs, soff; blk(id, cd, ls, gs, soff);
-      for (int c = 0; c < ls; ++c) M.cdmap[cd + c] = pos + c;
-      kept_ids[w].push_back(id); kept_cd[w].push_back(pos - M.m); kept_gs[w].push_back(gs); kept_soff[w].push_back(soff);
-      pos += ls;
-    }
-    M.n = pos - M.m;
-    if (M.n > VILO_MAX_PRIOR_DIM || (int)kept.size() > VILO_MAX_PRIOR_BLOCKS || M.m > 1200) { return VILO_ERR_UNSUPPORTED; }
+    MargWindow &m = win[w];
+    m.desc = in + w; m.mode = modes[w];
+    if (m.mode < 0) continue;
+    m.prior = vilo_win_prior(in[w], rf);
+    if (m.mode == 0) m.sum_dt0 = vilo_win_sum_dt(in[w], rf, 0);
+    m.L = bt->lm.L[w]; m.perm = bt->lm.perm.data() + bt->lm.lm_off[w]; m.mask = bt->mask.host(bt->lm.lm_off[w]);
   }
-  std::vector<int> drop_flat((size_t)W * max_l0, 0);
-  for (int w = 0; w < W; ++w)
-    for (size_t i = 0; i < drops[w].size(); ++i) drop_flat[(size_t)w * max_l0 + i] = drops[w][i];
+  return plan_marginalization(W, win.data(), plan).code;
+}
+
+// Behind the marginalisation's kernels on the stream: k_marg_imu0_bad folds its flag per window, the stream drains, the three rows of
+// flags come back. launch_err: what vilo_last_error says of a launch or the stream that failed (null: nothing).
+int marg_read_flags(vilo_ctx *ctx, const BatchDev &bd, int W, MargMem &mem, const char *launch_err) {
+  if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, mem.d_flags + 2 * (size_t)W);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    if (launch_err) ctx->err = launch_err;
+    return VILO_ERR_HIP;
+  }
+  if (hipMemcpy(mem.flags.data(), mem.d_flags, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return VILO_ERR_HIP;
+  return VILO_OK;
+}
+
+// VILO_MARG_CLOCKS: the phases of k_marginalize_lds on window 0
+void marg_print_clocks(const long long *d_clk) {
+  long long c[8];
+  if (hipMemcpy(c, d_clk, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess)
+    fprintf(stderr, "[k_marginalize_lds] window 0 cycles: assemble %lld, landmarks %lld, cholesky %lld, schur %lld, pivoted cholesky %lld, jacobi %lld, output %lld\n", c[1] - c[0],
+            c[2] - c[1], c[3] - c[2], c[4] - c[3], c[7] - c[4], c[5] - c[7], c[6] - c[5]);
+}
+
+// The windows marked general — rank-deficient Amm (or an over-sized problem) — through k_marginalize: thresholded eigen pseudo-inverse of
+// the full Amm in global memory
+int marg_run_general(BatchCall &call, BatchDev &bd, MargPlan &plan, MargMem &mem, const int *d_drop) {
+  vilo_ctx *ctx = call.ctx;
+  const int W = (int)plan.wins.size();
+  const size_t scratch_total = assign_marg_scratch(plan.wins);
+  // the updated window tables go up in stream order behind the first copy, from the same staging updated in place (with the forced
+  // path that copy may still be reading it: whatever it reads, this one lands last)
+  memcpy(mem.h_mw, plan.wins.data(), sizeof(MargWin) * (size_t)W);
+  double *d_scr = (double *)call.scope->alloc(sizeof(double) * std::max<size_t>(1, scratch_total));   // (sized only now: an allocation of its own)
+  if (!d_scr || hipMemcpyAsync(mem.d_mw, mem.h_mw, sizeof(MargWin) * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+  hipLaunchKernelGGL(k_marginalize, dim3(W), dim3(MT), 0, ctx->stream, bd, mem.d_mw, d_drop, plan.max_l0, d_scr, mem.d_J0, mem.d_r0, mem.d_flags);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize launch failed"; return VILO_ERR_HIP; }
+  return VILO_OK;
+}
+
+// Step 2: the plan's tables go up, the factors are linearised at the batch's state, k_marginalize_lds runs every window and k_marginalize
+// those it hands on; J0 / r0 stay on the device, the flags are on the host when it returns.
+int marg_run(BatchCall &call, MargPlan &plan, MargMem &mem) {
+  vilo_ctx *ctx = call.ctx;
+  BatchDev &bd = call.bt->d;
+  const int W = (int)plan.wins.size();
   // The call's device memory (BatchCall: given back when the call returns) starts with one block for what goes up (window tables,
   // dropped-landmark lists, prior-pool slots) and the flags that come back (status, need_general, "the IMU factor of interval 0 stands on
   // a covariance without sqrt_info"): one upload, one download per call — a one-window call per image used to spend more time in its
   // dozen synchronous copies and allocations than in its kernels. Behind it J0, r0 and the clock stamps, which stay on the device.
   const bool want_clk = getenv("VILO_MARG_CLOCKS") != nullptr;
-  BatchCall call(ctx, bt, &vilo_ctx::last_marg_ms);
-  const size_t off_mw = call.lay.take<MargWin>(W), off_drop = call.lay.take<int>(drop_flat.size());
+  const size_t off_mw = call.lay.take<MargWin>(W), off_drop = call.lay.take<int>(plan.drop_lm.size());
   const size_t off_flags = call.lay.take<int>(3 * (size_t)W), off_slots = call.lay.take<int>(2 * (size_t)W), blob_bytes = call.lay.bytes();
-  const size_t nJ0 = (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM, nr0 = (size_t)W * VILO_MAX_PRIOR_DIM;
-  const size_t off_J0 = call.lay.take<double>(nJ0), off_r0 = call.lay.take<double>(nr0), off_clk = call.lay.take<long long>(8 * (size_t)W, want_clk);
+  mem.nJ0 = (size_t)W * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM; mem.nr0 = (size_t)W * VILO_MAX_PRIOR_DIM;
+  const size_t off_J0 = call.lay.take<double>(mem.nJ0), off_r0 = call.lay.take<double>(mem.nr0), off_clk = call.lay.take<long long>(8 * (size_t)W, want_clk);
   // (the context's reusable page-locked staging: the scope's closing sync outlives the asynchronous copies on every return path)
-  char *hblob = (char *)vilo_host_stage(ctx, 6, blob_bytes);
-  if (!hblob) return VILO_ERR_HIP;
-  memset(hblob, 0, blob_bytes);
-  memcpy(hblob + off_mw, mws.data(), sizeof(MargWin) * (size_t)W);
-  if (!drop_flat.empty()) memcpy(hblob + off_drop, drop_flat.data(), sizeof(int) * drop_flat.size());
+  mem.hblob = (char *)vilo_host_stage(ctx, 6, blob_bytes);
+  if (!mem.hblob) return VILO_ERR_HIP;
+  mem.h_mw = (MargWin *)(mem.hblob + off_mw); mem.h_slots = (int *)(mem.hblob + off_slots);
+  memset(mem.hblob, 0, blob_bytes);
+  memcpy(mem.h_mw, plan.wins.data(), sizeof(MargWin) * (size_t)W);
+  if (!plan.drop_lm.empty()) memcpy(mem.hblob + off_drop, plan.drop_lm.data(), sizeof(int) * plan.drop_lm.size());
   if (call.begin() != VILO_OK) return VILO_ERR_HIP;
-  double *d_J0 = call.ptr<double>(off_J0), *d_r0 = call.ptr<double>(off_r0);
+  mem.d_J0 = call.ptr<double>(off_J0); mem.d_r0 = call.ptr<double>(off_r0);
   long long *d_clk = want_clk ? call.ptr<long long>(off_clk) : nullptr;
-  MargWin *d_mw = call.ptr<MargWin>(off_mw);   // (the first block: the blob starts here)
-  int *d_drop = call.ptr<int>(off_drop), *d_status = call.ptr<int>(off_flags), *d_general = d_status + W, *d_pbad = d_status + 2 * (size_t)W;
-  int *d_slots = call.ptr<int>(off_slots);   // [2][W] prior-pool slots: destination, source
-  if (hipMemcpyAsync(d_mw, hblob, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+  mem.d_mw = call.ptr<MargWin>(off_mw);   // (the first block: the blob starts here)
+  mem.d_flags = call.ptr<int>(off_flags); mem.d_slots = call.ptr<int>(off_slots);
+  int *d_drop = call.ptr<int>(off_drop), *d_status = mem.d_flags, *d_general = mem.d_flags + W;
+  if (hipMemcpyAsync(mem.d_mw, mem.hblob, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
   // preMarginalize: evaluate the factors at the current state (marginalization_factor.cpp:119-138)
   VILO_HIP(call.start());
-  rc = vilo_marg_linearize(ctx, bd);
+  int rc = vilo_marg_linearize(ctx, bd);
   if (rc != VILO_OK) return rc;
   const size_t lds_bytes = (size_t)MG_LDS_DOUBLES * sizeof(double);
   if (!ctx->marg_attr_set) {   // (per context = per device and host thread)
@@ -1255,140 +1000,97 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
     ctx->marg_attr_set = true;
   }
   const bool force_general = getenv("VILO_MARG_GENERAL") != nullptr;   // test hook: every window through the global-memory eigen path
-  std::vector<int> general(W, force_general ? 1 : 0), flags(3 * (size_t)W, 0);   // flags: status | need_general | IMU factor 0 without sqrt_info
-  bool have_flags = false;
+  mem.flags.assign(3 * (size_t)W, 0);
   if (!force_general) {
-    have_flags = true;
-    hipLaunchKernelGGL(k_marginalize_lds, dim3(W), dim3(MGT), lds_bytes, ctx->stream, bd, d_mw, d_drop, max_l0, d_J0, d_r0, d_status, d_general, d_clk,
+    hipLaunchKernelGGL(k_marginalize_lds, dim3(W), dim3(MGT), lds_bytes, ctx->stream, bd, mem.d_mw, d_drop, plan.max_l0, mem.d_J0, mem.d_r0, d_status, d_general, d_clk,
                        ctx->prior_form);
-    if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, d_pbad);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize_lds launch failed"; return VILO_ERR_HIP; }
-    if (hipMemcpy(flags.data(), d_status, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return VILO_ERR_HIP;
-    for (int w = 0; w < W; ++w) general[w] = flags[(size_t)W + w];
-    if (want_clk) {
-      long long c[8];
-      if (hipMemcpy(c, d_clk, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess)
-        fprintf(stderr, "[k_marginalize_lds] window 0 cycles: assemble %lld, landmarks %lld, cholesky %lld, schur %lld, pivoted cholesky %lld, jacobi %lld, output %lld\n", c[1] - c[0],
-                c[2] - c[1], c[3] - c[2], c[4] - c[3], c[7] - c[4], c[5] - c[7], c[6] - c[5]);
-    }
+    rc = marg_read_flags(ctx, bd, W, mem, "k_marginalize_lds launch failed");
+    if (rc != VILO_OK) return rc;
+    if (want_clk) marg_print_clocks(d_clk);
   }
   ctx->marg_general_count = 0;
   for (int w = 0; w < W; ++w)
-    if (general[w] && mws[w].m > 0 && mws[w].n > 0) { mws[w].general = 1; ++ctx->marg_general_count; }
+    if ((force_general || mem.flags[(size_t)W + w]) && plan.wins[w].m > 0 && plan.wins[w].n > 0) { plan.wins[w].general = 1; ++ctx->marg_general_count; }
   if (ctx->marg_general_count > 0) {
-    // rank-deficient Amm (or an over-sized problem): thresholded eigen pseudo-inverse of the full Amm in global memory
-    size_t scratch_total = 0;
-    for (int w = 0; w < W; ++w) {
-      MargWin &M = mws[w];
-      if (!M.general) continue;
-      M.scratch_off = (long long)scratch_total;
-      const size_t T = (size_t)M.m + M.n;
-      scratch_total += T * T + T + 3 * (size_t)M.m * M.m + (size_t)M.n * M.m + 3 * (size_t)M.n * M.n + 2 * M.n + 64;
-    }
-    // the updated window tables go up in stream order behind the first copy, from the same staging updated in place (with the forced
-    // path that copy may still be reading it: whatever it reads, this one lands last)
-    memcpy(hblob + off_mw, mws.data(), sizeof(MargWin) * (size_t)W);
-    double *d_scr = (double *)call.scope->alloc(sizeof(double) * std::max<size_t>(1, scratch_total));   // (sized only now: an allocation of its own)
-    if (!d_scr || hipMemcpyAsync(d_mw, hblob + off_mw, sizeof(MargWin) * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
-    have_flags = false;   // (this kernel writes status too: read again below)
-    hipLaunchKernelGGL(k_marginalize, dim3(W), dim3(MT), 0, ctx->stream, bd, d_mw, d_drop, max_l0, d_scr, d_J0, d_r0, d_status);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "k_marginalize launch failed"; return VILO_ERR_HIP; }
+    rc = marg_run_general(call, bd, plan, mem, d_drop);
+    if (rc != VILO_OK) return rc;
   }
   VILO_HIP(call.finish());
-  // Status first: a window whose result is unusable must not overwrite a pool slot either.
-  std::vector<int> status(W, 0);
-  int any_bad = 0;
-  if (!have_flags) {
-    if (bd.prep_bad) hipLaunchKernelGGL(k_marg_imu0_bad, dim3((W + 255) / 256), dim3(256), 0, ctx->stream, W, bd.prep_bad, bd.imu_skip, d_pbad);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(flags.data(), d_status, sizeof(int) * 3 * (size_t)W, hipMemcpyDeviceToHost) != hipSuccess) return VILO_ERR_HIP;
+  // (k_marginalize writes status too, and the forced path has read nothing yet)
+  if (force_general || ctx->marg_general_count > 0) return marg_read_flags(ctx, bd, W, mem, nullptr);
+  return VILO_OK;
+}
+
+// Windows with a prior pool leave J0 / r0 on the device (slot next_prior_slot): k_prior_scatter moves them there, or the unchanged prior
+// from its old slot; only their kept-block bookkeeping is host side. any_host: some window's prior goes back to host memory.
+int marg_scatter_pooled(vilo_ctx *ctx, const MargPlan &plan, MargMem &mem, const vilo_resident_refs *refs, const std::vector<int> &status, bool *any_host) {
+  const int W = (int)plan.wins.size();
+  std::vector<int> dst_slot(W, -1), src_slot(W, -1);
+  for (int w = 0; w < W; ++w) {
+    if (plan.skip[w]) continue;
+    if (refs && refs[w].prior_pool) {
+      vilo_prior_pool *pl = refs[w].prior_pool;
+      if (refs[w].next_prior_slot < 0 || refs[w].next_prior_slot >= pl->n) return VILO_ERR_BAD_ARG;
+      if (plan.keep_prior[w]) { if (refs[w].prior_slot != refs[w].next_prior_slot) src_slot[w] = refs[w].prior_slot; else continue; }
+      else if (status[w] || plan.wins[w].m == 0 || plan.wins[w].n == 0) continue;   // (no prior comes out of this window: its slot is left alone, meta.valid cleared by the caller)
+      dst_slot[w] = refs[w].next_prior_slot;
+    } else {
+      *any_host = true;
+    }
   }
-  for (int w = 0; w < W; ++w) status[w] = flags[w];
+  if (refs && refs[0].prior_pool) {
+    int *h_slots = mem.h_slots;   // (the stream has drained: no copy reads the staging any more)
+    memcpy(h_slots, dst_slot.data(), sizeof(int) * W);
+    memcpy(h_slots + W, src_slot.data(), sizeof(int) * W);
+    if (hipMemcpyAsync(mem.d_slots, h_slots, sizeof(int) * 2 * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+    hipLaunchKernelGGL(k_prior_scatter, dim3(W), dim3(256), 0, ctx->stream, W, mem.d_mw, mem.d_slots, mem.d_slots + W, mem.d_J0, mem.d_r0, refs[0].prior_pool->dJ,
+                       refs[0].prior_pool->dr);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return VILO_ERR_HIP;
+  }
+  return VILO_OK;
+}
+
+// Step 3: every window's new prior, into its pool slot or out[w]
+int marg_store(vilo_ctx *ctx, const BatchDev &bd, const MargPlan &plan, MargMem &mem, const vilo_window_desc *in, const vilo_resident_refs *refs,
+               const vilo_window_state *state, vilo_prior *out) {
+  const int W = (int)plan.wins.size();
+  // Status first: a window whose result is unusable must not overwrite a pool slot either.
+  std::vector<int> status(mem.flags.begin(), mem.flags.begin() + W);
   // A preintegration covariance that is not positive definite has no sqrt_info (its bad pivots were replaced by 1 so that the arithmetic
   // stays finite): an IMU factor built on it would give a finite but meaningless prior. Only the factors that ENTER this marginalisation
   // count — MARGIN_OLD uses the factor of interval 0 alone (estimator.cpp:1271-1297), MARGIN_SECOND_NEW no IMU factor at all
   // (:1389-1410) —, like the reference, which would yield a valid prior whatever the other intervals look like. The flags are those of
   // the records in force: written by the preparation (batch creation / vilo_batch_prepare) or, with re-propagation, by the mode-0 pass
-  // above (k_marg_imu0_bad folds them per window behind the marginalisation's kernels). Treated like a non-finite result: the window goes
-  // on without a prior and the call reports VILO_ERR_NUMERIC.
+  // of the linearisation (k_marg_imu0_bad folds them per window behind the marginalisation's kernels). Treated like a non-finite result:
+  // the window goes on without a prior and the call reports VILO_ERR_NUMERIC.
   if (bd.prep_bad)
     for (int w = 0; w < W; ++w)
-      if (!skip[w] && modes[w] == 0 && flags[2 * (size_t)W + w]) status[w] = 1;
-  // windows with a prior pool leave J0 / r0 on the device (slot next_prior_slot); only their kept-block bookkeeping is host side
-  std::vector<int> dst_slot(W, -1), src_slot(W, -1);
+      if (!plan.skip[w] && plan.wins[w].mode == 0 && mem.flags[2 * (size_t)W + w]) status[w] = 1;
   bool any_host = false;
-  for (int w = 0; w < W; ++w) {
-    if (skip[w]) continue;
-    if (refs && refs[w].prior_pool) {
-      vilo_prior_pool *pl = refs[w].prior_pool;
-      if (refs[w].next_prior_slot < 0 || refs[w].next_prior_slot >= pl->n) return VILO_ERR_BAD_ARG;
-      if (keep_prior[w]) { if (refs[w].prior_slot != refs[w].next_prior_slot) src_slot[w] = refs[w].prior_slot; else continue; }
-      else if (status[w] || mws[w].m == 0 || mws[w].n == 0) continue;   // (no prior comes out of this window: its slot is left alone, meta.valid cleared below)
-      dst_slot[w] = refs[w].next_prior_slot;
-    } else {
-      any_host = true;
-    }
-  }
-  if (refs && refs[0].prior_pool) {
-    int *h_slots = (int *)(hblob + off_slots);   // (the stream has drained: no copy reads the staging any more)
-    memcpy(h_slots, dst_slot.data(), sizeof(int) * W);
-    memcpy(h_slots + W, src_slot.data(), sizeof(int) * W);
-    if (hipMemcpyAsync(d_slots, h_slots, sizeof(int) * 2 * (size_t)W, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return VILO_ERR_HIP;
-    hipLaunchKernelGGL(k_prior_scatter, dim3(W), dim3(256), 0, ctx->stream, W, d_mw, d_slots, d_slots + W, d_J0, d_r0, refs[0].prior_pool->dJ,
-                       refs[0].prior_pool->dr);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return VILO_ERR_HIP;
-  }
+  const int rc = marg_scatter_pooled(ctx, plan, mem, refs, status, &any_host);
+  if (rc != VILO_OK) return rc;
   // priors that go back to host memory: through the context's reusable page-locked staging (a fresh pageable vector of W x 74 KB was
   // zero-filled, then filled again through the runtime's bounce buffer: most of a fleet's marginalisation call)
   const double *J0 = nullptr, *r0 = nullptr;
   if (any_host) {
-    double *hJ = (double *)vilo_host_stage(ctx, 7, sizeof(double) * (nJ0 + nr0));
+    double *hJ = (double *)vilo_host_stage(ctx, 7, sizeof(double) * (mem.nJ0 + mem.nr0));
     if (!hJ) return VILO_ERR_HIP;
-    if (hipMemcpyAsync(hJ, d_J0, nJ0 * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(hJ + nJ0, d_r0, nr0 * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+    if (hipMemcpyAsync(hJ, mem.d_J0, mem.nJ0 * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(hJ + mem.nJ0, mem.d_r0, mem.nr0 * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
       return VILO_ERR_HIP;
-    J0 = hJ; r0 = hJ + nJ0;
+    J0 = hJ; r0 = hJ + mem.nJ0;
   }
+  int any_bad = 0;
   for (int w = 0; w < W; ++w) {
-    const MargWin &M = mws[w];
-    if (skip[w]) continue;
-    const int mode = modes[w];
+    const MargWin &M = plan.wins[w];
+    if (plan.skip[w]) continue;
     const bool pooled = refs && refs[w].prior_pool;
     vilo_prior &p = pooled ? refs[w].prior_pool->meta[refs[w].next_prior_slot] : out[w];
-    if (keep_prior[w]) {
-      const vilo_prior &q = *vilo_win_prior(in[w], refs ? refs + w : nullptr);
-      if (&p != &q) {
-        int sum_g = 0;
-        for (int k = 0; k < q.n_blocks; ++k) { p.block_id[k] = q.block_id[k]; p.block_size[k] = q.block_size[k]; p.block_idx[k] = q.block_idx[k]; sum_g += q.block_size[k]; }
-        p.n = q.n; p.n_blocks = q.n_blocks; p.valid = 1;
-        memmove(p.x0, q.x0, sizeof(double) * sum_g);
-        if (!pooled) {
-          memmove(p.J0, q.J0, sizeof(double) * (size_t)q.n * q.n);
-          memmove(p.r0, q.r0, sizeof(double) * q.n);
-        }
-      }
-      continue;
-    }
+    if (plan.keep_prior[w]) { copy_prior_meta(*vilo_win_prior(in[w], refs ? refs + w : nullptr), p, pooled); continue; }
     if (M.m == 0 || M.n == 0) { p.valid = 0; p.n = 0; continue; }
     // a non-finite result concerns this window alone: it goes on without a prior, the others keep theirs (the call still reports it)
     if (status[w]) { p.valid = 0; p.n = 0; any_bad = 1; continue; }
-    const int WS = in[w].n_frames - 1;
-    p.n = M.n; p.n_blocks = (int)kept_ids[w].size(); p.valid = 1;
-    int xo = 0;
-    const double *xs[6] = {state[w].pose, state[w].speed_bias, state[w].leg_bias, state[w].ex_pose, state[w].td, nullptr};
-    for (int k = 0; k < p.n_blocks; ++k) {
-      int id = kept_ids[w][k];
-      const int kind = id / 16, index = id % 16;
-      const double *src = kind == VILO_BLK_POSE ? xs[0] + 7 * index : kind == VILO_BLK_SB ? xs[1] + 9 * index : kind == VILO_BLK_LB ? xs[2] + 4 * index : kind == VILO_BLK_EX ? xs[3] + 7 * index : xs[4];
-      // addr_shift: MARGIN_OLD frame k -> k-1 (estimator.cpp:1358-1368); MARGIN_SECOND_NEW frame WS -> WS-1 (:1413-1447)
-      if (kind <= VILO_BLK_LB) {
-        if (mode == 0) id = kind * 16 + (index - 1);
-        else if (index == WS) id = kind * 16 + (index - 1);
-      }
-      p.block_id[k] = id; p.block_size[k] = kept_gs[w][k]; p.block_idx[k] = kept_cd[w][k];
-      for (int c = 0; c < kept_gs[w][k]; ++c) p.x0[xo + c] = src[c];
-      xo += kept_gs[w][k];
-    }
+    write_prior_meta(plan, w, in[w].n_frames, state[w], p);
     if (pooled) continue;
     memcpy(p.J0, J0 + (size_t)w * VILO_MAX_PRIOR_DIM * VILO_MAX_PRIOR_DIM, sizeof(double) * (size_t)M.n * M.n);   // (n x n packed on both sides)
     memcpy(p.r0, r0 + (size_t)w * VILO_MAX_PRIOR_DIM, sizeof(double) * M.n);
@@ -1397,12 +1099,32 @@ static int marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_wi
   return VILO_OK;
 }
 
+}  // namespace
+
+extern "C" double vilo_last_marginalize_ms(const vilo_ctx *ctx) { return ctx ? ctx->last_marg_ms : 0.0; }
+extern "C" int vilo_debug_marg_general_count(const vilo_ctx *ctx) { return ctx ? ctx->marg_general_count : 0; }
+
+// Every return below the BatchCall happens while it is alive: its closing synchronisation is what makes the asynchronous copies out of
+// the staging safe.
+int vilo_marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *state,
+                           const int *modes, vilo_prior *out) {
+  if (bt->mask.stale(ctx, "vilo_batch_marginalize") != VILO_OK) return VILO_ERR_HIP;
+  MargPlan plan;
+  int rc = marg_plan(bt, W, in, refs, modes, plan);
+  if (rc != VILO_OK) return rc;
+  BatchCall call(ctx, bt, &vilo_ctx::last_marg_ms);
+  MargMem mem;
+  rc = marg_run(call, plan, mem);
+  if (rc != VILO_OK) return rc;
+  return marg_store(ctx, bt->d, plan, mem, in, refs, state, out);
+}
+
 extern "C" int vilo_marginalize(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_window_state *state, int mode,
                                 vilo_prior *out) {
   if (!ctx || W <= 0 || !in || !state || !out || (mode != 0 && mode != 1)) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
   std::vector<int> modes(W, mode);
-  return vilo_with_batch(ctx, W, in, state, [&](vilo_batch *bt) { return marginalize_batch(ctx, bt, W, in, nullptr, state, modes.data(), out); });
+  return vilo_with_batch(ctx, W, in, state, [&](vilo_batch *bt) { return vilo_marginalize_batch(ctx, bt, W, in, nullptr, state, modes.data(), out); });
 }
 
 // The marginalisation half on a batch that is already resident (after vilo_batch_solve + vilo_batch_download): linearised at the batch's
@@ -1413,126 +1135,5 @@ extern "C" int vilo_batch_marginalize(vilo_ctx *ctx, vilo_batch *bt, int W, cons
   for (int w = 0; w < W; ++w)
     if (modes[w] > 1) return VILO_ERR_BAD_ARG;
   VILO_HIP(hipSetDevice(ctx->device));
-  return marginalize_batch(ctx, bt, W, in, nullptr, state, modes, out);
-}
-
-// Estimator::optimization() (estimator.cpp:1054-1458) as one call on one device-resident batch: ceres::Solve, double2vector's
-// gauge fix, then the marginalisation linearised at that result.
-extern "C" int vilo_optimize_windows_resident(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, vilo_window_state *inout,
-                                              const vilo_solve_opts *opts, const int *marginalization_flag, vilo_prior *next_prior,
-                                              vilo_solve_summary *summaries) {
-  if (!ctx || W <= 0 || !in || !inout || !opts) return VILO_ERR_BAD_ARG;
-  if (marginalization_flag && !next_prior) {
-    for (int w = 0; w < W; ++w)
-      if (!refs || !refs[w].prior_pool) return VILO_ERR_BAD_ARG;
-  }
-  VILO_HIP(hipSetDevice(ctx->device));
-  const bool timing = getenv("VILO_HOST_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  vilo_batch *bt = nullptr;
-  int rc = vilo_batch_create_refs(ctx, W, in, refs, inout, &bt);
-  if (rc != VILO_OK) return rc;
-  const double t1 = now();
-  rc = vilo_batch_solve(ctx, bt, opts);
-  const double t2 = now();
-  if (rc == VILO_OK) rc = vilo_gauge_fix_batch(ctx, bt->d);
-  if (rc == VILO_OK) rc = vilo_batch_download(ctx, bt, inout, summaries);
-  const double t3 = now();
-  if (rc == VILO_OK && marginalization_flag) {
-    // the reference only marginalises full windows (estimator.cpp:1243-1244)
-    std::vector<int> modes(W);
-    for (int w = 0; w < W; ++w) modes[w] = (in[w].n_frames == VILO_MAX_FRAMES) ? marginalization_flag[w] : -1;
-    rc = marginalize_batch(ctx, bt, W, in, refs, inout, modes.data(), next_prior);
-  }
-  const double t4 = now();
-  vilo_batch_destroy(ctx, bt);
-  if (timing)
-    fprintf(stderr, "[vilo_optimize_windows] W=%d create %.2f ms, solve %.2f ms, gauge fix + download %.2f ms, marginalise %.2f ms (kernels %.2f), destroy %.2f ms\n", W,
-            t1 - t0, t2 - t1, t3 - t2, t4 - t3, ctx->last_marg_ms, now() - t4);
-  return rc;
-}
-
-// Estimator::optimization() (estimator.cpp:1054-1458) as one call on one device-resident batch: ceres::Solve, double2vector's
-// gauge fix, then the marginalisation linearised at that result.
-extern "C" int vilo_optimize_windows(vilo_ctx *ctx, int W, const vilo_window_desc *in, vilo_window_state *inout, const vilo_solve_opts *opts,
-                                     const int *marginalization_flag, vilo_prior *next_prior, vilo_solve_summary *summaries) {
-  if (marginalization_flag && !next_prior) return VILO_ERR_BAD_ARG;
-  if (!ctx || W <= 0 || !in || !inout || !opts) return VILO_ERR_BAD_ARG;
-  // many host windows: sub-batches over the context's pipeline lanes (vilo_set_host_pipeline), like vilo_solve_windows — each window's
-  // solve, gauge fix and marginalisation are its own, so the call's results are the one batch's
-  int rc = VILO_OK;
-  if (vilo_run_on_lanes(ctx, W, in, inout, [&](vilo_ctx *l, int w0, int n) {
-        return vilo_optimize_windows_resident(l, n, in + w0, nullptr, inout + w0, opts, marginalization_flag ? marginalization_flag + w0 : nullptr,
-                                              next_prior ? next_prior + w0 : nullptr, summaries ? summaries + w0 : nullptr);
-      }, &rc))
-    return rc;
-  return vilo_optimize_windows_resident(ctx, W, in, nullptr, inout, opts, marginalization_flag, next_prior, summaries);
-}
-
-// ---- prior pool ----
-extern "C" int vilo_prior_pool_create(vilo_ctx *ctx, int n, vilo_prior_pool **out) {
-  if (!ctx || n <= 0 || !out) return VILO_ERR_BAD_ARG;
-  VILO_HIP(hipSetDevice(ctx->device));
-  vilo_prior_pool *pl = new vilo_prior_pool();
-  pl->n = n; pl->device = ctx->device; pl->dJ = pl->dr = nullptr;
-  if (hipMalloc((void **)&pl->dJ, sizeof(double) * (size_t)n * 96 * 96) != hipSuccess || hipMalloc((void **)&pl->dr, sizeof(double) * (size_t)n * 96) != hipSuccess) {
-    if (pl->dJ) (void)hipFree(pl->dJ);
-    delete pl;
-    ctx->err = "vilo_prior_pool_create: allocation failed";
-    return VILO_ERR_HIP;
-  }
-  pl->meta.resize(n);
-  pl->x0_store.assign((size_t)n * 7 * VILO_MAX_PRIOR_BLOCKS, 0.0);
-  for (int i = 0; i < n; ++i) {
-    memset(&pl->meta[i], 0, sizeof(vilo_prior));
-    pl->meta[i].x0 = &pl->x0_store[(size_t)i * 7 * VILO_MAX_PRIOR_BLOCKS];
-  }
-  *out = pl;
-  return VILO_OK;
-}
-extern "C" void vilo_prior_pool_destroy(vilo_ctx *ctx, vilo_prior_pool *pl) {
-  if (!pl) return;
-  (void)ctx;
-  (void)hipSetDevice(pl->device);
-  (void)hipFree(pl->dJ);
-  (void)hipFree(pl->dr);
-  delete pl;
-}
-extern "C" int vilo_prior_pool_dim(const vilo_prior_pool *pl, int slot) {
-  if (!pl || slot < 0 || slot >= pl->n || !pl->meta[slot].valid) return 0;
-  return pl->meta[slot].n;
-}
-extern "C" int vilo_prior_pool_upload(vilo_ctx *ctx, vilo_prior_pool *pl, int slot, const vilo_prior *p) {
-  if (!ctx || !pl || slot < 0 || slot >= pl->n) return VILO_ERR_BAD_ARG;
-  vilo_prior &m = pl->meta[slot];
-  if (!p || !p->valid || p->n <= 0) { m.valid = 0; m.n = 0; m.n_blocks = 0; return VILO_OK; }
-  if (p->n > VILO_MAX_PRIOR_DIM || p->n_blocks > VILO_MAX_PRIOR_BLOCKS || !p->x0 || !p->J0 || !p->r0) return VILO_ERR_BAD_ARG;
-  VILO_HIP(hipSetDevice(ctx->device));
-  double *x0 = m.x0;
-  m = *p;
-  m.x0 = x0; m.J0 = nullptr; m.r0 = nullptr;
-  int sum_g = 0;
-  for (int k = 0; k < p->n_blocks; ++k) sum_g += p->block_size[k];
-  memcpy(m.x0, p->x0, sizeof(double) * sum_g);
-  VILO_HIP(hipMemcpy(pl->dJ + (size_t)slot * 96 * 96, p->J0, sizeof(double) * (size_t)p->n * p->n, hipMemcpyHostToDevice));
-  VILO_HIP(hipMemcpy(pl->dr + (size_t)slot * 96, p->r0, sizeof(double) * p->n, hipMemcpyHostToDevice));
-  return VILO_OK;
-}
-extern "C" int vilo_prior_pool_download(vilo_ctx *ctx, vilo_prior_pool *pl, int slot, vilo_prior *out) {
-  if (!ctx || !pl || !out || slot < 0 || slot >= pl->n) return VILO_ERR_BAD_ARG;
-  const vilo_prior &m = pl->meta[slot];
-  double *x0 = out->x0, *J0 = out->J0, *r0 = out->r0;
-  if (!m.valid || m.n <= 0) { out->valid = 0; out->n = 0; out->n_blocks = 0; return VILO_OK; }
-  if (!x0 || !J0 || !r0) return VILO_ERR_BAD_ARG;
-  VILO_HIP(hipSetDevice(ctx->device));
-  VILO_HIP(hipStreamSynchronize(ctx->stream));
-  *out = m;
-  out->x0 = x0; out->J0 = J0; out->r0 = r0;
-  int sum_g = 0;
-  for (int k = 0; k < m.n_blocks; ++k) sum_g += m.block_size[k];
-  memcpy(x0, m.x0, sizeof(double) * sum_g);
-  VILO_HIP(hipMemcpy(J0, pl->dJ + (size_t)slot * 96 * 96, sizeof(double) * (size_t)m.n * m.n, hipMemcpyDeviceToHost));
-  VILO_HIP(hipMemcpy(r0, pl->dr + (size_t)slot * 96, sizeof(double) * m.n, hipMemcpyDeviceToHost));
-  return VILO_OK;
+  return vilo_marginalize_batch(ctx, bt, W, in, nullptr, state, modes, out);
 }

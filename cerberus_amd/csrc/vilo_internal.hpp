@@ -223,3 +223,10 @@ int vilo_resid_landmark_flags_launch(vilo_ctx *ctx, const BatchDev &b, double th
 bool vilo_run_on_lanes(vilo_ctx *ctx, int n_windows, const vilo_window_desc *in, vilo_window_state *inout,
                        const std::function<int(vilo_ctx *lane, int w0, int n)> &fn, int *rc_out);
 int vilo_batch_create_refs(vilo_ctx *ctx, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *init, vilo_batch **out);
+// kernels_gauge.hip: double2vector's gauge fix in place on a batch's device state, unchecked, on the context's stream (vilo_optimize_windows)
+int vilo_gauge_fix_batch(vilo_ctx *ctx, BatchDev &b);
+// kernels_marg.hip: marginalisation of every window of a batch at its current device state (b.x, b.lam). `state` holds the same values on
+// the host (they become keep_block_data of the new prior); refs: null, or [W]; modes[w]: 0 MARGIN_OLD, 1 MARGIN_SECOND_NEW, < 0 skip
+// (out[w] untouched). A window with a prior pool leaves its prior in slot next_prior_slot. The batch is left alive.
+int vilo_marginalize_batch(vilo_ctx *ctx, vilo_batch *bt, int W, const vilo_window_desc *in, const vilo_resident_refs *refs, const vilo_window_state *state,
+                           const int *modes, vilo_prior *out);

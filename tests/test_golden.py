@@ -480,7 +480,7 @@ def test_oracle_gauge_fix_at_the_euler_singularity(gwin):
 
 @pytest.mark.gpu
 def test_gpu_gauge_fix_at_the_euler_singularity(ctx, gwin):
-    """vilo_gauge_fix (k_gauge_fix, kernels_marg.hip) with frame 0 pitched to +-89.5 / +-90 / 88.9 -> 89.2 degrees before and / or after
+    """vilo_gauge_fix (k_gauge_fix, kernels_gauge.hip) with frame 0 pitched to +-89.5 / +-90 / 88.9 -> 89.2 degrees before and / or after
     the solve, against the reference-built fixture."""
     worst = _gauge_cases(ctx.gauge_fix, gwin)
     print("gauge fix, worst absolute difference to the reference-built fixture: %.2e" % worst)
